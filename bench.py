@@ -18,6 +18,12 @@ over one reference-image Problem: 1 reference + 8 source views, 1600x1200, singl
 single-GPU configurations of BASELINE.json (cfg 2, cfg 3) and the two non-headline formats of cfg 1 (fp32 textures, 20 source
 views), each with its own k_update average and roofline fraction; `cpu_baseline` is the oracle on the host cores.
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line: `value`
+and the figures read from those same steps (`roofline`, `kernel_ms_per_step`, `within_1pct_of_gt`).  Every other reading --
+pipelined_value, resident_value, the with-upload readings (`value_survey_8d*`), `secondary`, `cpu_baseline`, and with N > 1 the
+peer tables, the peer-copy check and configs[4] -- runs only with --full.  --dump-outputs DIR writes what the last timed step
+returned as .npy files.
+
 Multi-GPU (--gpus N): one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process is
 one rank; started plainly (`python bench.py --gpus N`), it becomes a launcher that never touches the GPU: it starts N fresh child
 processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, forwards rank 0's JSON line and exits non-zero if any rank failed
@@ -183,6 +189,21 @@ def roofline_of(upd_avg_ms, w, h, v):
 def pinned(shape):
     import torch
     return torch.empty(shape, dtype=torch.float32, pin_memory=True).numpy()
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (inputs and seeds are fixed by the arguments, so two builds can
+    be compared file for file)"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def timed_runs(pm, ctx, prm, seed, steps, bufs=None):
@@ -437,8 +458,9 @@ def secondary(pm, engine, dev_index, cams, imgs_f32, gts, prm, args):
 # ---------------------------------------------------------------------------------------------------------------------
 # cfg 4
 # ---------------------------------------------------------------------------------------------------------------------
-def run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier, steps=None, warmup=None):
-    """configs[4]; every rank calls it, rank 0 gets the result line (a dict), the others None"""
+def run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier, steps=None, warmup=None, dump=None):
+    """configs[4]; every rank calls it, rank 0 gets the result line (a dict), the others None.  dump: directory for the maps rank 0
+    holds after the last step, a fixed, seeded sample of pixels (the same in every map)"""
     import torch
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -473,6 +495,13 @@ def run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier, steps=None
         dt = float(t.item())
     res = s.fetch()
     acc = [float((np.abs(r[0][..., 3] - gts[i]) / gts[i] < 0.01).mean()) for i, r in res.items()]
+    if dump is not None and rank == 0:
+        ids = sorted(res)
+        k = min(w4 * h4, DUMP_LIMIT_BYTES // (6 * 4 * len(ids)))   # 6 floats per pixel: plane (4), cost, geometric cost
+        pix = np.sort(np.random.default_rng(0).choice(w4 * h4, k, replace=False))
+        dump_outputs(dump, {"planes": np.stack([res[i][0].reshape(-1, 4)[pix] for i in ids]),
+                            "costs": np.stack([res[i][1].reshape(-1)[pix] for i in ids]),
+                            "geom_costs": np.stack([res[i][2].reshape(-1)[pix] for i in ids])})
     if rank == 0:
         n = g * g
         passes = s.timing[-3:]
@@ -659,165 +688,12 @@ def peer_copy_check(pm, engine, ctx, cams, gts, prm, dev_index, allow_self=False
             "note": "geometric-cost probe after the GPU-to-GPU copies == after a host upload of the same maps" if ok else "the probe DIFFERS after the GPU-to-GPU copies"}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None)
-    ap.add_argument("--warmup", type=int, default=None)
-    ap.add_argument("--workload", default="cfg1", choices=["cfg1", "cfg4"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (cfg 2, cfg 3, fp32 textures, 20 views)")
-    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
-                    help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path on one GPU)")
-    ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank uses GPU 0")
-    ap.add_argument("--float-images", action="store_true",
-                    help="keep the rendered images as non-integer fp32 (rescaled-image case) instead of 8-bit camera-like images")
-    ap.add_argument("--cfg4-size", default="1600x1200")
-    ap.add_argument("--cfg4-grid", type=int, default=8)
-    ap.add_argument("--workers", type=int, default=6, help="cfg4: host threads per rank driving its Problems (measured on one MI355X, 64 Problems: 1 / 3 / 6 / 10 threads 14.6 / 10.7 / 9.4 / 9.7 s)")
-    ap.add_argument("--size", default=None, help="WxH of the cfg-1 Problem instead of 1600x1200 (tests of the multi-rank plumbing; the line says so)")
-    ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--child-seed", type=int, default=12345, help=argparse.SUPPRESS)
-    ap.add_argument("--no-overlap-phase", action="store_true",
-                    help="skip the untimed two-context pipeline (value_survey_8d_pipelined): its kernels overlap, which inflates the per-kernel "
-                         "durations of a kernel trace of this command (tools/profile_gpu.sh, tools/trace_kernels.sh use it)")
-    ap.add_argument("--peer-check-self", action="store_true", help=argparse.SUPPRESS)   # rehearsal of the peer-copy check on a one-GPU box (the device copies from itself)
-    ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--launch-check-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    global W, H
-    if args.size:
-        W, H = (int(v) for v in args.size.lower().split("x"))
-    if args.cpu_baseline_child:
-        cpu_baseline_child(args.cpu_baseline_child, args.child_seed, not args.float_images)
-        return
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started plainly: become the launcher (nothing below this line runs in this process, which never touches the GPU)
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
-    if args.launch_check:
-        launch_check(args)
-        return
-    if args.steps is None:
-        args.steps = 5 if args.workload == "cfg1" else 1
-    if args.warmup is None:
-        args.warmup = 1 if (args.workload == "cfg1" or args.gpus > 1) else 0   # cfg4 with ranks: the first collective sets up the communicator
-
+def other_readings(pm, engine, ctx, dev_index, cams, imgs, prm, seed, args, bufs, barrier, dist):
+    """--full: the other readings of the metric after the timed region; every time is the max over the ranks.  Returns the
+    seconds of the pipelined, kernel-only, with-upload and two-context steps and the host time per step of the last"""
     import torch
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start it plainly (python bench.py --gpus N launches its own ranks) or with "
-                         f"torch.distributed.run --nproc-per-node {args.gpus}")
-    dist = None
-    dev_index = 0 if args.share_device else local_rank
-    torch.cuda.set_device(dev_index)
-    if world > 1:
-        import torch.distributed as dist
-        with stage(rank, f"torch.distributed.init_process_group({args.backend!r}) on cuda:{dev_index}"), native_stdout_to_stderr():
-            if args.backend == "nccl":
-                dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
-            else:
-                dist.init_process_group("gloo")
-            dist.barrier()   # the communicator comes up here, whatever the workload does first (and says what it has to say on stderr)
-    # a CPU-only side channel (gloo) for the diagnostics that must get through even if a GPU call of some rank never returns
-    side = None
-    if dist is not None:
-        try:
-            if args.backend == "nccl" and "GLOO_SOCKET_IFNAME" not in os.environ:
-                import socket
-                try:
-                    socket.gethostbyname(socket.gethostname())
-                except OSError:   # a container whose hostname does not resolve: gloo would not find its own address; one node, so loopback does
-                    os.environ["GLOO_SOCKET_IFNAME"] = "lo"
-            if args.backend == "nccl":
-                with native_stdout_to_stderr():
-                    side = dist.new_group(backend="gloo")
-            else:
-                side = dist.group.WORLD
-        except Exception as e:   # noqa: BLE001 -- no side channel: the peer-copy check is skipped (it would have no safe way to report)
-            print(f"bench.py: rank {rank}: no gloo side channel ({type(e).__name__}: {e}); the peer-copy check will be skipped", file=sys.stderr, flush=True)
-
-    pm = importlib.import_module("mp-mvs_amd")
-    engine = importlib.import_module("mp-mvs_amd.engine")
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    if args.workload == "cfg4":
-        with stage(rank, "configs[4] (SceneScheduler.run: one all_gather_into_tensor of the depth maps per pass)"):
-            out = run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier)
-        if rank == 0:
-            print(json.dumps(out), flush=True)
-        if dist is not None:
-            dist.barrier()
-            dist.destroy_process_group()
-        return
-
-    quantize = not args.float_images
-    if rank == 0:
-        cams, imgs_f32, gts = load_views(pm, W, H, problem_centers(pm, V), f"p{V}")   # renders once, the other ranks read the cache
-    if dist is not None:
-        dist.barrier()
-    if rank != 0:
-        cams, imgs_f32, gts = load_views(pm, W, H, problem_centers(pm, V), f"p{V}")
-    imgs = [np.rint(im).astype(np.float32) for im in imgs_f32] if quantize else imgs_f32
-    gt = gts[0]
-    dmin, dmax = pm.synth.kernel_depth_range(cams[0])
-    prm = pm.PatchMatchParams(num_images=V + 1, depth_min=float(dmin), depth_max=float(dmax), max_scale=0, max_iterations=ITERS)
-    ctx = engine.create(dev_index)
-    ctx.set_views(cams, imgs)   # inputs resident in HBM from here on
-    ctx.set_profiling(True)
-    seed = 12345 + rank
-    bufs = (pinned((H, W, 4)), pinned((H, W)))
     bufs2 = (pinned((H, W, 4)), pinned((H, W)))
-
-    devices = None
-    peers = None
-    if dist is not None:
-        # every rank sees the whole job, on a device of its own (unless --share-device rehearses on one GPU)
-        with stage(rank, "first collective (all_gather of rank / device ids: sets the communicator up)"), native_stdout_to_stderr():
-            assert dist.get_world_size() == args.gpus, f"rank {rank}: the process group has {dist.get_world_size()} ranks, --gpus {args.gpus}"
-            mine = torch.tensor([rank, torch.cuda.current_device()], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
-            seen = [torch.empty_like(mine) for _ in range(world)]
-            dist.all_gather(seen, mine)
-            devices = {int(t[0]): int(t[1]) for t in seen}
-            assert sorted(devices) == list(range(world)), f"ranks seen by the collective: {sorted(devices)}"
-            if not args.share_device:
-                assert len(set(devices.values())) == world, f"ranks share devices: {devices}"
-        # how this rank's GPU reaches the others (hipDeviceCanAccessPeer, link type, hops): printed per rank before anything is
-        # measured, and gathered into the line
-        with stage(rank, "mpmvs_peer_info"):
-            mine_peers = peer_table(engine, dev_index)
-            print(f"bench.py: rank {rank} on cuda:{dev_index} of {engine.device_count()} visible: peers {json.dumps(mine_peers)}", file=sys.stderr, flush=True)
-            gathered = [None] * world
-            dist.all_gather_object(gathered, {"rank": rank, "device": dev_index, "peers": mine_peers})
-            peers = gathered
-
-    # THE timed region (driver contract): W untimed steps, then exactly K steps between barriers.  A step is ONE blocking call,
-    # mpmvs_run_get: the launches of Run() and the device-to-host copies that end it (ref .cu:1246-1251) -- the headline of
-    # rounds 2 and 3.  (Round 4 pipelined the steps here; that figure is `pipelined_value` below, measured after the timed region.)
-    with stage(rank, "the timed region (warm-up, barrier, K x mpmvs_run_get, barrier, max over the ranks)"):
-        for i in range(args.warmup):
-            ctx.run_into(prm, seed + 1000 * (i + 1), *bufs)
-        barrier()
-        t0 = time.perf_counter()
-        _, upd_ms, upd_n, all_ms = timed_runs(pm, ctx, prm, seed, args.steps, bufs)
-        barrier()
-        dt = time.perf_counter() - t0
-        if dist is not None:
-            t = torch.tensor([dt], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-
-    # sanity of the last result
-    planes, costs = bufs[0].copy(), bufs[1].copy()
-    rel = np.abs(planes[..., 3] - gt) / gt
-    within = float((rel < 0.01).mean())
-
-    # other readings of the metric (untimed by the driver): pipelined steps, kernels only, and with the image upload
+    # untimed by the driver: pipelined steps, kernels only, and with the image upload
     ctx.run_into_async(prm, seed + 999, *bufs2)
     ctx.wait()
     barrier()
@@ -870,13 +746,184 @@ def main():
         t = torch.tensor([dt_res, dt_h2d, dt_pipelined, dt_h2d_pipe], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_res, dt_h2d, dt_pipelined, dt_h2d_pipe = (float(v) for v in t.tolist())
+    return dt_pipelined, dt_res, dt_h2d, dt_h2d_pipe, pipe_host_ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--workload", default="cfg1", choices=["cfg1", "cfg4"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: pipelined / resident / with-upload readings, the "
+                         "secondary configurations, the CPU baseline, and with --gpus N > 1 the peer tables, the peer-copy check and configs[4]")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; cfg4: a fixed, seeded sample of pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configurations (cfg 2, cfg 3, fp32 textures, 20 views)")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
+                    help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path on one GPU)")
+    ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank uses GPU 0")
+    ap.add_argument("--float-images", action="store_true",
+                    help="keep the rendered images as non-integer fp32 (rescaled-image case) instead of 8-bit camera-like images")
+    ap.add_argument("--cfg4-size", default="1600x1200")
+    ap.add_argument("--cfg4-grid", type=int, default=8)
+    ap.add_argument("--workers", type=int, default=6, help="cfg4: host threads per rank driving its Problems (measured on one MI355X, 64 Problems: 1 / 3 / 6 / 10 threads 14.6 / 10.7 / 9.4 / 9.7 s)")
+    ap.add_argument("--size", default=None, help="WxH of the cfg-1 Problem instead of 1600x1200 (tests of the multi-rank plumbing; the line says so)")
+    ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-seed", type=int, default=12345, help=argparse.SUPPRESS)
+    ap.add_argument("--no-overlap-phase", action="store_true",
+                    help="with --full: skip the untimed two-context pipeline (value_survey_8d_pipelined): its kernels overlap, which inflates the per-kernel "
+                         "durations of a kernel trace of this command (tools/profile_gpu.sh, tools/trace_kernels.sh use it)")
+    ap.add_argument("--peer-check-self", action="store_true", help=argparse.SUPPRESS)   # rehearsal of the peer-copy check on a one-GPU box (the device copies from itself)
+    ap.add_argument("--launch-check", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--launch-check-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    global W, H
+    if args.size:
+        W, H = (int(v) for v in args.size.lower().split("x"))
+    if args.cpu_baseline_child:
+        cpu_baseline_child(args.cpu_baseline_child, args.child_seed, not args.float_images)
+        return
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # started plainly: become the launcher (nothing below this line runs in this process, which never touches the GPU)
+        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+    if args.launch_check:
+        launch_check(args)
+        return
+    if args.steps is None:
+        args.steps = 5 if args.workload == "cfg1" else 1
+    if args.warmup is None:
+        args.warmup = 1 if (args.workload == "cfg1" or args.gpus > 1) else 0   # cfg4 with ranks: the first collective sets up the communicator
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+
+    import torch
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: start it plainly (python bench.py --gpus N launches its own ranks) or with "
+                         f"torch.distributed.run --nproc-per-node {args.gpus}")
+    dist = None
+    dev_index = 0 if args.share_device else local_rank
+    torch.cuda.set_device(dev_index)
+    if world > 1:
+        import torch.distributed as dist
+        with stage(rank, f"torch.distributed.init_process_group({args.backend!r}) on cuda:{dev_index}"), native_stdout_to_stderr():
+            if args.backend == "nccl":
+                dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
+            else:
+                dist.init_process_group("gloo")
+            dist.barrier()   # the communicator comes up here, whatever the workload does first (and says what it has to say on stderr)
+    # a CPU-only side channel (gloo) for the diagnostics that must get through even if a GPU call of some rank never returns
+    side = None
+    if dist is not None and args.full:
+        try:
+            if args.backend == "nccl" and "GLOO_SOCKET_IFNAME" not in os.environ:
+                import socket
+                try:
+                    socket.gethostbyname(socket.gethostname())
+                except OSError:   # a container whose hostname does not resolve: gloo would not find its own address; one node, so loopback does
+                    os.environ["GLOO_SOCKET_IFNAME"] = "lo"
+            if args.backend == "nccl":
+                with native_stdout_to_stderr():
+                    side = dist.new_group(backend="gloo")
+            else:
+                side = dist.group.WORLD
+        except Exception as e:   # noqa: BLE001 -- no side channel: the peer-copy check is skipped (it would have no safe way to report)
+            print(f"bench.py: rank {rank}: no gloo side channel ({type(e).__name__}: {e}); the peer-copy check will be skipped", file=sys.stderr, flush=True)
+
+    pm = importlib.import_module("mp-mvs_amd")
+    engine = importlib.import_module("mp-mvs_amd.engine")
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    if args.workload == "cfg4":
+        with stage(rank, "configs[4] (SceneScheduler.run: one all_gather_into_tensor of the depth maps per pass)"):
+            out = run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier, dump=args.dump_outputs)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    quantize = not args.float_images
+    if rank == 0:
+        cams, imgs_f32, gts = load_views(pm, W, H, problem_centers(pm, V), f"p{V}")   # renders once, the other ranks read the cache
+    if dist is not None:
+        dist.barrier()
+    if rank != 0:
+        cams, imgs_f32, gts = load_views(pm, W, H, problem_centers(pm, V), f"p{V}")
+    imgs = [np.rint(im).astype(np.float32) for im in imgs_f32] if quantize else imgs_f32
+    gt = gts[0]
+    dmin, dmax = pm.synth.kernel_depth_range(cams[0])
+    prm = pm.PatchMatchParams(num_images=V + 1, depth_min=float(dmin), depth_max=float(dmax), max_scale=0, max_iterations=ITERS)
+    ctx = engine.create(dev_index)
+    ctx.set_views(cams, imgs)   # inputs resident in HBM from here on
+    ctx.set_profiling(True)
+    seed = 12345 + rank
+    bufs = (pinned((H, W, 4)), pinned((H, W)))
+
+    devices = None
+    peers = None
+    if dist is not None:
+        # every rank sees the whole job, on a device of its own (unless --share-device rehearses on one GPU)
+        with stage(rank, "first collective (all_gather of rank / device ids: sets the communicator up)"), native_stdout_to_stderr():
+            assert dist.get_world_size() == args.gpus, f"rank {rank}: the process group has {dist.get_world_size()} ranks, --gpus {args.gpus}"
+            mine = torch.tensor([rank, torch.cuda.current_device()], dtype=torch.int64, device="cuda" if args.backend == "nccl" else "cpu")
+            seen = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(seen, mine)
+            devices = {int(t[0]): int(t[1]) for t in seen}
+            assert sorted(devices) == list(range(world)), f"ranks seen by the collective: {sorted(devices)}"
+            if not args.share_device:
+                assert len(set(devices.values())) == world, f"ranks share devices: {devices}"
+    if dist is not None and args.full:
+        # how this rank's GPU reaches the others (hipDeviceCanAccessPeer, link type, hops): printed per rank before anything is
+        # measured, and gathered into the line
+        with stage(rank, "mpmvs_peer_info"):
+            mine_peers = peer_table(engine, dev_index)
+            print(f"bench.py: rank {rank} on cuda:{dev_index} of {engine.device_count()} visible: peers {json.dumps(mine_peers)}", file=sys.stderr, flush=True)
+            gathered = [None] * world
+            dist.all_gather_object(gathered, {"rank": rank, "device": dev_index, "peers": mine_peers})
+            peers = gathered
+
+    # THE timed region (driver contract): W untimed steps, then exactly K steps between barriers.  A step is ONE blocking call,
+    # mpmvs_run_get: the launches of Run() and the device-to-host copies that end it (ref .cu:1246-1251) -- the headline of
+    # rounds 2 and 3.  (Round 4 pipelined the steps here; that figure is `pipelined_value`, measured after the timed region with --full.)
+    with stage(rank, "the timed region (warm-up, barrier, K x mpmvs_run_get, barrier, max over the ranks)"):
+        for i in range(args.warmup):
+            ctx.run_into(prm, seed + 1000 * (i + 1), *bufs)
+        barrier()
+        t0 = time.perf_counter()
+        _, upd_ms, upd_n, all_ms = timed_runs(pm, ctx, prm, seed, args.steps, bufs)
+        barrier()
+        dt = time.perf_counter() - t0
+        if dist is not None:
+            t = torch.tensor([dt], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+
+    # sanity of the last result
+    planes, costs = bufs[0].copy(), bufs[1].copy()
+    rel = np.abs(planes[..., 3] - gt) / gt
+    within = float((rel < 0.01).mean())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"planes": planes, "costs": costs})
+
+    readings = other_readings(pm, engine, ctx, dev_index, cams, imgs, prm, seed, args, bufs, barrier, dist) if args.full else None
 
     # configs[4] in the same invocation when there is more than one rank: the only workload whose passes exchange depth maps
     # (one all-gather per pass), so that one driver command yields the weak-scaling line AND an execution of the collective.
     # One untimed warm-up step first: the communicator is set up by the first collective, and `passes_last_step` should show a
     # steady-state exchange, not that.
     cfg4_line = None
-    if world > 1 and not args.no_secondary:
+    if world > 1 and args.full and not args.no_secondary:
         del ctx
         with stage(rank, "configs[4] (SceneScheduler.run: one all_gather_into_tensor of the depth maps per pass)"):
             cfg4_line = run_cfg4(args, pm, engine, dist, rank, world, dev_index, barrier, steps=1, warmup=1)
@@ -924,6 +971,8 @@ def main():
         hbm_bytes_per_launch = W * H * (4 * (V + 1) + 36)      # SURVEY.md 8d COMPULSORY_HBM_BYTES / L
         gbps = hbm_bytes_per_launch / (upd_avg_ms * 1e-3) / 1e9
         prof = profile_counters(upd_avg_ms)
+        if readings is not None:
+            dt_pipelined, dt_res, dt_h2d, dt_h2d_pipe, pipe_host_ms = readings
         out = {
             "metric": f"Mpix/s depth+normal (fixed iters, {W}x{H}, 8 src views)",
             "value": round(mpix, 3),
@@ -942,11 +991,12 @@ def main():
                                    "ref .cu:1246-1251; every map of every step is in host memory when its call returns); "
                                    "the 9 images are resident in HBM when the timed region "
                                    "starts (bench contract), i.e. the image upload (H2D) is EXCLUDED from `value` -- SURVEY 8(d)'s wording of the metric, "
-                                   "upload + Run() + D2H per step, is `value_survey_8d` in this line",
+                                   "upload + Run() + D2H per step, is `value_survey_8d` in the line of a --full run",
                        "width": W, "height": H, "src_views": V, "max_scale": 0, "iterations": ITERS},
+            "blocking_value": round(mpix, 3),
+            **({} if readings is None else {
             "comparable_across_rounds": "`value` is Run() + D2H one blocking step at a time: the headline of rounds 2, 3 and 5 and round 4's `blocking_value`; round 4's `value` "
                                         "(steps pipelined through mpmvs_run_get_async) is `pipelined_value` here; `resident_value` (kernels only) was round 1's headline",
-            "blocking_value": round(mpix, 3),
             "pipelined_value": round(world * W * H * args.steps / dt_pipelined / 1e6, 3),
             "pipelined_value_is": "the same steps through mpmvs_run_get_async on one context: the maps of step i cross PCIe while step i + 1 computes (every map of every step is in "
                                   "host memory when the region ends); a re-run of one resident Problem, which a real job -- set_views per Problem -- never does: reported, not the headline",
@@ -958,6 +1008,7 @@ def main():
             "value_survey_8d_pipelined_is": "the same work -- every step uploads its 9 images, runs and returns its maps inside the timed region -- as a pipeline over two contexts "
                                             "(Problem i + 1 is uploaded and Problem i - 1 downloaded while Problem i computes): what a job with many Problems gets",
             "value_survey_8d_pipelined_host_ms_per_step": pipe_host_ms,
+            }),
             "roofline": {
                 "kernel": "k_update<photometric> (BlackPixelUpdate/RedPixelUpdate)",
                 "bound": "valu_fp32",
@@ -995,14 +1046,14 @@ def main():
             out["ranks"] = {"world_size_seen_by_the_collective": len(devices), "backend": args.backend,
                             "cuda_device_of_rank": {str(r): d for r, d in sorted(devices.items())},
                             "peer_access": peers, "peer_copy_check": peer_checks}
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del ctx
             out["secondary"] = secondary(pm, engine, dev_index, cams, imgs_f32, gts, prm, args)
             ctx = engine.create(dev_index)
             ctx.set_views(cams, imgs)
         if cfg4_line is not None:
             out.setdefault("secondary", {})["cfg4"] = cfg4_line
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pm, ctx, cams, imgs, prm, seed, quantize)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -333,7 +333,7 @@ def test_folder_schedule_fused_from_resident_contexts(pm, engine, tmp_path):
 
 
 def test_bench_self_launched_two_ranks_share_the_gpu():
-    """`python bench.py --gpus 2` started plainly: the launcher (which never touches the GPU) starts two fresh ranks; here both
+    """`python bench.py --gpus 2 --full` started plainly: the launcher (which never touches the GPU) starts two fresh ranks; here both
     use GPU 0 over gloo (a 1-GPU box cannot run RCCL between two ranks).  One JSON line: the cfg-1 weak-scaling figures and,
     in the same invocation, configs[4] with its per-pass exchange (`secondary.cfg4`)."""
     import json
@@ -343,7 +343,7 @@ def test_bench_self_launched_two_ranks_share_the_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--size", "320x240",
-                        "--cfg4-size", "160x120", "--cfg4-grid", "3", "--steps", "2", "--warmup", "1", "--workers", "2", "--peer-check-self"],
+                        "--cfg4-size", "160x120", "--cfg4-grid", "3", "--steps", "2", "--warmup", "1", "--workers", "2", "--peer-check-self", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
