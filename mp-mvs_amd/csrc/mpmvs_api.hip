@@ -29,6 +29,7 @@
 #include <map>
 #include <mutex>
 #include <unordered_map>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1122,18 +1123,39 @@ static hipEvent_t get_event(mpmvs_ctx* c) {
     return e;
 }
 
-template <bool U8, int NT = 256>
 static dim3 checker_grid(const mpmvs_ctx* c, const LaunchArgs& a) {
     const int rows = c->H < a.ylimit ? c->H : a.ylimit;
-    return dim3(((c->W + kChkBlockW<U8, NT> - 1) / kChkBlockW<U8, NT>) * ((rows + kChkBlockH<U8, NT> - 1) / kChkBlockH<U8, NT>));
+    return dim3(((c->W + kChkBlockW - 1) / kChkBlockW) * ((rows + kChkBlockH<> - 1) / kChkBlockH<>));
 }
-// The per-view arrays of the update kernel (8 x V candidate costs and four V-vectors, in scratch) are sized by a template
-// bound on the number of source views: buckets of 8 keep that scratch and the register pressure around it proportional to the
-// Problem (the shipped configuration allows 20 views, reference config/config.yaml:19; the hard limit is 32, ref .cu:500).
-template <bool GEOM, bool PRIOR, bool U8, int SCALE>
-static void launch_update3(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& ch0) {
-    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW<U8, NT>, BH = kChkBlockH<U8, NT>;
-    const int V = c->hP.V;
+// The kernel variant that serves a launch.  The NCC kernels are instantiated per bound MAXV on the number of source views, texel
+// format (U8: fp16 texels) and window scale (a template parameter: pm_device.hpp, Win).  dispatch_variant calls
+// launch(MAXV, U8, SCALE), as std::integral_constant values, for V views (the first of the BUCKETS that holds them; the last one
+// takes the rest), the format `u8` and `scale` in 0..2 -- or scale 0 only where SCALE0_ONLY, and then no other scale is instantiated.
+// The per-view arrays of the update kernel (8 x V candidate costs and four V-vectors, in scratch) are sized by MAXV: buckets of 8
+// keep that scratch and the register pressure around it proportional to the Problem (the shipped configuration allows 20 views,
+// reference config/config.yaml:19; the hard limit is 32, ref .cu:500).
+template <bool SCALE0_ONLY, int BUCKET, int... BUCKETS, class F>
+static void dispatch_variant(int V, bool u8, int scale, F&& launch) {
+    if constexpr (sizeof...(BUCKETS) > 0) {
+        if (V > BUCKET) return dispatch_variant<SCALE0_ONLY, BUCKETS...>(V, u8, scale, launch);
+    }
+    const auto with_format = [&](auto fmt) {
+        using MaxV = std::integral_constant<int, BUCKET>;
+        if (scale == 0) launch(MaxV{}, fmt, std::integral_constant<int, 0>{});
+        if constexpr (!SCALE0_ONLY) {
+            if (scale == 1) launch(MaxV{}, fmt, std::integral_constant<int, 1>{});
+            if (scale == 2) launch(MaxV{}, fmt, std::integral_constant<int, 2>{});
+        }
+    };
+    if (u8)
+        with_format(std::true_type{});
+    else
+        with_format(std::false_type{});
+}
+
+template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
+static void launch_update_chain(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& ch0) {
+    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
     const int rows = c->H < a.ylimit ? c->H : a.ylimit;
     ChainArgs ch = ch0;
     ch.nbx = (c->W + BW - 1) / BW;
@@ -1142,41 +1164,22 @@ static void launch_update3(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& c
     ch.sync = c->d_sync;
     ch.spin_limit = c->spin_limit;
     ch.stall_pos = c->dbg_stall_pos;
-    if (ch.nb > c->sync_blocks) {   // (measurement builds with other block shapes: never write past the completion words)
+    if (ch.nb > c->sync_blocks) {   // (never write past the completion words, whatever the block shape)
         c->sync_overflow = true;
         return;
     }
     const dim3 grid((unsigned)(ch.n_pass * ch.nb));   // one block per work item (pass, position), handed out by ticket (k_update)
     const size_t lds = update_lds_bytes<NT>();
     const dim3 blk(NT);
-    if (V <= 8)
-        hipLaunchKernelGGL((k_update<GEOM, PRIOR, 8, U8, SCALE>), grid, blk, lds, c->stream, c->dP, c->S, a, ch);
-    else if (V <= 16)
-        hipLaunchKernelGGL((k_update<GEOM, PRIOR, 16, U8, SCALE>), grid, blk, lds, c->stream, c->dP, c->S, a, ch);
-    else if (V <= 24)
-        hipLaunchKernelGGL((k_update<GEOM, PRIOR, 24, U8, SCALE>), grid, blk, lds, c->stream, c->dP, c->S, a, ch);
-    else
-        hipLaunchKernelGGL((k_update<GEOM, PRIOR, kMaxViews, U8, SCALE>), grid, blk, lds, c->stream, c->dP, c->S, a, ch);
+    hipLaunchKernelGGL((k_update<GEOM, PRIOR, MAXV, U8, SCALE>), grid, blk, lds, c->stream, c->dP, c->S, a, ch);
 }
-// The window scale is a template parameter of the NCC kernels (pm_device.hpp, Win).  The photometric update exists at the
-// scales 0..2 of the multi-scale schedule; the geometric and the prior update run at scale 0 only, as Run() does (ref
-// .cu:1188-1254: the scale loop belongs to the photometric branch).
-template <bool GEOM, bool PRIOR, bool U8>
-static void launch_update2(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& ch) {
-    if constexpr (GEOM || PRIOR) {
-        launch_update3<GEOM, PRIOR, U8, 0>(c, a, ch);
-    } else {
-        if (a.scale == 0) launch_update3<false, false, U8, 0>(c, a, ch);
-        if (a.scale == 1) launch_update3<false, false, U8, 1>(c, a, ch);
-        if (a.scale == 2) launch_update3<false, false, U8, 2>(c, a, ch);
-    }
-}
+// The photometric update exists at the scales 0..2 of the multi-scale schedule; the geometric and the prior update run at scale 0
+// only, as Run() does (ref .cu:1188-1254: the scale loop belongs to the photometric branch).
 template <bool GEOM, bool PRIOR>
 static void launch_update(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& ch) {
-    if (c->all_u8)
-        launch_update2<GEOM, PRIOR, true>(c, a, ch);
-    else
-        launch_update2<GEOM, PRIOR, false>(c, a, ch);
+    dispatch_variant<GEOM || PRIOR, 8, 16, 24, kMaxViews>(c->hP.V, c->all_u8, a.scale, [&](auto maxv, auto u8, auto scale) {
+        launch_update_chain<GEOM, PRIOR, maxv, u8, scale>(c, a, ch);
+    });
 }
 
 // the spatial half of the bilateral weight exponent (ref .cu:318-323) of the 36 window taps at `scale`, [column][row]
@@ -1247,35 +1250,14 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
     }
     const dim3 blk(256);
     const dim3 grid_dense((c->W + 15) / 16, (c->H + 15) / 16);
-    const dim3 grid_chk = checker_grid<true>(c, a);  // k_filter (checker_pixel<true>)
+    const dim3 grid_chk = checker_grid(c, a);  // k_filter (checker_pixel)
     switch (kind) {
         case MPMVS_KIND_INIT: {
             c->depth_plane_valid = false;
             const size_t lds = ncc_lds_bytes(16, 16, a.scale);
-            const int V = c->hP.V;
-#define PM_LAUNCH_INIT2(MV, SC)                                                                                             \
-    do {                                                                                                                    \
-        if (c->all_u8)                                                                                                      \
-            hipLaunchKernelGGL((k_init<MV, true, SC>), grid_dense, blk, lds, c->stream, c->dP, c->S, a);                    \
-        else                                                                                                                \
-            hipLaunchKernelGGL((k_init<MV, false, SC>), grid_dense, blk, lds, c->stream, c->dP, c->S, a);                   \
-    } while (0)
-#define PM_LAUNCH_INIT(MV)                  \
-    do {                                    \
-        if (a.scale == 0) PM_LAUNCH_INIT2(MV, 0); \
-        if (a.scale == 1) PM_LAUNCH_INIT2(MV, 1); \
-        if (a.scale == 2) PM_LAUNCH_INIT2(MV, 2); \
-    } while (0)
-            if (V <= 8)
-                PM_LAUNCH_INIT(8);
-            else if (V <= 16)
-                PM_LAUNCH_INIT(16);
-            else if (V <= 24)
-                PM_LAUNCH_INIT(24);
-            else
-                PM_LAUNCH_INIT(kMaxViews);
-#undef PM_LAUNCH_INIT2
-#undef PM_LAUNCH_INIT
+            dispatch_variant<false, 8, 16, 24, kMaxViews>(c->hP.V, c->all_u8, a.scale, [&](auto maxv, auto u8, auto scale) {
+                hipLaunchKernelGGL((k_init<maxv, u8, scale>), grid_dense, blk, lds, c->stream, c->dP, c->S, a);
+            });
             break;
         }
         case MPMVS_KIND_BLACK:
@@ -1601,23 +1583,9 @@ static int eval_ncc_impl(mpmvs_ctx* c, const mpmvs_params* p, const void* planes
     {
         const dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
         const size_t lds = ncc_lds_bytes(16, 16, scale);
-#define PM_LAUNCH_EVAL(MV, U, SC) hipLaunchKernelGGL((k_eval_ncc<MV, U, SC>), grid, dim3(256), lds, c->stream, c->dP, d_pl.as<float4>(), nh, d_out.as<float>(), a)
-#define PM_LAUNCH_EVAL_SC(MV, U)            \
-    do {                                    \
-        if (scale == 0) PM_LAUNCH_EVAL(MV, U, 0); \
-        if (scale == 1) PM_LAUNCH_EVAL(MV, U, 1); \
-        if (scale == 2) PM_LAUNCH_EVAL(MV, U, 2); \
-    } while (0)
-        if (V <= 8 && c->all_u8)
-            PM_LAUNCH_EVAL_SC(8, true);
-        else if (V <= 8)
-            PM_LAUNCH_EVAL_SC(8, false);
-        else if (c->all_u8)
-            PM_LAUNCH_EVAL_SC(kMaxViews, true);
-        else
-            PM_LAUNCH_EVAL_SC(kMaxViews, false);
-#undef PM_LAUNCH_EVAL_SC
-#undef PM_LAUNCH_EVAL
+        dispatch_variant<false, 8, kMaxViews>(V, c->all_u8, scale, [&](auto maxv, auto u8, auto sc) {
+            hipLaunchKernelGGL((k_eval_ncc<maxv, u8, sc>), grid, dim3(256), lds, c->stream, c->dP, d_pl.as<float4>(), nh, d_out.as<float>(), a);
+        });
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(e1, c->stream));

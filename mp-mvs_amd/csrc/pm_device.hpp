@@ -96,11 +96,7 @@ PM_DEV float d_rcp(float z) {
 // whose sum is not finite returns the sentinel cost 2.  Six full-rate adds and one v_cmp_class_f32 per evaluation
 // (measured on the update kernel: 1.4 % of its time; a class test per column cost 1.8 %).
 PM_DEV bool rcp_sum_not_finite(float racc) {
-#ifdef PM_NO_RCP_GUARD  // measurement builds only
-    return false;
-#else
     return __builtin_amdgcn_class(racc, 0x207);  // sNaN qNaN -inf +inf
-#endif
 }
 
 // d_exp for arguments known to lie in [-80, 80] (no NaN): the same value, without the range tests
@@ -363,13 +359,6 @@ template <int SCALE, int BW, int BH, int TILE_MAX = 2048>
 struct Win {
     static constexpr int step = 2 << SCALE, radius = 5 * step / 2, pitch = BW + 2 * radius, rows = BH + 2 * radius;
     static constexpr bool tile_in_lds = pitch * rows <= TILE_MAX;
-    // A checkerboard launch whose tap offsets are all EVEN (window scales 1 and 2: step 4 / 8, radius 10 / 20) only ever reads tile
-    // positions of the pass's own colour -- the taps of a pixel (x, y) lie at (x + even, y + even).  Stored compactly, [row][column / 2],
-    // that half tile of scale 2 (56 x 72 / 2 = 2016 floats for the 16 x 32 block) fits where the whole one (4032) does not, and a tap is
-    // still a compile-time offset from the pixel's own slot: dy * (pitch / 2) + dx / 2.  (Round 6; before, the scale-2 prologue read its 37
-    // reference values per pixel from the L2-resident padded image.)
-    static constexpr bool tile_checker = !tile_in_lds && (radius % 2 == 0) && (step % 2 == 0) && (pitch % 2 == 0) && (BW % 2 == 0) && (BH % 2 == 0) &&
-                                         (pitch / 2) * rows <= TILE_MAX;
 };
 
 // cooperative load of the tile [x0-radius, x0+BW+radius) x [y0-radius, y0+BH+radius)
@@ -381,22 +370,6 @@ PM_DEV void load_ref_tile(const ProblemDev& P, float* tile, int x0, int y0, int 
     const int xmin = -kRefApron, xmax = P.W + kRefApron - 1, ymin = -kRefApron, ymax = P.H + kRefApron - 1;
     for (int i = threadIdx.x; i < tw * th; i += NT) {
         const int ty = i / tw, tx = i - ty * tw;
-        int gx = x0 - radius + tx, gy = y0 - radius + ty;
-        gx = gx < xmin ? xmin : (gx > xmax ? xmax : gx);
-        gy = gy < ymin ? ymin : (gy > ymax ? ymax : gy);
-        tile[i] = P.ref_img[(long)gy * P.ref_pitch + gx];
-    }
-}
-
-// the same for the compact half tile of one colour (Win::tile_checker): tile[ty * (tw / 2) + tx / 2] for the positions with
-// (tx + ty) of the parity the pass's pixels have in tile coordinates (block origin and radius are even: the image parity)
-template <int NT>
-PM_DEV void load_ref_tile_checker(const ProblemDev& P, float* tile, int x0, int y0, int bw, int bh, int radius, int parity) {
-    const int tw = bw + 2 * radius, th = bh + 2 * radius, hw = tw / 2;
-    const int xmin = -kRefApron, xmax = P.W + kRefApron - 1, ymin = -kRefApron, ymax = P.H + kRefApron - 1;
-    for (int i = threadIdx.x; i < hw * th; i += NT) {
-        const int ty = i / hw, k = i - ty * hw;
-        const int tx = 2 * k + ((parity + ty) & 1);
         int gx = x0 - radius + tx, gy = y0 - radius + ty;
         gx = gx < xmin ? xmin : (gx > xmax ? xmax : gx);
         gy = gy < ymin ? ymin : (gy > ymax ? ymax : gy);
@@ -448,19 +421,11 @@ PM_DEV void ref_window(float4* lw, TAP tap, const float (&spatial)[36], float tw
 }
 
 // stages the block's reference tile if it is to live in LDS and fills the pixel's weight column
-// CHECKER: the launch visits the pixels of ONE colour (`parity`: (x + y) & 1 of its pixels) -- enables the half tile where it applies
-template <int SCALE, int BW, int BH, int NT = kBlockThreads, int TILE_MAX = 2048, bool CHECKER = false>
-PM_DEV void ref_window_of_pixel(const ProblemDev& P, int x, int y, int x0, int y0, bool valid, const float (&spatial)[36], float two_sc, RefWin& rw, int parity = 0) {
+template <int SCALE, int BW, int BH, int NT = kBlockThreads, int TILE_MAX = 2048>
+PM_DEV void ref_window_of_pixel(const ProblemDev& P, int x, int y, int x0, int y0, bool valid, const float (&spatial)[36], float two_sc, RefWin& rw) {
     typedef Win<SCALE, BW, BH, TILE_MAX> Wn;
     float4* lw = (float4*)pm_lds + threadIdx.x;
-    if constexpr (CHECKER && Wn::tile_checker) {
-        constexpr int hw = Wn::pitch / 2;
-        load_ref_tile_checker<NT>(P, pm_lds + kLdsWeightFloatsOf<NT>, x0, y0, BW, BH, Wn::radius, parity);
-        __syncthreads();
-        if (!valid) return;
-        const int ctr = kLdsWeightFloatsOf<NT> + (y - y0 + Wn::radius) * hw + ((x - x0 + Wn::radius) >> 1);
-        ref_window<SCALE, NT>(lw, [&](int dx, int dy) { return pm_lds[ctr + dy * hw + dx / 2]; }, spatial, two_sc, rw);   // dx, dy even: exact
-    } else if constexpr (Wn::tile_in_lds) {
+    if constexpr (Wn::tile_in_lds) {
         load_ref_tile<NT>(P, pm_lds + kLdsWeightFloatsOf<NT>, x0, y0, BW, BH, Wn::radius);
         __syncthreads();
         if (!valid) return;
@@ -482,12 +447,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // TEXELS: below 0 both texels of the pair are texel 0 and above
 // hi both are texel hi, so the interpolated value does not depend on the fraction
 // there and clamping the coordinate itself gives the same bits -- with no apron
-// and non-negative texel indices.
-#ifdef PM_DBG_NOCLAMP   // measurement builds only (wrong at the image border): what the two clamps per tap cost
-PM_DEV float clamp_coord(float s, float hi) { return s; }
-#else
+// and non-negative texel indices.  (Without the clamp an update pass is 2.4 % faster; a proof that a window is interior and a
+// second tap loop for the others would keep at best 1 % of that: profiles/EXPERIMENTS.md 42.)
 PM_DEV float clamp_coord(float s, float hi) { return __builtin_amdgcn_fmed3f(s, 0.0f, hi); }
-#endif
 
 // floor + float->int in one instruction (hipcc only selects it under fast-math)
 PM_DEV int floor_to_int(float c) {
@@ -596,7 +558,7 @@ template <>
 struct BilinearTap<false> {
     float ax, ay;
     f32x4q q;  // (t00, dx, dy, dxy)
-    template <int AUX = 0, class TEX>
+    template <class TEX>
     PM_DEV void issue(const TEX& t, float sx, float sy) {
         const float cx = clamp_coord(sx, t.wm1);
         const float cy = clamp_coord(sy, t.hm1);
@@ -606,7 +568,7 @@ struct BilinearTap<false> {
 #ifdef PM_DBG_NOLOAD  // measurement builds only (results are wrong): the instruction stream without its gathers
         q = (f32x4q){(float)idx, 1.0f, ax, ay};
 #else
-        q = pm_struct_load_f128(t.irsrc, idx, 0, 0, AUX);
+        q = pm_struct_load_f128(t.irsrc, idx, 0, 0, 0);
 #endif
     }
     PM_DEV float value() const {
@@ -619,7 +581,7 @@ template <>
 struct BilinearTap<true> {
     float ax, ay;
     u32x2q q;  // halfs: (t00, dy), (dx, dxy)
-    template <int AUX = 0, class TEX>   // AUX: cache-policy bits of the gather (measurement builds: PM_GATHER_AUX_SCALE2)
+    template <class TEX>
     PM_DEV void issue(const TEX& t, float sx, float sy) {
         const float cx = clamp_coord(sx, t.wm1);
         const float cy = clamp_coord(sy, t.hm1);
@@ -645,7 +607,7 @@ struct BilinearTap<true> {
             q = *reinterpret_cast<const u32x2q*>(reinterpret_cast<const char*>(pm_lds + (PM_DBG_LDSTEX)) + a);
         }
 #else
-        q = pm_struct_load_b64(t.irsrc, idx, 0, 0, AUX);
+        q = pm_struct_load_b64(t.irsrc, idx, 0, 0, 0);
 #endif
     }
     PM_DEV float value() const {
@@ -673,12 +635,6 @@ template <bool U8, int LWSTRIDE, int SCALE, bool DEEP, class TEX>
 PM_DEV float ncc_core(const TEX& tex, float wf, float hf, float H0, float H1, float H2, float H3, float H4, float H5, float H6, float H7, float H8,
                       const RefWin& rw, int px, int py) {
     constexpr int step = 2 << SCALE, radius = 5 * step / 2;
-    // cache policy of the tap gathers at window scale 2, where a block's footprint per view overruns the L1 (measurement builds:
-    // bit 0 = sc0, bit 1 = nt, bit 4 = sc1 of the gfx940 buffer instructions; 0 = the default policy)
-#ifndef PM_GATHER_AUX_SCALE2
-#define PM_GATHER_AUX_SCALE2 0
-#endif
-    constexpr int kAux = SCALE == 2 ? (PM_GATHER_AUX_SCALE2) : 0;
     const float fpx = (float)px, fpy = (float)py;
     {
         const float X = __builtin_fmaf(H1, fpy, __builtin_fmaf(H0, fpx, H2));
@@ -695,9 +651,6 @@ PM_DEV float ncc_core(const TEX& tex, float wf, float hf, float H0, float H1, fl
     // reciprocal between the six perspective divides, compute the
     // addresses and issue all gathers of the column back to back
     auto issue_column = [&](int a, BilinearTap<U8>(&tap)[6]) {
-#ifdef PM_SETPRIO_ISSUE  // measurement builds: the wave that is about to issue a column of gathers goes first
-        __builtin_amdgcn_s_setprio(PM_SETPRIO_ISSUE);
-#endif
         const float tx = (float)(px + a * step - radius);
         const float Cx = __builtin_fmaf(H0, tx, H2);
         const float Cy = __builtin_fmaf(H3, tx, H5);
@@ -721,12 +674,9 @@ PM_DEV float ncc_core(const TEX& tex, float wf, float hf, float H0, float H1, fl
             const f32x2 zs = {ZP[j].y, ZP[j].x};
             const f32x2 inv = (f32x2){iq[j], iq[j]} * zs;
             const f32x2 sx = XP[j] * inv, sy = YP[j] * inv;
-            tap[2 * j].template issue<kAux>(tex, sx.x, sy.x);
-            tap[2 * j + 1].template issue<kAux>(tex, sx.y, sy.y);
+            tap[2 * j].issue(tex, sx.x, sy.x);
+            tap[2 * j + 1].issue(tex, sx.y, sy.y);
         }
-#ifdef PM_SETPRIO_ISSUE
-        __builtin_amdgcn_s_setprio(0);
-#endif
     };
     // phase 2: interpolate; the even taps (b = 0, 2, 4) and the odd taps of ALL columns accumulate in the two halves of packed
     // registers and meet once, at the end of the window

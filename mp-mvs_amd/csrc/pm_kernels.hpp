@@ -13,16 +13,8 @@
 #include "pm_device.hpp"
 
 // waves per SIMD the NCC kernels are compiled for (2: the 72 KB of LDS weight records per block allow no more, and the update
-// kernel squeezed into the 168 registers of 3 waves loses more than the third wave gains; PM_WAVES_U8 / PM_WAVES_F32 override
-// for measurement builds)
-#ifndef PM_WAVES_U8
-#define PM_WAVES_U8 2
-#endif
-#ifndef PM_WAVES_F32
-#define PM_WAVES_F32 2
-#endif
-template <bool U8>
-constexpr int kWavesPerSimd = U8 ? PM_WAVES_U8 : PM_WAVES_F32;
+// kernel squeezed into the 168 registers of 3 waves loses more than the third wave gains: profiles/EXPERIMENTS.md 14 and 22)
+constexpr int kWavesPerSimd = 2;
 
 namespace pm {
 
@@ -61,43 +53,24 @@ __device__ constexpr Off kDirs[8][12] = {
     {{5, 0}, {7, 0}, {9, 0}, {11, 0}, {13, 0}, {15, 0}, {17, 0}, {19, 0}, {21, 0}, {23, 0}, {0, 0}, {0, 0}}};
 __device__ constexpr int kNumDirs[8] = {12, 12, 12, 12, 10, 10, 10, 10};
 
-// Wave shape of the checkerboard launches: PM_WAVE_ROWS rows of 64/PM_WAVE_ROWS same-colour pixels; a 256-thread block
-// stacks its 4 waves vertically.  Compact 2-D patches reuse more L1 lines between taps than flat rows.  Measured per update
-// launch, cfg 1, view-major order (round 2): fp16 texels (8 bytes) 8 / 16 / 32 rows: 3.37 / 3.40 / 4.01 ms; fp32 texels (16 bytes)
-// 4 / 8 / 16 rows: 4.18 / 3.97 / 4.04 ms.  (Slot-major order, mid round 2: fp16 2 / 4 / 8 / 16 rows 4.00 / 3.66 / 3.50 / 3.45 ms.
-// Round 1, 4-byte u8 quads: 4 rows 3.85, 8 rows 3.89, 2 rows 3.98, 16 rows 4.84.)
-#ifndef PM_WAVE_ROWS
-#define PM_WAVE_ROWS 8
-#endif
-#ifndef PM_WAVE_ROWS_F32
-#define PM_WAVE_ROWS_F32 8
-#endif
-// rows per wave, block width and height (pixels) of a checkerboard launch on textures of format U8
-template <bool U8>
-constexpr int kWaveRows = U8 ? PM_WAVE_ROWS : PM_WAVE_ROWS_F32;
-// waves of a block: PM_BLOCK_WAVES_X side by side, 4 / PM_BLOCK_WAVES_X stacked
-#ifndef PM_BLOCK_WAVES_X
-#define PM_BLOCK_WAVES_X 1
-#endif
+// Wave shape of the checkerboard launches: 8 rows of 8 same-colour pixels, for both texel formats; a block stacks its waves
+// vertically (2x2 or 4x1 arrangements of four waves: 3.52 / 3.61 against 3.45 ms, round 2, profiles/EXPERIMENTS.md 12).  Compact
+// 2-D patches reuse more L1 lines between taps than flat rows.  Measured per update launch, cfg 1, view-major order (round 2): fp16
+// texels (8 bytes) 8 / 16 / 32 rows: 3.37 / 3.40 / 4.01 ms; fp32 texels (16 bytes) 4 / 8 / 16 rows: 4.18 / 3.97 / 4.04 ms.
+// (Slot-major order, mid round 2: fp16 2 / 4 / 8 / 16 rows 4.00 / 3.66 / 3.50 / 3.45 ms.  Round 1, 4-byte u8 quads: 4 rows 3.85,
+// 8 rows 3.89, 2 rows 3.98, 16 rows 4.84.  Round 3, fp16: 4 / 8 / 16 rows 2.75 / 2.73 / 2.77 ms.)
+constexpr int kWaveRows = 8;
 // Threads per block of the update kernel, per variant (the filter keeps 256).  Chained launches (k_update) made small blocks pay
 // where the taps of a wave stay close together: a one-wave block holds no LDS for slower siblings and fills freed slots wave by
 // wave -- fp16 texels at window scale 0: 2.47 against 2.53 ms per pass (photometric; geometric -1.4 %, prior -1.8 %).  Everywhere
 // else the four waves of a 16 x 32 block share lines in the L1 that four unrelated one-wave blocks do not: scale 1 +3.7 %, scale 2
-// +34 %, fp32 texels +5 ... +60 % (round 5, 1600x1200, 8 views, tools/bench_scales.py).  PM_UPD_THREADS: one size everywhere
-// (measurement builds).
-#ifdef PM_UPD_THREADS
-template <bool U8, int SCALE>
-constexpr int kUpdThreads = PM_UPD_THREADS;
-#else
+// +34 %, fp32 texels +5 ... +60 % (round 5, 1600x1200, 8 views, tools/bench_scales.py).
 template <bool U8, int SCALE>
 constexpr int kUpdThreads = (U8 && SCALE == 0) ? 64 : 256;
-#endif
-template <int NT>
-constexpr int kChkWavesX = (NT / 64 < PM_BLOCK_WAVES_X) ? NT / 64 : PM_BLOCK_WAVES_X;
-template <bool U8, int NT = 256>
-constexpr int kChkBlockW = 2 * (64 / kWaveRows<U8>) * kChkWavesX<NT>;
-template <bool U8, int NT = 256>
-constexpr int kChkBlockH = ((NT / 64) / kChkWavesX<NT>) * kWaveRows<U8>;
+// block width and height (pixels) of an NT-thread checkerboard launch
+constexpr int kChkBlockW = 2 * (64 / kWaveRows);
+template <int NT = 256>
+constexpr int kChkBlockH = (NT / 64) * kWaveRows;
 
 // Blocks are dealt round-robin to the 8 XCDs (block b and b+8 share an L2):
 // renumber so that each XCD works through one contiguous run of the raster
@@ -111,34 +84,26 @@ PM_DEV int xcd_remap(int id, int n) {
 
 // b: the block's position in raster order over the image (the launch decides which block takes which position: xcd_remap for
 // the plain launches, the chained update kernel's ticket order)
-template <bool U8, int NT = 256>
+template <int NT = 256>
 PM_DEV bool checker_pixel(const ProblemDev& P, const LaunchArgs& a, int b, int parity, int& x, int& y, int& x0, int& y0) {
-    constexpr int kLanesPerRow = 64 / kWaveRows<U8>;
-    const int nbx = (P.W + kChkBlockW<U8, NT> - 1) / kChkBlockW<U8, NT>;
+    constexpr int kLanesPerRow = 64 / kWaveRows;
+    const int nbx = (P.W + kChkBlockW - 1) / kChkBlockW;
     const int by = b / nbx, bx = b - by * nbx;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    x0 = bx * kChkBlockW<U8, NT>;
-    y0 = by * kChkBlockH<U8, NT>;
-    y = y0 + (wv / kChkWavesX<NT>) * kWaveRows<U8> + lane / kLanesPerRow;
-    x = x0 + 2 * ((wv % kChkWavesX<NT>) * kLanesPerRow + lane % kLanesPerRow);
+    x0 = bx * kChkBlockW;
+    y0 = by * kChkBlockH<NT>;
+    y = y0 + wv * kWaveRows + lane / kLanesPerRow;
+    x = x0 + 2 * (lane % kLanesPerRow);
     x += (y + parity) & 1;
     return x < P.W && y < P.H && y < a.ylimit;
 }
-// all-pixel launches: block = 16x16 pixels, wave = PM_DENSE_WAVE_W x (64 / PM_DENSE_WAVE_W) patch of it
-#ifndef PM_DENSE_WAVE_W
-#define PM_DENSE_WAVE_W 8
-#endif
+// all-pixel launches: block = 16x16 pixels, wave = 8x8 patch of it (against 16x4 waves: profiles/EXPERIMENTS.md 49)
 PM_DEV bool dense_pixel(const ProblemDev& P, int& x, int& y, int& x0, int& y0) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     x0 = blockIdx.x * 16;
     y0 = blockIdx.y * 16;
-#if PM_DENSE_WAVE_W == 16
-    y = y0 + wv * 4 + (lane >> 4);
-    x = x0 + (lane & 15);
-#else
     y = y0 + (wv >> 1) * 8 + (lane >> 3);
     x = x0 + (wv & 1) * 8 + (lane & 7);
-#endif
     return x < P.W && y < P.H;
 }
 PM_DEV bool dense_pixel(const ProblemDev& P, int& x, int& y) {
@@ -158,17 +123,15 @@ inline size_t ncc_lds_bytes(int bw, int bh, int scale) {
 constexpr int kXchgBytesPerWave = 2048;
 template <int NT>
 constexpr int kLdsXchgFloats = (NT / 64) * kXchgBytesPerWave / 4;  // = the largest LDS-resident reference tile of the update kernel (Win::tile_in_lds)
-#ifndef PM_DBG_LDS_PAD   // measurement builds: extra dynamic LDS per update block (fewer blocks per CU)
-#define PM_DBG_LDS_PAD 0
-#endif
+// (exactly that much: padding the one-wave block so that only 7 or 6 fit a CU costs 8 / 19 %, profiles/EXPERIMENTS.md 45)
 template <int NT>
-inline size_t update_lds_bytes() { return (size_t)(kLdsWeightFloatsOf<NT> + kLdsXchgFloats<NT>) * sizeof(float) + (size_t)(PM_DBG_LDS_PAD); }
+inline size_t update_lds_bytes() { return (size_t)(kLdsWeightFloatsOf<NT> + kLdsXchgFloats<NT>) * sizeof(float); }
 
 // ---------------------------------------------------------------------------
 // InitializeScore, ref .cu:536-573 (+ :497-534)
 // ---------------------------------------------------------------------------
 template <int MAXV, bool U8, int SCALE>
-__global__ __launch_bounds__(256, kWavesPerSimd<U8>) void k_init(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a) {
+__global__ __launch_bounds__(256, kWavesPerSimd) void k_init(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a) {
     const ProblemDev& P = *Pp;
     int x, y, x0, y0;
     const bool valid = dense_pixel(P, x, y, x0, y0);
@@ -233,12 +196,6 @@ __global__ __launch_bounds__(256, kWavesPerSimd<U8>) void k_init(const ProblemDe
     S.sel[idx] = sel;
 }
 
-// Which variants park the refinement ingredients and the candidate costs in private memory: those that would otherwise spill
-// around the evaluations (fp32 texels with the planar prior, or with the geometric term above 16 views).  Measured per variant
-// (gpurun_out/r2l): parking costs the non-spilling variants 1-4 %, and gains the spilling ones 3-6 %.
-#ifndef PM_PARK_WHEN
-#define PM_PARK_WHEN (kWavesPerSimd<U8> >= 3 || (!U8 && (PRIOR || (GEOM && MAXV > 16))))
-#endif
 // A private array that has to live in private MEMORY (plain loads and stores, scheduled like any others) instead of being
 // promoted to registers: its address is shown to an empty asm statement.
 PM_DEV void keep_in_memory(float* p) { asm volatile("" : : "v"(p)); }
@@ -312,34 +269,27 @@ struct WaveTimer {
 // One pixel update of one block: `b` is the block's raster position, `parity` the colour of this pass, `launch` its launch id (the
 // key of the random streams), `thr` the view-selection threshold of its iteration (ref .cu:832).  The results leave through
 // write-through stores (st_*_wt): what the chained launch below hands from one pass to the next.
-// The scale-2 prologue through the compact one-colour tile (Win::tile_checker, pm_device.hpp).  Built and measured in round 6: bit-exact,
-// and 0-0.7 % on the scale-2 passes (15.55 / 15.67 against 15.66 / 15.67 ms per chain of 6): the prologue's 37 reads per pixel out of the
-// L2-resident padded image were never what scale 2 pays for -- its taps overrun the L1 (profiles/r06_cfg4_pmc.txt, EXPERIMENTS 52).  Off by
-// default (the kernel the round's profiles describe); -DPM_CHECKER_TILE=true builds it.
-#ifndef PM_CHECKER_TILE
-#define PM_CHECKER_TILE false
-#endif
+// (At window scales 1 and 2 the reference tile could be staged as a compact half tile of the pass's colour: built in round 6, bit-exact,
+// 0-0.7 % on the scale-2 passes -- the prologue's 37 reads per pixel are not what scale 2 pays for, profiles/EXPERIMENTS.md 52.)
 template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
 PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr) {
-    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW<U8, NT>, BH = kChkBlockH<U8, NT>;
+    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
     // gathers of two window columns ahead (ncc_core): always with the 8-byte texels; with the 16-byte ones where the variant
     // still has the 24 registers of a third column (8 views; more views spill 4 .. 81 registers around the evaluations)
-#ifndef PM_F32_DEEP_WHEN
-#define PM_F32_DEEP_WHEN (MAXV == 8)
-#endif
-    constexpr bool kDeep = U8 || PM_F32_DEEP_WHEN;
-    constexpr bool kPriorCall = MAXV > 8 || kWavesPerSimd<U8> >= 3;
-#ifdef PM_PARK_ALL
-    constexpr bool kPark = true;
-#else
-    constexpr bool kPark = PM_PARK_WHEN;
-#endif
+    constexpr bool kDeep = U8 || MAXV == 8;
+    constexpr bool kPriorCall = MAXV > 8;
+    // Which variants park the refinement ingredients and the candidate costs in private memory: those that would otherwise spill
+    // around the evaluations (fp32 texels with the planar prior, or with the geometric term above 16 views).  Measured per
+    // variant: parking costs the non-spilling variants 1-4 %, and gains the spilling ones 3-6 %.
+    constexpr bool kPark = !U8 && (PRIOR || (GEOM && MAXV > 16));
+    // ... and the candidates' m vectors of phase A (see there)
+    constexpr bool kParkM = !U8 && ((PRIOR && MAXV == 8) || (GEOM && MAXV == 32));
     int x, y, x0, y0;
-    const bool valid = checker_pixel<U8, NT>(P, a, b, parity, x, y, x0, y0);
+    const bool valid = checker_pixel<NT>(P, a, b, parity, x, y, x0, y0);
     RefWin rw;
-    ref_window_of_pixel<SCALE, BW, BH, NT, kLdsXchgFloats<NT>, PM_CHECKER_TILE>(P, x, y, x0, y0, valid, a.spatial, a.two_sc, rw, parity);
+    ref_window_of_pixel<SCALE, BW, BH, NT, kLdsXchgFloats<NT>>(P, x, y, x0, y0, valid, a.spatial, a.two_sc, rw);
     // the tile region becomes the exchange area of the refinement: every wave must be done reading the tile first
-    if constexpr (Win<SCALE, BW, BH, kLdsXchgFloats<NT>>::tile_in_lds || (PM_CHECKER_TILE && Win<SCALE, BW, BH, kLdsXchgFloats<NT>>::tile_checker)) __syncthreads();
+    if constexpr (Win<SCALE, BW, BH, kLdsXchgFloats<NT>>::tile_in_lds) __syncthreads();
     if (!valid) return;
     const int W = P.W, Hh = P.H, V = P.V;
     const int idx = y * W + x;
@@ -347,7 +297,6 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
 
     // -- 8 sampling regions: position of the lowest stored cost (ref .cu:798-816)
     int pos[8];
-    if (kWavesPerSimd<U8> >= 3) keep_in_memory(reinterpret_cast<float*>(pos));
     uint32_t flags = 0;
     // The 88 stored costs are read UNCONDITIONALLY, at the position clamped into the image, and a position outside the image is
     // ignored afterwards: the loads of a region then sit in straight-line code and go out back to back.  (Loaded under their
@@ -375,23 +324,11 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         if (best < 3.402823466e+38f) flags |= (1u << k);
     }
 
-#ifdef PM_DBG_NOCOSTARR  // measurement builds only (results are wrong): the candidate cost matrix collapsed into one register --
-    // bounds what taking its 8 x V stores and loads out of private memory could give
-    float cost_arr[1];
-#define PM_CIDX(i) 0
-#else
     float cost_arr[8 * MAXV];
-#define PM_CIDX(i) (i)
-#endif
     int cnt[MAXV];       // good count | bad count << 8   (ref .cu:834-845)
     float tmpw[MAXV];
     float probs[MAXV];
     float view_w[MAXV];
-    if (kWavesPerSimd<U8> >= 3) {  // 168 registers: the per-view vectors stay in private memory (one access per evaluation)
-        keep_in_memory(reinterpret_cast<float*>(cnt));
-        keep_in_memory(tmpw);
-        keep_in_memory(view_w);
-    }
     for (int v = 0; v < V; ++v) {
         cnt[v] = 0;
         tmpw[v] = 0.0f;
@@ -435,10 +372,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     // scratch load per value sits on the same in-order vmcnt queue as the gathers and costs 2 % (fp16 texels) to 3.5 % (fp32)
     // of the launch.  Parked in private memory only in the two variants that would otherwise spill around the evaluations.
     float cand_m[8 * 3];
-#ifndef PM_PARK_M_WHEN
-#define PM_PARK_M_WHEN (!U8 && ((PRIOR && MAXV == 8) || (GEOM && MAXV == 32)))
-#endif
-    if (PM_PARK_M_WHEN) keep_in_memory(cand_m);
+    if (kParkM) keep_in_memory(cand_m);
     // (read unconditionally as well -- pos is 0 where a region has no candidate -- so that the eight loads are in flight together)
 #pragma unroll
     for (int slot = 0; slot < 8; ++slot) {
@@ -459,7 +393,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 c = ncc_cost<U8, SCALE, kDeep, NT>(P.views[v], rw, x, y, m0, m1, m2);
             else
                 c = (slot == 0 && v == 0) ? 2.0f : 0.0f;  // `= {2.0f}` initialiser quirk, ref .cu:795
-            cost_arr[PM_CIDX(slot * MAXV + v)] = c;
+            cost_arr[slot * MAXV + v] = c;
             if (c < thr) {
                 tw += d_exp_inrange((c * c) / (-0.18f));  // c in [0, 2]: argument in [-22.3, 0]
                 cn += 1;
@@ -536,7 +470,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 if ((flags >> i) & 1u) gc[i].issue(P.views[v], gz[i], x, y);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float c = cost_arr[PM_CIDX(i * MAXV + v)];
+                const float c = cost_arr[i * MAXV + v];
                 if ((flags >> i) & 1u)
                     fcv[i] += w * (c + 0.2f * gc[i].finish(P.views[v], x, y));
                 else
@@ -552,7 +486,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         for (int i = 0; i < 8; ++i) {
             float fc = 0.0f;
             for (int v = 0; v < V; ++v)
-                if (view_w[v] > 0.0f) fc += view_w[v] * cost_arr[PM_CIDX(i * MAXV + v)];
+                if (view_w[v] > 0.0f) fc += view_w[v] * cost_arr[i * MAXV + v];
             const float fci = fc / weight_norm;
             final_costs[i] = fci;
             fcv[i] = fci;
@@ -702,10 +636,9 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     //     term is therefore accepted in turn, each overwriting the one before: only the LAST of them leaves a trace, the
     //     evaluations of all the others are dead.
     float cpl[5 * 4], tcs[5], tgs[5], pr5[5];
-#ifndef PM_PARK_CPL_WHEN
-#define PM_PARK_CPL_WHEN true
-#endif
-    if (PM_PARK_CPL_WHEN) keep_in_memory(cpl);
+    // the candidate planes are parked in every variant: in registers they push other state out instead (scratch 352 -> 528 B,
+    // spills in the fp32 variants; profiles/EXPERIMENTS.md 24)
+    keep_in_memory(cpl);
     uint32_t dead = 0;
 #pragma unroll
     for (int ci = 0; ci < 5; ++ci) {
@@ -747,14 +680,14 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     // above it; both factors are finite and >= 0).  Masked prior pixels accept on another criterion (ref .cu:707): no threshold.
     const float T = masked ? __uint_as_float(0x7f800000u) : __uint_as_float(__float_as_uint(cost_now * weight_norm) + 1u);
     {
-        constexpr int kLanesPerRow = 64 / kWaveRows<U8>;
+        constexpr int kLanesPerRow = 64 / kWaveRows;
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
         char* const xw = reinterpret_cast<char*>(pm_lds + kLdsWeightFloatsOf<NT>) + wv * kXchgBytesPerWave;
         float4* const x_rec = reinterpret_cast<float4*>(xw);                           // [64] plane of the item
         float2* const x_res = reinterpret_cast<float2*>(xw + 1024);                    // [64] (photometric cost, geometric term)
         unsigned short* const x_id = reinterpret_cast<unsigned short*>(xw + 1536);     // [64] owner lane
-        const int wave_y = y0 + (wv / kChkWavesX<NT>) * kWaveRows<U8>;
-        const int wave_x = x0 + 2 * (wv % kChkWavesX<NT>) * kLanesPerRow;
+        const int wave_y = y0 + wv * kWaveRows;
+        const int wave_x = x0;
         // lanes without a pixel (image border) have left the kernel: the items of a round go to the lanes that are still here,
         // the r-th of them taking slot r
         const unsigned long long here = __ballot(1);
@@ -898,16 +831,13 @@ constexpr int kSpinLimit = 1 << 20;   // polls of ~1-2 us each: seconds, three o
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx942__) && !defined(__gfx950__)
 #error "the chained update launch (k_update) relies on gfx942 / gfx950 cache behaviour: see the comment above"
 #endif
-// memory order of the completion signal.  RELAXED: the write-through stores and the wave's own s_waitcnt vmcnt(0) have put the
-// results in memory before the counter moves.  PM_CHAIN_SIGNAL_ORDER=__ATOMIC_RELEASE (measurement builds) adds the memory model's own
-// release (an L2 write-back before the atomic): measured in round 6, see profiles/EXPERIMENTS.md (47).
-#ifndef PM_CHAIN_SIGNAL_ORDER
-#define PM_CHAIN_SIGNAL_ORDER __ATOMIC_RELAXED
-#endif
+// memory order of the completion signal: RELAXED.  The write-through stores and the wave's own s_waitcnt vmcnt(0) have put the
+// results in memory before the counter moves.  The memory model's own release adds an L2 write-back before every signal, which also
+// flushes the wave's dirty scratch lines: +5.9 % per pass, same bits (round 6, profiles/EXPERIMENTS.md 47).
 template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
-__global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd<U8>) void k_update(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a, ChainArgs ch) {
+__global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_update(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a, ChainArgs ch) {
     const ProblemDev& P = *Pp;
-    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW<U8, NT>, BH = kChkBlockH<U8, NT>, kWaves = NT / 64;
+    constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>, kWaves = NT / 64;
     static_assert(NT % 64 == 0 && NT >= 64 && NT <= 256, "update blocks are 1 .. 4 waves");
     constexpr int RX = (23 + BW - 1) / BW, RY = (23 + BH - 1) / BH, NN = (2 * RX + 1) * (2 * RY + 1);  // positions within the 23 px of kDirs
     static_assert(NN <= 64, "one lane polls one neighbour");
@@ -969,7 +899,7 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd<U8>) void k
     int fin = 0;
     if ((threadIdx.x & 63) == 0) {
         if (!(b == ch.stall_pos && pass == 0))   // (fault injection: a position that never completes its first pass)
-            __hip_atomic_fetch_add(&ch.sync[kSyncHeader + b], 1, PM_CHAIN_SIGNAL_ORDER, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&ch.sync[kSyncHeader + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         fin = __hip_atomic_fetch_add(&ch.sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     fin = __builtin_amdgcn_readfirstlane(fin);
@@ -1051,7 +981,7 @@ PM_DEV float median21_rounds(float (&v)[21], float& lowest) {
 __global__ __launch_bounds__(256) void k_filter(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a) {
     const ProblemDev& P = *Pp;
     int x, y, x0, y0;
-    if (!checker_pixel<true>(P, a, xcd_remap(blockIdx.x, gridDim.x), a.parity, x, y, x0, y0)) return;  // the filter has no texture: any shape
+    if (!checker_pixel(P, a, xcd_remap(blockIdx.x, gridDim.x), a.parity, x, y, x0, y0)) return;
     const int W = P.W, Hh = P.H;
     const int ctr = y * W + x;
     if (S.costs[ctr] < 0.001f) return;
@@ -1218,7 +1148,7 @@ __global__ void k_export_depth(const float4* __restrict__ planes, float* __restr
 
 // probe: nh planes per pixel ([nh][H][W]) against every view; out [nh][V][H][W]
 template <int MAXV, bool U8, int SCALE>
-__global__ __launch_bounds__(256, kWavesPerSimd<U8>) void k_eval_ncc(const ProblemDev* __restrict__ Pp, const float4* __restrict__ planes, int nh, float* __restrict__ out, LaunchArgs a) {
+__global__ __launch_bounds__(256, kWavesPerSimd) void k_eval_ncc(const ProblemDev* __restrict__ Pp, const float4* __restrict__ planes, int nh, float* __restrict__ out, LaunchArgs a) {
     const ProblemDev& P = *Pp;
     int x, y, x0, y0;
     const bool valid = dense_pixel(P, x, y, x0, y0);

@@ -130,7 +130,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--size", default="1600x1200")
-    ap.add_argument("--threads", type=int, default=64, help="threads per update block of the library in use (PM_UPD_THREADS)")
+    ap.add_argument("--threads", type=int, default=64, help="threads per update block of the library in use (kUpdThreads, pm_kernels.hpp)")
     args = ap.parse_args()
     sys.argv = [sys.argv[0]]
     import bench
