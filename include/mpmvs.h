@@ -284,6 +284,21 @@ int mpmvs_sky_bilateral(int device, const unsigned char* bgr, const float* mask,
 /* device time (ms, HIP events) of the kernel of the last mpmvs_sky_bilateral call */
 float mpmvs_sky_kernel_ms(void);
 
+/* ---- view selection of a COLMAP sparse model (tools/colmap2mvs.py) ------------ */
+/* The pair scores and per-image view lists of the reference's colmap2mvsnet_acm.py (calc_score, then the reversed
+ * argsort of each score row), restated point-major (csrc/pm_viewsel.hpp, contract in DESIGN.md section 11).
+ * centers: n_images x 3 camera centres (float64), xyz: n_points x 3, obs_off: n_images + 1 offsets into obs_pt, which holds
+ * every image's point3D_ids in file order as dense point indices (-1: none).  out_ids / out_scores (n_images x num_view,
+ * num_view <= n_images) receive each row by score descending, then index descending.  shared / small (n_images x n_images,
+ * either may be NULL; for tests) receive the counts of each pair i < j in [i][j], zero below the diagonal.  Host buffers.
+ * Returns 0, -1 (bad arguments; checked before the device is touched), -2 (n_images above MPMVS_VIEW_SELECT_MAX_IMAGES)
+ * or -100 (HIP failure). */
+#define MPMVS_VIEW_SELECT_MAX_IMAGES 32768
+int mpmvs_view_select(int device, int n_images, const double* centers, int n_points, const double* xyz, const int64_t* obs_off,
+                      const int32_t* obs_pt, int num_view, int32_t* out_ids, int32_t* out_scores, uint32_t* shared, uint32_t* small);
+/* device time (ms, HIP events) of the kernels of the last mpmvs_view_select call */
+float mpmvs_view_select_kernel_ms(void);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

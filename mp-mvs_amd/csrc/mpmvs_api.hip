@@ -38,6 +38,7 @@
 #include "pm_sky.hpp"
 #include "pm_kernels.hpp"
 #include "pm_prior.hpp"
+#include "pm_viewsel.hpp"
 
 using namespace pm;
 
@@ -2162,6 +2163,107 @@ int mpmvs_sky_bilateral(int device, const unsigned char* bgr, const float* mask,
     (void)pool_free(d_img);
     (void)pool_free(d_mask);
     (void)pool_free(d_out);
+    (void)hipStreamDestroy(st);
+    return rc;
+}
+
+static float g_viewsel_kernel_ms = 0.0f;
+float mpmvs_view_select_kernel_ms(void) { return g_viewsel_kernel_ms; }
+
+// view selection of a COLMAP model (pm_viewsel.hpp); host buffers in and out.  Every index the kernels follow is checked
+// here first: obs_off ascends from 0, obs_pt lies in [-1, n_points), and the track slots fit an int.
+int mpmvs_view_select(int device, int n_images, const double* centers, int n_points, const double* xyz, const int64_t* obs_off,
+                      const int32_t* obs_pt, int num_view, int32_t* out_ids, int32_t* out_scores, uint32_t* shared, uint32_t* small) {
+    if (n_images <= 0 || n_points < 0 || num_view < 0 || num_view > n_images || !centers || !obs_off || !out_ids || !out_scores ||
+        (n_points > 0 && !xyz))
+        return -1;
+    if (n_images > kVsMaxImages) return -2;
+    if (obs_off[0] != 0) return -1;
+    for (int i = 0; i < n_images; ++i)
+        if (obs_off[i + 1] < obs_off[i]) return -1;
+    const int64_t n_obs = obs_off[n_images];
+    if (n_obs > 0 && !obs_pt) return -1;
+    int64_t n_slots = 0;
+    for (int64_t k = 0; k < n_obs; ++k) {
+        if (obs_pt[k] < -1 || obs_pt[k] >= n_points) return -1;
+        n_slots += obs_pt[k] >= 0;
+    }
+    if (n_obs > INT32_MAX || n_slots > INT32_MAX - 256) return -1;
+    if (enter_device(device) != hipSuccess) return -100;
+
+    const size_t n = (size_t)n_images, nn = n * n;
+    const int ntiles = (n_points + kVsScanTile - 1) / kVsScanTile;
+    const int ns = (int)n_slots;
+    double *d_centers = nullptr, *d_xyz = nullptr;
+    int64_t* d_obs_off = nullptr;
+    int32_t *d_obs_pt = nullptr, *d_ids = nullptr, *d_scores = nullptr;
+    int *d_cnt = nullptr, *d_off = nullptr, *d_tsum = nullptr, *d_fill = nullptr, *d_trk_img = nullptr, *d_trk_pt = nullptr, *d_trk_mult = nullptr;
+    unsigned long long* d_acc = nullptr;
+    unsigned* d_score = nullptr;
+    hipStream_t st = nullptr;  // own stream: other contexts of this device keep running
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
+    int rc = 0;
+    // zero-sized arrays still get a (4-byte) buffer, so that no kernel argument is null
+    auto bytes = [](size_t b) { return b ? b : (size_t)4; };
+    if (pool_malloc(&d_centers, n * 24) != hipSuccess || pool_malloc(&d_xyz, bytes((size_t)n_points * 24)) != hipSuccess ||
+        pool_malloc(&d_obs_off, (n + 1) * 8) != hipSuccess || pool_malloc(&d_obs_pt, bytes((size_t)n_obs * 4)) != hipSuccess ||
+        pool_malloc(&d_cnt, bytes((size_t)n_points * 4)) != hipSuccess || pool_malloc(&d_off, ((size_t)n_points + 1) * 4) != hipSuccess ||
+        pool_malloc(&d_tsum, bytes((size_t)ntiles * 4)) != hipSuccess || pool_malloc(&d_fill, bytes((size_t)n_points * 4)) != hipSuccess ||
+        pool_malloc(&d_trk_img, bytes((size_t)ns * 4)) != hipSuccess || pool_malloc(&d_trk_pt, bytes((size_t)ns * 4)) != hipSuccess ||
+        pool_malloc(&d_trk_mult, bytes((size_t)ns * 4)) != hipSuccess || pool_malloc(&d_acc, nn * 8) != hipSuccess ||
+        pool_malloc(&d_score, nn * 4) != hipSuccess || pool_malloc(&d_ids, bytes(n * num_view * 4)) != hipSuccess ||
+        pool_malloc(&d_scores, bytes(n * num_view * 4)) != hipSuccess)
+        rc = -100;
+    if (!rc && (hipMemcpyAsync(d_centers, centers, n * 24, hipMemcpyHostToDevice, st) != hipSuccess ||
+                (n_points > 0 && hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 24, hipMemcpyHostToDevice, st) != hipSuccess) ||
+                hipMemcpyAsync(d_obs_off, obs_off, (n + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+                (n_obs > 0 && hipMemcpyAsync(d_obs_pt, obs_pt, (size_t)n_obs * 4, hipMemcpyHostToDevice, st) != hipSuccess) ||
+                hipMemsetAsync(d_cnt, 0, bytes((size_t)n_points * 4), st) != hipSuccess ||
+                hipMemsetAsync(d_off, 0, ((size_t)n_points + 1) * 4, st) != hipSuccess ||
+                hipMemsetAsync(d_fill, 0, bytes((size_t)n_points * 4), st) != hipSuccess || hipMemsetAsync(d_acc, 0, nn * 8, st) != hipSuccess))
+        rc = -100;
+    if (!rc) {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        (void)hipEventCreate(&ev0);
+        (void)hipEventCreate(&ev1);
+        (void)hipEventRecord(ev0, st);
+        if (n_slots > 0) {
+            hipLaunchKernelGGL(k_vs_count, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_cnt);
+            hipLaunchKernelGGL(k_vs_scan_tiles, dim3(ntiles), dim3(kVsScanTile), 0, st, d_cnt, n_points, d_off, d_tsum);
+            hipLaunchKernelGGL(k_vs_scan_sums, dim3(1), dim3(kVsScanTile), 0, st, d_tsum, ntiles, d_off, n_points);
+            hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kVsScanTile), 0, st, d_off, n_points, d_tsum);
+            hipLaunchKernelGGL(k_vs_scatter, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_off, d_fill, d_trk_img, d_trk_pt);
+            const dim3 gs((ns + 255) / 256);
+            hipLaunchKernelGGL(k_vs_mult, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_off, d_trk_mult);
+            hipLaunchKernelGGL(k_vs_pairs, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_trk_mult, d_off, d_centers, d_xyz, d_acc, n_images);
+        }
+        hipLaunchKernelGGL(k_vs_score, dim3((n_images + 255) / 256, n_images), dim3(256), 0, st, d_acc, n_images, d_score);
+        if (num_view > 0) hipLaunchKernelGGL(k_vs_select, dim3(n_images), dim3(256), 0, st, d_score, n_images, num_view, d_ids, d_scores);
+        if (hipGetLastError() != hipSuccess) rc = -100;
+        (void)hipEventRecord(ev1, st);
+        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
+        if (!rc) (void)hipEventElapsedTime(&g_viewsel_kernel_ms, ev0, ev1);
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+    }
+    if (!rc && num_view > 0 &&
+        (hipMemcpyAsync(out_ids, d_ids, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+         hipMemcpyAsync(out_scores, d_scores, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+        rc = -100;
+    std::vector<unsigned long long> acc;
+    if (!rc && (shared || small)) {
+        acc.resize(nn);
+        if (hipMemcpyAsync(acc.data(), d_acc, nn * 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path, before the buffers go back to the pool
+    if (!rc && (shared || small))
+        for (size_t k = 0; k < nn; ++k) {
+            if (shared) shared[k] = (uint32_t)(acc[k] >> 32);
+            if (small) small[k] = (uint32_t)(acc[k] & 0xffffffffull);
+        }
+    for (void* p : {(void*)d_centers, (void*)d_xyz, (void*)d_obs_off, (void*)d_obs_pt, (void*)d_cnt, (void*)d_off, (void*)d_tsum, (void*)d_fill,
+                    (void*)d_trk_img, (void*)d_trk_pt, (void*)d_trk_mult, (void*)d_acc, (void*)d_score, (void*)d_ids, (void*)d_scores})
+        (void)pool_free(p);
     (void)hipStreamDestroy(st);
     return rc;
 }

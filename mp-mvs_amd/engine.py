@@ -39,6 +39,8 @@ _EXTRA = {
     "free_pinned": (None, [C.c_void_p]),
     "peer_info": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "chain_status": (C.c_int, [_P]),
+    "view_select": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "view_select_kernel_ms": (C.c_float, []),
     "dbg_chain_stall": (C.c_int, [_P, C.c_int, C.c_int]),
     "eval_ncc_multi": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
 }
