@@ -90,6 +90,11 @@ struct mpmvs_ctx {
     int dbg_stall_pos = -1;        // fault injection: this block position never signals its first pass (mpmvs_dbg_chain_stall)
     bool sync_overflow = false;    // a chained launch needed more completion words than d_sync holds (refused, -100)
     bool chain_failed_check = false;  // per-pass launches because the device failed the self-check of the chained launch
+    // the banded end of mpmvs_run_get (enqueue_band_tail): row-band counters that the last update pass raises (pm_kernels.hpp, ChainArgs)
+    unsigned* d_band = nullptr;
+    unsigned band_run = 0;        // banded Run()s since the counters were last zeroed (the targets of the next one: band_run + 1 times its waves)
+    bool band_armed = false;      // the last update launch enqueued by this Run() raises the band counters
+    bool can_wait_value = false;  // hipStreamWaitValue32 is available on the device
     std::vector<hipEvent_t> event_pool;
     // Staging buffers of an upload that is still in flight on `stream` (mpmvs_set_views returns once its work is ENQUEUED): page-locked
     // host memory and pooled device memory, given back by release_deferred() right after the next synchronisation of the stream
@@ -271,6 +276,9 @@ static void free_views(mpmvs_ctx* c) {
     if (c->S.depth) (void)pool_free(c->S.depth);
     if (c->d_sync) (void)pool_free(c->d_sync);
     c->d_sync = nullptr;
+    if (c->d_band) (void)pool_free(c->d_band);
+    c->d_band = nullptr;
+    c->band_run = 0;
 #ifdef PM_DBG_WAVETIME
     if (c->S.wavetime) (void)hipFree(c->S.wavetime);
 #endif
@@ -615,18 +623,27 @@ static int run_chain_check(int device) {
     p.max_iterations = 3, p.num_images = V + 1, p.top_k = 4, p.sigma_spatial = 5.0f, p.sigma_color = 3.0f;
     p.depth_min = 2.0f, p.depth_max = 6.0f, p.max_scale = 1;
     const size_t wh = (size_t)W * H;
-    std::vector<float> pl[2], co[2];
+    // page-locked outputs: the chained Run() then ends in the banded tail (enqueue_band_tail) and is checked with it, against the
+    // per-pass launches and the whole-image tail
+    float* pl[2] = {static_cast<float*>(mpmvs_alloc_pinned(wh * 16)), static_cast<float*>(mpmvs_alloc_pinned(wh * 16))};
+    float* co[2] = {static_cast<float*>(mpmvs_alloc_pinned(wh * 4)), static_cast<float*>(mpmvs_alloc_pinned(wh * 4))};
     int verdict = 0;
-    if (mpmvs_set_views(c, V + 1, cams.data(), ptr.data(), nullptr) == 0) {
-        bool ran = true;
-        for (int k = 0; k < 2 && ran; ++k) {
+    if (pl[0] && pl[1] && co[0] && co[1] && mpmvs_set_views(c, V + 1, cams.data(), ptr.data(), nullptr) == 0) {
+        int rc[2];
+        for (int k = 0; k < 2; ++k) {
             c->chain = (k == 0);
-            pl[k].resize(wh * 4), co[k].resize(wh);
-            ran = mpmvs_run_get(c, &p, 0x5EEDC4A1ull, pl[k].data(), co[k].data(), nullptr) == 0;
+            rc[k] = mpmvs_run_get(c, &p, 0x5EEDC4A1ull, pl[k], co[k], nullptr);
         }
-        if (ran) verdict = (std::memcmp(pl[0].data(), pl[1].data(), wh * 16) == 0 && std::memcmp(co[0].data(), co[1].data(), wh * 4) == 0) ? 1 : -1;
+        // a chained Run() that fails (-101: a block gave up waiting; -100) where the per-pass one runs is a failed check; only
+        // when the per-pass Run() fails too could the check not run
+        if (rc[1] == 0)
+            verdict = (rc[0] == 0 && std::memcmp(pl[0], pl[1], wh * 16) == 0 && std::memcmp(co[0], co[1], wh * 4) == 0) ? 1 : -1;
     }
     mpmvs_destroy(c);
+    for (int k = 0; k < 2; ++k) {
+        if (pl[k]) mpmvs_free_pinned(pl[k]);
+        if (co[k]) mpmvs_free_pinned(co[k]);
+    }
     return verdict;
 }
 
@@ -696,6 +713,9 @@ mpmvs_ctx* mpmvs_create(int device) {
         return nullptr;
     }
     *c->h_sync_err = 0;
+    int wait_value = 0;
+    if (hipDeviceGetAttribute(&wait_value, hipDeviceAttributeCanUseStreamWaitValue, device) != hipSuccess) (void)hipGetLastError();
+    c->can_wait_value = wait_value != 0;
     if (const char* e = std::getenv("MPMVS_CHAIN")) c->chain = std::atoi(e) != 0;   // 0: one update launch per pass (measurements, bisecting)
     if (c->chain && !chain_check_passed(device)) {
         c->chain = false;
@@ -908,6 +928,10 @@ static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const f
         c->sync_blocks = ((c->W + 15) / 16 + 1) * ((c->H + 7) / 8 + 4);
         const size_t bytes = (size_t)(kSyncHeader + c->sync_blocks) * sizeof(int);
         if (pool_malloc(&c->d_sync, bytes) != hipSuccess || hipMemsetAsync(c->d_sync, 0, bytes, c->stream) != hipSuccess) rc = -100;
+        // one band counter per 8 image rows at most (bands are 32 rows and more), zeroed here and after a failed Run() only
+        const size_t band_bytes = (size_t)((c->H + 7) / 8 + 4) * sizeof(unsigned);
+        c->band_run = 0;
+        if (!rc && (pool_malloc(&c->d_band, band_bytes) != hipSuccess || hipMemsetAsync(c->d_band, 0, band_bytes, c->stream) != hipSuccess)) rc = -100;
     }
 #ifdef PM_DBG_WAVETIME
     // room for 16 launches of one wave per 64 pixels of a colour, 4 x u64 each (generous: blocks overhang the image border)
@@ -1169,6 +1193,7 @@ static void launch_update_chain(mpmvs_ctx* c, const LaunchArgs& a, const ChainAr
         c->sync_overflow = true;
         return;
     }
+    if (ch.band) c->band_armed = true;
     const dim3 grid((unsigned)(ch.n_pass * ch.nb));   // one block per work item (pass, position), handed out by ticket (k_update)
     const size_t lds = update_lds_bytes<NT>();
     const dim3 blk(NT);
@@ -1215,13 +1240,7 @@ static float host_exp_canonical(float x) {
     return out;
 }
 
-// One launch.  For the update kinds `passes` > 1 chains that many passes into it -- alternating colours starting with `kind`, launch
-// ids launch, launch + 1, ..., iterations iter, iter (+1 after every red pass): exactly the launches that many calls would make.
-static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int kind, int iter, int scale, uint32_t launch, int passes = 1) {
-    if (scale < 0 || scale > 2) return fail(c, -3, "scale must be 0..2");
-    if (passes < 1 || (passes + 1) / 2 + 1 > kChainMaxIters) return fail(c, -6, "too many passes in one update launch");
-    if ((kind == MPMVS_KIND_BLACK || kind == MPMVS_KIND_RED) && scale != 0 && (p->geom_consistency || p->planar_prior))
-        return fail(c, -3, "geometric / planar-prior updates run at scale 0 only (as Run() does)");
+static LaunchArgs make_args(const mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int kind, int iter, int scale, uint32_t launch) {
     LaunchArgs a;
     a.seed = seed;
     a.launch = launch;
@@ -1237,11 +1256,44 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
     fill_spatial_terms(a, scale);
     // ref .cu:832: double product, one rounding to float
     a.cost_threshold = (float)(0.8 * (double)host_exp_canonical((float)(iter * iter) / (-90.0f)));
+    a.init_random = (!p->geom_consistency && !p->planar_prior) ? 1 : 0;
+    a.use_prior = p->planar_prior ? 1 : 0;
+    return a;
+}
+
+// rows the checkerboard launches cover: the reference's grid (ref .cu:1196), at most the image
+static int checker_rows(const mpmvs_ctx* c) {
+    const int ylimit = 2 * 16 * (((c->H / 2) + 15) / 16);
+    return c->H < ylimit ? c->H : ylimit;
+}
+
+// Height of a row band of the banded end of Run() (enqueue_band_tail): about H / kTailBands rows, a multiple of 32 -- the block
+// height of the filter launches (kChkBlockH<256>), of two rows of k_depth_normal's blocks and of four 8-row groups of the band counters.
+constexpr int kTailBands = 12;
+static int band_rows(const mpmvs_ctx* c) {
+    const int k = (c->H + 16 * kTailBands) / (32 * kTailBands);
+    return 32 * (k > 1 ? k : 1);
+}
+
+// One launch.  For the update kinds `passes` > 1 chains that many passes into it -- alternating colours starting with `kind`, launch
+// ids launch, launch + 1, ..., iterations iter, iter (+1 after every red pass): exactly the launches that many calls would make.
+// signal_bands: the launch ends a banded Run() -- its last pass raises the band counters (enqueue_band_tail).
+static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int kind, int iter, int scale, uint32_t launch, int passes = 1,
+                        bool signal_bands = false) {
+    if (scale < 0 || scale > 2) return fail(c, -3, "scale must be 0..2");
+    if (passes < 1 || (passes + 1) / 2 + 1 > kChainMaxIters) return fail(c, -6, "too many passes in one update launch");
+    if ((kind == MPMVS_KIND_BLACK || kind == MPMVS_KIND_RED) && scale != 0 && (p->geom_consistency || p->planar_prior))
+        return fail(c, -3, "geometric / planar-prior updates run at scale 0 only (as Run() does)");
+    const LaunchArgs a = make_args(c, p, seed, kind, iter, scale, launch);
     ChainArgs ch{};
     ch.n_pass = passes;
     for (int j = 0; j < kChainMaxIters; ++j) ch.thr[j] = (float)(0.8 * (double)host_exp_canonical((float)((iter + j) * (iter + j)) / (-90.0f)));
-    a.init_random = (!p->geom_consistency && !p->planar_prior) ? 1 : 0;
-    a.use_prior = p->planar_prior ? 1 : 0;
+    if (signal_bands && passes > 1 && c->d_band) {
+        ch.band = c->d_band;
+        ch.band_groups = band_rows(c) / kWaveRows;
+        ch.n_groups = (checker_rows(c) + kWaveRows - 1) / kWaveRows;
+        ch.band_run = c->band_run + 1;
+    }
 
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->profiling) {
@@ -1272,7 +1324,7 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
                 launch_update<false, false>(c, a, ch);
             break;
         case MPMVS_KIND_DEPTH_NORMAL:
-            hipLaunchKernelGGL(k_depth_normal, grid_dense, blk, 0, c->stream, c->dP, c->S);
+            hipLaunchKernelGGL(k_depth_normal, grid_dense, blk, 0, c->stream, c->dP, c->S, 0);
             c->depth_plane_valid = true;
             break;
         case MPMVS_KIND_FILTER_BLACK:
@@ -1282,7 +1334,7 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
                 hipLaunchKernelGGL(k_export_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S.planes, c->S.depth, n);
                 c->depth_plane_valid = true;
             }
-            hipLaunchKernelGGL(k_filter, grid_chk, blk, 0, c->stream, c->dP, c->S, a);
+            hipLaunchKernelGGL(k_filter, grid_chk, blk, 0, c->stream, c->dP, c->S, a, 0);
             break;
         default:
             return fail(c, -6, "bad kernel kind");
@@ -1355,6 +1407,14 @@ static int abandon_run(mpmvs_ctx* c, int rc) {
         (void)hipMemsetAsync(c->d_sync, 0, (size_t)(kSyncHeader + c->sync_blocks) * sizeof(int), c->stream);
         (void)hipStreamSynchronize(c->stream);
     }
+    // the band counters: a launch that gave up lifted them to their targets and its blocks then added to them -- start over from
+    // zero, now that both streams are idle and no wait is armed
+    c->band_armed = false;
+    if (c->d_band) {
+        (void)hipMemsetAsync(c->d_band, 0, (size_t)((c->H + 7) / 8 + 4) * sizeof(unsigned), c->stream);
+        (void)hipStreamSynchronize(c->stream);
+        c->band_run = 0;
+    }
     (void)hipGetLastError();
     c->err = why;
     return rc;
@@ -1364,7 +1424,8 @@ static int abandon_run(mpmvs_ctx* c, int rc) {
 // random streams are keyed by the launch numbers, so the two entry points give the same bits only while they number alike.
 // enqueue_updates: InitializeScore and every Black / RedPixelUpdate (costs and geometric costs are final afterwards);
 // enqueue_finalize: GetDepthandNormal and the two median-filter launches.
-static int enqueue_updates(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, uint32_t& launch) {
+// signal_bands: the last launch raises the band counters (enqueue_band_tail); c->band_armed tells whether it was enqueued.
+static int enqueue_updates(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, uint32_t& launch, bool signal_bands = false) {
     int rc;
     if ((rc = enqueue_step(c, p, seed, MPMVS_KIND_INIT, 0, p->max_scale, launch++))) return rc;
     // the black / red passes of one window scale: one launch per pass (the reference's schedule, ref .cu:1211-1236), or -- the
@@ -1375,7 +1436,8 @@ static int enqueue_updates(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, u
         while (i < p->max_iterations) {
             const int n = c->chain ? std::min(p->max_iterations - i, kChainMaxIters - 1) : 1;
             if (c->chain) {
-                if ((rc = enqueue_step(c, p, seed, MPMVS_KIND_BLACK, i, s, launch, 2 * n))) return rc;
+                const bool last = s == 0 && i + n >= p->max_iterations;
+                if ((rc = enqueue_step(c, p, seed, MPMVS_KIND_BLACK, i, s, launch, 2 * n, signal_bands && last))) return rc;
                 launch += 2 * n;
             } else {
                 if ((rc = enqueue_step(c, p, seed, MPMVS_KIND_BLACK, i, s, launch++))) return rc;
@@ -1401,10 +1463,130 @@ static int enqueue_finalize(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, 
     return 0;
 }
 
+// A host buffer the banded copies may write into: page-locked (or registered) memory.  A copy into pageable memory is synchronous,
+// which would serialise the bands with the host.
+static bool host_pinned(const void* ptr) {
+    if (!ptr) return true;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == hipMemoryTypeHost;
+}
+
+// The banded end of Run() (mpmvs_run_get on the chained path).  Rows of the image become final in raster order during the last
+// update pass (its tickets are raster-ordered), so GetDepthandNormal, the two median-filter launches and the device-to-host copies
+// run band by band on the copy stream while that pass still works further down, instead of after it.  Step s, for band s of rows:
+//   * wait (hipStreamWaitValue32, >=) for the band counters that the last pass raises (pm_kernels.hpp, ChainArgs) until every
+//     wave whose candidates reach into the band (23 rows, kDirs) has completed: k_depth_normal rewrites the planes that the pass
+//     reads as candidates;
+//   * copy the band's costs (and geometric costs): final with the update;
+//   * k_depth_normal on the band: depths are done down to its end D;
+//   * k_filter black down to FB = D - 32 (the filter reads the other colour's depths 5 rows on, in place: they must all exist);
+//   * k_filter red down to FR = FB - 32 (it reads black depths filtered 5 rows on, while no black filter may still read the red
+//     depths it rewrites);
+//   * copy the planes down to FR: final.
+// The step whose wait covers the whole image -- every band counter -- takes everything down to the image's end.  Every launch and
+// copy keeps its arithmetic and its inputs, so the maps are the bits of the whole-image tail; the stream's launches follow one
+// another, which orders the reads and writes above.
+static int enqueue_band_tail(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, uint32_t launch, void* planes4, void* costs, void* geom) {
+    hipStream_t fs = c->copy_stream;
+    const int W = c->W, H = c->H, bh = band_rows(c), n_bands = (H + bh - 1) / bh;
+    const int rows = checker_rows(c), n_groups = (rows + kWaveRows - 1) / kWaveRows, gpb = bh / kWaveRows;
+    const unsigned per_group = (unsigned)((W + kChkBlockW - 1) / kChkBlockW);   // last-pass waves per 8-row group
+    const int nbx_f = (W + kChkBlockW - 1) / kChkBlockW, bh_f = kChkBlockH<256>;
+    static_assert(kChkBlockH<256> == 32, "the filter's lag behind the depths (32 rows) is one filter block row");
+    const LaunchArgs fa[2] = {make_args(c, p, seed, MPMVS_KIND_FILTER_BLACK, 0, 0, launch + 1), make_args(c, p, seed, MPMVS_KIND_FILTER_RED, 0, 0, launch + 2)};
+    const dim3 blk(256);
+    // a launch on the copy stream, timed like enqueue_step's when profiling (booked as one launch of its kind per band)
+    auto timed = [&](int kind, auto&& go) -> int {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (c->profiling) {
+            e0 = get_event(c);
+            e1 = get_event(c);
+            HIPCHK(c, hipEventRecord(e0, fs));
+        }
+        go();
+        HIPCHK(c, hipGetLastError());
+        if (c->profiling) {
+            HIPCHK(c, hipEventRecord(e1, fs));
+            c->pending.push_back({kind, e0, e1, 1});
+        }
+        return 0;
+    };
+    // rows [r0, r1) of one colour (r0 a multiple of 32)
+    auto filter = [&](int r0, int r1, int colour) -> int {
+        r1 = std::min(r1, rows);   // rows below the reference's checkerboard grid are not filtered
+        if (r1 <= r0) return 0;
+        const int f0 = r0 / bh_f, f1 = (r1 + bh_f - 1) / bh_f;
+        return timed(colour ? MPMVS_KIND_FILTER_RED : MPMVS_KIND_FILTER_BLACK, [&] {
+            hipLaunchKernelGGL(k_filter, dim3((unsigned)(nbx_f * (f1 - f0))), blk, 0, fs, c->dP, c->S, fa[colour], f0 * nbx_f);
+        });
+    };
+    int rc, waited = 0;          // band counters the stream waits for already
+    int done_fb = 0, done_fr = 0; // rows filtered black / red so far
+    for (int s = 0; s < n_bands; ++s) {
+        const int r0 = s * bh;
+        int r1 = std::min(H, r0 + bh);
+        // the 8-row groups whose last-pass waves read rows of this band: 8 g - 23 < r1
+        const int need = std::min(n_groups, (r1 + 22) / kWaveRows + 1);
+        for (; waited * gpb < need; ++waited) {
+            const int groups = std::min(n_groups, (waited + 1) * gpb) - waited * gpb;
+            HIPCHK(c, hipStreamWaitValue32(fs, c->d_band + waited, c->band_run * per_group * (unsigned)groups, hipStreamWaitValueGte, 0xFFFFFFFFu));
+        }
+        const bool last = waited * gpb >= n_groups;   // the update has ended: this step takes the rest of the image
+        if (last) r1 = H;
+        const size_t off = (size_t)r0 * W, n = (size_t)(r1 - r0) * W;
+        if (costs) HIPCHK(c, hipMemcpyAsync(static_cast<float*>(costs) + off, c->S.costs + off, n * 4, hipMemcpyDeviceToHost, fs));
+        if (geom) HIPCHK(c, hipMemcpyAsync(static_cast<float*>(geom) + off, c->S.geom + off, n * 4, hipMemcpyDeviceToHost, fs));
+        if ((rc = timed(MPMVS_KIND_DEPTH_NORMAL, [&] {
+                 hipLaunchKernelGGL(k_depth_normal, dim3((unsigned)((W + 15) / 16), (unsigned)((r1 - r0 + 15) / 16)), blk, 0, fs, c->dP, c->S, r0 / 16);
+             })))
+            return rc;
+        const int fb = last ? H : std::max(0, r1 - bh_f), fr = last ? H : std::max(0, fb - bh_f);
+        if (fb > done_fb) {
+            if ((rc = filter(done_fb, fb, 0))) return rc;
+            done_fb = fb;
+        }
+        if (fr > done_fr) {
+            if ((rc = filter(done_fr, fr, 1))) return rc;
+            const size_t po = (size_t)done_fr * W, pn = (size_t)(fr - done_fr) * W;
+            if (planes4) HIPCHK(c, hipMemcpyAsync(static_cast<float4*>(planes4) + po, c->S.planes + po, pn * 16, hipMemcpyDeviceToHost, fs));
+            done_fr = fr;
+        }
+        if (last) break;
+    }
+    c->depth_plane_valid = true;
+    return 0;
+}
+
 static int enqueue_run(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, void* planes4, void* costs, void* geom) {
     int rc;
     uint32_t launch = 0;
-    if ((rc = enqueue_updates(c, p, seed, launch))) return rc;
+    // the banded end: chained launches, stream waits, an output, page-locked host buffers; otherwise the whole-image tail below
+    const bool banded = c->chain && c->can_wait_value && c->d_band && (planes4 || costs || geom) && host_pinned(planes4) && host_pinned(costs) &&
+                        host_pinned(geom);
+    if (banded) {
+        if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        if (!c->costs_final) HIPCHK(c, hipEventCreateWithFlags(&c->costs_final, hipEventDisableTiming));
+        // targets grow with every banded Run(); long before they could overflow, start over from zero (nothing waits between Run()s)
+        if ((uint64_t)(c->band_run + 1) * (uint64_t)((c->W + kChkBlockW - 1) / kChkBlockW) * (uint64_t)(band_rows(c) / kWaveRows) > 0x7fffffffull) {
+            HIPCHK(c, hipMemsetAsync(c->d_band, 0, (size_t)((c->H + 7) / 8 + 4) * sizeof(unsigned), c->stream));
+            c->band_run = 0;
+        }
+        // the copy stream's waits come after everything enqueued on the context so far (the zeroing of the counters included)
+        HIPCHK(c, hipEventRecord(c->costs_final, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->costs_final, 0));
+    }
+    if ((rc = enqueue_updates(c, p, seed, launch, banded))) return rc;
+    if (c->band_armed) {
+        c->band_armed = false;
+        c->band_run++;
+        if ((rc = enqueue_band_tail(c, p, seed, launch, planes4, costs, geom))) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->copy_stream));
+        return finish(c);
+    }
     const size_t wh = (size_t)c->W * c->H;
     const bool early = costs || geom;
     if (early) {

@@ -98,10 +98,11 @@ PM_DEV bool checker_pixel(const ProblemDev& P, const LaunchArgs& a, int b, int p
     return x < P.W && y < P.H && y < a.ylimit;
 }
 // all-pixel launches: block = 16x16 pixels, wave = 8x8 patch of it (against 16x4 waves: profiles/EXPERIMENTS.md 49)
-PM_DEV bool dense_pixel(const ProblemDev& P, int& x, int& y, int& x0, int& y0) {
+// (by0: the first block row of a launch that covers a band of rows only, k_depth_normal in the banded end of Run())
+PM_DEV bool dense_pixel(const ProblemDev& P, int& x, int& y, int& x0, int& y0, int by0 = 0) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     x0 = blockIdx.x * 16;
-    y0 = blockIdx.y * 16;
+    y0 = (blockIdx.y + by0) * 16;
     y = y0 + (wv >> 1) * 8 + (lane >> 3);
     x = x0 + (wv & 1) * 8 + (lane & 7);
     return x < P.W && y < P.H;
@@ -812,6 +813,14 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
 // 96 % and are no faster, 2.46 ms with the registers the loop costs: the last slots add contention, not throughput.)
 // The sync words live in global memory: [0] ticket, [1] waves that have left the kernel, [2] error, [16 + b] waves that have
 // completed position b (monotonic over the passes).  The last wave to leave zeroes them for the next launch.
+//
+// Band counters (the banded end of Run(), mpmvs_api.hip enqueue_band_tail): in the LAST pass of the last update launch of a
+// Run() every wave also adds 1 to the counter of the row band that holds its 8 rows, right after its completion signal.  The
+// rows of band k are final once its counter has reached band_run x (waves of the last pass in band k): the host's finishing
+// stream waits for that (hipStreamWaitValue32) and then runs GetDepthandNormal, the median filter and the copies of the band
+// while the pass still works further down the image.  The counters live in their own buffer and are never reset while a wait may
+// be armed: band_run counts the banded Run()s of the context, so the targets only grow.  A block that gives up waiting (kSpinLimit,
+// the error word) first lifts every counter to its target, so that no wait of the finishing stream outlives the launch.
 // ---------------------------------------------------------------------------
 struct ChainArgs {
     int n_pass;    // passes in this launch; pass k has colour (a.parity + k) & 1, launch id a.launch + k, iteration a.iter + (a.parity + k) / 2
@@ -821,6 +830,10 @@ struct ChainArgs {
     int* sync;
     int spin_limit;  // polls after which a waiting block gives up (kSpinLimit unless a test shortens it)
     int stall_pos;   // fault injection (mpmvs_dbg_chain_stall): the block at this position never signals its first pass; -1 = off
+    unsigned* band;       // band counters, or nullptr: no band signals from this launch
+    int band_groups;      // 8-row groups (kWaveRows) per band
+    int n_groups;         // 8-row groups of the rows the launch updates: group g counts toward band g / band_groups
+    unsigned band_run;    // the banded Run() this launch ends (1, 2, ...): band k's target is band_run x nbx x (groups of band k)
 };
 constexpr int kChainMaxIters = 8;
 constexpr int kSyncHeader = 16;
@@ -869,6 +882,13 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
                     const bool give_up = spins >= ch.spin_limit || __hip_atomic_load(&ch.sync[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
                     if (__builtin_amdgcn_readfirstlane((int)give_up)) {
                         if (threadIdx.x == 0) __hip_atomic_store(&ch.sync[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (ch.band) {   // release every wait of the finishing stream: this Run() is lost (-101) anyway
+                            const int n_bands = (ch.n_groups + ch.band_groups - 1) / ch.band_groups;
+                            for (int k = threadIdx.x; k < n_bands; k += 64) {
+                                const int groups = min(ch.n_groups, (k + 1) * ch.band_groups) - k * ch.band_groups;
+                                __hip_atomic_fetch_max(&ch.band[k], ch.band_run * (unsigned)(ch.nbx * groups), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            }
+                        }
                         break;
                     }
                 }
@@ -900,6 +920,10 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
     if ((threadIdx.x & 63) == 0) {
         if (!(b == ch.stall_pos && pass == 0))   // (fault injection: a position that never completes its first pass)
             __hip_atomic_fetch_add(&ch.sync[kSyncHeader + b], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ch.band && pass == ch.n_pass - 1) {   // the last pass: this wave's 8 rows of the image are final
+            const int g = (b / ch.nbx) * kWaves + (int)(threadIdx.x >> 6);
+            if (g < ch.n_groups) __hip_atomic_fetch_add(&ch.band[g / ch.band_groups], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
         fin = __hip_atomic_fetch_add(&ch.sync[1], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     fin = __builtin_amdgcn_readfirstlane(fin);
@@ -916,10 +940,11 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
 // ---------------------------------------------------------------------------
 // GetDepthandNormal, ref .cu:1021-1034
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_depth_normal(const ProblemDev* __restrict__ Pp, StateDev S) {
+// by0: first block row (16 rows) of the launch -- the banded end of Run() launches it per band of rows, same arithmetic
+__global__ __launch_bounds__(256) void k_depth_normal(const ProblemDev* __restrict__ Pp, StateDev S, int by0) {
     const ProblemDev& P = *Pp;
-    int x, y;
-    if (!dense_pixel(P, x, y)) return;
+    int x, y, x0, y0;
+    if (!dense_pixel(P, x, y, x0, y0, by0)) return;
     const int idx = y * P.W + x;
     float4 pl = S.planes[idx];
     pl.w = depth_from_plane(P, pl, x, y);
@@ -978,10 +1003,14 @@ PM_DEV float median21_rounds(float (&v)[21], float& lowest) {
 // The depths are gathered from the dense plane S.depth (written by k_depth_normal, kept in step with planes[].w here): 4 bytes
 // per tap instead of the .w of a 16-byte float4 (4 x over-fetch; 84 -> 40 us per launch).  Every tap has the other colour, so
 // the in-place update of one colour is race free in both arrays.
-__global__ __launch_bounds__(256) void k_filter(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a) {
+// b0: block position of the launch's first block (a band of block rows in the banded end of Run(); 0 for the whole image).
+// At most 64 VGPRs (8 waves per SIMD; 72 unbounded): the banded end of Run() launches the filter while the last update pass holds
+// two waves of 224 VGPRs on every SIMD, and only 64 of a SIMD's 512 are left beside them -- at 72 a band's filter waited for the
+// update's last block (1.5 ms).
+__global__ __launch_bounds__(256, 8) void k_filter(const ProblemDev* __restrict__ Pp, StateDev S, LaunchArgs a, int b0) {
     const ProblemDev& P = *Pp;
     int x, y, x0, y0;
-    if (!checker_pixel(P, a, xcd_remap(blockIdx.x, gridDim.x), a.parity, x, y, x0, y0)) return;
+    if (!checker_pixel(P, a, b0 + xcd_remap(blockIdx.x, gridDim.x), a.parity, x, y, x0, y0)) return;
     const int W = P.W, Hh = P.H;
     const int ctr = y * W + x;
     if (S.costs[ctr] < 0.001f) return;
