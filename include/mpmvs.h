@@ -105,6 +105,32 @@ const char* mpmvs_last_error(const mpmvs_ctx* ctx);
  * waits for the stream (mpmvs_run*, mpmvs_get, ...) as -100. */
 int mpmvs_set_views(mpmvs_ctx* ctx, int n, const mpmvs_camera* cams, const float* const* images,
                     const size_t* pitch_bytes);
+/* The same upload from the BYTES the image files decoded to (the reference's imread(GRAYSCALE) before its convertTo,
+ * src/PatchMatch.cpp:877-882), at the files' own size: an image larger than its camera is shrunk on the device (the
+ * reference's cv::resize(INTER_LINEAR), :893-925).  cams[i].width/height is the size the Problem runs at and cams[i].K is
+ * already scaled to it, exactly as for mpmvs_set_views; src_widths[i] x src_heights[i] is the size of images[i] (both NULL:
+ * every image already has its camera's size); pitch_bytes[i] is the host row pitch in bytes (NULL = tightly packed).
+ * DEFINED BY EQUIVALENCE: the context ends in the state that mpmvs_set_views produces for the fp32 images F_i, where
+ * F_i = (float)bytes if the sizes agree and otherwise F_i = ResizeLinear((float)bytes, width, height) as
+ * mp-mvs_amd/host/PatchMatchHost.cpp states it: fp32, no contraction, sample position (x + 0.5f) * (src / dst) - 0.5f, an
+ * index below 0 or at / beyond the last one clamped with weight 0, value = top + ay * (bot - top) with
+ * top = s00 + ax * (s10 - s00).  Any ratio is legal; shrinking is the case that matters.
+ * Texture format: the sources take the 8-byte fp16 texels iff no SOURCE view is resampled and fp32 is not forced
+ * (mpmvs_set_texture_format); otherwise all sources take the 16-byte fp32 texels, the ones that were not resampled included.
+ * The reference image becomes the padded fp32 image either way.  (For a resampled image that happens to be all integers
+ * mpmvs_set_views would pick the 8-byte texels; both formats are bit-exact against the same oracle, so results agree.)
+ * Asynchronous like mpmvs_set_views: the bytes are read before the call returns, transfers and kernels are only enqueued, a
+ * later failure surfaces as -100 from the next call that waits.  The host work per image is one row-wise memcpy into the
+ * page-locked stage: no per-pixel test, no conversion.  Errors as for mpmvs_set_views (no half-built Problem is left behind);
+ * additionally -2 for a non-positive source size, a pitch smaller than the source width or only one of the two size arrays,
+ * and -3 for a source image of 2^32 bytes or more.  MPMVS_STAGE_MB groups the views by their source bytes. */
+int mpmvs_set_views_u8(mpmvs_ctx* ctx, int n, const mpmvs_camera* cams, const unsigned char* const* images,
+                       const int* src_widths, const int* src_heights, const size_t* pitch_bytes);
+/* probe: the resampling of mpmvs_set_views_u8 on its own, synchronous.  src = src_h rows of src_w bytes, pitch_bytes apart
+ * (0 = tightly packed); out = dense fp32 image of dst_h x dst_w pixels on the host.  0, -2 (bad argument), -3 (too large) or
+ * -100 (device error). */
+int mpmvs_resize_u8(int device, const unsigned char* src, int src_w, int src_h, size_t pitch_bytes, int dst_w, int dst_h,
+                    float* out);
 
 /* CudaMemInit source depth upload for geometric consistency
  * (src/PatchMatch.cpp:1027-1050, read at :941-948); n_src == n-1.  depths[i] == NULL keeps the map of source i that an

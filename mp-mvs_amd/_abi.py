@@ -180,6 +180,27 @@ class PatchMatchHandle:
         self.n_img = n
         self.H, self.W = imgs[0].shape
 
+    def set_views_u8(self, cams, images):
+        """views from uint8 arrays of any per-view shape (mpmvs_set_views_u8): an image whose shape is not its camera's is
+        resampled to it on the device; the arrays' row strides are honoured as the pitch (HIP library only)"""
+        n = len(cams)
+        assert n == len(images)
+        imgs = []
+        for im in images:
+            im = np.asarray(im)
+            assert im.dtype == np.uint8 and im.ndim == 2 and im.shape[0] > 0 and im.shape[1] > 0, (im.dtype, im.shape)
+            if im.strides[1] != 1 or im.strides[0] < im.shape[1]:   # rows must be runs of bytes; anything else is copied
+                im = np.ascontiguousarray(im)
+            imgs.append(im)
+        cam_arr = (Camera * n)(*cams)
+        ptrs = (C.POINTER(C.c_ubyte) * n)(*[im.ctypes.data_as(C.POINTER(C.c_ubyte)) for im in imgs])
+        ws = (C.c_int * n)(*[im.shape[1] for im in imgs])
+        hs = (C.c_int * n)(*[im.shape[0] for im in imgs])
+        pitches = (C.c_size_t * n)(*[im.strides[0] for im in imgs])
+        self._chk(self._f["set_views_u8"](self._ctx, n, cam_arr, ptrs, ws, hs, pitches), "set_views_u8")
+        self.n_img = n
+        self.H, self.W = cams[0].height, cams[0].width
+
     def set_src_depths(self, depths):
         n = len(depths)
         ds = [_f32(d) for d in depths]

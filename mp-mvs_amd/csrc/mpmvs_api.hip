@@ -39,6 +39,7 @@
 #include "pm_kernels.hpp"
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
+#include "pm_ingest.hpp"
 
 using namespace pm;
 
@@ -812,6 +813,45 @@ static void stage_known(int first, int last, const mpmvs_camera* cams, const flo
     row_pool().run(work);
 }
 
+// Second half of an image upload, shared by both entries (mpmvs_set_views, mpmvs_set_views_u8): the per-pixel state of the Problem and
+// its ProblemDev, enqueued behind the unpacking kernels
+static int finish_views(mpmvs_ctx* c) {
+    auto failed = [&](const char* what) {
+        (void)hipStreamSynchronize(c->stream);
+        release_deferred(c);
+        c->err = what;
+        return -100;
+    };
+    if (hipGetLastError() != hipSuccess) return failed("unpacking the images on the device failed");
+    const size_t wh = (size_t)c->W * c->H;
+    int rc = -100;
+    if (pool_malloc(&c->S.planes, wh * 16) == hipSuccess && pool_malloc(&c->S.costs, wh * 4) == hipSuccess &&
+        pool_malloc(&c->S.sel, wh * 4) == hipSuccess && pool_malloc(&c->S.geom, wh * 4) == hipSuccess && pool_malloc(&c->S.depth, wh * 4) == hipSuccess &&
+        hipMemsetAsync(c->S.planes, 0, wh * 16, c->stream) == hipSuccess && hipMemsetAsync(c->S.costs, 0, wh * 4, c->stream) == hipSuccess &&
+        hipMemsetAsync(c->S.sel, 0, wh * 4, c->stream) == hipSuccess && hipMemsetAsync(c->S.geom, 0, wh * 4, c->stream) == hipSuccess)
+        rc = 0;
+    c->depth_plane_valid = false;
+    if (!rc) {
+        // one completion word per update block (the smallest block the kernel can be built with is 16 x 8 pixels), zeroed once: every
+        // chained launch leaves them zeroed again
+        c->sync_blocks = ((c->W + 15) / 16 + 1) * ((c->H + 7) / 8 + 4);
+        const size_t bytes = (size_t)(kSyncHeader + c->sync_blocks) * sizeof(int);
+        if (pool_malloc(&c->d_sync, bytes) != hipSuccess || hipMemsetAsync(c->d_sync, 0, bytes, c->stream) != hipSuccess) rc = -100;
+        // one band counter per 8 image rows at most (bands are 32 rows and more), zeroed here and after a failed Run() only
+        const size_t band_bytes = (size_t)((c->H + 7) / 8 + 4) * sizeof(unsigned);
+        c->band_run = 0;
+        if (!rc && (pool_malloc(&c->d_band, band_bytes) != hipSuccess || hipMemsetAsync(c->d_band, 0, band_bytes, c->stream) != hipSuccess)) rc = -100;
+    }
+#ifdef PM_DBG_WAVETIME
+    // room for 16 launches of one wave per 64 pixels of a colour, 4 x u64 each (generous: blocks overhang the image border)
+    if (!rc && (hipMalloc(&c->S.wavetime, kWaveTimeBytes(c->W, c->H)) != hipSuccess || hipMemsetAsync(c->S.wavetime, 0, kWaveTimeBytes(c->W, c->H), c->stream) != hipSuccess)) rc = -100;
+#endif
+    if (rc) return failed("allocation of the per-pixel state failed");
+    // no synchronisation: everything later on this context follows on the same stream, and a transfer that fails is reported by the
+    // next call that waits for the stream (mpmvs_run*, mpmvs_get, ...) as -100
+    return upload_problem_async(c);
+}
+
 static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes) {
     c->n_img = n;
     c->cams.assign(cams, cams + n);
@@ -912,35 +952,7 @@ static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const f
             }
         }
     }
-    int rc = 0;
-    if (hipGetLastError() != hipSuccess) return failed("unpacking the images on the device failed");
-    const size_t wh = (size_t)c->W * c->H;
-    rc = -100;
-    if (pool_malloc(&c->S.planes, wh * 16) == hipSuccess && pool_malloc(&c->S.costs, wh * 4) == hipSuccess &&
-        pool_malloc(&c->S.sel, wh * 4) == hipSuccess && pool_malloc(&c->S.geom, wh * 4) == hipSuccess && pool_malloc(&c->S.depth, wh * 4) == hipSuccess &&
-        hipMemsetAsync(c->S.planes, 0, wh * 16, c->stream) == hipSuccess && hipMemsetAsync(c->S.costs, 0, wh * 4, c->stream) == hipSuccess &&
-        hipMemsetAsync(c->S.sel, 0, wh * 4, c->stream) == hipSuccess && hipMemsetAsync(c->S.geom, 0, wh * 4, c->stream) == hipSuccess)
-        rc = 0;
-    c->depth_plane_valid = false;
-    if (!rc) {
-        // one completion word per update block (the smallest block the kernel can be built with is 16 x 8 pixels), zeroed once: every
-        // chained launch leaves them zeroed again
-        c->sync_blocks = ((c->W + 15) / 16 + 1) * ((c->H + 7) / 8 + 4);
-        const size_t bytes = (size_t)(kSyncHeader + c->sync_blocks) * sizeof(int);
-        if (pool_malloc(&c->d_sync, bytes) != hipSuccess || hipMemsetAsync(c->d_sync, 0, bytes, c->stream) != hipSuccess) rc = -100;
-        // one band counter per 8 image rows at most (bands are 32 rows and more), zeroed here and after a failed Run() only
-        const size_t band_bytes = (size_t)((c->H + 7) / 8 + 4) * sizeof(unsigned);
-        c->band_run = 0;
-        if (!rc && (pool_malloc(&c->d_band, band_bytes) != hipSuccess || hipMemsetAsync(c->d_band, 0, band_bytes, c->stream) != hipSuccess)) rc = -100;
-    }
-#ifdef PM_DBG_WAVETIME
-    // room for 16 launches of one wave per 64 pixels of a colour, 4 x u64 each (generous: blocks overhang the image border)
-    if (!rc && (hipMalloc(&c->S.wavetime, kWaveTimeBytes(c->W, c->H)) != hipSuccess || hipMemsetAsync(c->S.wavetime, 0, kWaveTimeBytes(c->W, c->H), c->stream) != hipSuccess)) rc = -100;
-#endif
-    if (rc) return failed("allocation of the per-pixel state failed");
-    // no synchronisation: everything later on this context follows on the same stream, and a transfer that fails is reported by the
-    // next call that waits for the stream (mpmvs_run*, mpmvs_get, ...) as -100
-    return upload_problem_async(c);
+    return finish_views(c);
 }
 
 int mpmvs_set_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes) {
@@ -964,6 +976,182 @@ int mpmvs_set_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const float* 
         c->err = why;
     }
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// 8-bit entry (pm_ingest.hpp): the views arrive as bytes at their own size.  Nothing is tested or converted on the host -- the formats
+// follow from the sizes alone -- so the host work is one row-wise copy per image into the page-locked stage.
+// ---------------------------------------------------------------------------
+static IngestSrc ingest_src(const unsigned char* d_bytes, int src_w, int src_h, int dst_w, int dst_h) {
+    // the two ratios exactly as ResizeLinear forms them (host/PatchMatchHost.cpp)
+    return IngestSrc{d_bytes, src_w, src_h, (unsigned)src_w, (float)src_w / dst_w, (float)src_h / dst_h};
+}
+
+static int set_views_u8_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const unsigned char* const* images, const int* src_w,
+                             const int* src_h, const size_t* pitch_bytes) {
+    c->n_img = n;
+    c->cams.assign(cams, cams + n);
+    c->W = cams[0].width;
+    c->H = cams[0].height;
+    std::memset(&c->hP, 0, sizeof(ProblemDev));
+    precompute_views(c);
+    auto sw = [&](int i) { return src_w ? src_w[i] : cams[i].width; };
+    auto sh = [&](int i) { return src_h ? src_h[i] : cams[i].height; };
+    auto resampled = [&](int i) { return sw(i) != cams[i].width || sh(i) != cams[i].height; };
+    // the sources take the 8-byte fp16 texels iff none of them is resampled (a resampled image is not made of integers) and fp32 is not forced
+    bool src_u8 = !c->force_f32;
+    for (int v = 1; v < n; ++v) src_u8 = src_u8 && !resampled(v);
+    c->all_u8 = src_u8;
+    // a slot of src_w * src_h bytes per image, 256-byte aligned, in groups of at most MPMVS_STAGE_MB as in set_views_impl
+    std::vector<size_t> slot(n + 1, 0);
+    for (int i = 0; i < n; ++i) slot[i + 1] = slot[i] + (((size_t)sw(i) * sh(i) + 255) & ~(size_t)255);
+    size_t limit = 512;
+    if (const char* e = std::getenv("MPMVS_STAGE_MB")) limit = (size_t)std::max(1, std::atoi(e));
+    limit <<= 20;
+    std::vector<int> group_first{0};
+    for (int i = 1; i < n; ++i)
+        if (slot[i + 1] - slot[group_first.back()] > limit) group_first.push_back(i);
+    group_first.push_back(n);
+    const int n_groups = (int)group_first.size() - 1;
+    size_t stage_bytes = 0;
+    for (int g = 0; g < n_groups; ++g) stage_bytes = std::max(stage_bytes, slot[group_first[g + 1]] - slot[group_first[g]]);
+    char* const stage = (char*)mpmvs_alloc_pinned(stage_bytes);
+    if (!stage) return fail(c, -100, "no page-locked staging memory for the images");
+    c->deferred_pinned.push_back(stage);
+    void* d_stage_p = nullptr;
+    HIPCHK(c, pool_malloc_bytes(&d_stage_p, stage_bytes ? stage_bytes : 4));
+    c->deferred_dev.push_back(d_stage_p);
+    char* const d_stage = (char*)d_stage_p;
+    auto failed = [&](const char* what) {
+        (void)hipStreamSynchronize(c->stream);
+        release_deferred(c);
+        c->err = what;
+        return -100;
+    };
+    const int pw = c->W + 2 * kRefApron, ph = c->H + 2 * kRefApron;
+    if (pool_malloc(&c->d_ref, (size_t)pw * ph * 4) != hipSuccess) return failed("allocation of the reference image failed");
+    c->hP.ref_pitch = pw;
+    c->hP.ref_img = c->d_ref + (size_t)kRefApron * pw + kRefApron;
+    const size_t texel = src_u8 ? 8 : 16;
+    std::vector<size_t> tex_off(n, 0);
+    size_t tex_total = 0;
+    for (int v = 1; v < n; ++v) {
+        tex_off[v] = tex_total;
+        tex_total += ((size_t)cams[v].width * cams[v].height * texel + 255) & ~(size_t)255;
+    }
+    if (pool_malloc(&c->d_tex_all, tex_total) != hipSuccess) return failed("allocation of the source textures failed");
+    if (src_u8) c->d_src8.assign(n - 1, nullptr); else c->d_src.assign(n - 1, nullptr);
+    for (int g = 0; g < n_groups; ++g) {
+        const int first = group_first[g], last = group_first[g + 1];
+        if (g > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return failed("upload of the images failed");  // the staging buffers are free again
+        // the rows of the group, dealt to the pool in chunks: memcpy only
+        std::vector<long> row0(last - first + 1, 0);
+        for (int i = first; i < last; ++i) row0[i - first + 1] = row0[i - first] + sh(i);
+        const long total_rows = row0[last - first];
+        std::atomic<long> next(0);
+        const std::function<void()> work = [&]() {
+            const long chunk = 64;
+            for (;;) {
+                const long r0 = next.fetch_add(chunk);
+                if (r0 >= total_rows) return;
+                int k = 0;
+                while (r0 >= row0[k + 1]) ++k;
+                for (long r = r0; r < std::min(r0 + chunk, total_rows);) {
+                    while (r >= row0[k + 1]) ++k;
+                    const int i = first + k, y = (int)(r - row0[k]), w = sw(i);
+                    const long rows = std::min(std::min(r0 + chunk, total_rows), row0[k + 1]) - r;   // of this image in this chunk
+                    const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w;
+                    char* o = stage + (slot[i] - slot[first]) + (size_t)y * w;
+                    const char* in = (const char*)images[i] + (size_t)y * pitch;
+                    if (pitch == (size_t)w)
+                        std::memcpy(o, in, (size_t)rows * w);
+                    else
+                        for (long q = 0; q < rows; ++q) std::memcpy(o + (size_t)q * w, in + (size_t)q * pitch, (size_t)w);
+                    r += rows;
+                }
+            }
+        };
+        row_pool().run(work);
+        for (int i = first; i < last; ++i) {
+            const size_t off = slot[i] - slot[first];
+            if (hipMemcpyAsync(d_stage + off, stage + off, (size_t)sw(i) * sh(i), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                return failed("upload of the images failed");
+        }
+        for (int v = first; v < last; ++v) {
+            const unsigned char* src = (const unsigned char*)d_stage + (slot[v] - slot[first]);
+            const int w = cams[v].width, h = cams[v].height;
+            const IngestSrc s = ingest_src(src, sw(v), sh(v), w, h);
+            if (v == 0) {
+                if (resampled(0))
+                    hipLaunchKernelGGL(k_ingest_pad, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, s, w, h, c->d_ref, kRefApron);
+                else
+                    hipLaunchKernelGGL(k_pad_u8, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, src, w, h, c->d_ref, kRefApron);
+                continue;
+            }
+            ViewDev& o = c->hP.views[v - 1];
+            if (src_u8) {
+                c->d_src8[v - 1] = (uint32_t*)((char*)c->d_tex_all + tex_off[v]);
+                hipLaunchKernelGGL(k_pack_quads_u8, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, src, w, h, (uint2*)c->d_src8[v - 1]);
+                o.pitch8 = w;
+                o.img8 = c->d_src8[v - 1];
+            } else {
+                c->d_src[v - 1] = (float*)((char*)c->d_tex_all + tex_off[v]);
+                const dim3 grid((w + kIngestTW - 1) / kIngestTW, (h + kIngestTH - 1) / kIngestTH);
+                if (resampled(v))
+                    hipLaunchKernelGGL(k_ingest_quads<true>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, (float4*)c->d_src[v - 1]);
+                else
+                    hipLaunchKernelGGL(k_ingest_quads<false>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, (float4*)c->d_src[v - 1]);
+                o.pitch = w;
+                o.img = c->d_src[v - 1];
+            }
+        }
+    }
+    return finish_views(c);
+}
+
+int mpmvs_set_views_u8(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const unsigned char* const* images, const int* src_widths,
+                       const int* src_heights, const size_t* pitch_bytes) {
+    if (!c) return -1;
+    ENTER(c);
+    if (n < 2 || n - 1 > MPMVS_MAX_SRC_VIEWS) return fail(c, -1, "need 2..33 views");
+    if (!cams || !images || (src_widths == nullptr) != (src_heights == nullptr)) return fail(c, -2, "null argument (source widths and heights come together)");
+    for (int i = 0; i < n; ++i) {
+        if (cams[i].width <= 0 || cams[i].height <= 0 || !images[i]) return fail(c, -2, "bad image size or null image");
+        const int sw = src_widths ? src_widths[i] : cams[i].width, sh = src_heights ? src_heights[i] : cams[i].height;
+        if (sw <= 0 || sh <= 0) return fail(c, -2, "bad source image size");
+        if (pitch_bytes && pitch_bytes[i] < (size_t)sw) return fail(c, -2, "row pitch smaller than the source width");
+        if (cams[i].width >= (1 << 24) || cams[i].height >= (1 << 24) || (size_t)cams[i].width * cams[i].height * 16 >= (1ull << 32))
+            return fail(c, -3, "image too large (a view's texture must stay below 4 GB)");
+        if ((size_t)sw * sh >= (1ull << 32)) return fail(c, -3, "source image too large (it must stay below 4 GB)");
+    }
+    free_views(c);
+    const int rc = set_views_u8_impl(c, n, cams, images, src_widths, src_heights, pitch_bytes);
+    if (rc) {  // no half-built Problem is left behind: the context is as after mpmvs_create
+        const std::string why = c->err;
+        free_views(c);
+        c->n_img = c->W = c->H = 0;
+        c->cams.clear();
+        std::memset(&c->hP, 0, sizeof(ProblemDev));
+        c->err = why;
+    }
+    return rc;
+}
+
+int mpmvs_resize_u8(int device, const unsigned char* src, int src_w, int src_h, size_t pitch_bytes, int dst_w, int dst_h, float* out) {
+    if (!src || !out || src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0) return -2;
+    if (pitch_bytes == 0) pitch_bytes = (size_t)src_w;
+    if (pitch_bytes < (size_t)src_w) return -2;
+    if ((size_t)src_w * src_h >= (1ull << 32) || dst_w >= (1 << 24) || dst_h >= (1 << 24)) return -3;
+    if (enter_device(device) != hipSuccess) return -100;
+    DevBuf d_src, d_out;
+    const size_t out_bytes = (size_t)dst_w * dst_h * 4;
+    if (d_src.alloc((size_t)src_w * src_h) != hipSuccess || d_out.alloc(out_bytes) != hipSuccess) return -100;
+    if (hipMemcpy2D(d_src.p, (size_t)src_w, src, pitch_bytes, (size_t)src_w, (size_t)src_h, hipMemcpyHostToDevice) != hipSuccess) return -100;
+    hipLaunchKernelGGL(k_ingest_pad, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, 0,
+                       ingest_src(d_src.as<unsigned char>(), src_w, src_h, dst_w, dst_h), dst_w, dst_h, d_out.as<float>(), 0);
+    if (hipGetLastError() != hipSuccess) return -100;
+    if (hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return -100;   // waits for the kernel
+    return 0;
 }
 
 static int attach_depths(mpmvs_ctx* c, int n_src, const int* widths, const int* heights) {

@@ -42,6 +42,8 @@ _EXTRA = {
     "view_select": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "view_select_kernel_ms": (C.c_float, []),
     "dbg_chain_stall": (C.c_int, [_P, C.c_int, C.c_int]),
+    "set_views_u8": (C.c_int, [_P, C.c_int, C.POINTER(_abi.Camera), C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
+    "resize_u8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P]),
     "eval_ncc_multi": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx"]
@@ -223,6 +225,21 @@ def peer_info(device, peer):
     if fns["peer_info"](int(device), int(peer), C.byref(a), C.byref(b), C.byref(c)) != 0:
         raise RuntimeError(f"mpmvs_peer_info({device}, {peer}) failed")
     return a.value, b.value, c.value
+
+
+def resize_u8(img, new_w, new_h, device=0):
+    """the resampling of set_views_u8 on its own (mpmvs_resize_u8): uint8 [h, w] -> float32 [new_h, new_w], equal bit for bit to
+    hostlib.resize_linear of the widened image"""
+    _, fns = load()
+    im = np.asarray(img)
+    assert im.dtype == np.uint8 and im.ndim == 2, (im.dtype, im.shape)
+    if im.strides[1] != 1 or im.strides[0] < im.shape[1]:
+        im = np.ascontiguousarray(im)
+    out = np.empty((int(new_h), int(new_w)), np.float32)
+    rc = fns["resize_u8"](int(device), im.ctypes.data, im.shape[1], im.shape[0], im.strides[0], int(new_w), int(new_h), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"mpmvs_resize_u8 failed ({rc})")
+    return out
 
 
 def device_count():

@@ -178,12 +178,26 @@ class HostArray {
 // adopts it instead of uploading the images again.  Opaque here; owned by the Problem's reference Scene.
 struct ProblemDeviceCache;
 
+// 8-bit image as cv::imread returns it (interleaved channels; colour = B,G,R)
+struct Image8 {
+    int rows = 0, cols = 0, ch = 1;
+    std::vector<unsigned char> data;
+    bool empty() const { return data.empty(); }
+};
+
 // reference include/utility.h:17-26 (+ in-memory results instead of .dmb files)
 struct Scene {
     bool estimate = false;
     int refID = 0;
     std::vector<int> srcID;  // srcID[0] is the image itself, then its source views
-    Image image;             // grey, fp32 0..255
+    Image image;             // grey, fp32 0..255: filled by a caller that hands fp32 arrays in (mpmvs_host_run_pipeline); empty for a
+                             // Scene read from a folder, which keeps ...
+    Image8 image8;           // ... the decoded bytes at the FILE's size: a quarter of the fp32 image, shrunk on the device
+    int target_cols = 0, target_rows = 0;   // image8 only: the size the Problems run at, set by AdjustImageScale together with the scaled K
+    // the size every consumer of the Scene works at (result maps, exchange buffers, fusion)
+    int cols() const { return image8.empty() ? image.cols : (target_cols ? target_cols : image8.cols); }
+    int rows() const { return image8.empty() ? image.rows : (target_rows ? target_rows : image8.rows); }
+    bool has_image() const { return !image.empty() || !image8.empty(); }
     Camera cam{};            // what ReadCamera() would return for this image
     Image depth;             // last estimated depth map        (depths.dmb)
     Image normal;            // last estimated world normals    (normals.dmb)
@@ -213,13 +227,16 @@ mpmvs_ctx* ResidentResultContext(const Scene& s, int consumer_device = -1);
 
 // bilinear resize used by PatchMatchInit's "Adjust image scale" (reference src/PatchMatch.cpp:893-925)
 Image ResizeLinear(const Image& src, int new_cols, int new_rows);
-// that step for one Scene: an image above s.max_image_size is shrunk in place and s.cam.K follows (no-op otherwise)
+// that step for one Scene: an image above s.max_image_size is shrunk in place and s.cam.K follows (no-op otherwise).  A Scene that
+// holds bytes (image8) only gets its target size and the scaled K -- same arithmetic, cached as a pair like the shrunk image --
+// and is resampled on the device by mpmvs_set_views_u8.
 void AdjustImageScale(Scene& s);
 
 class PatchMatchCUDA {
    private:
     int num_img = 0;
     std::vector<const Image*> images;
+    std::vector<const Image8*> images8;  // the views as bytes (Scenes read from a folder): all of them or none
     std::vector<const Image*> depths;  // source depth maps of the previous pass (owned by the Scenes)
     std::vector<const Scene::DeviceDepth*> depth_slots;  // ... and where each lies in HBM, if it does (Scene::device_depth)
     std::vector<Camera> cameras;
@@ -270,7 +287,8 @@ class PatchMatchCUDA {
     float GetMaxDepth();
     int GetReferenceImageWidth();
     int GetReferenceImageHeight();
-    const Image& GetReferenceImage();
+    const Image& GetReferenceImage();           // the fp32 image; empty for a Scene that holds bytes
+    const void* ViewBuffer(size_t i) const;     // the host buffer view i is uploaded from (bytes or fp32): identity of a resident context's contents
     const Camera& GetReferenceCamera() const { return cameras[0]; }
     float4 GetPlaneHypothesis(const int index);
     const float4* GetPlaneHypotheses() {  // the whole hostPlaneHypotheses array (no per-pixel call)

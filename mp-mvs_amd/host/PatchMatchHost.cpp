@@ -53,7 +53,7 @@ Image ResizeLinear(const Image& src, int new_cols, int new_rows) {
 struct ProblemDeviceCache {
     mpmvs_ctx* ctx = nullptr;
     int device = -1;
-    std::vector<const float*> image_data;
+    std::vector<const void*> image_data;   // the fp32 or byte buffers of the views it was filled from
     std::vector<Camera> cameras;
     uint64_t state_stamp = 0;            // Image::stamp of the maps whose state (planes, costs) the context holds
     std::vector<uint64_t> depth_stamps;  // ... of the source depth maps it holds
@@ -223,15 +223,27 @@ struct StageTimer {
 
 void AdjustImageScale(Scene& s) {
     const int max_image_size = s.max_image_size;
-    if (s.image.empty() || (s.image.cols <= max_image_size && s.image.rows <= max_image_size)) return;
-    const float factor_x = static_cast<float>(max_image_size) / s.image.cols;
-    const float factor_y = static_cast<float>(max_image_size) / s.image.rows;
+    const bool bytes = !s.image8.empty();
+    if (bytes && s.target_cols) return;   // done before: target size and K are a cached pair
+    const int cols = bytes ? s.image8.cols : s.image.cols, rows = bytes ? s.image8.rows : s.image.rows;
+    if (bytes) {
+        s.target_cols = cols;
+        s.target_rows = rows;
+    }
+    if (!s.has_image() || (cols <= max_image_size && rows <= max_image_size)) return;
+    const float factor_x = static_cast<float>(max_image_size) / cols;
+    const float factor_y = static_cast<float>(max_image_size) / rows;
     const float factor = std::min(factor_x, factor_y);
-    const int new_cols = (int)std::round(s.image.cols * factor);
-    const int new_rows = (int)std::round(s.image.rows * factor);
-    const float scale_x = new_cols / static_cast<float>(s.image.cols);
-    const float scale_y = new_rows / static_cast<float>(s.image.rows);
-    s.image = ResizeLinear(s.image, new_cols, new_rows);
+    const int new_cols = (int)std::round(cols * factor);
+    const int new_rows = (int)std::round(rows * factor);
+    const float scale_x = new_cols / static_cast<float>(cols);
+    const float scale_y = new_rows / static_cast<float>(rows);
+    if (bytes) {   // resampled on the device (mpmvs_set_views_u8)
+        s.target_cols = new_cols;
+        s.target_rows = new_rows;
+    } else {
+        s.image = ResizeLinear(s.image, new_cols, new_rows);
+    }
     s.cam.K[0] *= scale_x;
     s.cam.K[2] *= scale_x;
     s.cam.K[4] *= scale_y;
@@ -241,6 +253,7 @@ void AdjustImageScale(Scene& s) {
 void PatchMatchCUDA::PatchMatchInit(std::vector<Scene>& Scenes, const int ID) {
     ref_scene = &Scenes[ID];
     images.clear();
+    images8.clear();
     depths.clear();
     depth_slots.clear();
     cameras.clear();
@@ -251,20 +264,28 @@ void PatchMatchCUDA::PatchMatchInit(std::vector<Scene>& Scenes, const int ID) {
     // shrunk image, so the scaled intrinsics are cached with it (s.cam) -- a later call finds a consistent pair.
     for (int i = 0; i < num_img; ++i) {
         Scene& s = Scenes[srcID[i]];
-        if (s.image.empty()) {
+        if (!s.has_image()) {
             std::cout << "Can not read this image !" << srcID[i] << std::endl;
             exit(EXIT_FAILURE);
         }
         AdjustImageScale(s);
     }
+    int n_bytes = 0;
     for (int i = 0; i < num_img; ++i) {
         Scene& s = Scenes[srcID[i]];
         images.push_back(&s.image);
+        n_bytes += s.image8.empty() ? 0 : 1;
         Camera cam = s.cam;
-        cam.height = s.image.rows;
-        cam.width = s.image.cols;
+        cam.height = s.rows();
+        cam.width = s.cols();
         cameras.push_back(cam);
     }
+    if (n_bytes != 0 && n_bytes != num_img) {   // (no shipped path mixes them: a folder gives bytes, a caller's arrays are fp32)
+        std::cout << "The views of a Problem must all be 8-bit or all be fp32 images !" << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    if (n_bytes)
+        for (int i = 0; i < num_img; ++i) images8.push_back(&Scenes[srcID[i]].image8);
     params.depth_min = cameras[0].depth_min * 0.6f;  // reference :929-930
     params.depth_max = cameras[0].depth_max * 1.2f;
     params.num_images = num_img;
@@ -291,7 +312,7 @@ void PatchMatchCUDA::AllocatePatchMatch() {
         ref_scene->device_cache.reset();
         bool same = cached->ctx && cached->device == device && cached->image_data.size() == images.size() &&
                     std::memcmp(cached->cameras.data(), cameras.data(), cameras.size() * sizeof(Camera)) == 0;
-        for (size_t i = 0; same && i < images.size(); ++i) same = cached->image_data[i] == images[i]->data.data();
+        for (size_t i = 0; same && i < images.size(); ++i) same = cached->image_data[i] == ViewBuffer(i);
         if (same) {
             ctx = cached->ctx;
             cached->ctx = nullptr;
@@ -323,13 +344,25 @@ void PatchMatchCUDA::AllocatePatchMatch() {
 
 // reference src/PatchMatch.cpp:998-1089
 void PatchMatchCUDA::CudaMemInit(Scene& scene) {
-    std::vector<const float*> ptrs;
-    std::vector<size_t> pitches;
-    for (int i = 0; i < num_img; ++i) {
-        ptrs.push_back(images[i]->data.data());
-        pitches.push_back((size_t)images[i]->cols * sizeof(float));
+    if (!views_resident && !images8.empty()) {
+        // Scenes read from a folder: the bytes the files decoded to, at the files' size; the device shrinks what is oversized
+        std::vector<const unsigned char*> ptrs;
+        std::vector<int> ws, hs;
+        for (const Image8* im : images8) {
+            ptrs.push_back(im->data.data());
+            ws.push_back(im->cols);
+            hs.push_back(im->rows);
+        }
+        check(mpmvs_set_views_u8(ctx, num_img, cameras.data(), ptrs.data(), ws.data(), hs.data(), nullptr), "mpmvs_set_views_u8");
+    } else if (!views_resident) {
+        std::vector<const float*> ptrs;
+        std::vector<size_t> pitches;
+        for (int i = 0; i < num_img; ++i) {
+            ptrs.push_back(images[i]->data.data());
+            pitches.push_back((size_t)images[i]->cols * sizeof(float));
+        }
+        check(mpmvs_set_views(ctx, num_img, cameras.data(), ptrs.data(), pitches.data()), "mpmvs_set_views");
     }
-    if (!views_resident) check(mpmvs_set_views(ctx, num_img, cameras.data(), ptrs.data(), pitches.data()), "mpmvs_set_views");
     host_state_valid = false;
     if (params.geom_consistency) {
         std::vector<const float*> dptr;
@@ -470,6 +503,7 @@ float PatchMatchCUDA::GetMaxDepth() { return params.depth_max; }
 int PatchMatchCUDA::GetReferenceImageWidth() { return cameras[0].width; }
 int PatchMatchCUDA::GetReferenceImageHeight() { return cameras[0].height; }
 const Image& PatchMatchCUDA::GetReferenceImage() { return *images[0]; }
+const void* PatchMatchCUDA::ViewBuffer(size_t i) const { return images8.empty() ? (const void*)images[i]->data.data() : (const void*)images8[i]->data.data(); }
 float4 PatchMatchCUDA::GetPlaneHypothesis(const int index) {
     fetch_host_state();
     return hostPlaneHypotheses[index];
@@ -527,7 +561,7 @@ void PatchMatchCUDA::Release(std::vector<Scene>&, const int&) {
             auto keep = std::make_shared<ProblemDeviceCache>();
             keep->ctx = ctx;
             keep->device = device;
-            for (const Image* im : images) keep->image_data.push_back(im->data.data());
+            for (size_t i = 0; i < images.size(); ++i) keep->image_data.push_back(ViewBuffer(i));
             keep->cameras = cameras;
             keep->state_stamp = resident_state_stamp;
             keep->depth_stamps = resident_depth_stamps;

@@ -16,6 +16,7 @@
 #include <thread>
 #include <cfloat>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -256,6 +257,19 @@ bool readGrayImage(const std::string& path, Image& img) {
     return true;
 }
 
+bool readGrayImage8(const std::string& path, Image8& img) { return read_image8(path, 1, img); }
+
+bool readSceneImage(const std::string& path, Scene& s) {
+    const char* e = std::getenv("MPMVS_HOST_FLOAT_IMAGES");
+    s.target_cols = s.target_rows = 0;
+    if (e && std::atoi(e) != 0) {
+        s.image8 = Image8();
+        return readGrayImage(path, s.image);
+    }
+    s.image = Image();
+    return readGrayImage8(path, s.image8);
+}
+
 bool readColorImage(const std::string& path, Image8& bgr) { return read_image8(path, 3, bgr); }
 
 bool writeGrayImage(const std::string& path, const Image8& img) {
@@ -314,8 +328,8 @@ void ProcessProblem(const std::string& input_folder, const std::string& output_f
     // PatchMatchInit's file half (reference :871-890, :934-950, :1052-1063)
     for (int sid : scene.srcID) {
         Scene& s = Scenes[sid];
-        if (s.image.empty()) {
-            if (!readGrayImage(FindImageFile(input_folder + "/images", sid), s.image)) {
+        if (!s.has_image()) {
+            if (!readSceneImage(FindImageFile(input_folder + "/images", sid), s)) {
                 std::cout << "Can not read this image !" << input_folder + "/images/" + id8(sid) + ".jpg" << std::endl;
                 exit(EXIT_FAILURE);
             }
@@ -367,7 +381,7 @@ int RunFolderJacobi(const std::string& input_folder, int max_src, int max_image_
     for (int i = 0; i < n; ++i) {
         if (!needed[i]) continue;
         Scene& s = Scenes[i];
-        if (!readGrayImage(FindImageFile(input_folder + "/images", i), s.image)) {
+        if (!readSceneImage(FindImageFile(input_folder + "/images", i), s)) {
             ok = false;
             continue;
         }
@@ -397,7 +411,7 @@ int RunFolderJacobi(const std::string& input_folder, int max_src, int max_image_
         for (size_t k = 0; k < todo.size(); ++k) {
             Scene& s = Scenes[todo[k]];
             const int device = devices[k % devices.size()];
-            const size_t bytes = (size_t)s.image.rows * s.image.cols * sizeof(float);
+            const size_t bytes = (size_t)s.rows() * s.cols() * sizeof(float);
             for (Scene::DeviceDepth* slot : {&s.device_depth, &s.device_depth_next}) {
                 slot->ptr = static_cast<float*>(mpmvs_device_alloc(device, bytes));
                 slot->device = device;

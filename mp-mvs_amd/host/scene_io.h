@@ -29,15 +29,15 @@ void StoreColorPlyFileBinaryPointCloud(const std::string& plyFilePath, const std
 // there without an upload (mpmvs_fuse_ply_ctx); cameras, colour images and sky masks are read as before.  Same PLY, byte for byte.
 long RunFusion(const std::string& input_folder, const std::string& output_folder, std::vector<Scene>& Scenes, bool use_dynamic_consistency, int device = 0,
                bool sky_seg = false, bool resident = false);
-// 8-bit image as cv::imread returns it (interleaved channels; colour = B,G,R)
-struct Image8 {
-    int rows = 0, cols = 0, ch = 1;
-    std::vector<unsigned char> data;
-    bool empty() const { return data.empty(); }
-};
 // cv::imread(path, IMREAD_GRAYSCALE) + convertTo(CV_32F) (reference src/PatchMatch.cpp:877-882): JPEG (own decoder,
 // jpeg_decode.h), binary PGM (P5) or PPM (P6, converted with OpenCV's fixed-point BGR2GRAY weights); format by content
 bool readGrayImage(const std::string& path, Image& img);
+// the same without the convertTo: the bytes imread returns, which is what the 8-bit entry takes (mpmvs_set_views_u8)
+bool readGrayImage8(const std::string& path, Image8& img);
+// The grey image of a Scene that is read from a folder: the decoded bytes at the file's size (Scene::image8).  With
+// MPMVS_HOST_FLOAT_IMAGES=1 in the environment (read on every call; for A/B runs) the image is widened to fp32 into Scene::image as
+// before the 8-bit entry existed: AdjustImageScale then shrinks it on the host and CudaMemInit takes mpmvs_set_views.
+bool readSceneImage(const std::string& path, Scene& s);
 // cv::imread(path, IMREAD_COLOR) (reference :324): JPEG, PPM or PGM -> 3 channels B,G,R
 bool readColorImage(const std::string& path, Image8& bgr);
 bool writeGrayImage(const std::string& path, const Image8& img);  // binary PGM
