@@ -310,6 +310,62 @@ int mpmvs_sky_bilateral(int device, const unsigned char* bgr, const float* mask,
 /* device time (ms, HIP events) of the kernel of the last mpmvs_sky_bilateral call */
 float mpmvs_sky_kernel_ms(void);
 
+/* ---- sky-segmentation network ------------ */
+/* The network that produces the coarse sky mask: the reference loads an ncnn .param / .bin pair (SkySegment::SkySegment,
+ * SkySegment/src/SkyRegionDetect.cpp:541-547) and runs it through ncnn on the CPU (maskExtractor, :549-561).  Here the pair is
+ * data for an inference engine on the device (csrc/pm_skyseg.hpp).  Supported operators: Input, Convolution (3x3 with pad =
+ * dilation, or 1x1; stride 1, group 1; activation none / ReLU / sigmoid; weight tag 0x01306B47 = fp16 or 0 = fp32), Pooling (max
+ * 2x2 stride 2, ncnn's default pad mode = ceil mode), Interp (bilinear to a fixed size, no align_corner), BinaryOp (sum of two
+ * blobs), Concat (channels), Split, Sigmoid.  Anything else is refused at load with one of the codes below and a
+ * mpmvs_last_error(NULL) text that names the layer (the text is per host thread, as after a failed mpmvs_create). */
+#define MPMVS_SKYSEG_E_FILE (-20)     /* a file cannot be read */
+#define MPMVS_SKYSEG_E_MAGIC (-21)    /* not an ncnn text .param: wrong magic, or a malformed count / layer line */
+#define MPMVS_SKYSEG_E_LAYER (-22)    /* unknown layer type (also: a second Input, a Concat along another axis) */
+#define MPMVS_SKYSEG_E_CONV (-23)     /* Convolution with stride != 1, group != 1, a non-square kernel, another kernel / pad / activation */
+#define MPMVS_SKYSEG_E_TAG (-24)      /* int8 or unknown weight tag */
+#define MPMVS_SKYSEG_E_POOL (-25)     /* Pooling other than max 2x2 stride 2 */
+#define MPMVS_SKYSEG_E_INTERP (-26)   /* Interp other than bilinear to a fixed size without align_corner */
+#define MPMVS_SKYSEG_E_BINARY (-27)   /* BinaryOp other than the sum of two blobs */
+#define MPMVS_SKYSEG_E_ORDER (-28)    /* a blob is read before it is written (or written twice) */
+#define MPMVS_SKYSEG_E_SHORT (-29)    /* the .bin ends before the last weight */
+#define MPMVS_SKYSEG_E_LEFTOVER (-30) /* the .bin has bytes left over after the last weight */
+#define MPMVS_SKYSEG_E_SHAPE (-31)    /* the graph does not close for the given input size (Concat / sum of different sizes, channel count) */
+#define MPMVS_SKYSEG_E_OUTPUT (-32)   /* no blob of the requested output name */
+#define MPMVS_SKYSEG_E_NOKEEP (-33)   /* mpmvs_skyseg_blob without keep mode, or before the first run in keep mode */
+#define MPMVS_SKYSEG_E_NOBLOB (-34)   /* mpmvs_skyseg_blob: no live blob of that name */
+#define MPMVS_SKYSEG_MAX_CONCAT 6     /* most parts a Concat that feeds a Convolution may have */
+typedef struct mpmvs_skyseg mpmvs_skyseg;
+/* What the loader makes of the pair for an in_h x in_w input, without touching a device: counts[0] layers, [1] blobs (as the
+ * .param declares them), [2] convolutions, [3] live layers (those output_blob depends on; NULL / "" = the last layer's output),
+ * [4] bytes of the .bin consumed, [5] multiply-adds of all convolutions per image.  0 or a code above (-2: bad argument). */
+int mpmvs_skyseg_inspect(const char* param_path, const char* bin_path, int in_h, int in_w, const char* output_blob, long long counts[6]);
+/* Net::load_param + load_model (SkyRegionDetect.cpp:543-546): reads the pair, repacks the weights for the matrix instruction,
+ * plans one arena for the intermediate blobs by liveness and uploads.  A failed load leaves no device allocation behind. */
+int mpmvs_skyseg_load(int device, const char* param_path, const char* bin_path, int in_h, int in_w, const char* output_blob, mpmvs_skyseg** net);
+/* ex.input + ex.extract (SkyRegionDetect.cpp:553-556): the bare network.  chw_fp32_in = input channels x in_h x in_w floats,
+ * out = the output blob (channels x height x width floats); host buffers.  Blocks until done.  Deterministic. */
+int mpmvs_skyseg_run(mpmvs_skyseg* net, const float* chw_fp32_in, float* out);
+/* maskExtractor (SkyRegionDetect.cpp:549-561) with the pyrDown loop in front of it (src/PatchMatch.cpp:16-18): bgr = h rows of w
+ * B,G,R byte triples, pitch_bytes apart (0 = tightly packed).  While h > 768 and w > 768 the image is halved (5x5 binomial,
+ * reflect-101 border, (s + 128) >> 8, size (w / 2, h / 2)); then resized to the network's input size with the ResizeLinear
+ * geometry, rounded to bytes, split into R,G,B planes and normalised ((v - mean) * norm with the reference's constants); then
+ * the network runs.  All on the device.  out_prob = the output blob.  The network must take 3 channels (-2 otherwise). */
+int mpmvs_skyseg_run_u8(mpmvs_skyseg* net, const unsigned char* bgr, int h, int w, size_t pitch_bytes, float* out_prob);
+/* probe: only the preprocessing of mpmvs_skyseg_run_u8; out_chw receives the 3 x in_h x in_w floats the network would be given */
+int mpmvs_skyseg_preprocess_u8(mpmvs_skyseg* net, const unsigned char* bgr, int h, int w, size_t pitch_bytes, float* out_chw);
+/* keep != 0: every blob gets its own place in the arena (no reuse), so that mpmvs_skyseg_blob can fetch any of them after a
+ * run; 0 (the default) plans by liveness again.  The results are the same bits either way. */
+int mpmvs_skyseg_set_keep(mpmvs_skyseg* net, int keep);
+/* the blob `name` of the last run (keep mode only): dims[0..2] = channels, height, width (always written when the blob exists);
+ * out may be NULL to ask for the size alone.  A Concat result is assembled here, on the way out. */
+int mpmvs_skyseg_blob(mpmvs_skyseg* net, const char* name, float* out, int dims[3]);
+/* shape of the input and of the output blob: dims[0..2] input c, h, w, dims[3..5] output c, h, w; kernel launches per run in dims[6] */
+int mpmvs_skyseg_dims(const mpmvs_skyseg* net, int dims[7]);
+/* device time (ms, HIP events) of the last run: the kernels of the network, without the copies; for mpmvs_skyseg_run_u8
+ * *pre_ms (may be NULL) receives the time of the preprocessing kernels in front of it */
+float mpmvs_skyseg_ms(const mpmvs_skyseg* net, float* pre_ms);
+void mpmvs_skyseg_destroy(mpmvs_skyseg* net);
+
 /* ---- view selection of a COLMAP sparse model (tools/colmap2mvs.py) ------------ */
 /* The pair scores and per-image view lists of the reference's colmap2mvsnet_acm.py (calc_score, then the reversed
  * argsort of each score row), restated point-major (csrc/pm_viewsel.hpp, contract in DESIGN.md section 11).

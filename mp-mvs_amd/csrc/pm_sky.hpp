@@ -2,8 +2,8 @@
 // the reference's only other device kernel, Pixel_bilateral_filter
 // (SkySegment/src/SkyRegionDetect.cu:3-34).  Per pixel: a 37 x 37 window, weight
 // exp(-|offset| / 72 - |colour difference| / 8), weighted mean of the coarse mask,
-// threshold 0.6 -> 255 / 0.  The segmentation network that produces the coarse mask is
-// outside the scope (external runtime); the filter and the mask's use in fusion are here.
+// threshold 0.6 -> 255 / 0.  The segmentation network that produces the coarse mask is in
+// pm_skyseg.hpp; the filter and the mask's use in fusion are here.
 //
 // Arithmetic (canonical): IEEE sqrt and division, own exp; the
 // reference's tap order (x offset outer, y offset inner) is kept, out-of-image taps

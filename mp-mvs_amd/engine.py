@@ -44,6 +44,16 @@ _EXTRA = {
     "dbg_chain_stall": (C.c_int, [_P, C.c_int, C.c_int]),
     "set_views_u8": (C.c_int, [_P, C.c_int, C.POINTER(_abi.Camera), C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "resize_u8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P]),
+    "skyseg_inspect": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_longlong)]),
+    "skyseg_load": (C.c_int, [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),
+    "skyseg_run": (C.c_int, [_P, _P, _P]),
+    "skyseg_run_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, _P]),
+    "skyseg_preprocess_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_size_t, _P]),
+    "skyseg_set_keep": (C.c_int, [_P, C.c_int]),
+    "skyseg_blob": (C.c_int, [_P, C.c_char_p, _P, C.POINTER(C.c_int)]),
+    "skyseg_dims": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "skyseg_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "skyseg_destroy": (None, [_P]),
     "eval_ncc_multi": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx"]
@@ -240,6 +250,116 @@ def resize_u8(img, new_w, new_h, device=0):
     if rc != 0:
         raise RuntimeError(f"mpmvs_resize_u8 failed ({rc})")
     return out
+
+
+class SkySegError(RuntimeError):
+    """a refused model or call of the sky-segmentation engine; .code is the negative code of include/mpmvs.h"""
+
+    def __init__(self, what, code, text):
+        super().__init__(f"{what} failed ({code}): {text}")
+        self.code = code
+        self.text = text
+
+
+def _skyseg_raise(fns, what, rc):
+    msg = fns["last_error"](None)
+    raise SkySegError(what, rc, msg.decode() if msg else "")
+
+
+SKYSEG_COUNTS = ("layers", "blobs", "convolutions", "live_layers", "weight_bytes", "macs")
+
+
+def skyseg_inspect(param_path, bin_path, in_h=384, in_w=384, output_blob=None):
+    """what the loader makes of an ncnn .param / .bin pair (mpmvs_skyseg_inspect), as a dict; touches no device"""
+    _, fns = load()
+    counts = (C.c_longlong * 6)()
+    rc = fns["skyseg_inspect"](str(param_path).encode(), str(bin_path).encode(), int(in_h), int(in_w),
+                               output_blob.encode() if output_blob else None, counts)
+    if rc != 0:
+        _skyseg_raise(fns, "skyseg_inspect", rc)
+    return dict(zip(SKYSEG_COUNTS, (int(v) for v in counts)))
+
+
+class SkySeg:
+    """The sky-segmentation network on one MI355X (mpmvs_skyseg_*): the reference's SkySegment object
+    (reference SkySegment/src/SkyRegionDetect.cpp:541-561).  There is no CPU path."""
+
+    def __init__(self, param_path, bin_path, in_h=384, in_w=384, output_blob=None, device=0):
+        _, self._f = load()
+        net = C.c_void_p(None)
+        rc = self._f["skyseg_load"](int(device), str(param_path).encode(), str(bin_path).encode(), int(in_h), int(in_w),
+                                    output_blob.encode() if output_blob else None, C.byref(net))
+        self._net = None
+        if rc != 0:
+            _skyseg_raise(self._f, "skyseg_load", rc)
+        self._net = net
+        d = (C.c_int * 7)()
+        self._f["skyseg_dims"](self._net, d)
+        self.in_shape, self.out_shape, self.launches = tuple(d[0:3]), tuple(d[3:6]), int(d[6])
+
+    def close(self):
+        if self._net:
+            self._f["skyseg_destroy"](self._net)
+            self._net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            _skyseg_raise(self._f, what, rc)
+
+    def run(self, chw):
+        """the bare network: float32 [c, h, w] -> the output blob [c', h', w']"""
+        x = np.ascontiguousarray(chw, np.float32)
+        if x.shape != self.in_shape:
+            raise SkySegError("skyseg_run", -2, f"input of shape {x.shape}, the network takes {self.in_shape}")
+        out = np.empty(self.out_shape, np.float32)
+        self._chk(self._f["skyseg_run"](self._net, x.ctypes.data, out.ctypes.data), "skyseg_run")
+        return out
+
+    @staticmethod
+    def _bgr(img):
+        im = np.asarray(img)
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise SkySegError("skyseg_run_u8", -2, f"need a uint8 [h, w, 3] B,G,R image, got {im.dtype} {im.shape}")
+        if im.strides[2] != 1 or im.strides[1] != 3 or im.strides[0] < 3 * im.shape[1]:
+            im = np.ascontiguousarray(im)
+        return im
+
+    def run_u8(self, bgr):
+        """maskExtractor with the pyrDown loop in front: uint8 [h, w, 3] (B,G,R) -> the output blob"""
+        im = self._bgr(bgr)
+        out = np.empty(self.out_shape, np.float32)
+        self._chk(self._f["skyseg_run_u8"](self._net, im.ctypes.data, im.shape[0], im.shape[1], im.strides[0], out.ctypes.data), "skyseg_run_u8")
+        return out
+
+    def preprocess_u8(self, bgr):
+        """probe: what run_u8 feeds the network, float32 [3, in_h, in_w]"""
+        im = self._bgr(bgr)
+        out = np.empty(self.in_shape, np.float32)
+        self._chk(self._f["skyseg_preprocess_u8"](self._net, im.ctypes.data, im.shape[0], im.shape[1], im.strides[0], out.ctypes.data), "skyseg_preprocess_u8")
+        return out
+
+    def set_keep(self, keep=True):
+        """keep every blob of a run (no buffer reuse) so that blob() can fetch it"""
+        self._chk(self._f["skyseg_set_keep"](self._net, 1 if keep else 0), "skyseg_set_keep")
+
+    def blob(self, name):
+        d = (C.c_int * 3)()
+        self._chk(self._f["skyseg_blob"](self._net, name.encode(), None, d), "skyseg_blob")
+        out = np.empty(tuple(d), np.float32)
+        self._chk(self._f["skyseg_blob"](self._net, name.encode(), out.ctypes.data, d), "skyseg_blob")
+        return out
+
+    def ms(self):
+        """(network ms, preprocessing ms) of the last run, device time"""
+        pre = C.c_float(0.0)
+        net = self._f["skyseg_ms"](self._net, C.byref(pre))
+        return float(net), float(pre.value)
 
 
 def device_count():

@@ -548,6 +548,116 @@ int RefineSkyMasks(const std::string& input_folder, const std::vector<Scene>& Sc
 }
 
 // ---------------------------------------------------------------------------
+// the segmentation network in front of the refinement (reference src/PatchMatch.cpp:4-57, SkySegment/src/SkyRegionDetect.cpp:541-561)
+// ---------------------------------------------------------------------------
+static int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
+    return i;
+}
+
+// cv::pyrDown(src, dst, Size(cols / 2, rows / 2)) of an 8-bit image: 5x5 binomial [1 4 6 4 1]^2 / 256 around (2x, 2y),
+// reflect-101 border, (s + 128) >> 8.  Restated from OpenCV's documented behaviour, not pinned against its output.
+Image8 PyrDown8(const Image8& src) {
+    Image8 out;
+    out.rows = src.rows / 2;
+    out.cols = src.cols / 2;
+    out.ch = src.ch;
+    out.data.resize((size_t)out.rows * out.cols * out.ch);
+    static const int kw[5] = {1, 4, 6, 4, 1};
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < out.rows; ++y)
+        for (int x = 0; x < out.cols; ++x)
+            for (int c = 0; c < src.ch; ++c) {
+                int s = 0;
+                for (int j = 0; j < 5; ++j) {
+                    const int yy = reflect101(2 * y + j - 2, src.rows);
+                    int row = 0;
+                    for (int k = 0; k < 5; ++k) row += kw[k] * (int)src.data[((size_t)yy * src.cols + reflect101(2 * x + k - 2, src.cols)) * src.ch + c];
+                    s += kw[j] * row;
+                }
+                out.data[((size_t)y * out.cols + x) * out.ch + c] = (unsigned char)((s + 128) >> 8);
+            }
+    return out;
+}
+
+// What mpmvs_skyseg_run_u8 feeds the network, stated on the host: the pyrDown loop (src/PatchMatch.cpp:16-18), the resize to the
+// network's size with ResizeLinear8 (ncnn's from_pixels_resize resizes the bytes; its fixed-point coefficients are not
+// reproduced: parity unpinned), B,G,R -> R,G,B planes, (v - mean) * norm (SkyRegionDetect.cpp:627-630).  3 planes, planar.
+Image SkyPreprocess(const Image8& bgr, int net_rows, int net_cols) {
+    Image8 img = bgr;
+    while (img.rows > 768 && img.cols > 768) img = PyrDown8(img);
+    const Image8 small = (img.rows != net_rows || img.cols != net_cols) ? ResizeLinear8(img, net_cols, net_rows) : img;
+    const float mean_vals[3] = {0.485f * 255.f, 0.456f * 255.f, 0.406f * 255.f};
+    const float norm_vals[3] = {1 / 0.229f / 255.f, 1 / 0.224f / 255.f, 1 / 0.225f / 255.f};
+    Image out(3 * net_rows, net_cols, 1);  // three planes one below the other
+    const size_t hw = (size_t)net_rows * net_cols;
+    for (int c = 0; c < 3; ++c)
+        for (size_t i = 0; i < hw; ++i) out.data[c * hw + i] = ((float)small.data[i * 3 + (2 - c)] - mean_vals[c]) * norm_vals[c];
+    return out;
+}
+
+SkySegment::SkySegment(const char* param, const char* model, int device) {
+    if (mpmvs_skyseg_load(device, param, model, 384, 384, "1959", &net_) != 0) {  // input size and output blob: SkyRegionDetect.cpp:627,636
+        std::cout << "SkySegment: " << mpmvs_last_error(nullptr) << std::endl;
+        net_ = nullptr;
+    }
+}
+SkySegment::~SkySegment() {
+    if (net_) mpmvs_skyseg_destroy(net_);
+}
+Image SkySegment::maskExtractor(const Image8& bgr) {
+    Image out;
+    if (!net_ || bgr.ch != 3 || bgr.empty()) return out;
+    out = Image(384, 384, 1);
+    if (mpmvs_skyseg_run_u8(net_, bgr.data.data(), bgr.rows, bgr.cols, 0, out.data.data()) != 0) {
+        std::cout << "SkySegment: " << mpmvs_last_error(nullptr) << std::endl;
+        return Image();
+    }
+    return out;
+}
+
+int GenerateSkyRegionMask(const std::string& input_folder, const std::vector<Scene>& Scenes, const std::string& model_dir, int max_image_size, int device) {
+    const std::string stem = model_dir + "/skysegsmall_sim-opt-fp16";  // the file names of the reference (src/PatchMatch.cpp:5-6)
+    SkySegment Skyseg((stem + ".param").c_str(), (stem + ".bin").c_str(), device);
+    if (!Skyseg.ok()) return -1;
+    int written = 0;
+    for (const Scene& s : Scenes) {
+        Image8 bgr;
+        if (!readColorImage(FindImageFile(input_folder + "/images", s.refID), bgr)) return -1;
+        const Image prob = Skyseg.maskExtractor(bgr);  // runs the pyrDown loop of :16-18 on the device
+        if (prob.empty()) return -1;
+        int w = bgr.cols, h = bgr.rows;
+        if (bgr.cols > max_image_size || bgr.rows > max_image_size) {  // :24-32
+            const float factor = std::min((float)max_image_size / bgr.cols, (float)max_image_size / bgr.rows);
+            w = (int)std::round(bgr.cols * factor);
+            h = (int)std::round(bgr.rows * factor);
+            bgr = ResizeLinear8(bgr, w, h);
+        }
+        const Image mask = ResizeLinear(prob, w, h);  // :34, the fp32 mask: the reference refines it as it is and only STORES 8 bits
+        Image refined;
+        if (!bilateral_filter(bgr, mask, refined, device)) return -1;
+        Image8 coarse8, out;
+        coarse8.rows = out.rows = h;
+        coarse8.cols = out.cols = w;
+        coarse8.ch = out.ch = 1;
+        coarse8.data.resize(mask.data.size());
+        out.data.resize(refined.data.size());
+        for (size_t i = 0; i < mask.data.size(); ++i) {  // 255 * mask, saturate-rounded (:44)
+            const float v = std::nearbyintf(255.0f * mask.data[i]);
+            coarse8.data[i] = (unsigned char)(v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v);
+        }
+        for (size_t i = 0; i < refined.data.size(); ++i) out.data[i] = refined.data[i] > 0.0f ? 255 : 0;
+        const std::string res = input_folder + "/MPMVS/2333_" + id8(s.refID);
+        mkdir((input_folder + "/MPMVS").c_str(), 0777);
+        mkdir(res.c_str(), 0777);
+        if (!writeGrayImage(res + "/skymask.pgm", coarse8) || !writeGrayImage(res + "/skymask_refine.pgm", out)) return -1;
+        ++written;
+    }
+    return written;
+}
+
+// ---------------------------------------------------------------------------
 // RunFusion over a dataset folder (reference src/PatchMatch.cpp:287-504): reads every
 // estimated image's depths.dmb / normals.dmb, camera and colour image (B,G,R), and with
 // sky_seg its skymask_refine image (:360-372, :385-388), fuses them on the GPU (mpmvs_fuse,
@@ -735,6 +845,30 @@ int mpmvs_host_refine_sky_masks(const char* input_folder, int device, int max_sr
     std::vector<Scene> Scenes;
     GenerateSampleList(input_folder, max_src, max_image_size, Scenes);
     return RefineSkyMasks(input_folder, Scenes, max_image_size, device);
+}
+int mpmvs_host_generate_sky_masks(const char* input_folder, const char* model_dir, int device, int max_src, int max_image_size) {
+    std::vector<Scene> Scenes;
+    GenerateSampleList(input_folder, max_src, max_image_size, Scenes);
+    return GenerateSkyRegionMask(input_folder, Scenes, model_dir, max_image_size, device);
+}
+// the host statement of the network's preprocessing (SkyPreprocess) and of one pyrDown level, for the tests; no device involved
+int mpmvs_host_sky_preprocess(const unsigned char* bgr, int h, int w, int net_h, int net_w, float* out_chw) {
+    if (!bgr || !out_chw || h <= 0 || w <= 0 || net_h <= 0 || net_w <= 0) return -1;
+    Image8 img;
+    img.rows = h, img.cols = w, img.ch = 3;
+    img.data.assign(bgr, bgr + (size_t)h * w * 3);
+    const Image r = SkyPreprocess(img, net_h, net_w);
+    std::memcpy(out_chw, r.data.data(), r.data.size() * sizeof(float));
+    return 0;
+}
+int mpmvs_host_pyrdown8(const unsigned char* src, int h, int w, int ch, unsigned char* out) {
+    if (!src || !out || h < 2 || w < 2 || ch <= 0) return -1;
+    Image8 img;
+    img.rows = h, img.cols = w, img.ch = ch;
+    img.data.assign(src, src + (size_t)h * w * ch);
+    const Image8 r = PyrDown8(img);
+    std::memcpy(out, r.data.data(), r.data.size());
+    return 0;
 }
 // cv::imread stand-in for the tests: channels 1 (IMREAD_GRAYSCALE) or 3 (IMREAD_COLOR, B,G,R); call with data = NULL for the size
 int mpmvs_host_read_image(const char* path, int channels, unsigned char* data, size_t capacity, int* h, int* w) {

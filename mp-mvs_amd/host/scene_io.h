@@ -51,6 +51,32 @@ bool bilateral_filter(const Image8& img_bgr, const Image& mask, Image& result, i
 // network's output as the reference stores it, <input>/MPMVS/2333_<id>/skymask.{jpg,pgm} (8 bit = 255 x probability), resizes
 // image and mask as :21-34 do, refines, and writes skymask_refine.pgm (0 / 255) beside it.  Returns the number of masks written or -1.
 int RefineSkyMasks(const std::string& input_folder, const std::vector<Scene>& Scenes, int max_image_size, int device = 0);
+// cv::pyrDown(src, dst, Size(cols / 2, rows / 2)) for 8-bit images (5x5 binomial, reflect-101, (s + 128) >> 8)
+Image8 PyrDown8(const Image8& src);
+// the input of the segmentation network for a B,G,R image, stated on the host (what mpmvs_skyseg_run_u8 computes on the device, bit
+// for bit): pyrDown while rows > 768 && cols > 768, ResizeLinear8 to the network's size, R,G,B planes, (v - mean) * norm.
+// Returns 3 * net_rows rows of net_cols floats (the planes one below the other).
+Image SkyPreprocess(const Image8& bgr, int net_rows, int net_cols);
+// reference SkySegment/include/SkyRegionDetect.h SkySegment(param, model) / maskExtractor(bgr): the network runs on the GPU
+// (mpmvs_skyseg_*, csrc/pm_skyseg.hpp) instead of ncnn on the CPU.  maskExtractor returns the 384 x 384 sky probability
+// (empty on failure) and includes the pyrDown loop of the caller (src/PatchMatch.cpp:16-18), which the device does.
+class SkySegment {
+public:
+    SkySegment(const char* param, const char* model, int device = 0);
+    ~SkySegment();
+    SkySegment(const SkySegment&) = delete;
+    SkySegment& operator=(const SkySegment&) = delete;
+    bool ok() const { return net_ != nullptr; }
+    Image maskExtractor(const Image8& bgr);
+
+private:
+    mpmvs_skyseg* net_ = nullptr;
+};
+// reference GenerateSkyRegionMask (src/PatchMatch.cpp:4-57) in full: network, resize of the fp32 probability and of the image
+// (:21-35), refinement of the fp32 mask (:47); writes <input>/MPMVS/2333_<id>/skymask.pgm (255 x probability, :44) and
+// skymask_refine.pgm (0 / 255); skymask_fuse.jpg is a visualisation and is not written.  model_dir holds
+// skysegsmall_sim-opt-fp16.{param,bin}.  Returns the number of images done or -1.
+int GenerateSkyRegionMask(const std::string& input_folder, const std::vector<Scene>& Scenes, const std::string& model_dir, int max_image_size, int device = 0);
 // The pass loops of the reference's main() (src/main.cpp:20-41) over a dataset folder in the JACOBI order of DESIGN.md
 // section 7: every Problem of a pass reads the previous pass's maps (kept in memory), so the Problems of a pass are
 // independent and are processed by `workers` host threads dealt round-robin to `devices` -- the Delaunay / file work of

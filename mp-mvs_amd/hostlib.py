@@ -13,7 +13,8 @@ LIB_PATH = os.path.join(_HERE, "host", "libmpmvs_host.so")
 SYMBOLS = ["mpmvs_host_triangulate_vertices", "mpmvs_host_delaunay", "mpmvs_host_build_prior", "mpmvs_host_run_pipeline",
            "mpmvs_host_write_dmb", "mpmvs_host_read_dmb", "mpmvs_host_read_camera", "mpmvs_host_sample_list", "mpmvs_host_read_pgm",
            "mpmvs_host_run_folder", "mpmvs_host_resize_linear", "mpmvs_host_write_ply", "mpmvs_host_fuse_folder", "mpmvs_host_read_image",
-           "mpmvs_host_decode_jpeg", "mpmvs_host_refine_sky_masks", "mpmvs_host_run_folder_jacobi", "mpmvs_host_prior_from_triangles", "mpmvs_host_run_folder_jacobi_fused"]
+           "mpmvs_host_decode_jpeg", "mpmvs_host_refine_sky_masks", "mpmvs_host_run_folder_jacobi", "mpmvs_host_prior_from_triangles", "mpmvs_host_run_folder_jacobi_fused",
+           "mpmvs_host_generate_sky_masks", "mpmvs_host_sky_preprocess", "mpmvs_host_pyrdown8"]
 _cache = {}
 
 
@@ -63,6 +64,12 @@ def load():
         lib.mpmvs_host_write_ply.argtypes = [C.c_char_p, P, C.c_int]
         lib.mpmvs_host_resize_linear.restype = C.c_int
         lib.mpmvs_host_resize_linear.argtypes = [P, C.c_int, C.c_int, P, C.c_int, C.c_int]
+        lib.mpmvs_host_generate_sky_masks.restype = C.c_int
+        lib.mpmvs_host_generate_sky_masks.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
+        lib.mpmvs_host_sky_preprocess.restype = C.c_int
+        lib.mpmvs_host_sky_preprocess.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, P]
+        lib.mpmvs_host_pyrdown8.restype = C.c_int
+        lib.mpmvs_host_pyrdown8.argtypes = [P, C.c_int, C.c_int, C.c_int, P]
         _cache["lib"] = lib
     return _cache["lib"]
 
@@ -324,6 +331,36 @@ def refine_sky_masks(folder, device=0, max_src=20, max_image_size=3200):
     if n < 0:
         raise RuntimeError("refine_sky_masks failed")
     return int(n)
+
+
+def generate_sky_masks(folder, model_dir, device=0, max_src=20, max_image_size=3200):
+    """GenerateSkyRegionMask: the segmentation network (model_dir/skysegsmall_sim-opt-fp16.{param,bin}) on every image of the
+    folder, then the refinement of the fp32 mask -> skymask.pgm and skymask_refine.pgm per image; returns the number done.
+    Runs on the GPU; there is no CPU path."""
+    n = load().mpmvs_host_generate_sky_masks(str(folder).encode(), str(model_dir).encode(), device, max_src, max_image_size)
+    if n < 0:
+        raise RuntimeError("generate_sky_masks failed")
+    return int(n)
+
+
+def sky_preprocess(bgr, net_h=384, net_w=384):
+    """the host statement of the network's preprocessing: uint8 [h, w, 3] B,G,R -> float32 [3, net_h, net_w]; no device involved"""
+    im = np.ascontiguousarray(bgr, np.uint8)
+    assert im.ndim == 3 and im.shape[2] == 3
+    out = np.empty((3, net_h, net_w), np.float32)
+    if load().mpmvs_host_sky_preprocess(im.ctypes.data, im.shape[0], im.shape[1], net_h, net_w, out.ctypes.data) != 0:
+        raise RuntimeError("sky_preprocess failed")
+    return out
+
+
+def pyrdown8(img):
+    """cv::pyrDown to (w // 2, h // 2) of a uint8 [h, w] or [h, w, c] image as the host states it"""
+    im = np.ascontiguousarray(img, np.uint8)
+    ch = 1 if im.ndim == 2 else im.shape[2]
+    out = np.empty((im.shape[0] // 2, im.shape[1] // 2) + (() if im.ndim == 2 else (ch,)), np.uint8)
+    if load().mpmvs_host_pyrdown8(im.ctypes.data, im.shape[0], im.shape[1], ch, out.ctypes.data) != 0:
+        raise RuntimeError("pyrdown8 failed")
+    return out
 
 
 def fuse_folder(folder, device=0, max_src=20, use_dynamic=True, sky_seg=False):
