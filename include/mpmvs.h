@@ -381,6 +381,41 @@ int mpmvs_view_select(int device, int n_images, const double* centers, int n_poi
 /* device time (ms, HIP events) of the kernels of the last mpmvs_view_select call */
 float mpmvs_view_select_kernel_ms(void);
 
+/* ---- undistortion of COLMAP camera models (tools/colmap2mvs.py --undistort) --- */
+/* model_id indexes COLMAP's 11 camera models in the order of mp-mvs_amd/colmap.py CAMERA_MODELS (0 SIMPLE_PINHOLE ... 10
+ * THIN_PRISM_FISHEYE); params holds the model's n_params parameters in the order of a cameras file (f | fx fy, cx, cy, then the
+ * distortion terms).  The models, the output-camera rule and the warp are stated once, in fp64 without contraction and without
+ * any libm transcendental on the forward path, in mp-mvs_amd/csrc/pm_undistort_model.hpp (contract: DESIGN.md section 12). */
+/* The PINHOLE camera an image of the given camera is resampled to: COLMAP's UndistortCamera rule with the options
+ * blank_pixels (0: no blank pixel in the output ... 1: every source pixel kept), min_scale and max_scale (COLMAP's defaults:
+ * 0, 0.2, 2.0).  out_pinhole receives fx fy cx' cy' (the focal lengths are the source's), *out_width / *out_height the size
+ * W' x H'; a SIMPLE_PINHOLE or PINHOLE source comes back unchanged.  Host only: touches no device.
+ * Returns 0, or -2 for an unknown model, a wrong parameter count, a parameter that is not finite, a focal length or size that
+ * is not positive, or options outside 0 <= blank_pixels <= 1, 0 < min_scale <= max_scale. */
+int mpmvs_undistort_camera(int model_id, const double* params, int n_params, int width, int height, double blank_pixels,
+                           double min_scale, double max_scale, double out_pinhole[4], int* out_width, int* out_height);
+/* The warp: src = height rows of width pixels of `channels` (1 or 3) interleaved bytes, pitch_bytes apart (0 = tightly packed),
+ * taken by the camera (model_id, params); out = dense dst_height x dst_width x channels bytes of the PINHOLE camera dst_pinhole
+ * (fx fy cx cy); out_valid (may be NULL) = dst_height x dst_width bytes, 1 where the pixel has a source and 0 where not.
+ * DEFINED BY EQUIVALENCE: the bytes of the host statement in mp-mvs_amd/host/undistort.cpp, bit for bit.  Per output pixel
+ * (X, Y): u = (X + 0.5 - cx) / fx, v = (Y + 0.5 - cy) / fy, (x, y) = forward map of the model, sx = x - 0.5, sy = y - 0.5; the
+ * pixel is valid iff 0 <= sx <= width - 1 and 0 <= sy <= height - 1, otherwise every channel is 0; x0 = floor(sx),
+ * ax = sx - x0, x1 = min(x0 + 1, width - 1), likewise in y; per channel top = s00 + ax * (s10 - s00),
+ * bot = s01 + ax * (s11 - s01), val = top + ay * (bot - top) in fp64; the byte is (int)(val + 0.5).
+ * The validity rule is strict, so an identity warp (a pinhole camera, or a model with all-zero distortion, onto its own pinhole
+ * and size) returns the source bytes everywhere it is valid, but with a focal length that is no power of two
+ * fx * ((X + 0.5 - cx) / fx) + cx - 0.5 can miss X by an ulp and put a pixel of the outermost row or column just outside the
+ * image: that pixel comes back 0 / invalid.  Callers that need the identity copy such images (the converter does).
+ * Host buffers in and out; blocks until done; runs on a stream of its own.  Returns 0, -2 (a NULL src / out / dst_pinhole,
+ * channels other than 1 or 3, a non-positive size, a pitch below width * channels, a camera mpmvs_undistort_camera refuses;
+ * checked before the device is touched), -3 (an output of 2^31 bytes or more, a source row of 2^31 bytes or more, or a source
+ * of 2^40 bytes or more) or -100 (HIP failure, a bad device included). */
+int mpmvs_undistort_u8(int device, const unsigned char* src, int channels, int width, int height, size_t pitch_bytes, int model_id,
+                       const double* params, int n_params, const double dst_pinhole[4], int dst_width, int dst_height,
+                       unsigned char* out, unsigned char* out_valid);
+/* device time (ms, HIP events) of the kernel of the calling thread's last successful mpmvs_undistort_u8 call */
+float mpmvs_undistort_kernel_ms(void);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

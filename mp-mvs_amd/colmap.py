@@ -1,6 +1,8 @@
 """COLMAP sparse model -> the MVSNet-style folder the pipeline reads (cams/%08d_cam.txt, pair.txt, images/%08d.*): the
 outputs of the reference's colmap2mvsnet_acm.py, with the model read in C++ (host/colmap_io.cpp) and the view selection
-on the GPU (mpmvs_view_select, csrc/pm_viewsel.hpp).  Contract: DESIGN.md section 11.  CLI: tools/colmap2mvs.py."""
+on the GPU (mpmvs_view_select, csrc/pm_viewsel.hpp).  Contract: DESIGN.md section 11.  With undistort=True the images of
+distorted cameras are resampled to pinhole cameras on the GPU first (mpmvs_undistort_u8, csrc/pm_undistort.hpp; DESIGN.md
+section 12), the step COLMAP's image_undistorter does.  CLI: tools/colmap2mvs.py."""
 import ctypes as C
 import os
 import shutil
@@ -142,6 +144,35 @@ def intrinsics(model, warn=True):
     return out
 
 
+def camera_params(model, k):
+    """(model name, its parameters in file order) of the k-th camera"""
+    name = CAMERA_MODELS[model.cam_model[k]]
+    return name, model.cam_params[k][:len(PARAMS[name])]
+
+
+def is_distorted(model, k):
+    """the k-th camera has a distortion parameter that is not zero"""
+    name, prm = camera_params(model, k)
+    return any(v != 0 for n, v in zip(PARAMS[name], prm) if n not in ("f", "fx", "fy", "cx", "cy"))
+
+
+def undistorted_cameras(model, blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
+    """{camera id: (3x3 K', W', H')}: the pinhole camera each camera's images are undistorted to (mpmvs_undistort_camera);
+    a pinhole camera and a camera whose distortion parameters are all zero keep their K and size"""
+    from . import engine
+    K = intrinsics(model, warn=False)
+    out = {}
+    for k, cid in enumerate(model.cam_id):
+        w, h = int(model.cam_width[k]), int(model.cam_height[k])
+        if is_distorted(model, k):
+            name, prm = camera_params(model, k)
+            (fx, fy, cx, cy), w, h = engine.undistort_camera(name, prm, w, h, blank_pixels, min_scale, max_scale)
+            out[int(cid)] = (np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]]), w, h)
+        else:
+            out[int(cid)] = (K[int(cid)], w, h)
+    return out
+
+
 def depth_ranges(model, max_d=192, interval_scale=1.0, K=None):
     """(N, 4): depth_min, interval, depth_num, depth_max per image, the reference's expressions over the z of the image's
     observed points (with multiplicity, -1 skipped) in its camera frame"""
@@ -176,9 +207,10 @@ def cam_text(E, K, rng):
     return s + "\n%f %f %f %f\n" % tuple(rng)
 
 
-def write_cams(model, save_folder, max_d=192, interval_scale=1.0):
-    """save_folder/cams/%08d_cam.txt for every image (no GPU needed)"""
-    K = intrinsics(model)
+def write_cams(model, save_folder, max_d=192, interval_scale=1.0, K=None):
+    """save_folder/cams/%08d_cam.txt for every image (no GPU needed); K: {camera id: 3x3} in place of the model's own
+    intrinsics (the undistorted cameras)"""
+    K = intrinsics(model) if K is None else K
     E = extrinsics(model)
     rngs = depth_ranges(model, max_d, interval_scale, K)
     d = os.path.join(save_folder, "cams")
@@ -233,29 +265,94 @@ def _write_pnm(path, a):
         f.write(np.ascontiguousarray(a, np.uint8).tobytes())
 
 
+def _decode_pil(src, name):
+    """uint8 [h, w] (grey) or [h, w, 3] (R,G,B) of an image file PIL reads"""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError(f"{name}: images other than JPEG are decoded with PIL, which is not installed") from e
+    with Image.open(src) as im:
+        if im.mode in ("L", "I;16", "I", "1"):
+            return np.asarray(im.convert("L"))
+        return np.asarray(im.convert("RGB"))
+
+
+def _copy_image(src, name, out_dir, i):
+    if os.path.splitext(name)[1] in (".jpg", ".jpeg", ".JPG"):
+        shutil.copyfile(src, os.path.join(out_dir, "%08d.jpg" % i))
+        return
+    a = _decode_pil(src, name)
+    _write_pnm(os.path.join(out_dir, "%08d.%s" % (i, "pgm" if a.ndim == 2 else "ppm")), a)
+
+
 def copy_images(model, image_dir, out_dir):
     """images/%08d.jpg: JPEG files byte for byte; other formats decoded with PIL and written losslessly as .pgm / .ppm"""
     os.makedirs(out_dir, exist_ok=True)
     for i, name in enumerate(model.names):
+        _copy_image(os.path.join(image_dir, name), name, out_dir, i)
+
+
+def _jpeg_components(path):
+    """number of colour components of a JPEG file (its frame header), 0 if none is found.  A plain walk over the marker
+    segments: fill bytes (0xFF padding) in front of a marker, or a marker without a length field in front of the frame header,
+    end it with 0, which the caller takes as colour -- right for a colour file; a grey file of that rare kind is then warped
+    and written with three equal channels, which the pipeline reads like a grey image."""
+    with open(path, "rb") as f:
+        d = f.read()
+    k = 2
+    while k + 4 <= len(d) and d[k] == 0xFF:
+        marker, size = d[k + 1], int.from_bytes(d[k + 2:k + 4], "big")
+        if 0xC0 <= marker <= 0xCF and marker not in (0xC4, 0xC8, 0xCC):   # any start-of-frame marker
+            return d[k + 9] if k + 9 < len(d) else 0
+        if marker == 0xDA:
+            break
+        k += 2 + size
+    return 0
+
+
+def _decode(src, name):
+    """uint8 [h, w] (grey) or [h, w, 3] (R,G,B): JPEG / PGM / PPM through the host library's reader, other formats through PIL"""
+    ext = os.path.splitext(name)[1].lower()
+    if ext in (".jpg", ".jpeg", ".pgm", ".ppm"):
+        grey = ext == ".pgm" or (ext != ".ppm" and _jpeg_components(src) == 1)
+        if grey:
+            return hostlib.read_image(src, 1)
+        return np.ascontiguousarray(hostlib.read_image(src, 3)[..., ::-1])   # B,G,R -> R,G,B
+    return _decode_pil(src, name)
+
+
+def undistort_images(model, image_dir, out_dir, cams, device=0):
+    """images/%08d.pgm / .ppm: every image of a distorted camera warped to its camera of `cams` (undistorted_cameras) on the
+    GPU and written losslessly; the images of the other cameras are copied as copy_images copies them"""
+    from . import engine
+    os.makedirs(out_dir, exist_ok=True)
+    index = {int(cid): k for k, cid in enumerate(model.cam_id)}
+    fisheye = [int(cid) for k, cid in enumerate(model.cam_id) if "FISHEYE" in CAMERA_MODELS[model.cam_model[k]] and not is_distorted(model, k)]
+    if fisheye:
+        print(f"warning: camera(s) {fisheye} are fisheye models whose distortion parameters are all zero; their images are copied as "
+              "they are, although such a camera is no pinhole", file=sys.stderr)
+    for i, name in enumerate(model.names):
         src = os.path.join(image_dir, name)
-        if os.path.splitext(name)[1] in (".jpg", ".jpeg", ".JPG"):
-            shutil.copyfile(src, os.path.join(out_dir, "%08d.jpg" % i))
+        k = index[int(model.image_cam[i])]
+        if not is_distorted(model, k):
+            _copy_image(src, name, out_dir, i)
             continue
-        try:
-            from PIL import Image
-        except ImportError as e:
-            raise RuntimeError(f"{name}: images other than JPEG are decoded with PIL, which is not installed") from e
-        with Image.open(src) as im:
-            if im.mode in ("L", "I;16", "I", "1"):
-                a = np.asarray(im.convert("L"))
-                _write_pnm(os.path.join(out_dir, "%08d.pgm" % i), a)
-            else:
-                _write_pnm(os.path.join(out_dir, "%08d.ppm" % i), np.asarray(im.convert("RGB")))
+        a = _decode(src, name)
+        w, h = int(model.cam_width[k]), int(model.cam_height[k])
+        if a.shape[:2] != (h, w):
+            raise ValueError(f"{name}: the image is {a.shape[1]} x {a.shape[0]}, its camera {int(model.cam_id[k])} is {w} x {h}")
+        Kn, ow, oh = cams[int(model.cam_id[k])]
+        cname, prm = camera_params(model, k)
+        out = engine.undistort_u8(a, cname, prm, ((Kn[0, 0], Kn[1, 1], Kn[0, 2], Kn[1, 2]), ow, oh), device)
+        _write_pnm(os.path.join(out_dir, "%08d.%s" % (i, "pgm" if out.ndim == 2 else "ppm")), out)
 
 
-def convert(dense_folder, save_folder, max_d=192, interval_scale=1.0, model_ext=None, num_view=20, device=0, overwrite=False):
+def convert(dense_folder, save_folder, max_d=192, interval_scale=1.0, model_ext=None, num_view=20, device=0, overwrite=False,
+            undistort=False, blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
     """dense_folder/{images,sparse} -> save_folder/{cams,images,pair.txt}; returns the stage times (s).  Refuses to touch
-    non-empty save_folder/images or /cams unless overwrite=True (which removes them first)."""
+    non-empty save_folder/images or /cams unless overwrite=True (which removes them first).  undistort=True: the cameras
+    written are the pinhole cameras of undistorted_cameras(blank_pixels, min_scale, max_scale) and the images of distorted
+    cameras are warped to them on the GPU (images/%08d.pgm / .ppm); the default expects COLMAP's undistorted dense folder."""
     cam_dir, img_dir = os.path.join(save_folder, "cams"), os.path.join(save_folder, "images")
     for d in (cam_dir, img_dir):
         if os.path.isdir(d) and os.listdir(d):
@@ -271,12 +368,16 @@ def convert(dense_folder, save_folder, max_d=192, interval_scale=1.0, model_ext=
     ids, scores = select_views(model, num_view, device)
     times["select"] = time.perf_counter() - t
     t = time.perf_counter()
-    write_cams(model, save_folder, max_d, interval_scale)
+    cams = undistorted_cameras(model, blank_pixels, min_scale, max_scale) if undistort else None
+    write_cams(model, save_folder, max_d, interval_scale, {cid: c[0] for cid, c in cams.items()} if undistort else None)
     times["cams"] = time.perf_counter() - t
     t = time.perf_counter()
     write_pairs(os.path.join(save_folder, "pair.txt"), ids, scores)
     times["pairs"] = time.perf_counter() - t
     t = time.perf_counter()
-    copy_images(model, os.path.join(dense_folder, "images"), img_dir)
+    if undistort:
+        undistort_images(model, os.path.join(dense_folder, "images"), img_dir, cams, device)
+    else:
+        copy_images(model, os.path.join(dense_folder, "images"), img_dir)
     times["images"] = time.perf_counter() - t
     return times

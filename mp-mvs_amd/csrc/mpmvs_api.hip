@@ -40,6 +40,7 @@
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
 #include "pm_ingest.hpp"
+#include "pm_undistort.hpp"
 #include "pm_skyseg.hpp"
 #include "pm_skyseg_model.hpp"
 
@@ -2636,6 +2637,93 @@ int mpmvs_view_select(int device, int n_images, const double* centers, int n_poi
     for (void* p : {(void*)d_centers, (void*)d_xyz, (void*)d_obs_off, (void*)d_obs_pt, (void*)d_cnt, (void*)d_off, (void*)d_tsum, (void*)d_fill,
                     (void*)d_trk_img, (void*)d_trk_pt, (void*)d_trk_mult, (void*)d_acc, (void*)d_score, (void*)d_ids, (void*)d_scores})
         (void)pool_free(p);
+    (void)hipStreamDestroy(st);
+    return rc;
+}
+
+// the output camera of the undistortion (pm_undistort_model.hpp: und_output_camera); host only, touches no device
+int mpmvs_undistort_camera(int model_id, const double* params, int n_params, int width, int height, double blank_pixels, double min_scale,
+                           double max_scale, double out_pinhole[4], int* out_width, int* out_height) {
+    UndModel m;
+    if (!out_pinhole || !out_width || !out_height || !und_model_init(m, model_id, params, n_params) ||
+        !und_options_ok(width, height, blank_pixels, min_scale, max_scale))
+        return -2;
+    int w = 0, h = 0;
+    double k[4];
+    if (!und_output_camera(m, width, height, blank_pixels, min_scale, max_scale, k, w, h)) return -2;
+    std::memcpy(out_pinhole, k, sizeof k);
+    *out_width = w;
+    *out_height = h;
+    return 0;
+}
+
+static thread_local float g_undistort_kernel_ms = 0.0f;   // per calling thread: concurrent calls do not overwrite each other's reading
+float mpmvs_undistort_kernel_ms(void) { return g_undistort_kernel_ms; }
+
+// the undistortion warp (pm_undistort.hpp); host buffers in and out
+int mpmvs_undistort_u8(int device, const unsigned char* src, int channels, int width, int height, size_t pitch_bytes, int model_id,
+                       const double* params, int n_params, const double dst_pinhole[4], int dst_width, int dst_height, unsigned char* out,
+                       unsigned char* out_valid) {
+    UndModel m;
+    if (!src || !out || !dst_pinhole || (channels != 1 && channels != 3) || width <= 0 || height <= 0 || dst_width <= 0 || dst_height <= 0 ||
+        !und_model_init(m, model_id, params, n_params))
+        return -2;
+    const size_t row = (size_t)width * channels;
+    if (pitch_bytes == 0) pitch_bytes = row;
+    if (pitch_bytes < row) return -2;
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(dst_pinhole[i])) return -2;
+    if (!(dst_pinhole[0] > 0.0) || !(dst_pinhole[1] > 0.0)) return -2;
+    const size_t n_pix = (size_t)dst_width * dst_height, out_bytes = n_pix * channels, src_bytes = row * height;
+    if (out_bytes >= (1ull << 31) || row >= (1ull << 31) || src_bytes >= (1ull << 40)) return -3;
+    if (enter_device(device) != hipSuccess) return -100;
+    hipStream_t st = nullptr;  // own stream: other contexts of this device keep running
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
+    // one page-locked stage for the three host arrays (each part starts on a 16-byte boundary; the outputs are rounded up to the
+    // dword the kernel stores last)
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_out = up16(src_bytes), o_valid = o_out + up16(out_bytes), stage_bytes = o_valid + up16(n_pix);
+    unsigned char* stage = (unsigned char*)mpmvs_alloc_pinned(stage_bytes);
+    unsigned char *d_src = nullptr, *d_out = nullptr, *d_valid = nullptr;
+    int rc = stage ? 0 : -100;
+    if (!rc && (pool_malloc(&d_src, up16(src_bytes)) != hipSuccess || pool_malloc(&d_out, up16(out_bytes)) != hipSuccess ||
+                (out_valid && pool_malloc(&d_valid, up16(n_pix)) != hipSuccess)))
+        rc = -100;
+    if (!rc) {
+        for (int y = 0; y < height; ++y) std::memcpy(stage + (size_t)y * row, src + (size_t)y * pitch_bytes, row);
+        if (hipMemcpyAsync(d_src, stage, src_bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = -100;
+    }
+    if (!rc) {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess || hipEventRecord(ev0, st) != hipSuccess) rc = -100;
+        if (!rc) {
+            UndPinhole dst;
+            std::memcpy(dst.p, dst_pinhole, sizeof dst.p);
+            const dim3 grid((unsigned)((n_pix + kUndThreads - 1) / kUndThreads));
+            if (channels == 1)
+                hipLaunchKernelGGL(k_undistort<1>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width,
+                                   (unsigned)n_pix, (unsigned*)d_out, (unsigned*)d_valid);
+            else
+                hipLaunchKernelGGL(k_undistort<3>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width,
+                                   (unsigned)n_pix, (unsigned*)d_out, (unsigned*)d_valid);
+            if (hipGetLastError() != hipSuccess || hipEventRecord(ev1, st) != hipSuccess) rc = -100;
+        }
+        if (!rc && (hipMemcpyAsync(stage + o_out, d_out, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    (out_valid && hipMemcpyAsync(stage + o_valid, d_valid, n_pix, hipMemcpyDeviceToHost, st) != hipSuccess)))
+            rc = -100;
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;
+        if (!rc && hipEventElapsedTime(&g_undistort_kernel_ms, ev0, ev1) != hipSuccess) rc = -100;
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path, before the buffers go back to the pool
+    if (!rc) {
+        std::memcpy(out, stage + o_out, out_bytes);
+        if (out_valid) std::memcpy(out_valid, stage + o_valid, n_pix);
+    }
+    for (void* p : {(void*)d_src, (void*)d_out, (void*)d_valid})
+        if (p) (void)pool_free(p);
+    if (stage) mpmvs_free_pinned(stage);
     (void)hipStreamDestroy(st);
     return rc;
 }

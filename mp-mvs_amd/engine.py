@@ -54,6 +54,9 @@ _EXTRA = {
     "skyseg_dims": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "skyseg_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
     "skyseg_destroy": (None, [_P]),
+    "undistort_camera": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "undistort_u8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "undistort_kernel_ms": (C.c_float, []),
     "eval_ncc_multi": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx"]
@@ -250,6 +253,52 @@ def resize_u8(img, new_w, new_h, device=0):
     if rc != 0:
         raise RuntimeError(f"mpmvs_resize_u8 failed ({rc})")
     return out
+
+
+def _camera_args(model, params):
+    """(model id, float64 parameter array) from a model id or a COLMAP model name"""
+    from .colmap import CAMERA_MODELS
+    mid = CAMERA_MODELS.index(model) if isinstance(model, str) else int(model)
+    return mid, np.ascontiguousarray(params, np.float64).reshape(-1)
+
+
+def undistort_camera(model, params, width, height, blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
+    """the PINHOLE camera an image of COLMAP camera (model, params) is undistorted to (mpmvs_undistort_camera; host only):
+    ((fx, fy, cx', cy'), W', H').  model: id or name of colmap.CAMERA_MODELS, params in the order of a cameras file"""
+    _, fns = load()
+    mid, prm = _camera_args(model, params)
+    k = np.zeros(4)
+    w, h = C.c_int(0), C.c_int(0)
+    rc = fns["undistort_camera"](mid, prm.ctypes.data, len(prm), int(width), int(height), float(blank_pixels), float(min_scale), float(max_scale),
+                                 k.ctypes.data, C.byref(w), C.byref(h))
+    if rc != 0:
+        raise ValueError(f"mpmvs_undistort_camera refused the camera or the options ({rc})")
+    return tuple(float(v) for v in k), w.value, h.value
+
+
+def undistort_u8(img, model, params, dst, device=0, valid=False):
+    """mpmvs_undistort_u8: uint8 [h, w] or [h, w, 3] taken by COLMAP camera (model, params) -> the image of the pinhole camera
+    dst = ((fx, fy, cx, cy), W', H') as undistort_camera returns it, same channels; valid=True: also the uint8 [H', W'] mask of
+    the pixels that have a source"""
+    _, fns = load()
+    mid, prm = _camera_args(model, params)
+    im = np.asarray(img)
+    if im.dtype != np.uint8 or im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3)):
+        raise ValueError(f"need a uint8 [h, w], [h, w, 1] or [h, w, 3] image, got {im.dtype} {im.shape}")
+    ch = 1 if im.ndim == 2 else im.shape[2]
+    if im.strides[-1] != 1 or (im.ndim == 3 and im.strides[1] != ch) or im.strides[0] < im.shape[1] * ch:
+        im = np.ascontiguousarray(im)
+    k, dw, dh = dst
+    k = np.ascontiguousarray(k, np.float64)
+    out = np.empty((int(dh), int(dw)) + im.shape[2:], np.uint8)
+    ok = np.empty((int(dh), int(dw)), np.uint8) if valid else None
+    rc = fns["undistort_u8"](int(device), im.ctypes.data, ch, im.shape[1], im.shape[0], im.strides[0], mid, prm.ctypes.data, len(prm), k.ctypes.data,
+                             int(dw), int(dh), out.ctypes.data, ok.ctypes.data if valid else None)
+    if rc == -2:
+        raise ValueError("mpmvs_undistort_u8 refused its arguments (-2)")
+    if rc != 0:
+        raise RuntimeError(f"mpmvs_undistort_u8 failed ({rc})")
+    return (out, ok) if valid else out
 
 
 class SkySegError(RuntimeError):

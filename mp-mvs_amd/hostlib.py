@@ -14,7 +14,8 @@ SYMBOLS = ["mpmvs_host_triangulate_vertices", "mpmvs_host_delaunay", "mpmvs_host
            "mpmvs_host_write_dmb", "mpmvs_host_read_dmb", "mpmvs_host_read_camera", "mpmvs_host_sample_list", "mpmvs_host_read_pgm",
            "mpmvs_host_run_folder", "mpmvs_host_resize_linear", "mpmvs_host_write_ply", "mpmvs_host_fuse_folder", "mpmvs_host_read_image",
            "mpmvs_host_decode_jpeg", "mpmvs_host_refine_sky_masks", "mpmvs_host_run_folder_jacobi", "mpmvs_host_prior_from_triangles", "mpmvs_host_run_folder_jacobi_fused",
-           "mpmvs_host_generate_sky_masks", "mpmvs_host_sky_preprocess", "mpmvs_host_pyrdown8"]
+           "mpmvs_host_generate_sky_masks", "mpmvs_host_sky_preprocess", "mpmvs_host_pyrdown8", "mpmvs_host_undistort_u8", "mpmvs_host_undistort_atan",
+           "mpmvs_host_undistort_forward", "mpmvs_host_undistort_inverse", "mpmvs_host_undistort_threads"]
 _cache = {}
 
 
@@ -70,6 +71,16 @@ def load():
         lib.mpmvs_host_sky_preprocess.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, P]
         lib.mpmvs_host_pyrdown8.restype = C.c_int
         lib.mpmvs_host_pyrdown8.argtypes = [P, C.c_int, C.c_int, C.c_int, P]
+        lib.mpmvs_host_undistort_u8.restype = C.c_int
+        lib.mpmvs_host_undistort_u8.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, P, C.c_int, P, C.c_int, C.c_int, P, P]
+        lib.mpmvs_host_undistort_threads.restype = C.c_int
+        lib.mpmvs_host_undistort_threads.argtypes = []
+        lib.mpmvs_host_undistort_atan.restype = None
+        lib.mpmvs_host_undistort_atan.argtypes = [P, C.c_int, P]
+        lib.mpmvs_host_undistort_forward.restype = C.c_int
+        lib.mpmvs_host_undistort_forward.argtypes = [C.c_int, P, C.c_int, P, C.c_int, P]
+        lib.mpmvs_host_undistort_inverse.restype = C.c_int
+        lib.mpmvs_host_undistort_inverse.argtypes = [C.c_int, P, C.c_int, P, C.c_int, P]
         _cache["lib"] = lib
     return _cache["lib"]
 
@@ -361,6 +372,58 @@ def pyrdown8(img):
     if load().mpmvs_host_pyrdown8(im.ctypes.data, im.shape[0], im.shape[1], ch, out.ctypes.data) != 0:
         raise RuntimeError("pyrdown8 failed")
     return out
+
+
+def undistort_u8(img, model_id, params, dst, valid=False, pitch=None):
+    """the host statement of the undistortion warp (mpmvs_host_undistort_u8), arguments as engine.undistort_u8 with a numeric
+    model id; no device involved"""
+    im = np.asarray(img)
+    assert im.dtype == np.uint8 and im.ndim in (2, 3)
+    ch = 1 if im.ndim == 2 else im.shape[2]
+    if im.strides[-1] != 1 or (im.ndim == 3 and im.strides[1] != ch) or im.strides[0] < im.shape[1] * ch:
+        im = np.ascontiguousarray(im)
+    prm = np.ascontiguousarray(params, np.float64).reshape(-1)
+    k, dw, dh = dst
+    k = np.ascontiguousarray(k, np.float64)
+    out = np.empty((int(dh), int(dw)) + im.shape[2:], np.uint8)
+    ok = np.empty((int(dh), int(dw)), np.uint8) if valid else None
+    rc = load().mpmvs_host_undistort_u8(im.ctypes.data, ch, im.shape[1], im.shape[0], im.strides[0] if pitch is None else pitch, int(model_id),
+                                        prm.ctypes.data, len(prm), k.ctypes.data, int(dw), int(dh), out.ctypes.data, ok.ctypes.data if valid else None)
+    if rc != 0:
+        raise ValueError(f"mpmvs_host_undistort_u8 refused its arguments ({rc})")
+    return (out, ok) if valid else out
+
+
+def undistort_threads():
+    """the size of the OpenMP team undistort_u8 runs on"""
+    return int(load().mpmvs_host_undistort_threads())
+
+
+def undistort_atan(x):
+    """probe: the atan of csrc/pm_undistort_model.hpp (+ - * / sqrt only) on a float64 array"""
+    a = np.ascontiguousarray(x, np.float64)
+    out = np.empty_like(a)
+    load().mpmvs_host_undistort_atan(a.ctypes.data, a.size, out.ctypes.data)
+    return out
+
+
+def _undistort_points(fn, model_id, params, pts):
+    prm = np.ascontiguousarray(params, np.float64).reshape(-1)
+    a = np.ascontiguousarray(pts, np.float64).reshape(-1, 2)
+    out = np.empty_like(a)
+    if fn(int(model_id), prm.ctypes.data, len(prm), a.ctypes.data, len(a), out.ctypes.data) != 0:
+        raise ValueError("unknown camera model or wrong parameter count")
+    return out
+
+
+def undistort_forward(model_id, params, uv):
+    """probe: normalised pinhole coordinates [n, 2] -> image points [n, 2] of the distorted camera"""
+    return _undistort_points(load().mpmvs_host_undistort_forward, model_id, params, uv)
+
+
+def undistort_inverse(model_id, params, xy):
+    """probe: image points [n, 2] -> normalised pinhole coordinates [n, 2] (the Newton inverse the output camera uses)"""
+    return _undistort_points(load().mpmvs_host_undistort_inverse, model_id, params, xy)
 
 
 def fuse_folder(folder, device=0, max_src=20, use_dynamic=True, sky_seg=False):

@@ -5,6 +5,11 @@ and the view selection runs on the GPU (mp-mvs_amd/colmap.py; contract in DESIGN
 
   python tools/colmap2mvs.py --dense_folder <colmap dense folder> --save_folder <out> [--max_d 192] [--interval_scale 1]
                              [--model_ext .bin|.txt] [--num_view 20] [--device 0] [--overwrite]
+                             [--undistort [--blank_pixels 0] [--min_scale 0.2] [--max_scale 2.0]]
+
+--undistort takes a plain sparse model with distorted cameras (SIMPLE_RADIAL, OPENCV, the fisheye models ...): the images are
+resampled on the GPU to the pinhole cameras COLMAP's image_undistorter would choose and written as .pgm / .ppm, and cams/
+holds those cameras.  Without it the input is expected to be COLMAP's undistorted dense folder.
 
 Differences from the reference: it refuses to replace non-empty <save_folder>/images or /cams unless --overwrite is
 given (the reference deletes them); .jpeg / .JPG images are copied byte for byte like .jpg (the reference re-encodes
@@ -31,12 +36,17 @@ def main():
     ap.add_argument("--num_view", type=int, default=20, help="views listed per image (at most N - 1)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--overwrite", action="store_true", help="replace existing save_folder/images and /cams")
+    ap.add_argument("--undistort", action="store_true", help="undistort the images of distorted cameras on the GPU (no image_undistorter run needed)")
+    ap.add_argument("--blank_pixels", type=float, default=0.0, help="with --undistort: 0 = no blank pixel in the output ... 1 = every source pixel kept")
+    ap.add_argument("--min_scale", type=float, default=0.2, help="with --undistort: lower limit of the change of image size")
+    ap.add_argument("--max_scale", type=float, default=2.0, help="with --undistort: upper limit of the change of image size")
     a = ap.parse_args()
     colmap = importlib.import_module("mp-mvs_amd.colmap")
     t0 = time.perf_counter()
     try:
         times = colmap.convert(a.dense_folder, a.save_folder, max_d=a.max_d, interval_scale=a.interval_scale, model_ext=a.model_ext,
-                               num_view=a.num_view, device=a.device, overwrite=a.overwrite)
+                               num_view=a.num_view, device=a.device, overwrite=a.overwrite, undistort=a.undistort, blank_pixels=a.blank_pixels,
+                               min_scale=a.min_scale, max_scale=a.max_scale)
     except (FileExistsError, ValueError) as e:
         print(f"colmap2mvs: {e}", file=sys.stderr)
         return 2
