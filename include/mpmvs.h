@@ -469,6 +469,15 @@ int mpmvs_chain_status(mpmvs_ctx* ctx);
  * -101), the context stays usable.  block_pos < 0 switches the fault off. */
 int mpmvs_dbg_chain_stall(mpmvs_ctx* ctx, int block_pos, int spin_limit);
 
+/* ---- per-view costs kept from InitializeScore ------------------------------ */
+/* InitializeScore evaluates every pixel's plane against every source view; the context keeps these costs (4 x views x W x H bytes)
+ * and the first black and the first red update pass that follow at the same window scale read them back instead of evaluating the
+ * unchanged plane again ("the current plane under the new weights", src/PatchMatch.cu:901-913) -- the same bits, one evaluation
+ * round per view less.  Anything else that writes the planes or changes the views ends their validity.
+ * enable = 0: every pass recomputes; 1: the default; < 0: leave the setting as it is.  *passes_served (may be NULL): update passes
+ * of this context enqueued so far with the kept costs in use.  For tests and same-process A/B measurements. */
+int mpmvs_dbg_own_costs(mpmvs_ctx* ctx, int enable, int* passes_served);
+
 #ifdef __cplusplus
 }
 #endif

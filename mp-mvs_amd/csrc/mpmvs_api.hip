@@ -73,6 +73,14 @@ struct mpmvs_ctx {
     std::vector<float*> d_depth; // dense source depth maps
     StateDev S{};
     bool depth_plane_valid = false;  // S.depth mirrors planes[].w (true from GetDepthandNormal until planes are rewritten)
+    // S.own (the per-view costs InitializeScore stored) describes the planes of colour k as long as own_scale[k] >= 0: the window scale
+    // and the bilateral sigmas it was evaluated with (own_ss / own_sc).  Set by enqueuing k_init; an update pass of colour k may read
+    // the buffer iff it runs with these, and enqueuing it clears k; every other writer of S.planes and every change of the views clears
+    // both (own_invalidate).  Host-side and conservative: the kernels are only ever told what holds for the whole launch.
+    int own_scale[2] = {-1, -1};
+    float own_ss = 0.0f, own_sc = 0.0f;
+    bool own_enabled = true;   // mpmvs_dbg_own_costs(0): every pass recomputes
+    int own_served = 0;        // update passes enqueued with the buffer in use
     float4* d_prior = nullptr;
     uint32_t* d_mask = nullptr;
     bool have_prior = false, have_depths = false;
@@ -260,6 +268,10 @@ struct PoolBuf {
     T* as() const { return (T*)p; }
 };
 
+// S.own no longer describes the planes (or the images, or the texture format they were evaluated in): called by whatever writes
+// S.planes other than k_init and the update passes themselves, and by whatever changes the views
+static void own_invalidate(mpmvs_ctx* c) { c->own_scale[0] = c->own_scale[1] = -1; }
+
 static void release_deferred(mpmvs_ctx* c);
 static void free_views(mpmvs_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);  // nothing may still use what goes back to the pool
@@ -278,6 +290,8 @@ static void free_views(mpmvs_ctx* c) {
     if (c->S.sel) (void)pool_free(c->S.sel);
     if (c->S.geom) (void)pool_free(c->S.geom);
     if (c->S.depth) (void)pool_free(c->S.depth);
+    if (c->S.own) (void)pool_free(c->S.own);
+    own_invalidate(c);
     if (c->d_sync) (void)pool_free(c->d_sync);
     c->d_sync = nullptr;
     if (c->d_band) (void)pool_free(c->d_band);
@@ -830,6 +844,7 @@ static int finish_views(mpmvs_ctx* c) {
     int rc = -100;
     if (pool_malloc(&c->S.planes, wh * 16) == hipSuccess && pool_malloc(&c->S.costs, wh * 4) == hipSuccess &&
         pool_malloc(&c->S.sel, wh * 4) == hipSuccess && pool_malloc(&c->S.geom, wh * 4) == hipSuccess && pool_malloc(&c->S.depth, wh * 4) == hipSuccess &&
+        pool_malloc(&c->S.own, wh * 4 * (size_t)std::max(1, c->n_img - 1)) == hipSuccess &&   // one plane per source view of THIS Problem; written by k_init before any read
         hipMemsetAsync(c->S.planes, 0, wh * 16, c->stream) == hipSuccess && hipMemsetAsync(c->S.costs, 0, wh * 4, c->stream) == hipSuccess &&
         hipMemsetAsync(c->S.sel, 0, wh * 4, c->stream) == hipSuccess && hipMemsetAsync(c->S.geom, 0, wh * 4, c->stream) == hipSuccess)
         rc = 0;
@@ -1256,6 +1271,7 @@ int mpmvs_set_state(mpmvs_ctx* c, const void* planes4, const void* costs) {
     ENTER(c);
     if (!c->S.planes) return fail(c, -1, "set_views first");
     const size_t wh = (size_t)c->W * c->H;
+    own_invalidate(c);
     if (planes4) {
         c->depth_plane_valid = false;
         HIPCHK(c, hipMemcpyAsync(c->S.planes, planes4, wh * 16, hipMemcpyHostToDevice, c->stream));
@@ -1495,6 +1511,7 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
     const dim3 blk(256);
     const dim3 grid_dense((c->W + 15) / 16, (c->H + 15) / 16);
     const dim3 grid_chk = checker_grid(c, a);  // k_filter (checker_pixel)
+    int own_passes = 0;   // passes of this launch that read S.own
     switch (kind) {
         case MPMVS_KIND_INIT: {
             c->depth_plane_valid = false;
@@ -1502,11 +1519,24 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
             dispatch_variant<false, 8, 16, 24, kMaxViews>(c->hP.V, c->all_u8, a.scale, [&](auto maxv, auto u8, auto scale) {
                 hipLaunchKernelGGL((k_init<maxv, u8, scale>), grid_dense, blk, lds, c->stream, c->dP, c->S, a);
             });
+            // S.own now holds the per-view costs of every pixel's plane, as evaluated with this window
+            c->own_scale[0] = c->own_scale[1] = a.scale;
+            c->own_ss = p->sigma_spatial;
+            c->own_sc = p->sigma_color;
             break;
         }
         case MPMVS_KIND_BLACK:
         case MPMVS_KIND_RED:
             c->depth_plane_valid = false;
+            // the first pass of a colour after k_init reads S.own; every pass rewrites the planes of its colour
+            for (int k = 0; k < passes; ++k) {
+                const int colour = (a.parity + k) & 1;
+                if (k < 2 && c->own_enabled && c->own_scale[colour] == a.scale && c->own_ss == p->sigma_spatial && c->own_sc == p->sigma_color) {
+                    ch.own_mask |= 1 << colour;
+                    own_passes++;
+                }
+                c->own_scale[colour] = -1;
+            }
             if (p->geom_consistency)
                 launch_update<true, false>(c, a, ch);
             else if (p->planar_prior)
@@ -1517,9 +1547,11 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
         case MPMVS_KIND_DEPTH_NORMAL:
             hipLaunchKernelGGL(k_depth_normal, grid_dense, blk, 0, c->stream, c->dP, c->S, 0);
             c->depth_plane_valid = true;
+            own_invalidate(c);   // the planes change form (world normal, depth)
             break;
         case MPMVS_KIND_FILTER_BLACK:
         case MPMVS_KIND_FILTER_RED:
+            own_invalidate(c);   // the filter rewrites planes[].w
             if (!c->depth_plane_valid) {  // a filter step on a state that did not come from GetDepthandNormal (mpmvs_set_state + mpmvs_step)
                 const int n = c->W * c->H;
                 hipLaunchKernelGGL(k_export_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S.planes, c->S.depth, n);
@@ -1539,6 +1571,7 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
         }
         return fail(c, -100, "the update launch has more block positions than completion words (d_sync)");
     }
+    c->own_served += own_passes;
     if (c->profiling) {
         HIPCHK(c, hipEventRecord(e1, c->stream));
         c->pending.push_back({kind, e0, e1, passes});
@@ -1594,6 +1627,7 @@ static int abandon_run(mpmvs_ctx* c, int rc) {
         c->event_pool.push_back(pe.e1);
     }
     c->pending.clear();
+    own_invalidate(c);   // whatever the failed launches left in the planes, S.own does not describe it
     if (c->d_sync) {  // a launch that did not finish leaves them dirty
         (void)hipMemsetAsync(c->d_sync, 0, (size_t)(kSyncHeader + c->sync_blocks) * sizeof(int), c->stream);
         (void)hipStreamSynchronize(c->stream);
@@ -1749,6 +1783,7 @@ static int enqueue_band_tail(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed,
         if (last) break;
     }
     c->depth_plane_valid = true;
+    own_invalidate(c);   // k_depth_normal and the filter have rewritten the planes
     return 0;
 }
 
@@ -2788,6 +2823,7 @@ void mpmvs_free_pinned(void* p) {
 int mpmvs_set_texture_format(mpmvs_ctx* c, int force_fp32) {
     if (!c) return -1;
     c->force_f32 = force_fp32 != 0;
+    own_invalidate(c);
     return 0;
 }
 
@@ -2837,6 +2873,13 @@ int mpmvs_dbg_chain_stall(mpmvs_ctx* c, int block_pos, int spin_limit) {
     if (!c) return -1;
     c->dbg_stall_pos = block_pos < 0 ? -1 : block_pos;
     c->spin_limit = spin_limit > 0 ? spin_limit : kSpinLimit;
+    return 0;
+}
+
+int mpmvs_dbg_own_costs(mpmvs_ctx* c, int enable, int* passes_served) {
+    if (!c) return -1;
+    if (enable >= 0) c->own_enabled = enable != 0;
+    if (passes_served) *passes_served = c->own_served;
     return 0;
 }
 

@@ -68,6 +68,9 @@ struct StateDev {
     const float4* prior;
     const uint32_t* mask;
     float* depth;  // dense copy of planes[].w after GetDepthandNormal: what the median filter gathers (4 instead of 16 bytes per tap)
+    // photometric cost of every pixel's stored plane against every view as InitializeScore evaluated it, view-major (own[v * W*H + idx],
+    // V planes): the first update pass of either colour reads it back instead of evaluating the plane again (pm_kernels.hpp, update_body)
+    float* own;
 #ifdef PM_DBG_WAVETIME
     unsigned long long* wavetime;  // measurement builds: per-wave start / end stamps of the update launches (pm_kernels.hpp, WaveTimer)
 #endif

@@ -170,8 +170,12 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_init(const ProblemDev* _
     float m0, m1, m2;
     plane_to_m(P, pl, m0, m1, m2);
     int n_valid = 0;
+    // every per-view cost of the stored plane is kept (S.own): the first update pass of either colour needs exactly these numbers
+    // for "the current plane under the new weights" (update_body, phase B) as long as the pixel still holds this plane
+    const size_t wh = (size_t)P.W * P.H;
     for (int v = 0; v < V; ++v) {
         const float c = ncc_cost<U8, SCALE, true>(P.views[v], rw, x, y, m0, m1, m2);
+        (S.own + v * wh)[idx] = c;
         cv[v] = c;
         sorted[v] = c;
         if (c < 2.0f) n_valid++;
@@ -270,10 +274,12 @@ struct WaveTimer {
 // One pixel update of one block: `b` is the block's raster position, `parity` the colour of this pass, `launch` its launch id (the
 // key of the random streams), `thr` the view-selection threshold of its iteration (ref .cu:832).  The results leave through
 // write-through stores (st_*_wt): what the chained launch below hands from one pass to the next.
+// `use_own` (the same for the whole launch item): every pixel of this pass still holds the plane InitializeScore stored, and S.own
+// holds that plane's photometric cost per view at this window scale -- phase B reads them instead of evaluating the plane again.
 // (At window scales 1 and 2 the reference tile could be staged as a compact half tile of the pass's colour: built in round 6, bit-exact,
 // 0-0.7 % on the scale-2 passes -- the prologue's 37 reads per pixel are not what scale 2 pays for, profiles/EXPERIMENTS.md 52.)
 template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
-PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr) {
+PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr, bool use_own) {
     constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
     // gathers of two window columns ahead (ncc_core): always with the 8-byte texels; with the 16-byte ones where the variant
     // still has the 24 registers of a third column (8 views; more views spill 4 .. 81 registers around the evaluations)
@@ -509,25 +515,63 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     {
         const float4 pl = S.planes[pinned_here(idx)];
         plane_now = pl;
-        float m0, m1, m2;
-        plane_to_m(P, pl, m0, m1, m2);
         float gz = 0.0f;
         if (GEOM) gz = depth_from_plane(P, pl, x, y);
         float tc = 0.0f, tg = 0.0f;
-        float w_next = view_w[0];  // one view ahead: hides the latency of private memory
-        for (int v = 0; v < V; ++v) {
-            const float w = w_next;
-            w_next = view_w[v + 1 < MAXV ? v + 1 : v];
-            if (!(w > 0.0f)) continue;
-            GeomCheck gc;
-            if (GEOM) gc.issue(P.views[v], gz, x, y);  // the depth gather travels behind the NCC evaluation
-            const float c = ncc_cost<U8, SCALE, kDeep, NT>(P.views[v], rw, x, y, m0, m1, m2);
-            if (GEOM) {
-                const float gt = 0.2f * gc.finish(P.views[v], x, y);
-                tc += w * (c + gt);
-                tg += w * gt;
+        if (use_own) {
+            // The first pass of this colour after InitializeScore: `pl` is the plane k_init stored and evaluated, and the photometric
+            // cost is a function of (pixel, plane, view, window scale, images) alone, so S.own holds the bits ncc_cost would return.
+            // Same views, same ascending order, same sums; the loads sit outside every per-lane branch and travel together.
+            const int idx_c = pinned_here(idx);
+            const size_t wh = (size_t)W * Hh;
+            if constexpr (GEOM) {
+                // one view ahead: the stored cost and the depth gather of view v + 1 travel while the check of view v is finished
+                float w_n = view_w[0], c_n = S.own[idx_c];
+                GeomCheck gc_n{};
+                if (w_n > 0.0f) gc_n.issue(P.views[0], gz, x, y);
+                for (int v = 0; v < V; ++v) {
+                    const float w = w_n, c = c_n;
+                    const GeomCheck gc = gc_n;
+                    if (v + 1 < V) {
+                        w_n = view_w[v + 1];
+                        c_n = (S.own + (v + 1) * wh)[idx_c];
+                        if (w_n > 0.0f) gc_n.issue(P.views[v + 1], gz, x, y);
+                    }
+                    if (!(w > 0.0f)) continue;
+                    const float gt = 0.2f * gc.finish(P.views[v], x, y);
+                    tc += w * (c + gt);
+                    tg += w * gt;
+                }
             } else {
-                tc += w * c;
+                float oc[MAXV];  // (views beyond V repeat the last one: a load, no branch)
+#pragma unroll
+                for (int v = 0; v < MAXV; ++v) oc[v] = (S.own + (v < V ? v : V - 1) * wh)[idx_c];
+#pragma unroll
+                for (int v = 0; v < MAXV; ++v) {
+                    if (v >= V) break;
+                    const float w = view_w[v];
+                    if (!(w > 0.0f)) continue;
+                    tc += w * oc[v];
+                }
+            }
+        } else {
+            float m0, m1, m2;
+            plane_to_m(P, pl, m0, m1, m2);
+            float w_next = view_w[0];  // one view ahead: hides the latency of private memory
+            for (int v = 0; v < V; ++v) {
+                const float w = w_next;
+                w_next = view_w[v + 1 < MAXV ? v + 1 : v];
+                if (!(w > 0.0f)) continue;
+                GeomCheck gc;
+                if (GEOM) gc.issue(P.views[v], gz, x, y);  // the depth gather travels behind the NCC evaluation
+                const float c = ncc_cost<U8, SCALE, kDeep, NT>(P.views[v], rw, x, y, m0, m1, m2);
+                if (GEOM) {
+                    const float gt = 0.2f * gc.finish(P.views[v], x, y);
+                    tc += w * (c + gt);
+                    tg += w * gt;
+                } else {
+                    tc += w * c;
+                }
             }
         }
         cost_now = tc / weight_norm;
@@ -834,6 +878,9 @@ struct ChainArgs {
     int band_groups;      // 8-row groups (kWaveRows) per band
     int n_groups;         // 8-row groups of the rows the launch updates: group g counts toward band g / band_groups
     unsigned band_run;    // the banded Run() this launch ends (1, 2, ...): band k's target is band_run x nbx x (groups of band k)
+    // bit c: the FIRST pass of colour c in this launch (pass 0 or 1) reads its current planes' per-view costs from S.own (update_body);
+    // set by the host for the passes that follow InitializeScore at its window scale with no writer of the planes in between
+    int own_mask;
 };
 constexpr int kChainMaxIters = 8;
 constexpr int kSyncHeader = 16;
@@ -909,7 +956,8 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
 #endif
     {
         const int k = a.parity + pass;
-        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0]);
+        const bool use_own = pass < 2 && ((ch.own_mask >> (k & 1)) & 1) != 0;
+        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0], use_own);
     }
     // completion: this wave's stores have left (write-through) before it counts itself done
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

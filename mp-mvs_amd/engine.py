@@ -42,6 +42,7 @@ _EXTRA = {
     "view_select": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "view_select_kernel_ms": (C.c_float, []),
     "dbg_chain_stall": (C.c_int, [_P, C.c_int, C.c_int]),
+    "dbg_own_costs": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "set_views_u8": (C.c_int, [_P, C.c_int, C.POINTER(_abi.Camera), C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "resize_u8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, _P]),
     "skyseg_inspect": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_longlong)]),
@@ -169,6 +170,13 @@ class HipPatchMatch(_abi.PatchMatchHandle):
     def dbg_chain_stall(self, block_pos, spin_limit=0):
         """fault injection (tests): the update block at `block_pos` never signals its first pass; block_pos < 0 switches it off"""
         self._chk(self._f["dbg_chain_stall"](self._ctx, int(block_pos), int(spin_limit)), "dbg_chain_stall")
+
+    def dbg_own_costs(self, enable=None):
+        """the per-view costs kept from InitializeScore (mpmvs_dbg_own_costs): enable False makes every update pass recompute
+        them, True is the default, None leaves the setting; returns the number of update passes enqueued so far that read them"""
+        n = C.c_int(0)
+        self._chk(self._f["dbg_own_costs"](self._ctx, -1 if enable is None else (1 if enable else 0), C.byref(n)), "dbg_own_costs")
+        return int(n.value)
 
     def set_profiling(self, on=True):
         self._chk(self._f["set_profiling"](self._ctx, 1 if on else 0), "set_profiling")

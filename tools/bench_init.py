@@ -15,6 +15,8 @@ dmin, dmax = pm.synth.kernel_depth_range(cams[0])
 h = engine.create(0)
 h.set_views(cams, imgs)
 h.set_profiling(True)
+if os.environ.get("MPMVS_OWN_COSTS") == "0":   # A/B in one build: every update pass recomputes its current plane's costs
+    h.dbg_own_costs(False)
 p = pm.PatchMatchParams(num_images=9, depth_min=float(dmin), depth_max=float(dmax), max_scale=0, max_iterations=1)
 out = {}
 for rep in range(3):

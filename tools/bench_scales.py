@@ -16,6 +16,8 @@ if os.environ.get("MPMVS_FORCE_F32"):   # the fp32 texture format on the same 8-
     h.set_texture_format(True)
 h.set_views(cams, imgs)
 h.set_profiling(True)
+if os.environ.get("MPMVS_OWN_COSTS") == "0":   # A/B in one build: every update pass recomputes its current plane's costs
+    h.dbg_own_costs(False)
 p = pm.PatchMatchParams(num_images=V + 1, depth_min=float(dmin), depth_max=float(dmax), max_scale=2)
 h.run(p, 1)  # converged state
 out = {}
