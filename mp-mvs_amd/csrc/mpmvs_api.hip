@@ -1,6 +1,7 @@
 // mpmvs_api.hip -- host side of the C ABI declared in include/mpmvs.h: context
-// and HBM residency management, uploads, the Run() launch schedule
-// (reference src/PatchMatch.cu:1188-1254) and the probes used by the parity tests.
+// and HBM residency management, uploads (upload_views for both image entries; its host half, the staging
+// plan and the row work, is pm_stage.hpp), the Run() launch schedule (reference src/PatchMatch.cu:1188-1254),
+// the stateless calls (DeviceCall: fusion, sky mask, view selection, undistortion) and the probes used by the parity tests.
 //
 // HBM layout per context:
 //   reference image   (W+40) x (H+40) fp32, replicated apron 20  (window radius <= 20)
@@ -14,14 +15,11 @@
 // There is no per-pixel RNG state (the reference keeps 48 B/pixel of cuRAND).
 #include <hip/hip_runtime.h>
 
-#include <pthread.h>
-
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <condition_variable>
 #include <string>
 #include <atomic>
 #include <thread>
@@ -43,6 +41,7 @@
 #include "pm_undistort.hpp"
 #include "pm_skyseg.hpp"
 #include "pm_skyseg_model.hpp"
+#include "pm_stage.hpp"
 
 using namespace pm;
 
@@ -246,31 +245,93 @@ struct PinnedPool {
 PinnedPool g_pinned;
 }  // namespace
 
-// scratch device buffer of a probe call: released on every return path (hipFree waits for the device)
-struct DevBuf {
+// page-locked scratch of one call: back to its pool on every return path
+struct PinnedBuf {
     void* p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
+    ~PinnedBuf() {
+        if (p) mpmvs_free_pinned(p);
     }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-    template <typename T>
-    T* as() const { return (T*)p; }
 };
 
-// pooled scratch buffer of one call: back to the pool on every return path (the caller synchronises the stream first)
-struct PoolBuf {
+// Pooled scratch buffer of one call on a stream that outlives it (a context's, the sky network's): on every return path the
+// stream is synchronised first, then the buffer goes back to the pool -- nothing returns to the pool while the stream may use it.
+struct Scratch {
+    hipStream_t st;
     void* p = nullptr;
-    ~PoolBuf() {
-        if (p) (void)pool_free(p);
+    explicit Scratch(hipStream_t stream) : st(stream) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        if (!p) return;
+        (void)hipStreamSynchronize(st);
+        (void)pool_free(p);
     }
     hipError_t alloc(size_t bytes) { return pool_malloc_bytes(&p, bytes ? bytes : 4); }
     template <typename T>
     T* as() const { return (T*)p; }
 };
 
+// One stateless call on a device (fusion, sky mask, view selection, undistortion, the probes): a non-blocking stream of its own --
+// the PatchMatch contexts other host threads drive on this device keep running -- and the pooled buffers of the call.  The
+// destructor synchronises the stream, THEN gives the buffers back and destroys the events and the stream, on every return path.
+class DeviceCall {
+    hipStream_t st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    std::vector<void*> bufs;
+    bool entered_ = false, own_stream = false;
+
+   public:
+    explicit DeviceCall(int device) : entered_(enter_device(device) == hipSuccess) {
+        own_stream = entered_ && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess;
+    }
+    // a probe without a device argument: the current device and its null stream
+    DeviceCall() : entered_(true) { (void)hipGetLastError(); }  // drop a stale error of an earlier call (see enter_device)
+    DeviceCall(const DeviceCall&) = delete;
+    DeviceCall& operator=(const DeviceCall&) = delete;
+    ~DeviceCall() {
+        if (!entered_) return;
+        (void)hipStreamSynchronize(st);
+        for (void* p : bufs) (void)pool_free(p);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream) (void)hipStreamDestroy(st);
+    }
+    bool entered() const { return entered_; }         // the device could be selected
+    bool ok() const { return own_stream; }            // ... and the stream exists
+    hipStream_t stream() const { return st; }
+    // nullptr: no memory.  Zero-sized arrays still get a (4-byte) buffer, so that no kernel argument is null.
+    template <typename T>
+    T* alloc(size_t bytes) {
+        void* p = nullptr;
+        if (pool_malloc_bytes(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        return (T*)p;
+    }
+    // begin() ... end() around the kernels; once the stream is synchronised, elapsed() is their device time
+    bool begin() { return hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventRecord(ev[0], st) == hipSuccess; }
+    bool end() { return hipEventRecord(ev[1], st) == hipSuccess; }
+    bool elapsed(float* ms) const { return hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess; }
+};
+
 // S.own no longer describes the planes (or the images, or the texture format they were evaluated in): called by whatever writes
 // S.planes other than k_init and the update passes themselves, and by whatever changes the views
 static void own_invalidate(mpmvs_ctx* c) { c->own_scale[0] = c->own_scale[1] = -1; }
+
+// the device staging buffers of mpmvs_run_get_async: all three or none
+static void free_run_stage(mpmvs_ctx* c) {
+    if (c->stage_planes) (void)pool_free(c->stage_planes);
+    if (c->stage_costs) (void)pool_free(c->stage_costs);
+    if (c->stage_geom) (void)pool_free(c->stage_geom);
+    c->stage_planes = nullptr;
+    c->stage_costs = c->stage_geom = nullptr;
+}
+
+static void reset_kernel_times(mpmvs_ctx* c) {
+    for (int k = 0; k < 6; ++k) {
+        c->k_ms[k] = 0.0f;
+        c->k_cnt[k] = 0;
+    }
+}
 
 static void release_deferred(mpmvs_ctx* c);
 static void free_views(mpmvs_ctx* c) {
@@ -300,11 +361,7 @@ static void free_views(mpmvs_ctx* c) {
 #ifdef PM_DBG_WAVETIME
     if (c->S.wavetime) (void)hipFree(c->S.wavetime);
 #endif
-    if (c->stage_planes) (void)pool_free(c->stage_planes);
-    if (c->stage_costs) (void)pool_free(c->stage_costs);
-    if (c->stage_geom) (void)pool_free(c->stage_geom);
-    c->stage_planes = nullptr;
-    c->stage_costs = c->stage_geom = nullptr;
+    free_run_stage(c);
     if (c->d_prior) (void)pool_free(c->d_prior);
     if (c->d_mask) (void)pool_free(c->d_mask);
     c->S = StateDev{};
@@ -427,168 +484,6 @@ static int upload_problem(mpmvs_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     release_deferred(c);
     return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Image upload (CudaMemInit's image half, ref .cpp:999-1025).  The caller's images are pageable fp32 arrays; copied as they
-// are, the runtime stages them through its own bounce buffers at a fraction of the PCIe rate and every copy is synchronous.
-// Here the rows are converted (8-bit exact images: to bytes, which also quarters the traffic) or copied into ONE page-locked
-// staging buffer by a few host threads, go to the device in asynchronous DMA transfers, and are unpacked there; the call
-// does not synchronise (round 6): both staging buffers stay with the context until its stream is next synchronised (release_deferred).
-// ---------------------------------------------------------------------------
-namespace {
-// a small persistent pool for the row work (thread creation costs as much as converting an image); a caller that finds it
-// busy -- several Problems upload at once in the multi-Problem schedule -- works with a few short-lived threads instead
-class RowPool {
-    std::vector<std::thread> workers;
-    std::mutex mu, busy;
-    std::condition_variable wake;
-    const std::function<void()>* job = nullptr;
-    std::atomic<int> running{0};
-    unsigned long generation = 0;
-    bool quit = false;
-    void worker() {
-        unsigned long seen = 0;
-        for (;;) {
-            const std::function<void()>* fn;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                wake.wait(lk, [&] { return quit || generation != seen; });
-                if (quit) return;
-                seen = generation;
-                fn = job;
-            }
-            (*fn)();
-            running.fetch_sub(1, std::memory_order_release);
-        }
-    }
-
-   public:
-    RowPool() {
-        const unsigned hw = std::thread::hardware_concurrency();
-        const int n = (int)std::max(1u, std::min(16u, hw ? hw : 1u));
-        for (int t = 1; t < n; ++t) workers.emplace_back(&RowPool::worker, this);
-    }
-    ~RowPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            quit = true;
-        }
-        wake.notify_all();
-        for (std::thread& t : workers) t.join();
-    }
-    // a forked child inherits this object but not its threads: it works on its own thread
-    static std::atomic<bool>& forked() {
-        static std::atomic<bool> f(false);
-        return f;
-    }
-    // fn() on every worker and on the caller (fn pulls its own work items from a shared counter)
-    void run(const std::function<void()>& fn) {
-        if (forked().load(std::memory_order_relaxed)) {
-            fn();
-            return;
-        }
-        if (!busy.try_lock()) {
-            std::vector<std::thread> tmp;
-            for (int t = 0; t < 3; ++t) tmp.emplace_back(fn);
-            fn();
-            for (std::thread& t : tmp) t.join();
-            return;
-        }
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            job = &fn;
-            running.store((int)workers.size(), std::memory_order_relaxed);
-            ++generation;
-        }
-        wake.notify_all();
-        fn();
-        while (running.load(std::memory_order_acquire) > 0) std::this_thread::yield();
-        busy.unlock();
-    }
-};
-RowPool& row_pool() {
-    // deliberately leaked (never destroyed at process exit): in the child of a fork() the object names threads that do not exist
-    // there and its condition variable still counts the parent's waiters -- joining / destroying them blocks forever in exit()
-    static RowPool& p = *new RowPool;
-    static const int registered = pthread_atfork(nullptr, nullptr, [] { RowPool::forked().store(true); });
-    (void)registered;
-    return p;
-}
-
-struct PinnedBuf {
-    void* p = nullptr;
-    ~PinnedBuf() {
-        if (p) mpmvs_free_pinned(p);
-    }
-};
-}  // namespace
-
-// Stages the n images: slot[i] = byte offset of image i in `stage` (room for w * h floats each).  An image whose pixels are all
-// integers in [0, 255] (the reference's imread(GRAYSCALE) -> CV_32F input, ref .cpp:877-882) is staged as w * h BYTES and
-// is_u8[i] set; the sources are treated as one group (the texture format is the same for all of them: `src_u8`), view 0 on
-// its own.  Rows are dealt to the pool in chunks; a group found inexact is staged again as fp32 rows.
-static void stage_images(int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes, bool try_src_u8, char* stage,
-                         const std::vector<size_t>& slot, bool& ref_u8, bool& src_u8) {
-    std::vector<long> row0(n + 1, 0);
-    for (int i = 0; i < n; ++i) row0[i + 1] = row0[i] + cams[i].height;
-    const long total_rows = row0[n];
-    auto image_of_row = [&](long k) {
-        int i = 0;
-        while (k >= row0[i + 1]) ++i;
-        return i;
-    };
-    std::atomic<bool> ref_exact(true), src_exact(try_src_u8);
-    {
-        std::atomic<long> next(0);
-        const std::function<void()> work = [&]() {
-            const long chunk = 32;
-            for (;;) {
-                const long r0 = next.fetch_add(chunk);
-                if (r0 >= total_rows) return;
-                int i = image_of_row(r0);
-                for (long k = r0; k < std::min(r0 + chunk, total_rows); ++k) {
-                    while (k >= row0[i + 1]) ++i;
-                    std::atomic<bool>& exact = i == 0 ? ref_exact : src_exact;
-                    if (!exact.load(std::memory_order_relaxed)) continue;
-                    const int y = (int)(k - row0[i]), w = cams[i].width;
-                    const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w * 4;
-                    const float* row = (const float*)((const char*)images[i] + (size_t)y * pitch);
-                    unsigned char* o = (unsigned char*)(stage + slot[i]) + (size_t)y * w;
-                    bool ok = true;
-                    for (int x = 0; x < w; ++x) {
-                        const float f = row[x];
-                        const int q = (int)(f >= 0.0f && f <= 255.0f ? f : -1.0f);
-                        ok &= (float)q == f;
-                        o[x] = (unsigned char)q;
-                    }
-                    if (!ok) exact.store(false, std::memory_order_relaxed);
-                }
-            }
-        };
-        row_pool().run(work);
-    }
-    ref_u8 = ref_exact.load();
-    src_u8 = src_exact.load();
-    if (ref_u8 && src_u8) return;
-    // second sweep: the fp32 rows of whatever is not 8-bit exact
-    std::atomic<long> next(0);
-    const std::function<void()> work = [&]() {
-        const long chunk = 32;
-        for (;;) {
-            const long r0 = next.fetch_add(chunk);
-            if (r0 >= total_rows) return;
-            int i = image_of_row(r0);
-            for (long k = r0; k < std::min(r0 + chunk, total_rows); ++k) {
-                while (k >= row0[i + 1]) ++i;
-                if (i == 0 ? ref_u8 : src_u8) continue;
-                const int y = (int)(k - row0[i]), w = cams[i].width;
-                const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w * 4;
-                std::memcpy(stage + slot[i] + (size_t)y * w * 4, (const char*)images[i] + (size_t)y * pitch, (size_t)w * 4);
-            }
-        }
-    };
-    row_pool().run(work);
 }
 
 // ---------------------------------------------------------------------------
@@ -761,85 +656,25 @@ void mpmvs_destroy(mpmvs_ctx* c) {
 
 const char* mpmvs_last_error(const mpmvs_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
-// Exactness of the images without staging anything (the first pass of an upload in bounded slices): is the reference image / is
-// every source image made of integers in [0, 255]?  Row chunks on the pool; a group's rows are skipped once its flag has dropped.
-static void probe_exact(int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes, bool try_src_u8, bool& ref_u8, bool& src_u8) {
-    std::vector<long> row0(n + 1, 0);
-    for (int i = 0; i < n; ++i) row0[i + 1] = row0[i] + cams[i].height;
-    const long total_rows = row0[n];
-    std::atomic<bool> ref_exact(true), src_exact(try_src_u8);
-    std::atomic<long> next(0);
-    const std::function<void()> work = [&]() {
-        const long chunk = 32;
-        for (;;) {
-            const long r0 = next.fetch_add(chunk);
-            if (r0 >= total_rows) return;
-            int i = 0;
-            while (r0 >= row0[i + 1]) ++i;
-            for (long k = r0; k < std::min(r0 + chunk, total_rows); ++k) {
-                while (k >= row0[i + 1]) ++i;
-                std::atomic<bool>& exact = i == 0 ? ref_exact : src_exact;
-                if (!exact.load(std::memory_order_relaxed)) continue;
-                const int y = (int)(k - row0[i]), w = cams[i].width;
-                const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w * 4;
-                const float* row = (const float*)((const char*)images[i] + (size_t)y * pitch);
-                bool ok = true;
-                for (int x = 0; x < w; ++x) {
-                    const float f = row[x];
-                    const int q = (int)(f >= 0.0f && f <= 255.0f ? f : -1.0f);
-                    ok &= (float)q == f;
-                }
-                if (!ok) exact.store(false, std::memory_order_relaxed);
-            }
-        }
-    };
-    row_pool().run(work);
-    ref_u8 = ref_exact.load();
-    src_u8 = src_exact.load();
+// ---------------------------------------------------------------------------
+// Image upload (CudaMemInit's image half, ref .cpp:999-1025).  The caller's images are pageable fp32 arrays; copied as they
+// are, the runtime stages them through its own bounce buffers at a fraction of the PCIe rate and every copy is synchronous.
+// Here the rows are converted (8-bit exact images: to bytes, which also quarters the traffic) or copied into ONE page-locked
+// staging buffer by a few host threads, go to the device in asynchronous DMA transfers, and are unpacked there; the call
+// does not synchronise (round 6): both staging buffers stay with the context until its stream is next synchronised (release_deferred).
+// The host half -- slots, groups, the row work -- is pm_stage.hpp.
+// ---------------------------------------------------------------------------
+// an upload gives up: nothing of it stays in flight, the staging buffers go back
+static int upload_failed(mpmvs_ctx* c, const char* what) {
+    (void)hipStreamSynchronize(c->stream);
+    release_deferred(c);
+    c->err = what;
+    return -100;
 }
 
-// Stages images [first, last) whose formats are already known (ref_u8 / src_u8): bytes or fp32 rows into `stage` at slot[i] - slot[first]
-static void stage_known(int first, int last, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes, char* stage,
-                        const std::vector<size_t>& slot, bool ref_u8, bool src_u8) {
-    std::vector<long> row0(last - first + 1, 0);
-    for (int i = first; i < last; ++i) row0[i - first + 1] = row0[i - first] + cams[i].height;
-    const long total_rows = row0[last - first];
-    std::atomic<long> next(0);
-    const std::function<void()> work = [&]() {
-        const long chunk = 32;
-        for (;;) {
-            const long r0 = next.fetch_add(chunk);
-            if (r0 >= total_rows) return;
-            int g = 0;
-            while (r0 >= row0[g + 1]) ++g;
-            for (long k = r0; k < std::min(r0 + chunk, total_rows); ++k) {
-                while (k >= row0[g + 1]) ++g;
-                const int i = first + g, y = (int)(k - row0[g]), w = cams[i].width;
-                const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w * 4;
-                const float* row = (const float*)((const char*)images[i] + (size_t)y * pitch);
-                char* base = stage + (slot[i] - slot[first]);
-                if (i == 0 ? ref_u8 : src_u8) {
-                    unsigned char* o = (unsigned char*)base + (size_t)y * w;
-                    for (int x = 0; x < w; ++x) o[x] = (unsigned char)(int)row[x];
-                } else {
-                    std::memcpy(base + (size_t)y * w * 4, row, (size_t)w * 4);
-                }
-            }
-        }
-    };
-    row_pool().run(work);
-}
-
-// Second half of an image upload, shared by both entries (mpmvs_set_views, mpmvs_set_views_u8): the per-pixel state of the Problem and
-// its ProblemDev, enqueued behind the unpacking kernels
+// Second half of an image upload: the per-pixel state of the Problem and its ProblemDev, enqueued behind the unpacking kernels
 static int finish_views(mpmvs_ctx* c) {
-    auto failed = [&](const char* what) {
-        (void)hipStreamSynchronize(c->stream);
-        release_deferred(c);
-        c->err = what;
-        return -100;
-    };
-    if (hipGetLastError() != hipSuccess) return failed("unpacking the images on the device failed");
+    if (hipGetLastError() != hipSuccess) return upload_failed(c, "unpacking the images on the device failed");
     const size_t wh = (size_t)c->W * c->H;
     int rc = -100;
     if (pool_malloc(&c->S.planes, wh * 16) == hipSuccess && pool_malloc(&c->S.costs, wh * 4) == hipSuccess &&
@@ -864,65 +699,68 @@ static int finish_views(mpmvs_ctx* c) {
     // room for 16 launches of one wave per 64 pixels of a colour, 4 x u64 each (generous: blocks overhang the image border)
     if (!rc && (hipMalloc(&c->S.wavetime, kWaveTimeBytes(c->W, c->H)) != hipSuccess || hipMemsetAsync(c->S.wavetime, 0, kWaveTimeBytes(c->W, c->H), c->stream) != hipSuccess)) rc = -100;
 #endif
-    if (rc) return failed("allocation of the per-pixel state failed");
+    if (rc) return upload_failed(c, "allocation of the per-pixel state failed");
     // no synchronisation: everything later on this context follows on the same stream, and a transfer that fails is reported by the
     // next call that waits for the stream (mpmvs_run*, mpmvs_get, ...) as -100
     return upload_problem_async(c);
 }
 
-static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes) {
+static IngestSrc ingest_src(const unsigned char* d_bytes, int src_w, int src_h, int dst_w, int dst_h) {
+    // the two ratios exactly as ResizeLinear forms them (host/PatchMatchHost.cpp)
+    return IngestSrc{d_bytes, src_w, src_h, (unsigned)src_w, (float)src_w / dst_w, (float)src_h / dst_h};
+}
+
+// What the two entries hand to the one upload (upload_views): the images as the caller holds them, and how their rows reach the stage.
+struct ViewsInput {
+    std::vector<pmstage::HostImage> im;   // per view the size it is staged at (the byte entry: its own, it may be shrunk on the device)
+    size_t slot_px;                       // staging room per pixel, bytes
+    // Whether the reference image / the sources are staged as bytes (else as fp32 rows), decided before the first group is staged:
+    // the texture format of the sources must be known before the first of them is packed.  May stage group 0 on the way when
+    // that is all there is, and says so (true).  Absent: everything is bytes.
+    std::function<bool(const pmstage::StagePlan&, char* stage, bool& ref_bytes, bool& src_bytes)> formats;
+    std::function<void(const pmstage::StagePlan&, int g, char* stage, bool ref_bytes, bool src_bytes)> stage_group;
+};
+
+// THE image upload, for both entries.  `in` says how the rows are staged; which kernel unpacks a view follows from what was staged:
+//   reference   bytes, same size   k_pad_u8              source, fp16 texels   bytes, same size   k_pack_quads_u8
+//               bytes, resampled   k_ingest_pad          source, fp32 texels   fp32               k_pack_quads_f32
+//               fp32               k_pad                                       bytes              k_ingest_quads<resampled>
+// The sources take the 8-byte fp16 texels iff they are staged as bytes (8-bit exact: the reference's imread path, ref .cpp:877-882),
+// none of them is resampled (a resampled image is not made of integers) and fp32 is not forced; else the 16-byte fp32 ones.  One
+// inexact source sends all sources to fp32; the reference image decides its own format.
+static int upload_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const ViewsInput& in) {
     c->n_img = n;
     c->cams.assign(cams, cams + n);
     c->W = cams[0].width;
     c->H = cams[0].height;
     std::memset(&c->hP, 0, sizeof(ProblemDev));
     precompute_views(c);
-    // host staging (page-locked, pooled) and its device twin: a slot of w * h floats per image, 256-byte aligned
-    std::vector<size_t> slot(n + 1, 0);
-    for (int i = 0; i < n; ++i) slot[i + 1] = slot[i] + (((size_t)cams[i].width * cams[i].height * 4 + 255) & ~(size_t)255);
-    // The images are staged in GROUPS of consecutive views of at most MPMVS_STAGE_MB (default 512) megabytes: ordinary inputs are
-    // one group (one pass over the images that decides the formats while it stages, no synchronisation); very many large
-    // views (33 x 3200 x 3200 floats = 1.35 GB) go through bounded staging buffers that are re-used group by group, after a first
-    // pass that only decides the formats (the texture format of the sources must be known before the first of them is packed).
-    size_t limit = 512;
-    if (const char* e = std::getenv("MPMVS_STAGE_MB")) limit = (size_t)std::max(1, std::atoi(e));
-    limit <<= 20;
-    std::vector<int> group_first{0};
-    for (int i = 1; i < n; ++i)
-        if (slot[i + 1] - slot[group_first.back()] > limit) group_first.push_back(i);
-    group_first.push_back(n);
-    const int n_groups = (int)group_first.size() - 1;
-    size_t stage_bytes = 0;
-    for (int g = 0; g < n_groups; ++g) stage_bytes = std::max(stage_bytes, slot[group_first[g + 1]] - slot[group_first[g]]);
+    const pmstage::HostImage* im = in.im.data();
+    auto resampled = [&](int i) { return im[i].w != cams[i].width || im[i].h != cams[i].height; };
+    // host staging (page-locked, pooled) and its device twin: a slot per image, 256-byte aligned, in groups under the staging limit
+    const pmstage::StagePlan plan = pmstage::plan_stage(im, n, in.slot_px, pmstage::stage_limit_bytes());
+    const int n_groups = plan.groups();
+    const size_t stage_bytes = plan.stage_bytes;
     // Both staging buffers stay with the context until the stream has been synchronised the next time (release_deferred): the call
     // returns as soon as the transfers and the unpacking kernels are ENQUEUED, so that the upload of one Problem overlaps whatever else
     // the GPU and the host are doing -- the other contexts of a multi-Problem job, this context's own next call (ref src/main.cpp:20-41).
-    struct { void* p; } stage{mpmvs_alloc_pinned(stage_bytes)};
-    if (!stage.p) return fail(c, -100, "no page-locked staging memory for the images");
-    c->deferred_pinned.push_back(stage.p);
-    bool ref_u8 = false, src_u8 = false;
-    // 8-bit exact sources (the reference's imread path, ref .cpp:877-882) take the 8-byte fp16 texel format; anything else,
-    // or force_f32, the 16-byte fp32 one
-    if (n_groups == 1)
-        stage_images(n, cams, images, pitch_bytes, !c->force_f32, (char*)stage.p, slot, ref_u8, src_u8);
-    else
-        probe_exact(n, cams, images, pitch_bytes, !c->force_f32, ref_u8, src_u8);
-    c->all_u8 = src_u8;
+    char* const stage = (char*)mpmvs_alloc_pinned(stage_bytes);
+    if (!stage) return fail(c, -100, "no page-locked staging memory for the images");
+    c->deferred_pinned.push_back(stage);
     void* d_stage_p = nullptr;
     HIPCHK(c, pool_malloc_bytes(&d_stage_p, stage_bytes ? stage_bytes : 4));
     c->deferred_dev.push_back(d_stage_p);
     char* const d_stage = (char*)d_stage_p;
-    auto failed = [&](const char* what) {
-        (void)hipStreamSynchronize(c->stream);
-        release_deferred(c);
-        c->err = what;
-        return -100;
-    };
+    bool ref_bytes = true, src_bytes = true;
+    const bool staged = in.formats && in.formats(plan, stage, ref_bytes, src_bytes);
+    bool src_u8 = src_bytes && !c->force_f32;
+    for (int v = 1; v < n; ++v) src_u8 = src_u8 && !resampled(v);
+    c->all_u8 = src_u8;
     // reference image (replicate-padded fp32) and one allocation for the textures of all views, each 256-byte aligned.  Every
     // view is addressed through its own buffer resource (base = the view's first texel, 32-bit offsets inside it), so only a
     // single view is limited to 4 GB (checked by the caller), not the allocation: 32 views of 3200 x 3200 fp32 texels are 5.2 GB.
     const int pw = c->W + 2 * kRefApron, ph = c->H + 2 * kRefApron;
-    if (pool_malloc(&c->d_ref, (size_t)pw * ph * 4) != hipSuccess) return failed("allocation of the reference image failed");
+    if (pool_malloc(&c->d_ref, (size_t)pw * ph * 4) != hipSuccess) return upload_failed(c, "allocation of the reference image failed");
     c->hP.ref_pitch = pw;
     c->hP.ref_img = c->d_ref + (size_t)kRefApron * pw + kRefApron;
     const size_t texel = src_u8 ? 8 : 16;
@@ -932,28 +770,31 @@ static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const f
         tex_off[v] = tex_total;
         tex_total += ((size_t)cams[v].width * cams[v].height * texel + 255) & ~(size_t)255;
     }
-    if (pool_malloc(&c->d_tex_all, tex_total) != hipSuccess) return failed("allocation of the source textures failed");
+    if (pool_malloc(&c->d_tex_all, tex_total) != hipSuccess) return upload_failed(c, "allocation of the source textures failed");
     if (src_u8) c->d_src8.assign(n - 1, nullptr); else c->d_src.assign(n - 1, nullptr);
     for (int g = 0; g < n_groups; ++g) {
-        const int first = group_first[g], last = group_first[g + 1];
-        if (n_groups > 1) {
-            if (g > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return failed("upload of the images failed");  // the staging buffers are free again
-            stage_known(first, last, cams, images, pitch_bytes, (char*)stage.p, slot, ref_u8, src_u8);
-        }
+        const int first = plan.group_first[g], last = plan.group_first[g + 1];
+        // (with one group nothing synchronises: g == 0)
+        if (g > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return upload_failed(c, "upload of the images failed");  // the staging buffers are free again
+        if (!staged) in.stage_group(plan, g, stage, ref_bytes, src_bytes);
         for (int i = first; i < last; ++i) {
-            const size_t off = slot[i] - slot[first];
-            const size_t bytes = (size_t)cams[i].width * cams[i].height * ((i == 0 ? ref_u8 : src_u8) ? 1 : 4);
-            if (hipMemcpyAsync(d_stage + off, (const char*)stage.p + off, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                return failed("upload of the images failed");
+            const size_t off = plan.at(g, i);
+            const size_t bytes = (size_t)im[i].w * im[i].h * ((i == 0 ? ref_bytes : src_bytes) ? 1 : 4);
+            if (hipMemcpyAsync(d_stage + off, stage + off, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+                return upload_failed(c, "upload of the images failed");
         }
         for (int v = first; v < last; ++v) {
-            const char* src = d_stage + (slot[v] - slot[first]);
+            const char* src = d_stage + plan.at(g, v);
             const int w = cams[v].width, h = cams[v].height;
+            const IngestSrc s = ingest_src((const unsigned char*)src, im[v].w, im[v].h, w, h);   // (read where the view is staged as bytes)
             if (v == 0) {
-                if (ref_u8)
-                    hipLaunchKernelGGL(k_pad_u8, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, (const unsigned char*)src, c->W, c->H, c->d_ref, kRefApron);
+                const dim3 grid((pw + 255) / 256, ph);
+                if (!ref_bytes)
+                    hipLaunchKernelGGL(k_pad, grid, dim3(256), 0, c->stream, (const float*)src, w, h, c->d_ref, kRefApron);
+                else if (resampled(0))
+                    hipLaunchKernelGGL(k_ingest_pad, grid, dim3(256), 0, c->stream, s, w, h, c->d_ref, kRefApron);
                 else
-                    hipLaunchKernelGGL(k_pad, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, (const float*)src, c->W, c->H, c->d_ref, kRefApron);
+                    hipLaunchKernelGGL(k_pad_u8, grid, dim3(256), 0, c->stream, (const unsigned char*)src, w, h, c->d_ref, kRefApron);
                 continue;
             }
             ViewDev& o = c->hP.views[v - 1];
@@ -962,197 +803,104 @@ static int set_views_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const f
                 hipLaunchKernelGGL(k_pack_quads_u8, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, (const unsigned char*)src, w, h, (uint2*)c->d_src8[v - 1]);
                 o.pitch8 = w;
                 o.img8 = c->d_src8[v - 1];
-            } else {
-                c->d_src[v - 1] = (float*)((char*)c->d_tex_all + tex_off[v]);
-                hipLaunchKernelGGL(k_pack_quads_f32, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, (const float*)src, w, h, (float4*)c->d_src[v - 1]);
-                o.pitch = w;
-                o.img = c->d_src[v - 1];
+                continue;
             }
+            c->d_src[v - 1] = (float*)((char*)c->d_tex_all + tex_off[v]);
+            float4* const tex = (float4*)c->d_src[v - 1];
+            const dim3 grid((w + kIngestTW - 1) / kIngestTW, (h + kIngestTH - 1) / kIngestTH);
+            if (!src_bytes)
+                hipLaunchKernelGGL(k_pack_quads_f32, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, (const float*)src, w, h, tex);
+            else if (resampled(v))
+                hipLaunchKernelGGL(k_ingest_quads<true>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, tex);
+            else
+                hipLaunchKernelGGL(k_ingest_quads<false>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, tex);
+            o.pitch = w;
+            o.img = c->d_src[v - 1];
         }
     }
     return finish_views(c);
+}
+
+// What both entries check before they touch the context; the byte entry (src_w / src_h / pitch in bytes as it got them, any of
+// them null) adds the checks of its source sizes
+static int validate_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const void* const* images, bool bytes, const int* src_w, const int* src_h,
+                          const size_t* pitch_bytes) {
+    if (n < 2 || n - 1 > MPMVS_MAX_SRC_VIEWS) return fail(c, -1, "need 2..33 views");
+    if (bytes && (!cams || !images || (src_w == nullptr) != (src_h == nullptr))) return fail(c, -2, "null argument (source widths and heights come together)");
+    for (int i = 0; i < n; ++i) {
+        if (cams[i].width <= 0 || cams[i].height <= 0 || !images[i]) return fail(c, -2, "bad image size or null image");
+        const int sw = src_w ? src_w[i] : cams[i].width, sh = src_h ? src_h[i] : cams[i].height;
+        if (bytes) {
+            if (sw <= 0 || sh <= 0) return fail(c, -2, "bad source image size");
+            if (pitch_bytes && pitch_bytes[i] < (size_t)sw) return fail(c, -2, "row pitch smaller than the source width");
+        }
+        // texel indices are formed with a 24-bit multiply (texel_index, pm_device.hpp) and offsets inside a view are 32 bits
+        if (cams[i].width >= (1 << 24) || cams[i].height >= (1 << 24) || (size_t)cams[i].width * cams[i].height * 16 >= (1ull << 32))
+            return fail(c, -3, "image too large (a view's texture must stay below 4 GB)");
+        if (bytes && (size_t)sw * sh >= (1ull << 32)) return fail(c, -3, "source image too large (it must stay below 4 GB)");
+    }
+    return 0;
+}
+
+// the views of the context are replaced by an upload -- or by nothing
+static int replace_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const ViewsInput& in) {
+    free_views(c);
+    const int rc = upload_views(c, n, cams, in);
+    if (rc) {  // no half-built Problem is left behind: the context is as after mpmvs_create
+        const std::string why = c->err;
+        free_views(c);
+        c->n_img = c->W = c->H = 0;
+        c->cams.clear();
+        std::memset(&c->hP, 0, sizeof(ProblemDev));
+        c->err = why;
+    }
+    return rc;
 }
 
 int mpmvs_set_views(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const float* const* images, const size_t* pitch_bytes) {
     if (!c) return -1;
     ENTER(c);
-    if (n < 2 || n - 1 > MPMVS_MAX_SRC_VIEWS) return fail(c, -1, "need 2..33 views");
-    for (int i = 0; i < n; ++i) {
-        if (cams[i].width <= 0 || cams[i].height <= 0 || !images[i]) return fail(c, -2, "bad image size or null image");
-        // texel indices are formed with a 24-bit multiply (texel_index, pm_device.hpp) and offsets inside a view are 32 bits
-        if (cams[i].width >= (1 << 24) || cams[i].height >= (1 << 24) || (size_t)cams[i].width * cams[i].height * 16 >= (1ull << 32))
-            return fail(c, -3, "image too large (a view's texture must stay below 4 GB)");
-    }
-    free_views(c);
-    const int rc = set_views_impl(c, n, cams, images, pitch_bytes);
-    if (rc) {  // no half-built Problem is left behind: the context is as after mpmvs_create
-        const std::string why = c->err;
-        free_views(c);
-        c->n_img = c->W = c->H = 0;
-        c->cams.clear();
-        std::memset(&c->hP, 0, sizeof(ProblemDev));
-        c->err = why;
-    }
-    return rc;
+    const int bad = validate_views(c, n, cams, (const void* const*)images, false, nullptr, nullptr, nullptr);
+    if (bad) return bad;
+    ViewsInput in;
+    in.slot_px = 4;   // room for w * h floats; an image that is 8-bit exact is staged as w * h BYTES at the start of its slot
+    for (int i = 0; i < n; ++i)
+        in.im.push_back({(const char*)images[i], cams[i].width, cams[i].height, pitch_bytes ? pitch_bytes[i] : (size_t)cams[i].width * 4});
+    const pmstage::HostImage* im = in.im.data();
+    const bool try_src_u8 = !c->force_f32;
+    // ordinary inputs are one group: one pass over the images that decides the formats while it stages; several groups take a
+    // first pass that only decides the formats
+    in.formats = [=](const pmstage::StagePlan& plan, char* stage, bool& ref_u8, bool& src_u8) {
+        if (plan.groups() == 1) {
+            pmstage::stage_deciding(im, n, plan, try_src_u8, stage, ref_u8, src_u8);
+            return true;
+        }
+        pmstage::exact_sweep<false>(im, n, try_src_u8, nullptr, nullptr, ref_u8, src_u8);
+        return false;
+    };
+    in.stage_group = [=](const pmstage::StagePlan& plan, int g, char* stage, bool ref_u8, bool src_u8) {
+        pmstage::stage_known(im, plan, g, stage, ref_u8, src_u8);
+    };
+    return replace_views(c, n, cams, in);
 }
 
-// ---------------------------------------------------------------------------
 // 8-bit entry (pm_ingest.hpp): the views arrive as bytes at their own size.  Nothing is tested or converted on the host -- the formats
 // follow from the sizes alone -- so the host work is one row-wise copy per image into the page-locked stage.
-// ---------------------------------------------------------------------------
-static IngestSrc ingest_src(const unsigned char* d_bytes, int src_w, int src_h, int dst_w, int dst_h) {
-    // the two ratios exactly as ResizeLinear forms them (host/PatchMatchHost.cpp)
-    return IngestSrc{d_bytes, src_w, src_h, (unsigned)src_w, (float)src_w / dst_w, (float)src_h / dst_h};
-}
-
-static int set_views_u8_impl(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const unsigned char* const* images, const int* src_w,
-                             const int* src_h, const size_t* pitch_bytes) {
-    c->n_img = n;
-    c->cams.assign(cams, cams + n);
-    c->W = cams[0].width;
-    c->H = cams[0].height;
-    std::memset(&c->hP, 0, sizeof(ProblemDev));
-    precompute_views(c);
-    auto sw = [&](int i) { return src_w ? src_w[i] : cams[i].width; };
-    auto sh = [&](int i) { return src_h ? src_h[i] : cams[i].height; };
-    auto resampled = [&](int i) { return sw(i) != cams[i].width || sh(i) != cams[i].height; };
-    // the sources take the 8-byte fp16 texels iff none of them is resampled (a resampled image is not made of integers) and fp32 is not forced
-    bool src_u8 = !c->force_f32;
-    for (int v = 1; v < n; ++v) src_u8 = src_u8 && !resampled(v);
-    c->all_u8 = src_u8;
-    // a slot of src_w * src_h bytes per image, 256-byte aligned, in groups of at most MPMVS_STAGE_MB as in set_views_impl
-    std::vector<size_t> slot(n + 1, 0);
-    for (int i = 0; i < n; ++i) slot[i + 1] = slot[i] + (((size_t)sw(i) * sh(i) + 255) & ~(size_t)255);
-    size_t limit = 512;
-    if (const char* e = std::getenv("MPMVS_STAGE_MB")) limit = (size_t)std::max(1, std::atoi(e));
-    limit <<= 20;
-    std::vector<int> group_first{0};
-    for (int i = 1; i < n; ++i)
-        if (slot[i + 1] - slot[group_first.back()] > limit) group_first.push_back(i);
-    group_first.push_back(n);
-    const int n_groups = (int)group_first.size() - 1;
-    size_t stage_bytes = 0;
-    for (int g = 0; g < n_groups; ++g) stage_bytes = std::max(stage_bytes, slot[group_first[g + 1]] - slot[group_first[g]]);
-    char* const stage = (char*)mpmvs_alloc_pinned(stage_bytes);
-    if (!stage) return fail(c, -100, "no page-locked staging memory for the images");
-    c->deferred_pinned.push_back(stage);
-    void* d_stage_p = nullptr;
-    HIPCHK(c, pool_malloc_bytes(&d_stage_p, stage_bytes ? stage_bytes : 4));
-    c->deferred_dev.push_back(d_stage_p);
-    char* const d_stage = (char*)d_stage_p;
-    auto failed = [&](const char* what) {
-        (void)hipStreamSynchronize(c->stream);
-        release_deferred(c);
-        c->err = what;
-        return -100;
-    };
-    const int pw = c->W + 2 * kRefApron, ph = c->H + 2 * kRefApron;
-    if (pool_malloc(&c->d_ref, (size_t)pw * ph * 4) != hipSuccess) return failed("allocation of the reference image failed");
-    c->hP.ref_pitch = pw;
-    c->hP.ref_img = c->d_ref + (size_t)kRefApron * pw + kRefApron;
-    const size_t texel = src_u8 ? 8 : 16;
-    std::vector<size_t> tex_off(n, 0);
-    size_t tex_total = 0;
-    for (int v = 1; v < n; ++v) {
-        tex_off[v] = tex_total;
-        tex_total += ((size_t)cams[v].width * cams[v].height * texel + 255) & ~(size_t)255;
-    }
-    if (pool_malloc(&c->d_tex_all, tex_total) != hipSuccess) return failed("allocation of the source textures failed");
-    if (src_u8) c->d_src8.assign(n - 1, nullptr); else c->d_src.assign(n - 1, nullptr);
-    for (int g = 0; g < n_groups; ++g) {
-        const int first = group_first[g], last = group_first[g + 1];
-        if (g > 0 && hipStreamSynchronize(c->stream) != hipSuccess) return failed("upload of the images failed");  // the staging buffers are free again
-        // the rows of the group, dealt to the pool in chunks: memcpy only
-        std::vector<long> row0(last - first + 1, 0);
-        for (int i = first; i < last; ++i) row0[i - first + 1] = row0[i - first] + sh(i);
-        const long total_rows = row0[last - first];
-        std::atomic<long> next(0);
-        const std::function<void()> work = [&]() {
-            const long chunk = 64;
-            for (;;) {
-                const long r0 = next.fetch_add(chunk);
-                if (r0 >= total_rows) return;
-                int k = 0;
-                while (r0 >= row0[k + 1]) ++k;
-                for (long r = r0; r < std::min(r0 + chunk, total_rows);) {
-                    while (r >= row0[k + 1]) ++k;
-                    const int i = first + k, y = (int)(r - row0[k]), w = sw(i);
-                    const long rows = std::min(std::min(r0 + chunk, total_rows), row0[k + 1]) - r;   // of this image in this chunk
-                    const size_t pitch = pitch_bytes ? pitch_bytes[i] : (size_t)w;
-                    char* o = stage + (slot[i] - slot[first]) + (size_t)y * w;
-                    const char* in = (const char*)images[i] + (size_t)y * pitch;
-                    if (pitch == (size_t)w)
-                        std::memcpy(o, in, (size_t)rows * w);
-                    else
-                        for (long q = 0; q < rows; ++q) std::memcpy(o + (size_t)q * w, in + (size_t)q * pitch, (size_t)w);
-                    r += rows;
-                }
-            }
-        };
-        row_pool().run(work);
-        for (int i = first; i < last; ++i) {
-            const size_t off = slot[i] - slot[first];
-            if (hipMemcpyAsync(d_stage + off, stage + off, (size_t)sw(i) * sh(i), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-                return failed("upload of the images failed");
-        }
-        for (int v = first; v < last; ++v) {
-            const unsigned char* src = (const unsigned char*)d_stage + (slot[v] - slot[first]);
-            const int w = cams[v].width, h = cams[v].height;
-            const IngestSrc s = ingest_src(src, sw(v), sh(v), w, h);
-            if (v == 0) {
-                if (resampled(0))
-                    hipLaunchKernelGGL(k_ingest_pad, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, s, w, h, c->d_ref, kRefApron);
-                else
-                    hipLaunchKernelGGL(k_pad_u8, dim3((pw + 255) / 256, ph), dim3(256), 0, c->stream, src, w, h, c->d_ref, kRefApron);
-                continue;
-            }
-            ViewDev& o = c->hP.views[v - 1];
-            if (src_u8) {
-                c->d_src8[v - 1] = (uint32_t*)((char*)c->d_tex_all + tex_off[v]);
-                hipLaunchKernelGGL(k_pack_quads_u8, dim3((w + 255) / 256, h), dim3(256), 0, c->stream, src, w, h, (uint2*)c->d_src8[v - 1]);
-                o.pitch8 = w;
-                o.img8 = c->d_src8[v - 1];
-            } else {
-                c->d_src[v - 1] = (float*)((char*)c->d_tex_all + tex_off[v]);
-                const dim3 grid((w + kIngestTW - 1) / kIngestTW, (h + kIngestTH - 1) / kIngestTH);
-                if (resampled(v))
-                    hipLaunchKernelGGL(k_ingest_quads<true>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, (float4*)c->d_src[v - 1]);
-                else
-                    hipLaunchKernelGGL(k_ingest_quads<false>, grid, dim3(kIngestThreads), 0, c->stream, s, w, h, (float4*)c->d_src[v - 1]);
-                o.pitch = w;
-                o.img = c->d_src[v - 1];
-            }
-        }
-    }
-    return finish_views(c);
-}
-
 int mpmvs_set_views_u8(mpmvs_ctx* c, int n, const mpmvs_camera* cams, const unsigned char* const* images, const int* src_widths,
                        const int* src_heights, const size_t* pitch_bytes) {
     if (!c) return -1;
     ENTER(c);
-    if (n < 2 || n - 1 > MPMVS_MAX_SRC_VIEWS) return fail(c, -1, "need 2..33 views");
-    if (!cams || !images || (src_widths == nullptr) != (src_heights == nullptr)) return fail(c, -2, "null argument (source widths and heights come together)");
+    const int bad = validate_views(c, n, cams, (const void* const*)images, true, src_widths, src_heights, pitch_bytes);
+    if (bad) return bad;
+    ViewsInput in;
+    in.slot_px = 1;
     for (int i = 0; i < n; ++i) {
-        if (cams[i].width <= 0 || cams[i].height <= 0 || !images[i]) return fail(c, -2, "bad image size or null image");
         const int sw = src_widths ? src_widths[i] : cams[i].width, sh = src_heights ? src_heights[i] : cams[i].height;
-        if (sw <= 0 || sh <= 0) return fail(c, -2, "bad source image size");
-        if (pitch_bytes && pitch_bytes[i] < (size_t)sw) return fail(c, -2, "row pitch smaller than the source width");
-        if (cams[i].width >= (1 << 24) || cams[i].height >= (1 << 24) || (size_t)cams[i].width * cams[i].height * 16 >= (1ull << 32))
-            return fail(c, -3, "image too large (a view's texture must stay below 4 GB)");
-        if ((size_t)sw * sh >= (1ull << 32)) return fail(c, -3, "source image too large (it must stay below 4 GB)");
+        in.im.push_back({(const char*)images[i], sw, sh, pitch_bytes ? pitch_bytes[i] : (size_t)sw});
     }
-    free_views(c);
-    const int rc = set_views_u8_impl(c, n, cams, images, src_widths, src_heights, pitch_bytes);
-    if (rc) {  // no half-built Problem is left behind: the context is as after mpmvs_create
-        const std::string why = c->err;
-        free_views(c);
-        c->n_img = c->W = c->H = 0;
-        c->cams.clear();
-        std::memset(&c->hP, 0, sizeof(ProblemDev));
-        c->err = why;
-    }
-    return rc;
+    const pmstage::HostImage* im = in.im.data();
+    in.stage_group = [=](const pmstage::StagePlan& plan, int g, char* stage, bool, bool) { pmstage::stage_byte_rows(im, plan, g, stage); };
+    return replace_views(c, n, cams, in);
 }
 
 int mpmvs_resize_u8(int device, const unsigned char* src, int src_w, int src_h, size_t pitch_bytes, int dst_w, int dst_h, float* out) {
@@ -1160,15 +908,17 @@ int mpmvs_resize_u8(int device, const unsigned char* src, int src_w, int src_h, 
     if (pitch_bytes == 0) pitch_bytes = (size_t)src_w;
     if (pitch_bytes < (size_t)src_w) return -2;
     if ((size_t)src_w * src_h >= (1ull << 32) || dst_w >= (1 << 24) || dst_h >= (1 << 24)) return -3;
-    if (enter_device(device) != hipSuccess) return -100;
-    DevBuf d_src, d_out;
+    DeviceCall call(device);
+    if (!call.ok()) return -100;
     const size_t out_bytes = (size_t)dst_w * dst_h * 4;
-    if (d_src.alloc((size_t)src_w * src_h) != hipSuccess || d_out.alloc(out_bytes) != hipSuccess) return -100;
-    if (hipMemcpy2D(d_src.p, (size_t)src_w, src, pitch_bytes, (size_t)src_w, (size_t)src_h, hipMemcpyHostToDevice) != hipSuccess) return -100;
-    hipLaunchKernelGGL(k_ingest_pad, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, 0,
-                       ingest_src(d_src.as<unsigned char>(), src_w, src_h, dst_w, dst_h), dst_w, dst_h, d_out.as<float>(), 0);
+    unsigned char* d_src = call.alloc<unsigned char>((size_t)src_w * src_h);
+    float* d_out = call.alloc<float>(out_bytes);
+    if (!d_src || !d_out) return -100;
+    if (hipMemcpy2DAsync(d_src, (size_t)src_w, src, pitch_bytes, (size_t)src_w, (size_t)src_h, hipMemcpyHostToDevice, call.stream()) != hipSuccess) return -100;
+    hipLaunchKernelGGL(k_ingest_pad, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, call.stream(), ingest_src(d_src, src_w, src_h, dst_w, dst_h), dst_w, dst_h,
+                       d_out, 0);
     if (hipGetLastError() != hipSuccess) return -100;
-    if (hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return -100;   // waits for the kernel
+    if (hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, call.stream()) != hipSuccess || hipStreamSynchronize(call.stream()) != hipSuccess) return -100;
     return 0;
 }
 
@@ -1355,8 +1105,13 @@ static hipEvent_t get_event(mpmvs_ctx* c) {
     return e;
 }
 
-static dim3 checker_grid(const mpmvs_ctx* c, const LaunchArgs& a) {
-    const int rows = c->H < a.ylimit ? c->H : a.ylimit;
+// the row the reference's checkerboard grid reaches down to (ref .cu:1196), and the rows the checkerboard launches cover: that
+// grid, at most the image
+static int checker_ylimit(const mpmvs_ctx* c) { return 2 * 16 * (((c->H / 2) + 15) / 16); }
+static int checker_rows(const mpmvs_ctx* c) { return std::min(c->H, checker_ylimit(c)); }
+
+static dim3 checker_grid(const mpmvs_ctx* c) {
+    const int rows = checker_rows(c);
     return dim3(((c->W + kChkBlockW - 1) / kChkBlockW) * ((rows + kChkBlockH<> - 1) / kChkBlockH<>));
 }
 // The kernel variant that serves a launch.  The NCC kernels are instantiated per bound MAXV on the number of source views, texel
@@ -1388,7 +1143,7 @@ static void dispatch_variant(int V, bool u8, int scale, F&& launch) {
 template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
 static void launch_update_chain(mpmvs_ctx* c, const LaunchArgs& a, const ChainArgs& ch0) {
     constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
-    const int rows = c->H < a.ylimit ? c->H : a.ylimit;
+    const int rows = checker_rows(c);
     ChainArgs ch = ch0;
     ch.nbx = (c->W + BW - 1) / BW;
     ch.nby = (rows + BH - 1) / BH;
@@ -1454,7 +1209,7 @@ static LaunchArgs make_args(const mpmvs_ctx* c, const mpmvs_params* p, uint64_t 
     a.iter = iter;
     a.scale = scale;
     a.parity = (kind == MPMVS_KIND_RED || kind == MPMVS_KIND_FILTER_RED) ? 1 : 0;
-    a.ylimit = 2 * 16 * (((c->H / 2) + 15) / 16);  // ref .cu:1196
+    a.ylimit = checker_ylimit(c);
     a.top_k = p->top_k;
     a.depth_min = p->depth_min;
     a.depth_max = p->depth_max;
@@ -1466,12 +1221,6 @@ static LaunchArgs make_args(const mpmvs_ctx* c, const mpmvs_params* p, uint64_t 
     a.init_random = (!p->geom_consistency && !p->planar_prior) ? 1 : 0;
     a.use_prior = p->planar_prior ? 1 : 0;
     return a;
-}
-
-// rows the checkerboard launches cover: the reference's grid (ref .cu:1196), at most the image
-static int checker_rows(const mpmvs_ctx* c) {
-    const int ylimit = 2 * 16 * (((c->H / 2) + 15) / 16);
-    return c->H < ylimit ? c->H : ylimit;
 }
 
 // Height of a row band of the banded end of Run() (enqueue_band_tail): about H / kTailBands rows, a multiple of 32 -- the block
@@ -1510,7 +1259,7 @@ static int enqueue_step(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, int 
     }
     const dim3 blk(256);
     const dim3 grid_dense((c->W + 15) / 16, (c->H + 15) / 16);
-    const dim3 grid_chk = checker_grid(c, a);  // k_filter (checker_pixel)
+    const dim3 grid_chk = checker_grid(c);  // k_filter (checker_pixel)
     int own_passes = 0;   // passes of this launch that read S.own
     switch (kind) {
         case MPMVS_KIND_INIT: {
@@ -1837,10 +1586,7 @@ static int run_impl(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, void* pl
     ENTER(c);
     int rc = check_ready(c, p);
     if (rc) return rc;
-    for (int k = 0; k < 6; ++k) {
-        c->k_ms[k] = 0.0f;
-        c->k_cnt[k] = 0;
-    }
+    reset_kernel_times(c);
     rc = enqueue_run(c, p, seed, planes4, costs, geom);
     return rc ? abandon_run(c, rc) : 0;
 }
@@ -1871,22 +1617,14 @@ int mpmvs_run_get_async(mpmvs_ctx* c, const mpmvs_params* p, uint64_t seed, void
         // all three or none: a partial set left behind by a failed allocation would make the next call copy through a null pointer
         if ((!c->stage_planes && pool_malloc(&c->stage_planes, wh * 16) != hipSuccess) || (!c->stage_costs && pool_malloc(&c->stage_costs, wh * 4) != hipSuccess) ||
             (!c->stage_geom && pool_malloc(&c->stage_geom, wh * 4) != hipSuccess)) {
-            if (c->stage_planes) (void)pool_free(c->stage_planes);
-            if (c->stage_costs) (void)pool_free(c->stage_costs);
-            if (c->stage_geom) (void)pool_free(c->stage_geom);
-            c->stage_planes = nullptr;
-            c->stage_costs = c->stage_geom = nullptr;
+            free_run_stage(c);
             return fail(c, -100, "allocation of the staging buffers failed");
         }
     }
     if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
     if (!c->staged) HIPCHK(c, hipEventCreateWithFlags(&c->staged, hipEventDisableTiming));
     if (!c->staging_free) HIPCHK(c, hipEventCreateWithFlags(&c->staging_free, hipEventDisableTiming));
-    if (!c->async_outstanding)
-        for (int k = 0; k < 6; ++k) {   // the kernel times of pipelined Run()s accumulate until mpmvs_wait
-            c->k_ms[k] = 0.0f;
-            c->k_cnt[k] = 0;
-        }
+    if (!c->async_outstanding) reset_kernel_times(c);   // the kernel times of pipelined Run()s accumulate until mpmvs_wait
     c->async_outstanding++;
     uint32_t launch = 0;
     auto body = [&]() -> int {
@@ -1978,7 +1716,7 @@ static int eval_ncc_impl(mpmvs_ctx* c, const mpmvs_params* p, const void* planes
     if (nh < 1 || mapping != 0) return fail(c, -3, "bad probe arguments (only mapping 0 exists)");
     const size_t wh = (size_t)c->W * c->H;
     const int V = c->hP.V;
-    DevBuf d_pl, d_out;
+    Scratch d_pl(c->stream), d_out(c->stream);
     HIPCHK(c, d_pl.alloc(wh * 16 * nh));
     HIPCHK(c, d_out.alloc(wh * 4 * V * nh));
     HIPCHK(c, hipMemcpyAsync(d_pl.p, planes_cam4, wh * 16 * nh, hipMemcpyHostToDevice, c->stream));
@@ -1987,7 +1725,12 @@ static int eval_ncc_impl(mpmvs_ctx* c, const mpmvs_params* p, const void* planes
     a.two_ss = (2.0f * p->sigma_spatial) * p->sigma_spatial;
     a.two_sc = (2.0f * p->sigma_color) * p->sigma_color;
     fill_spatial_terms(a, scale);
-    hipEvent_t e0 = get_event(c), e1 = get_event(c);
+    struct Lent {   // two events of the context, back in its pool on every return path
+        mpmvs_ctx* c;
+        hipEvent_t e0, e1;
+        ~Lent() { c->event_pool.insert(c->event_pool.end(), {e0, e1}); }
+    } lent{c, get_event(c), get_event(c)};
+    const hipEvent_t e0 = lent.e0, e1 = lent.e1;
     HIPCHK(c, hipEventRecord(e0, c->stream));
     {
         const dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
@@ -2003,8 +1746,6 @@ static int eval_ncc_impl(mpmvs_ctx* c, const mpmvs_params* p, const void* planes
     float ms = 0.0f;
     (void)hipEventElapsedTime(&ms, e0, e1);
     if (kernel_ms) *kernel_ms = ms;
-    c->event_pool.push_back(e0);
-    c->event_pool.push_back(e1);
     return 0;
 }
 
@@ -2023,7 +1764,7 @@ int mpmvs_eval_geom(mpmvs_ctx* c, const mpmvs_params* p, const void* planes_cam4
     if (!c->have_depths) return fail(c, -4, "need source depth maps");
     const size_t wh = (size_t)c->W * c->H;
     const int V = c->hP.V;
-    DevBuf d_pl, d_out;
+    Scratch d_pl(c->stream), d_out(c->stream);
     HIPCHK(c, d_pl.alloc(wh * 16));
     HIPCHK(c, d_out.alloc(wh * 4 * V));
     HIPCHK(c, hipMemcpyAsync(d_pl.p, planes_cam4, wh * 16, hipMemcpyHostToDevice, c->stream));
@@ -2039,7 +1780,7 @@ int mpmvs_homography(mpmvs_ctx* c, const void* plane4, int v, void* H9) {
     if (!c) return -1;
     ENTER(c);
     if (c->n_img < 2 || v < 0 || v >= c->hP.V) return fail(c, -1, "bad source view");
-    DevBuf d_h;
+    Scratch d_h(c->stream);
     HIPCHK(c, d_h.alloc(9 * 4));
     const float* pf = (const float*)plane4;
     hipLaunchKernelGGL(k_homography, dim3(1), dim3(64), 0, c->stream, c->dP, make_float4(pf[0], pf[1], pf[2], pf[3]), v, d_h.as<float>());
@@ -2059,7 +1800,7 @@ int mpmvs_prior_vertices(mpmvs_ctx* c, int geom_rule, int* out_xy, int cap, int*
     const int W = c->W, H = c->H;
     const int ncx = (W + kPriorCell - 1) / kPriorCell, ncy = (H + kPriorCell - 1) / kPriorCell, ncells = ncx * ncy;
     const int nb = (ncells + 255) / 256;
-    PoolBuf d_cnt, d_pts, d_sums, d_xy;
+    Scratch d_cnt(c->stream), d_pts(c->stream), d_sums(c->stream), d_xy(c->stream);
     int rc = 0, total = 0;
     if (d_cnt.alloc((size_t)ncells * 4) != hipSuccess || d_pts.alloc((size_t)ncells * 12) != hipSuccess || d_sums.alloc((size_t)(nb + 1) * 4) != hipSuccess ||
         d_xy.alloc((size_t)cap * 8) != hipSuccess)
@@ -2146,7 +1887,7 @@ int mpmvs_prior_from_triangles(mpmvs_ctx* c, const mpmvs_params* p, const int* t
         }
     });
     const int n_tasks = (int)task_tri.size();
-    PoolBuf d_tri, d_pl, d_tt, d_tr;
+    Scratch d_tri(c->stream), d_pl(c->stream), d_tt(c->stream), d_tr(c->stream);
     int rc = 0;
     if (d_tri.alloc((size_t)n * 24) != hipSuccess || d_pl.alloc((size_t)n * 16) != hipSuccess || d_tt.alloc((size_t)n_tasks * 4) != hipSuccess ||
         d_tr.alloc((size_t)n_tasks * 4) != hipSuccess)
@@ -2165,7 +1906,7 @@ int mpmvs_prior_from_triangles(mpmvs_ctx* c, const mpmvs_params* p, const int* t
                            c->d_mask, c->d_prior);
         if (hipGetLastError() != hipSuccess) rc = -100;
     }
-    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = -100;  // the scratch buffers go back to the pool
+    if (hipStreamSynchronize(c->stream) != hipSuccess) rc = -100;
     if (rc) return fail(c, rc, "prior construction failed on the device");
     c->S.prior = c->d_prior;
     c->S.mask = c->d_mask;
@@ -2186,48 +1927,35 @@ int mpmvs_get_prior(mpmvs_ctx* c, void* prior4, void* mask) {
 
 int mpmvs_math(int fn, const void* in, void* out, int n) {
     if (fn < 0 || fn > 6 || n <= 0) return -1;
-    (void)hipGetLastError();  // drop a stale error of an earlier call (see enter_device)
-    float *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc(&d_in, (size_t)n * 4) != hipSuccess) return -100;
-    if (hipMalloc(&d_out, (size_t)n * 4) != hipSuccess) return -100;
-    int rc = 0;
-    if (hipMemcpy(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) rc = -100;
-    if (!rc) {
-        hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, d_in, d_out, n);
-        if (hipGetLastError() != hipSuccess) rc = -100;
-    }
-    if (!rc && hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = -100;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return rc;
+    DeviceCall call;
+    float *d_in = call.alloc<float>((size_t)n * 4), *d_out = call.alloc<float>((size_t)n * 4);
+    if (!d_in || !d_out) return -100;
+    if (hipMemcpy(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return -100;
+    hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, call.stream(), fn, d_in, d_out, n);
+    if (hipGetLastError() != hipSuccess) return -100;
+    return hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
 
 int mpmvs_verify_rcp(unsigned long long counts[4]) {
     if (!counts) return -1;
-    (void)hipGetLastError();
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, 32) != hipSuccess) return -100;
-    int rc = hipMemset(d, 0, 32) == hipSuccess ? 0 : -100;
-    for (uint64_t base = 0; !rc && base < (1ULL << 32); base += (1ULL << 24)) {
-        hipLaunchKernelGGL(k_verify_rcp, dim3(1 << 16), dim3(256), 0, nullptr, (uint32_t)base, d);
-        if (hipGetLastError() != hipSuccess) rc = -100;
+    DeviceCall call;
+    unsigned long long* d = call.alloc<unsigned long long>(32);
+    if (!d || hipMemset(d, 0, 32) != hipSuccess) return -100;
+    for (uint64_t base = 0; base < (1ULL << 32); base += (1ULL << 24)) {
+        hipLaunchKernelGGL(k_verify_rcp, dim3(1 << 16), dim3(256), 0, call.stream(), (uint32_t)base, d);
+        if (hipGetLastError() != hipSuccess) return -100;
     }
-    if (!rc && hipMemcpy(counts, d, 32, hipMemcpyDeviceToHost) != hipSuccess) rc = -100;
-    (void)hipFree(d);
-    return rc;
+    return hipMemcpy(counts, d, 32, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
 
 int mpmvs_rng(uint64_t seed, uint32_t pix, uint32_t launch_id, int n, void* out) {
     if (n <= 0) return -1;
-    (void)hipGetLastError();
-    float* d_out = nullptr;
-    if (hipMalloc(&d_out, (size_t)n * 4) != hipSuccess) return -100;
-    int rc = 0;
-    hipLaunchKernelGGL(k_rng, dim3(1), dim3(64), 0, nullptr, seed, pix, launch_id, n, d_out);
-    if (hipGetLastError() != hipSuccess) rc = -100;
-    if (!rc && hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = -100;
-    (void)hipFree(d_out);
-    return rc;
+    DeviceCall call;
+    float* d_out = call.alloc<float>((size_t)n * 4);
+    if (!d_out) return -100;
+    hipLaunchKernelGGL(k_rng, dim3(1), dim3(64), 0, call.stream(), seed, pix, launch_id, n, d_out);
+    if (hipGetLastError() != hipSuccess) return -100;
+    return hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
 
 static float g_fuse_kernel_ms = 0.0f;
@@ -2253,7 +1981,9 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     const int use_dynamic = flags & MPMVS_FUSE_DYNAMIC_CONSISTENCY;
     const bool exact = (flags & MPMVS_FUSE_REFERENCE_ORDER) != 0;
     g_fuse_passes_total = g_fuse_passes_max = 0;
-    if (n <= 0 || (color_channels != 1 && color_channels != 3) || enter_device(device) != hipSuccess) return -1;
+    // own stream: a fusion call must not stall the PatchMatch contexts other host threads drive on this device
+    DeviceCall call(device);
+    if (n <= 0 || (color_channels != 1 && color_channels != 3) || !call.entered()) return -1;
     // every view id is used as an index below (host vectors, FuseView table, masks): reject lists that name images that do
     // not exist before anything is launched (the reference looks ids up in a map, src/PatchMatch.cpp:306-312)
     if (!src_off || !src_ids || src_off[0] != 0) return -2;
@@ -2269,17 +1999,9 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
                 if (src_ids[k2] == src_ids[k]) return -2;
         }
     }
-    // own stream: a fusion call must not stall the PatchMatch contexts other host threads drive on this device
-    hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
+    if (!call.ok()) return -100;
+    const hipStream_t st = call.stream();
     std::vector<FuseView> hv(n);
-    std::vector<void*> to_free;
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (pool_malloc_bytes(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-        to_free.push_back(p);
-        return p;
-    };
     int rc = 0;
     std::vector<unsigned char*> d_valid(n, nullptr);
     std::vector<float*> d_out(n, nullptr);
@@ -2293,8 +2015,8 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
         }
     // with `records` the per-pixel outputs of an image are consumed (compacted) before the next image is fused: one buffer
     // of the largest size serves all images (the per-image form would be 37 B per pixel of the whole dataset)
-    unsigned char* shared_valid = records ? (unsigned char*)dalloc(max_wh) : nullptr;
-    float* shared_out = records ? (float*)dalloc(max_wh * 36) : nullptr;
+    unsigned char* shared_valid = records ? call.alloc<unsigned char>(max_wh) : nullptr;
+    float* shared_out = records ? call.alloc<float>(max_wh * 36) : nullptr;
     if (records && (!shared_valid || !shared_out)) rc = -100;
     for (int i = 0; i < n && !rc; ++i) {
         const size_t wh = (size_t)cams[i].width * cams[i].height;
@@ -2306,16 +2028,16 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
         cam_to_dev(cams[i], v.cam);
         v.w = cams[i].width;
         v.h = cams[i].height;
-        float* dd = (float*)dalloc(wh * 4);
-        float* dn = (float*)dalloc(wh * 12);
-        unsigned char* dg = (unsigned char*)dalloc(wh * color_channels);
-        unsigned char* dsky = (sky && sky[i]) ? (unsigned char*)dalloc(wh) : nullptr;
-        d_mask[i] = (unsigned char*)dalloc(wh);
-        d_next[i] = (unsigned char*)dalloc(wh);
-        d_valid[i] = records ? shared_valid : (unsigned char*)dalloc(wh);
-        d_out[i] = records ? shared_out : (float*)dalloc(wh * 36);
-        int* dtau = exact ? (int*)dalloc(wh * 4) : nullptr;
-        int* dtau_new = exact ? (int*)dalloc(wh * 4) : nullptr;
+        float* dd = call.alloc<float>(wh * 4);
+        float* dn = call.alloc<float>(wh * 12);
+        unsigned char* dg = call.alloc<unsigned char>(wh * color_channels);
+        unsigned char* dsky = (sky && sky[i]) ? call.alloc<unsigned char>(wh) : nullptr;
+        d_mask[i] = call.alloc<unsigned char>(wh);
+        d_next[i] = call.alloc<unsigned char>(wh);
+        d_valid[i] = records ? shared_valid : call.alloc<unsigned char>(wh);
+        d_out[i] = records ? shared_out : call.alloc<float>(wh * 36);
+        int* dtau = exact ? call.alloc<int>(wh * 4) : nullptr;
+        int* dtau_new = exact ? call.alloc<int>(wh * 4) : nullptr;
         if (exact && (!dtau || !dtau_new)) { rc = -100; break; }
         v.tau = dtau;
         v.tau_new = dtau_new;
@@ -2329,7 +2051,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
                 if (hipStreamSynchronize(cx->stream) != hipSuccess) { rc = -100; break; }
             } else {
                 // another GPU of the node: its stream is drained there, the planes cross xGMI into a scratch buffer here
-                float4* tmp = (float4*)dalloc(wh * 16);
+                float4* tmp = call.alloc<float4>(wh * 16);
                 if (!tmp || hipSetDevice(cx->device) != hipSuccess || hipStreamSynchronize(cx->stream) != hipSuccess || hipSetDevice(device) != hipSuccess ||
                     hipMemcpyPeerAsync(tmp, device, cx->S.planes, cx->device, wh * 16, st) != hipSuccess) {
                     (void)hipSetDevice(device);
@@ -2367,16 +2089,16 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     long long* d_base = nullptr;
     unsigned char* d_records = nullptr;
     if (!rc) {
-        d_views = (FuseView*)dalloc(sizeof(FuseView) * n);
-        d_src = (int*)dalloc(sizeof(int) * (src_off[n] > 0 ? src_off[n] : 1));
+        d_views = call.alloc<FuseView>(sizeof(FuseView) * n);
+        d_src = call.alloc<int>(sizeof(int) * (src_off[n] > 0 ? src_off[n] : 1));
         if (!d_views || !d_src || hipMemcpyAsync(d_views, hv.data(), sizeof(FuseView) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipMemcpyAsync(d_src, src_ids, sizeof(int) * src_off[n], hipMemcpyHostToDevice, st) != hipSuccess)
             rc = -100;
     }
     if (!rc && records) {
-        d_blocks = (int*)dalloc(sizeof(int) * (max_blocks + 1));
-        d_base = (long long*)dalloc(sizeof(long long));
-        d_records = (unsigned char*)dalloc(total_px * kPlyRecord);  // upper bound: every pixel a point
+        d_blocks = call.alloc<int>(sizeof(int) * (max_blocks + 1));
+        d_base = call.alloc<long long>(sizeof(long long));
+        d_records = call.alloc<unsigned char>(total_px * kPlyRecord);  // upper bound: every pixel a point
         if (!d_blocks || !d_base || !d_records || hipMemsetAsync(d_base, 0, sizeof(long long), st) != hipSuccess) rc = -100;
     }
     // exact mode scratch: per source slot the consistent source pixel of every pixel, the chunk carries of the scan, a counter
@@ -2385,15 +2107,12 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     int* d_diff = nullptr;
     const size_t max_chunks = (max_wh + 255) / 256;
     if (!rc && exact) {
-        d_consq = (int*)dalloc((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_wh * 4);
-        d_carry = (int*)dalloc((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_chunks * 4);
-        d_diff = (int*)dalloc(4);
+        d_consq = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_wh * 4);
+        d_carry = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_chunks * 4);
+        d_diff = call.alloc<int>(4);
         if (!d_consq || !d_carry || !d_diff) rc = -100;
     }
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    (void)hipEventCreate(&ev0);
-    (void)hipEventCreate(&ev1);
-    (void)hipEventRecord(ev0, st);
+    (void)call.begin();
     for (int i = 0; i < n && !rc; ++i) {
         if (!estimate[i]) continue;
         const int b = src_off[i], num_ngb = src_off[i + 1] - b;
@@ -2462,11 +2181,9 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
             if (hipGetLastError() != hipSuccess) rc = -100;
         }
     }
-    (void)hipEventRecord(ev1, st);
+    (void)call.end();
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
-    if (!rc) (void)hipEventElapsedTime(&g_fuse_kernel_ms, ev0, ev1);
-    (void)hipEventDestroy(ev0);
-    (void)hipEventDestroy(ev1);
+    if (!rc) (void)call.elapsed(&g_fuse_kernel_ms);
     for (int i = 0; i < n && !rc; ++i) {
         const size_t wh = (size_t)hv[i].w * hv[i].h;
         if ((out_valid && hipMemcpyAsync(out_valid[i], d_valid[i], wh, hipMemcpyDeviceToHost, st) != hipSuccess) ||
@@ -2490,9 +2207,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
             *n_records = count;
         }
     }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path: nothing may still use what goes back to the pool
-    for (void* p : to_free) (void)pool_free(p);
-    (void)hipStreamDestroy(st);
+    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;   // the outputs have arrived
     return rc;
 }
 
@@ -2541,38 +2256,25 @@ float mpmvs_sky_kernel_ms(void) { return g_sky_kernel_ms; }
 
 // joint-bilateral sky-mask refinement (pm_sky.hpp); host buffers in and out
 int mpmvs_sky_bilateral(int device, const unsigned char* bgr, const float* mask, float* out, int height, int width) {
-    if (!bgr || !mask || !out || height <= 0 || width <= 0 || enter_device(device) != hipSuccess) return -1;
+    DeviceCall call(device);
+    if (!bgr || !mask || !out || height <= 0 || width <= 0 || !call.entered()) return -1;
+    if (!call.ok()) return -100;
+    const hipStream_t st = call.stream();
     const size_t wh = (size_t)height * width;
-    unsigned char* d_img = nullptr;
-    float *d_mask = nullptr, *d_out = nullptr;
-    hipStream_t st = nullptr;  // own stream: other contexts of this device keep running
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
-    int rc = 0;
-    if (pool_malloc(&d_img, wh * 3) != hipSuccess || pool_malloc(&d_mask, wh * 4) != hipSuccess || pool_malloc(&d_out, wh * 4) != hipSuccess) rc = -100;
-    if (!rc && (hipMemcpyAsync(d_img, bgr, wh * 3, hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemcpyAsync(d_mask, mask, wh * 4, hipMemcpyHostToDevice, st) != hipSuccess))
-        rc = -100;
-    if (!rc) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        (void)hipEventCreate(&ev0);
-        (void)hipEventCreate(&ev1);
-        (void)hipEventRecord(ev0, st);
-        const dim3 grid((width + kSkyTW - 1) / kSkyTW, (height + kSkyTH - 1) / kSkyTH);
-        hipLaunchKernelGGL(k_sky_bilateral, grid, dim3(256), 0, st, d_img, d_mask, d_out, height, width);
-        if (hipGetLastError() != hipSuccess) rc = -100;
-        (void)hipEventRecord(ev1, st);
-        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
-        if (!rc) (void)hipEventElapsedTime(&g_sky_kernel_ms, ev0, ev1);
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-    }
-    if (!rc && hipMemcpyAsync(out, d_out, wh * 4, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path, before the buffers go back to the pool
-    (void)pool_free(d_img);
-    (void)pool_free(d_mask);
-    (void)pool_free(d_out);
-    (void)hipStreamDestroy(st);
-    return rc;
+    unsigned char* d_img = call.alloc<unsigned char>(wh * 3);
+    float *d_mask = call.alloc<float>(wh * 4), *d_out = call.alloc<float>(wh * 4);
+    if (!d_img || !d_mask || !d_out) return -100;
+    if (hipMemcpyAsync(d_img, bgr, wh * 3, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(d_mask, mask, wh * 4, hipMemcpyHostToDevice, st) != hipSuccess)
+        return -100;
+    (void)call.begin();
+    const dim3 grid((width + kSkyTW - 1) / kSkyTW, (height + kSkyTH - 1) / kSkyTH);
+    hipLaunchKernelGGL(k_sky_bilateral, grid, dim3(256), 0, st, d_img, d_mask, d_out, height, width);
+    if (hipGetLastError() != hipSuccess) return -100;
+    (void)call.end();
+    if (hipStreamSynchronize(st) != hipSuccess) return -100;
+    (void)call.elapsed(&g_sky_kernel_ms);
+    if (hipMemcpyAsync(out, d_out, wh * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -100;
+    return 0;
 }
 
 static float g_viewsel_kernel_ms = 0.0f;
@@ -2597,83 +2299,65 @@ int mpmvs_view_select(int device, int n_images, const double* centers, int n_poi
         n_slots += obs_pt[k] >= 0;
     }
     if (n_obs > INT32_MAX || n_slots > INT32_MAX - 256) return -1;
-    if (enter_device(device) != hipSuccess) return -100;
+    DeviceCall call(device);
+    if (!call.ok()) return -100;
+    const hipStream_t st = call.stream();
 
     const size_t n = (size_t)n_images, nn = n * n;
     const int ntiles = (n_points + kVsScanTile - 1) / kVsScanTile;
     const int ns = (int)n_slots;
-    double *d_centers = nullptr, *d_xyz = nullptr;
-    int64_t* d_obs_off = nullptr;
-    int32_t *d_obs_pt = nullptr, *d_ids = nullptr, *d_scores = nullptr;
-    int *d_cnt = nullptr, *d_off = nullptr, *d_tsum = nullptr, *d_fill = nullptr, *d_trk_img = nullptr, *d_trk_pt = nullptr, *d_trk_mult = nullptr;
-    unsigned long long* d_acc = nullptr;
-    unsigned* d_score = nullptr;
-    hipStream_t st = nullptr;  // own stream: other contexts of this device keep running
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
-    int rc = 0;
-    // zero-sized arrays still get a (4-byte) buffer, so that no kernel argument is null
+    double *d_centers = call.alloc<double>(n * 24), *d_xyz = call.alloc<double>((size_t)n_points * 24);
+    int64_t* d_obs_off = call.alloc<int64_t>((n + 1) * 8);
+    int32_t* d_obs_pt = call.alloc<int32_t>((size_t)n_obs * 4);
+    int *d_cnt = call.alloc<int>((size_t)n_points * 4), *d_off = call.alloc<int>(((size_t)n_points + 1) * 4);
+    int *d_tsum = call.alloc<int>((size_t)ntiles * 4), *d_fill = call.alloc<int>((size_t)n_points * 4);
+    int *d_trk_img = call.alloc<int>((size_t)ns * 4), *d_trk_pt = call.alloc<int>((size_t)ns * 4), *d_trk_mult = call.alloc<int>((size_t)ns * 4);
+    unsigned long long* d_acc = call.alloc<unsigned long long>(nn * 8);
+    unsigned* d_score = call.alloc<unsigned>(nn * 4);
+    int32_t *d_ids = call.alloc<int32_t>(n * num_view * 4), *d_scores = call.alloc<int32_t>(n * num_view * 4);
+    if (!d_centers || !d_xyz || !d_obs_off || !d_obs_pt || !d_cnt || !d_off || !d_tsum || !d_fill || !d_trk_img || !d_trk_pt || !d_trk_mult || !d_acc ||
+        !d_score || !d_ids || !d_scores)
+        return -100;
+    // (a zero-sized array has a 4-byte buffer: that much is cleared)
     auto bytes = [](size_t b) { return b ? b : (size_t)4; };
-    if (pool_malloc(&d_centers, n * 24) != hipSuccess || pool_malloc(&d_xyz, bytes((size_t)n_points * 24)) != hipSuccess ||
-        pool_malloc(&d_obs_off, (n + 1) * 8) != hipSuccess || pool_malloc(&d_obs_pt, bytes((size_t)n_obs * 4)) != hipSuccess ||
-        pool_malloc(&d_cnt, bytes((size_t)n_points * 4)) != hipSuccess || pool_malloc(&d_off, ((size_t)n_points + 1) * 4) != hipSuccess ||
-        pool_malloc(&d_tsum, bytes((size_t)ntiles * 4)) != hipSuccess || pool_malloc(&d_fill, bytes((size_t)n_points * 4)) != hipSuccess ||
-        pool_malloc(&d_trk_img, bytes((size_t)ns * 4)) != hipSuccess || pool_malloc(&d_trk_pt, bytes((size_t)ns * 4)) != hipSuccess ||
-        pool_malloc(&d_trk_mult, bytes((size_t)ns * 4)) != hipSuccess || pool_malloc(&d_acc, nn * 8) != hipSuccess ||
-        pool_malloc(&d_score, nn * 4) != hipSuccess || pool_malloc(&d_ids, bytes(n * num_view * 4)) != hipSuccess ||
-        pool_malloc(&d_scores, bytes(n * num_view * 4)) != hipSuccess)
-        rc = -100;
-    if (!rc && (hipMemcpyAsync(d_centers, centers, n * 24, hipMemcpyHostToDevice, st) != hipSuccess ||
-                (n_points > 0 && hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 24, hipMemcpyHostToDevice, st) != hipSuccess) ||
-                hipMemcpyAsync(d_obs_off, obs_off, (n + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-                (n_obs > 0 && hipMemcpyAsync(d_obs_pt, obs_pt, (size_t)n_obs * 4, hipMemcpyHostToDevice, st) != hipSuccess) ||
-                hipMemsetAsync(d_cnt, 0, bytes((size_t)n_points * 4), st) != hipSuccess ||
-                hipMemsetAsync(d_off, 0, ((size_t)n_points + 1) * 4, st) != hipSuccess ||
-                hipMemsetAsync(d_fill, 0, bytes((size_t)n_points * 4), st) != hipSuccess || hipMemsetAsync(d_acc, 0, nn * 8, st) != hipSuccess))
-        rc = -100;
-    if (!rc) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        (void)hipEventCreate(&ev0);
-        (void)hipEventCreate(&ev1);
-        (void)hipEventRecord(ev0, st);
-        if (n_slots > 0) {
-            hipLaunchKernelGGL(k_vs_count, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_cnt);
-            hipLaunchKernelGGL(k_vs_scan_tiles, dim3(ntiles), dim3(kVsScanTile), 0, st, d_cnt, n_points, d_off, d_tsum);
-            hipLaunchKernelGGL(k_vs_scan_sums, dim3(1), dim3(kVsScanTile), 0, st, d_tsum, ntiles, d_off, n_points);
-            hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kVsScanTile), 0, st, d_off, n_points, d_tsum);
-            hipLaunchKernelGGL(k_vs_scatter, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_off, d_fill, d_trk_img, d_trk_pt);
-            const dim3 gs((ns + 255) / 256);
-            hipLaunchKernelGGL(k_vs_mult, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_off, d_trk_mult);
-            hipLaunchKernelGGL(k_vs_pairs, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_trk_mult, d_off, d_centers, d_xyz, d_acc, n_images);
-        }
-        hipLaunchKernelGGL(k_vs_score, dim3((n_images + 255) / 256, n_images), dim3(256), 0, st, d_acc, n_images, d_score);
-        if (num_view > 0) hipLaunchKernelGGL(k_vs_select, dim3(n_images), dim3(256), 0, st, d_score, n_images, num_view, d_ids, d_scores);
-        if (hipGetLastError() != hipSuccess) rc = -100;
-        (void)hipEventRecord(ev1, st);
-        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
-        if (!rc) (void)hipEventElapsedTime(&g_viewsel_kernel_ms, ev0, ev1);
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
+    if (hipMemcpyAsync(d_centers, centers, n * 24, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (n_points > 0 && hipMemcpyAsync(d_xyz, xyz, (size_t)n_points * 24, hipMemcpyHostToDevice, st) != hipSuccess) ||
+        hipMemcpyAsync(d_obs_off, obs_off, (n + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        (n_obs > 0 && hipMemcpyAsync(d_obs_pt, obs_pt, (size_t)n_obs * 4, hipMemcpyHostToDevice, st) != hipSuccess) ||
+        hipMemsetAsync(d_cnt, 0, bytes((size_t)n_points * 4), st) != hipSuccess || hipMemsetAsync(d_off, 0, ((size_t)n_points + 1) * 4, st) != hipSuccess ||
+        hipMemsetAsync(d_fill, 0, bytes((size_t)n_points * 4), st) != hipSuccess || hipMemsetAsync(d_acc, 0, nn * 8, st) != hipSuccess)
+        return -100;
+    (void)call.begin();
+    if (n_slots > 0) {
+        hipLaunchKernelGGL(k_vs_count, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_cnt);
+        hipLaunchKernelGGL(k_vs_scan_tiles, dim3(ntiles), dim3(kVsScanTile), 0, st, d_cnt, n_points, d_off, d_tsum);
+        hipLaunchKernelGGL(k_vs_scan_sums, dim3(1), dim3(kVsScanTile), 0, st, d_tsum, ntiles, d_off, n_points);
+        hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kVsScanTile), 0, st, d_off, n_points, d_tsum);
+        hipLaunchKernelGGL(k_vs_scatter, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_off, d_fill, d_trk_img, d_trk_pt);
+        const dim3 gs((ns + 255) / 256);
+        hipLaunchKernelGGL(k_vs_mult, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_off, d_trk_mult);
+        hipLaunchKernelGGL(k_vs_pairs, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_trk_mult, d_off, d_centers, d_xyz, d_acc, n_images);
     }
-    if (!rc && num_view > 0 &&
-        (hipMemcpyAsync(out_ids, d_ids, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-         hipMemcpyAsync(out_scores, d_scores, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
-        rc = -100;
+    hipLaunchKernelGGL(k_vs_score, dim3((n_images + 255) / 256, n_images), dim3(256), 0, st, d_acc, n_images, d_score);
+    if (num_view > 0) hipLaunchKernelGGL(k_vs_select, dim3(n_images), dim3(256), 0, st, d_score, n_images, num_view, d_ids, d_scores);
+    if (hipGetLastError() != hipSuccess) return -100;
+    (void)call.end();
+    if (hipStreamSynchronize(st) != hipSuccess) return -100;
+    (void)call.elapsed(&g_viewsel_kernel_ms);
+    if (num_view > 0 && (hipMemcpyAsync(out_ids, d_ids, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                         hipMemcpyAsync(out_scores, d_scores, n * num_view * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+        return -100;
     std::vector<unsigned long long> acc;
-    if (!rc && (shared || small)) {
+    if (shared || small) {
         acc.resize(nn);
-        if (hipMemcpyAsync(acc.data(), d_acc, nn * 8, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
+        if (hipMemcpyAsync(acc.data(), d_acc, nn * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return -100;
     }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path, before the buffers go back to the pool
-    if (!rc && (shared || small))
-        for (size_t k = 0; k < nn; ++k) {
-            if (shared) shared[k] = (uint32_t)(acc[k] >> 32);
-            if (small) small[k] = (uint32_t)(acc[k] & 0xffffffffull);
-        }
-    for (void* p : {(void*)d_centers, (void*)d_xyz, (void*)d_obs_off, (void*)d_obs_pt, (void*)d_cnt, (void*)d_off, (void*)d_tsum, (void*)d_fill,
-                    (void*)d_trk_img, (void*)d_trk_pt, (void*)d_trk_mult, (void*)d_acc, (void*)d_score, (void*)d_ids, (void*)d_scores})
-        (void)pool_free(p);
-    (void)hipStreamDestroy(st);
-    return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return -100;
+    for (size_t k = 0; k < acc.size(); ++k) {
+        if (shared) shared[k] = (uint32_t)(acc[k] >> 32);
+        if (small) small[k] = (uint32_t)(acc[k] & 0xffffffffull);
+    }
+    return 0;
 }
 
 // the output camera of the undistortion (pm_undistort_model.hpp: und_output_camera); host only, touches no device
@@ -2711,56 +2395,39 @@ int mpmvs_undistort_u8(int device, const unsigned char* src, int channels, int w
     if (!(dst_pinhole[0] > 0.0) || !(dst_pinhole[1] > 0.0)) return -2;
     const size_t n_pix = (size_t)dst_width * dst_height, out_bytes = n_pix * channels, src_bytes = row * height;
     if (out_bytes >= (1ull << 31) || row >= (1ull << 31) || src_bytes >= (1ull << 40)) return -3;
-    if (enter_device(device) != hipSuccess) return -100;
-    hipStream_t st = nullptr;  // own stream: other contexts of this device keep running
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return -100;
+    PinnedBuf pinned;   // (outlives the call's stream work: destroyed after `call`)
+    DeviceCall call(device);
+    if (!call.ok()) return -100;
+    const hipStream_t st = call.stream();
     // one page-locked stage for the three host arrays (each part starts on a 16-byte boundary; the outputs are rounded up to the
     // dword the kernel stores last)
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_out = up16(src_bytes), o_valid = o_out + up16(out_bytes), stage_bytes = o_valid + up16(n_pix);
-    unsigned char* stage = (unsigned char*)mpmvs_alloc_pinned(stage_bytes);
-    unsigned char *d_src = nullptr, *d_out = nullptr, *d_valid = nullptr;
-    int rc = stage ? 0 : -100;
-    if (!rc && (pool_malloc(&d_src, up16(src_bytes)) != hipSuccess || pool_malloc(&d_out, up16(out_bytes)) != hipSuccess ||
-                (out_valid && pool_malloc(&d_valid, up16(n_pix)) != hipSuccess)))
-        rc = -100;
-    if (!rc) {
-        for (int y = 0; y < height; ++y) std::memcpy(stage + (size_t)y * row, src + (size_t)y * pitch_bytes, row);
-        if (hipMemcpyAsync(d_src, stage, src_bytes, hipMemcpyHostToDevice, st) != hipSuccess) rc = -100;
-    }
-    if (!rc) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess || hipEventRecord(ev0, st) != hipSuccess) rc = -100;
-        if (!rc) {
-            UndPinhole dst;
-            std::memcpy(dst.p, dst_pinhole, sizeof dst.p);
-            const dim3 grid((unsigned)((n_pix + kUndThreads - 1) / kUndThreads));
-            if (channels == 1)
-                hipLaunchKernelGGL(k_undistort<1>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width,
-                                   (unsigned)n_pix, (unsigned*)d_out, (unsigned*)d_valid);
-            else
-                hipLaunchKernelGGL(k_undistort<3>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width,
-                                   (unsigned)n_pix, (unsigned*)d_out, (unsigned*)d_valid);
-            if (hipGetLastError() != hipSuccess || hipEventRecord(ev1, st) != hipSuccess) rc = -100;
-        }
-        if (!rc && (hipMemcpyAsync(stage + o_out, d_out, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    (out_valid && hipMemcpyAsync(stage + o_valid, d_valid, n_pix, hipMemcpyDeviceToHost, st) != hipSuccess)))
-            rc = -100;
-        if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;
-        if (!rc && hipEventElapsedTime(&g_undistort_kernel_ms, ev0, ev1) != hipSuccess) rc = -100;
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = -100;  // also on an error path, before the buffers go back to the pool
-    if (!rc) {
-        std::memcpy(out, stage + o_out, out_bytes);
-        if (out_valid) std::memcpy(out_valid, stage + o_valid, n_pix);
-    }
-    for (void* p : {(void*)d_src, (void*)d_out, (void*)d_valid})
-        if (p) (void)pool_free(p);
-    if (stage) mpmvs_free_pinned(stage);
-    (void)hipStreamDestroy(st);
-    return rc;
+    unsigned char* const stage = (unsigned char*)(pinned.p = mpmvs_alloc_pinned(stage_bytes));
+    if (!stage) return -100;
+    unsigned char *d_src = call.alloc<unsigned char>(up16(src_bytes)), *d_out = call.alloc<unsigned char>(up16(out_bytes));
+    unsigned char* d_valid = out_valid ? call.alloc<unsigned char>(up16(n_pix)) : nullptr;
+    if (!d_src || !d_out || (out_valid && !d_valid)) return -100;
+    for (int y = 0; y < height; ++y) std::memcpy(stage + (size_t)y * row, src + (size_t)y * pitch_bytes, row);
+    if (hipMemcpyAsync(d_src, stage, src_bytes, hipMemcpyHostToDevice, st) != hipSuccess) return -100;
+    if (!call.begin()) return -100;
+    UndPinhole dst;
+    std::memcpy(dst.p, dst_pinhole, sizeof dst.p);
+    const dim3 grid((unsigned)((n_pix + kUndThreads - 1) / kUndThreads));
+    if (channels == 1)
+        hipLaunchKernelGGL(k_undistort<1>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width, (unsigned)n_pix,
+                           (unsigned*)d_out, (unsigned*)d_valid);
+    else
+        hipLaunchKernelGGL(k_undistort<3>, grid, dim3(kUndThreads), 0, st, m, dst, d_src, (unsigned)row, width, height, dst_width, (unsigned)n_pix,
+                           (unsigned*)d_out, (unsigned*)d_valid);
+    if (hipGetLastError() != hipSuccess || !call.end()) return -100;
+    if (hipMemcpyAsync(stage + o_out, d_out, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (out_valid && hipMemcpyAsync(stage + o_valid, d_valid, n_pix, hipMemcpyDeviceToHost, st) != hipSuccess))
+        return -100;
+    if (hipStreamSynchronize(st) != hipSuccess || !call.elapsed(&g_undistort_kernel_ms)) return -100;
+    std::memcpy(out, stage + o_out, out_bytes);
+    if (out_valid) std::memcpy(out_valid, stage + o_valid, n_pix);
+    return 0;
 }
 
 void* mpmvs_device_alloc(int device, size_t bytes) {
@@ -3121,7 +2788,7 @@ int mpmvs_skyseg_run(mpmvs_skyseg* n, const float* in, float* out) {
 }
 
 // the preprocessing of mpmvs_skyseg_run_u8, enqueued: bytes -> pyrDown loop -> resize + normalise into the input blob
-static int seg_preprocess(mpmvs_skyseg* n, const unsigned char* bgr, int h, int w, size_t pitch, PoolBuf& a, PoolBuf& b) {
+static int seg_preprocess(mpmvs_skyseg* n, const unsigned char* bgr, int h, int w, size_t pitch, Scratch& a, Scratch& b) {
     const skyseg::Blob& ib = n->m.blobs[n->m.input_blob];
     if (!bgr || h <= 0 || w <= 0 || h > 32768 || w > 32768) return seg_fail(-2, "skyseg: bad image size");
     if (ib.c != 3) return seg_fail(-2, "skyseg: the network does not take a 3-channel image");
@@ -3155,10 +2822,9 @@ static int seg_preprocess(mpmvs_skyseg* n, const unsigned char* bgr, int h, int 
 int mpmvs_skyseg_run_u8(mpmvs_skyseg* n, const unsigned char* bgr, int h, int w, size_t pitch_bytes, float* out) {
     if (!n || !out) return seg_fail(-2, "skyseg: bad argument");
     SEGCHK(enter_device(n->device));
-    PoolBuf a, b;
+    Scratch a(n->stream), b(n->stream);
     int rc = seg_preprocess(n, bgr, h, w, pitch_bytes, a, b);
-    if (!rc) rc = seg_run_tail(n, out);
-    (void)hipStreamSynchronize(n->stream);  // before the scratch buffers go back to the pool
+    if (!rc) rc = seg_run_tail(n, out);   // (ends synchronised)
     if (!rc) (void)hipEventElapsedTime(&n->pre_ms, n->ev[0], n->ev[1]);
     return rc;
 }
@@ -3166,10 +2832,9 @@ int mpmvs_skyseg_run_u8(mpmvs_skyseg* n, const unsigned char* bgr, int h, int w,
 int mpmvs_skyseg_preprocess_u8(mpmvs_skyseg* n, const unsigned char* bgr, int h, int w, size_t pitch_bytes, float* out_chw) {
     if (!n || !out_chw) return seg_fail(-2, "skyseg: bad argument");
     SEGCHK(enter_device(n->device));
-    PoolBuf a, b;
+    Scratch a(n->stream), b(n->stream);
     int rc = seg_preprocess(n, bgr, h, w, pitch_bytes, a, b);
     if (!rc) rc = seg_copy_out(n, n->m.blobs[n->m.input_blob], out_chw);
-    (void)hipStreamSynchronize(n->stream);
     n->ran = false;  // the blobs of the last run are no longer all there
     return rc;
 }
