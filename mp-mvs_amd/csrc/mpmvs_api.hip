@@ -1808,8 +1808,8 @@ int mpmvs_prior_vertices(mpmvs_ctx* c, int geom_rule, int* out_xy, int cap, int*
     if (!rc) {
         hipLaunchKernelGGL(k_prior_cells, dim3(nb), dim3(256), 0, c->stream, c->S.costs, c->S.geom, W, H, geom_rule ? 1 : 0, ncx, ncells, d_cnt.as<int>(),
                            d_pts.as<uint32_t>());
-        hipLaunchKernelGGL(k_prior_block_sums, dim3(nb), dim3(256), 0, c->stream, d_cnt.as<int>(), ncells, d_sums.as<int>());
-        hipLaunchKernelGGL(k_prior_scan, dim3(1), dim3(256), 0, c->stream, d_sums.as<int>(), nb);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nb), dim3(256), 0, c->stream, d_cnt.as<int>(), ncells, (int*)nullptr, d_sums.as<int>());
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, c->stream, d_sums.as<int>(), nb, 0, d_sums.as<int>() + nb);
         hipLaunchKernelGGL(k_prior_scatter, dim3(nb), dim3(256), 0, c->stream, d_cnt.as<int>(), d_pts.as<uint32_t>(), ncells, d_sums.as<int>(), cap, d_xy.as<int>());
         if (hipGetLastError() != hipSuccess) rc = -100;
     }
@@ -2145,7 +2145,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
                 hipLaunchKernelGGL(k_fuse<true>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
                 if (num_ngb > 1) {
                     hipLaunchKernelGGL(k_fuse_carry_local, dim3(nchunks, num_ngb - 1), dim3(256), 0, st, d_consq, npix, nchunks, d_carry);
-                    hipLaunchKernelGGL(k_fuse_carry_chunks, dim3(num_ngb - 1), dim3(256), 0, st, d_carry, nchunks);
+                    hipLaunchKernelGGL(k_scan_totals<LastValid>, dim3(num_ngb - 1), dim3(256), 0, st, d_carry, nchunks, -1, (int*)nullptr);
                     hipLaunchKernelGGL(k_fuse_mark, dim3(nchunks), dim3(256), 0, st, d_views, d_src + b, num_ngb, d_valid[i], d_consq, d_carry, npix, nchunks);
                 }
                 if (hipMemsetAsync(d_diff, 0, 4, st) != hipSuccess) rc = -100;
@@ -2175,7 +2175,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
         if (records && !rc) {
             const int wh = hv[i].w * hv[i].h, nb = (wh + 255) / 256;
             hipLaunchKernelGGL(k_fuse_count, dim3(nb), dim3(256), 0, st, d_valid[i], wh, d_blocks);
-            hipLaunchKernelGGL(k_fuse_scan, dim3(1), dim3(256), 0, st, d_blocks, nb);
+            hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, d_blocks, nb, 0, d_blocks + nb);
             hipLaunchKernelGGL(k_fuse_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_out[i], wh, d_blocks, d_base, d_records);
             hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, d_base, d_blocks + nb);
             if (hipGetLastError() != hipSuccess) rc = -100;
@@ -2304,7 +2304,7 @@ int mpmvs_view_select(int device, int n_images, const double* centers, int n_poi
     const hipStream_t st = call.stream();
 
     const size_t n = (size_t)n_images, nn = n * n;
-    const int ntiles = (n_points + kVsScanTile - 1) / kVsScanTile;
+    const int ntiles = (n_points + kScanBlock - 1) / kScanBlock;
     const int ns = (int)n_slots;
     double *d_centers = call.alloc<double>(n * 24), *d_xyz = call.alloc<double>((size_t)n_points * 24);
     int64_t* d_obs_off = call.alloc<int64_t>((n + 1) * 8);
@@ -2330,9 +2330,9 @@ int mpmvs_view_select(int device, int n_images, const double* centers, int n_poi
     (void)call.begin();
     if (n_slots > 0) {
         hipLaunchKernelGGL(k_vs_count, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_cnt);
-        hipLaunchKernelGGL(k_vs_scan_tiles, dim3(ntiles), dim3(kVsScanTile), 0, st, d_cnt, n_points, d_off, d_tsum);
-        hipLaunchKernelGGL(k_vs_scan_sums, dim3(1), dim3(kVsScanTile), 0, st, d_tsum, ntiles, d_off, n_points);
-        hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kVsScanTile), 0, st, d_off, n_points, d_tsum);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, st, d_cnt, n_points, d_off, d_tsum);
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_tsum, ntiles, 0, d_off + n_points);
+        hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kScanBlock), 0, st, d_off, n_points, d_tsum);
         hipLaunchKernelGGL(k_vs_scatter, dim3(n_images), dim3(256), 0, st, d_obs_off, d_obs_pt, d_off, d_fill, d_trk_img, d_trk_pt);
         const dim3 gs((ns + 255) / 256);
         hipLaunchKernelGGL(k_vs_mult, gs, dim3(256), 0, st, ns, d_trk_img, d_trk_pt, d_off, d_trk_mult);

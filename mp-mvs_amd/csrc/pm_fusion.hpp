@@ -10,8 +10,8 @@
 // image.  One thread = one pixel; HBM-bound (per pixel: own depth/normal/colour plus,
 // per source view, one mask byte, one depth, one normal, one colour).
 //
-// EXACT mode (k_fuse<true> + k_fuse_carry_* + k_fuse_mark) reproduces the reference's order-dependent result instead,
-// still in parallel, as a fixpoint: within the image being fused every source pixel q gets a time tau(q) = the raster index of
+// EXACT mode (k_fuse<true> + k_fuse_carry_local + k_scan_totals<LastValid> + k_fuse_mark) reproduces the reference's
+// order-dependent result instead, still in parallel, as a fixpoint: within the image being fused every source pixel q gets a time tau(q) = the raster index of
 // the first accepted pixel that masks it (-1: masked before this image, INT_MAX: never).  Given tau, every pixel t can be
 // evaluated independently -- source pixel q is masked for t exactly when tau(q) < t -- and yields its consistent source
 // pixels and its acceptance; the marks of an accepted pixel are the entries of the reference's used_list at that moment,
@@ -23,6 +23,7 @@
 #pragma once
 
 #include "pm_device.hpp"
+#include "pm_scan.hpp"
 
 namespace pm {
 
@@ -182,56 +183,18 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseView* __restrict__ views
 }
 
 // ---------------------------------------------------------------------------
-// exact mode: the used_list of the reference as an inclusive "last valid entry" scan over the raster order, per source slot.
-// Pass 1 scans chunks of 256 pixels in place and records each chunk's last valid entry; pass 2 turns those into the entry
-// carried INTO each chunk; k_fuse_mark combines both.
+// exact mode: the used_list of the reference as an inclusive "last valid entry" scan over the raster order, per source slot
+// (pm_scan.hpp, LastValid).  k_fuse_carry_local scans chunks of 256 pixels in place and records each chunk's last valid
+// entry; k_scan_totals<LastValid>, one row per slot, turns those into the entry carried INTO each chunk; k_fuse_mark
+// combines both.
 // ---------------------------------------------------------------------------
-PM_DEV int last_valid(int left, int right) { return right >= 0 ? right : left; }
-
-__global__ __launch_bounds__(256) void k_fuse_carry_local(int* __restrict__ consq, int npix, int nchunks, int* __restrict__ tails) {
-    const int slot = blockIdx.y, chunk = blockIdx.x, t = chunk * 256 + threadIdx.x;
+__global__ __launch_bounds__(kScanBlock) void k_fuse_carry_local(int* __restrict__ consq, int npix, int nchunks, int* __restrict__ tails) {
+    const int slot = blockIdx.y, chunk = blockIdx.x, t = chunk * kScanBlock + threadIdx.x;
     int* row = consq + (size_t)slot * npix;
-    int v = t < npix ? row[t] : -1;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(v, d, 64);
-        if (lane >= d) v = last_valid(up, v);
-    }
-    __shared__ int wave_tail[4];
-    if (lane == 63) wave_tail[wv] = v;
-    __syncthreads();
-    int carry = -1;
-    for (int k = 0; k < wv; ++k) carry = last_valid(carry, wave_tail[k]);
-    v = last_valid(carry, v);
+    int tail;
+    const int v = block_incl_scan<LastValid>(t < npix ? row[t] : -1, -1, tail);
     if (t < npix) row[t] = v;
-    if (threadIdx.x == 255) tails[(size_t)slot * nchunks + chunk] = v;
-}
-
-// tails[slot][chunk] -> the entry carried into the chunk (exclusive scan with last_valid), in place; one block per slot
-__global__ __launch_bounds__(256) void k_fuse_carry_chunks(int* __restrict__ tails, int nchunks) {
-    int* row = tails + (size_t)blockIdx.x * nchunks;
-    __shared__ int part[256];
-    const int per = (nchunks + 255) / 256, lo = min((int)threadIdx.x * per, nchunks), hi = min(lo + per, nchunks);
-    int s = -1;
-    for (int k = lo; k < hi; ++k) s = last_valid(s, row[k]);
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = -1;
-        for (int k = 0; k < 256; ++k) {
-            const int c = part[k];
-            part[k] = run;
-            run = last_valid(run, c);
-        }
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int k = lo; k < hi; ++k) {
-        const int c = row[k];
-        row[k] = run;
-        run = last_valid(run, c);
-    }
+    if (threadIdx.x == 0) tails[(size_t)slot * nchunks + chunk] = tail;
 }
 
 // marks of the accepted pixels: tau_new(q) = min(tau_new(q), t) for every entry of the used_list at time t
@@ -269,59 +232,27 @@ __global__ __launch_bounds__(256) void k_fuse_tau_to_mask(const int* __restrict_
 // Compaction of one image's fused points into the reference's PointCloud order (raster order inside the image; images are
 // appended in index order) as PLY vertex records: x y z nx ny nz (float32) red green blue (uint8), 27 bytes, exactly what
 // StoreColorPlyFileBinaryPointCloud writes (ref src/PatchMatch.cpp:145-198).  Three small passes, deterministic:
-// per-256-pixel block counts -> exclusive scan (one block) -> scatter with in-block ranks.
+// per-256-pixel block counts -> exclusive scan (k_scan_totals<Sum>) -> scatter with in-block ranks, counts and ranks
+// from the block scan of pm_scan.hpp over the 0/1 predicate.
 // ---------------------------------------------------------------------------
 constexpr int kPlyRecord = 27;
 
-__global__ __launch_bounds__(256) void k_fuse_count(const unsigned char* __restrict__ valid, int n, int* __restrict__ block_counts) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int v = (i < n && valid[i]) ? 1 : 0;
-    __shared__ int wave_sum[4];
-    const unsigned long long b = __ballot(v);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+__global__ __launch_bounds__(kScanBlock) void k_fuse_count(const unsigned char* __restrict__ valid, int n, int* __restrict__ block_counts) {
+    const int i = blockIdx.x * kScanBlock + threadIdx.x;
+    int total;
+    block_excl_scan<Sum>((i < n && valid[i]) ? 1 : 0, 0, total);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
 }
 
-// block_counts[0 .. nb) -> exclusive prefix sums in place; block_counts[nb] receives the image's point count
-__global__ __launch_bounds__(256) void k_fuse_scan(int* __restrict__ block_counts, int nb) {
-    __shared__ int part[256];
-    const int per = (nb + 255) / 256, lo = min(threadIdx.x * per, nb), hi = min(lo + per, nb);
-    int s = 0;
-    for (int k = lo; k < hi; ++k) s += block_counts[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int k = 0; k < 256; ++k) {
-            const int c = part[k];
-            part[k] = run;
-            run += c;
-        }
-        block_counts[nb] = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int k = lo; k < hi; ++k) {
-        const int c = block_counts[k];
-        block_counts[k] = run;
-        run += c;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_fuse_scatter(const unsigned char* __restrict__ valid, const float* __restrict__ pts9, int n,
-                                                      const int* __restrict__ block_offsets, const long long* __restrict__ base,
-                                                      unsigned char* __restrict__ records) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// block_offsets = block_counts after k_scan_totals<Sum>: exclusive prefix sums, [nb] = the image's point count
+__global__ __launch_bounds__(kScanBlock) void k_fuse_scatter(const unsigned char* __restrict__ valid, const float* __restrict__ pts9, int n,
+                                                             const int* __restrict__ block_offsets, const long long* __restrict__ base,
+                                                             unsigned char* __restrict__ records) {
+    const int i = blockIdx.x * kScanBlock + threadIdx.x;
     const int v = (i < n && valid[i]) ? 1 : 0;
-    __shared__ int wave_sum[4];
-    const unsigned long long b = __ballot(v);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (lane == 0) wave_sum[wv] = __popcll(b);
-    __syncthreads();
+    int total;
+    const int rank = block_excl_scan<Sum>(v, 0, total);
     if (!v) return;
-    int rank = __popcll(b & ((1ull << lane) - 1ull));
-    for (int k = 0; k < wv; ++k) rank += wave_sum[k];
     const long long slot = *base + block_offsets[blockIdx.x] + rank;
     const float* p = pts9 + (size_t)i * 9;
     float rec[6] = {p[0], p[1], p[2], p[3], p[4], p[5]};
@@ -336,7 +267,7 @@ __global__ __launch_bounds__(256) void k_fuse_scatter(const unsigned char* __res
     o[26] = (unsigned char)(int)p[6];  // blue
 }
 
-// *base += count of the image just scattered (block_counts[nb] from k_fuse_scan)
+// *base += count of the image just scattered (block_counts[nb] from k_scan_totals)
 __global__ void k_fuse_advance(long long* __restrict__ base, const int* __restrict__ image_count) { *base += *image_count; }
 
 }  // namespace pm

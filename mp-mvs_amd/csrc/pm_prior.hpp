@@ -1,7 +1,8 @@
 // pm_prior.hpp -- the planar-prior block of ProcessProblem (reference src/PatchMatch.cpp:532-604) on
 // the device, so that the maps a Run() left in HBM never cross PCIe between the two Run() calls of a Problem:
 //   k_prior_cells + scan/scatter   GetTriangulateVertices (ref :782-853): per 5x5 cell the reliable pixels, compacted in cell
-//                                  raster order -- only the vertex list (a few hundred KB) goes to the host;
+//                                  raster order by the shared block scan (pm_scan.hpp) -- only the vertex list (a few
+//                                  hundred KB) goes to the host;
 //   [host]                         Delaunay triangulation of the vertices (mp-mvs_amd/host/planar_prior.cpp);
 //   k_prior_raster                 triangle rasterisation by barycentric stepping (ref :554-570), "last triangle wins" as an
 //                                  atomic max over labels, and the plane through the three back-projected vertices
@@ -14,6 +15,7 @@
 #pragma once
 
 #include "pm_device.hpp"
+#include "pm_scan.hpp"
 
 namespace pm {
 
@@ -83,64 +85,14 @@ __global__ __launch_bounds__(256) void k_prior_cells(const float* __restrict__ c
     cell_pts[cell * 3 + 2] = where[2];
 }
 
-// per-256-cell block sums
-__global__ __launch_bounds__(256) void k_prior_block_sums(const int* __restrict__ cell_cnt, int ncells, int* __restrict__ block_sums) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    int v = i < ncells ? cell_cnt[i] : 0;
-    __shared__ int part[256];
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = part[0];
-}
-
-// block_sums[0 .. nb) -> exclusive prefix sums in place; block_sums[nb] = total (one block)
-__global__ __launch_bounds__(256) void k_prior_scan(int* __restrict__ block_sums, int nb) {
-    __shared__ int part[256];
-    const int per = (nb + 255) / 256, lo = min((int)threadIdx.x * per, nb), hi = min(lo + per, nb);
-    int s = 0;
-    for (int k = lo; k < hi; ++k) s += block_sums[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int k = 0; k < 256; ++k) {
-            const int c = part[k];
-            part[k] = run;
-            run += c;
-        }
-        block_sums[nb] = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int k = lo; k < hi; ++k) {
-        const int c = block_sums[k];
-        block_sums[k] = run;
-        run += c;
-    }
-}
-
-// vertices in cell raster order: out_xy[2 * k] = x, [2 * k + 1] = y
-__global__ __launch_bounds__(256) void k_prior_scatter(const int* __restrict__ cell_cnt, const uint32_t* __restrict__ cell_pts, int ncells,
-                                                       const int* __restrict__ block_offsets, int cap, int* __restrict__ out_xy) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
+// vertices in cell raster order: out_xy[2 * k] = x, [2 * k + 1] = y.  block_offsets = the exclusive scan of the per-block
+// counts (k_scan_tiles, k_scan_totals<Sum>: pm_scan.hpp)
+__global__ __launch_bounds__(kScanBlock) void k_prior_scatter(const int* __restrict__ cell_cnt, const uint32_t* __restrict__ cell_pts, int ncells,
+                                                              const int* __restrict__ block_offsets, int cap, int* __restrict__ out_xy) {
+    const int i = blockIdx.x * kScanBlock + threadIdx.x;
     const int v = i < ncells ? cell_cnt[i] : 0;
-    __shared__ int part[256];
-    part[threadIdx.x] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int k = 0; k < 256; ++k) {
-            const int c = part[k];
-            part[k] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-    const int base = block_offsets[blockIdx.x] + part[threadIdx.x];
+    int total;
+    const int base = block_offsets[blockIdx.x] + block_excl_scan<Sum>(v, 0, total);
     for (int k = 0; k < v; ++k) {
         if (base + k >= cap) return;
         const uint32_t p = cell_pts[i * 3 + k];

@@ -7,7 +7,8 @@
 //
 // Passes (all integer bookkeeping; the results do not depend on scheduling):
 //   1. k_vs_count / scan / k_vs_scatter: per-image observations -> point-major tracks (the image of
-//      every observation, in scatter order).
+//      every observation, in scatter order).  The scan of the per-point counts into track offsets is
+//      the shared one of pm_scan.hpp (k_scan_tiles, k_scan_totals<Sum>) followed by k_vs_scan_add.
 //   2. k_vs_mult: per track slot, whether it is the first slot of its image in the track (scanning
 //      the track) and, if so, the image's multiplicity in it; other slots get 0.  "First" depends on
 //      scatter order, the multiplicity it carries does not, so no per-track sort is needed.
@@ -23,10 +24,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pm_scan.hpp"
+
 namespace pm {
 
 constexpr int kVsMaxImages = 32768;   // dense N x N accumulators: 12 N^2 bytes (12.9 GB at the cap)
-constexpr int kVsScanTile = 1024;
 
 // one block per image: count the observations of every point
 __global__ __launch_bounds__(256) void k_vs_count(const int64_t* __restrict__ obs_off, const int32_t* __restrict__ obs_pt, int* __restrict__ cnt) {
@@ -37,62 +39,9 @@ __global__ __launch_bounds__(256) void k_vs_count(const int64_t* __restrict__ ob
     }
 }
 
-__device__ inline int vs_wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int u = __shfl_up(v, d, 64);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-
-// exclusive scan of one 1024-element tile per block; the tile's total goes to tsum[blockIdx.x]
-__device__ inline int vs_block_excl_scan(int v, int* wsum, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = vs_wave_incl_scan(v);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    if (w == 0) {
-        const int s = lane < 16 ? wsum[lane] : 0;
-        const int si = vs_wave_incl_scan(s);
-        if (lane < 16) wsum[16 + lane] = si - s;
-        if (lane == 15) wsum[32] = si;
-    }
-    __syncthreads();
-    total = wsum[32];
-    const int r = wsum[16 + w] + inc - v;
-    __syncthreads();  // wsum is reused by the caller's next round
-    return r;
-}
-
-__global__ __launch_bounds__(1024) void k_vs_scan_tiles(const int* __restrict__ cnt, int n, int* __restrict__ off, int* __restrict__ tsum) {
-    __shared__ int wsum[33];
-    const int64_t k = (int64_t)blockIdx.x * kVsScanTile + threadIdx.x;
-    const int v = k < n ? cnt[k] : 0;
-    int total = 0;
-    const int r = vs_block_excl_scan(v, wsum, total);
-    if (k < n) off[k] = r;
-    if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// one block: exclusive scan of the tile totals (in place), off[n] = grand total
-__global__ __launch_bounds__(1024) void k_vs_scan_sums(int* __restrict__ tsum, int ntiles, int* __restrict__ off, int n) {
-    __shared__ int wsum[33];
-    int carry = 0;
-    for (int base = 0; base < ntiles; base += kVsScanTile) {
-        const int k = base + threadIdx.x;
-        const int v = k < ntiles ? tsum[k] : 0;
-        int total = 0;
-        const int r = vs_block_excl_scan(v, wsum, total);
-        if (k < ntiles) tsum[k] = carry + r;
-        carry += total;
-    }
-    if (threadIdx.x == 0) off[n] = carry;
-}
-
-__global__ __launch_bounds__(1024) void k_vs_scan_add(int* __restrict__ off, int n, const int* __restrict__ tsum) {
-    const int64_t k = (int64_t)blockIdx.x * kVsScanTile + threadIdx.x;
+// off[k] += the scanned total of k's tile (after k_scan_tiles and k_scan_totals<Sum>, pm_scan.hpp)
+__global__ __launch_bounds__(kScanBlock) void k_vs_scan_add(int* __restrict__ off, int n, const int* __restrict__ tsum) {
+    const int64_t k = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
     if (k < n) off[k] += tsum[blockIdx.x];
 }
 

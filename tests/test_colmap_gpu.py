@@ -102,6 +102,36 @@ def test_view_select_matches_numpy(colmap, n):
     assert ids2.tobytes() == ids.tobytes() and sc2.tobytes() == sc.tobytes() and sh2.tobytes() == sh.tobytes() and sm2.tobytes() == sm.tobytes()
 
 
+# point counts at the edges of the track-offset scan (pm_scan.hpp, tiles of 256): the last partial tile, one full tile, one
+# point into the next, and 256 * 256 + 1 = one tile of tile totals into the second round of the totals scan
+@pytest.mark.parametrize("n_points", [255, 256, 257, 65537])
+def test_view_select_at_scan_edges(colmap, n_points):
+    """64 images, every point seen by exactly two distinct images: the pair list is the model itself"""
+    n, num_view = 64, 20
+    rng = np.random.default_rng(2000 + n_points)
+    clusters = rng.normal(0, 4.0, (8, 3))
+    C = clusters[rng.integers(0, 8, n)] + rng.normal(0, 0.02, (n, 3))
+    xyz = rng.normal(0, 1.0, (n_points, 3)) + np.array([0, 0, 30.0])
+    a = rng.integers(0, n, n_points)
+    b = (a + rng.integers(1, n, n_points)) % n
+    a, b = np.minimum(a, b), np.maximum(a, b)
+    # per-image lists in a shuffled order
+    img, pt = np.concatenate([a, b]), np.tile(np.arange(n_points, dtype=np.int32), 2)
+    order = rng.permutation(2 * n_points)
+    order = order[np.argsort(img[order], kind="stable")]
+    off = np.concatenate([[0], np.cumsum(np.bincount(img, minlength=n))]).astype(np.int64)
+    pts = np.ascontiguousarray(pt[order])
+    ids, sc, sh, sm = colmap.view_select(C, xyz, off, pts, num_view, counts=True)
+    esh = np.zeros((n, n), np.uint64)
+    esm = np.zeros((n, n), np.uint64)
+    np.add.at(esh, (a, b), np.uint64(1))
+    np.add.at(esm, (a, b), (angle(C[a], C[b], xyz) < 1).astype(np.uint64))
+    assert esh.sum() == n_points and esm.any() and ((esh > 0) & (esm == 0)).any()
+    assert np.array_equal(sh.astype(np.uint64), esh) and np.array_equal(sm.astype(np.uint64), esm)
+    eids, esc = rule_selection(esh, esm, num_view)
+    assert np.array_equal(ids, eids) and np.array_equal(sc, esc)
+
+
 def test_view_select_argument_errors(engine):
     _, fns = engine.load()
     C = np.zeros((4, 3))

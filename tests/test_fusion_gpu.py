@@ -110,11 +110,11 @@ def test_fusion_from_resident_contexts_equals_the_host_array_path(pm, engine, re
 
 
 @pytest.mark.parametrize("use_sky", [False, True])
-def test_fuse_ply_records_equal_uncompacted_path(pm, oracle, engine, use_sky):
+def test_fuse_ply_records_equal_uncompacted_path(pm, oracle, engine, use_sky, size=(131, 97)):
     """mpmvs_fuse_ply (device-side compaction into PLY vertex records) == the records built from mpmvs_fuse's per-pixel
     outputs == those built from the oracle's cloud, in the reference's PointCloud order; sizes that are not block multiples"""
     fusion = importlib.import_module("mp-mvs_amd.fusion")
-    sc, cams, depths, normals, grays, neigh = _scene(pm, size=(131, 97))
+    sc, cams, depths, normals, grays, neigh = _scene(pm, size=size)
     cols, sky = _colours_and_sky(grays)
     depths[1][5:9, 7:40] = np.inf                      # non-finite coordinates are written as 0 (reference :176-179)
     est = [True, True, False, True, True, True]
@@ -127,6 +127,12 @@ def test_fuse_ply_records_equal_uncompacted_path(pm, oracle, engine, use_sky):
     assert all(np.array_equal(a, b) for a, b in zip(masks, masks2))
     rec0, _ = fusion.fuse_ply(cams, [False] * 6, depths, normals, cols, neigh)
     assert rec0.shape == (0, 27)
+
+
+# 257 x 256 = 65 792 pixels = 257 blocks of 256: one block of block totals into the second round of the totals scan
+# (pm_scan.hpp), for the compaction's sum and below for the used_list's "last valid"
+def test_fuse_ply_records_above_65536_pixels(pm, oracle, engine):
+    test_fuse_ply_records_equal_uncompacted_path(pm, oracle, engine, False, size=(257, 256))
 
 
 def test_fusion_rejects_view_ids_that_do_not_exist(pm, engine):
@@ -143,12 +149,12 @@ def test_fusion_rejects_view_ids_that_do_not_exist(pm, engine):
 
 
 @pytest.mark.parametrize("variant", ["dynamic", "static", "colour+sky"])
-def test_reference_order_fusion_bit_exact(pm, oracle, engine, variant):
+def test_reference_order_fusion_bit_exact(pm, oracle, engine, variant, size=(160, 120)):
     """MPMVS_FUSE_REFERENCE_ORDER: the reference's order-dependent result (pixel-by-pixel in-place masks and the used_list that
     is never reset, ref src/PatchMatch.cpp:382,416,470-495) computed on the GPU as a parallel fixpoint == the sequential loop of
     the oracle (mode 2), bit for bit"""
     fusion = importlib.import_module("mp-mvs_amd.fusion")
-    sc, cams, depths, normals, grays, neigh = _scene(pm, size=(160, 120))
+    sc, cams, depths, normals, grays, neigh = _scene(pm, size=size)
     depths[2][10:30, 20:60] = 0.0
     cols, sky = grays, None
     if variant == "colour+sky":
@@ -169,3 +175,7 @@ def test_reference_order_fusion_bit_exact(pm, oracle, engine, variant):
     # records path (device-side compaction) gives the same points
     rec, _ = fusion.fuse_ply(cams, est, depths, normals, cols, neigh, dyn, sky=sky, reference_order=True)
     assert np.array_equal(rec, fusion.ply_records(cg))
+
+
+def test_reference_order_fusion_above_65536_pixels(pm, oracle, engine):
+    test_reference_order_fusion_bit_exact(pm, oracle, engine, "dynamic", size=(257, 256))

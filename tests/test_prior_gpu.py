@@ -1,6 +1,7 @@
 """Planar prior built on the device (mp-mvs_amd/csrc/pm_prior.hpp; reference src/PatchMatch.cpp:532-604, SURVEY a-16):
 against the independent scipy / numpy fixtures of tests/golden/prior_golden_v1.npz, and bit for bit against the host
 implementation (mp-mvs_amd/host/planar_prior.cpp) on the state of a real Run()."""
+import ctypes
 import os
 
 import numpy as np
@@ -35,6 +36,42 @@ def test_device_vertices_equal_bruteforce(pm, engine, gold, tag, geomprior):
     gpu.set_geom_costs(geom)
     got = gpu.prior_vertices(geomprior)
     assert np.array_equal(got, gold[f"vert_{tag}_geomprior" if geomprior else f"vert_{tag}_plain"])
+
+
+def _random_costs(w, h, seed):
+    """costs and geometric costs that leave roughly half the 5x5 cells with a vertex under either rule: 2.8 % of the pixels
+    are `low` (cost < 0.1, geometric cost 0.1), so 1 - 0.972^25 = 0.51 of the cells hold one; every other pixel costs at
+    least 0.25, above the plain rule's 0.1 and the geometric rule's floor of 0.2"""
+    rng = np.random.default_rng(seed)
+    costs = rng.uniform(0.0, 2.0, (h, w)).astype(np.float32)
+    low = rng.random((h, w)) < 0.028
+    costs[low] = rng.uniform(0.0, 0.1, int(low.sum())).astype(np.float32)
+    costs[~low] = np.maximum(costs[~low], np.float32(0.25))
+    geom = rng.uniform(0.0, 0.8, (h, w)).astype(np.float32)
+    geom[low] = np.float32(0.1)
+    return costs, geom
+
+
+# cell counts 255, 256, 257 (the last partial block, one full block, one cell into the next) and 257 * 256 = 65 792 (one
+# block of block totals into the second round of the totals scan)
+@pytest.mark.parametrize("geom_rule", [False, True])
+@pytest.mark.parametrize("w,h,ncells", [(85, 75, 255), (80, 80, 256), (1285, 5, 257), (1285, 1280, 65792)])
+def test_device_vertices_equal_host_at_block_edges(pm, engine, hostlib, w, h, ncells, geom_rule):
+    assert ((w + 4) // 5) * ((h + 4) // 5) == ncells
+    costs, geom = _random_costs(w, h, 7000 + ncells)
+    gpu = blank_context(pm, engine, make_cam([100, 0, w / 2, 0, 100, h / 2, 0, 0, 1], w, h), w, h)
+    gpu.set_state(None, costs)
+    gpu.set_geom_costs(geom)
+    want = hostlib.triangulate_vertices(costs, geom, geom_rule)
+    assert 0.3 * ncells < len(want) < (2.1 if geom_rule else 0.7) * ncells
+    got = gpu.prior_vertices(geom_rule)
+    assert np.array_equal(got, want)
+    # a buffer smaller than the list: the count is still the full one, the buffer holds the head of the list
+    cap = len(want) // 2 + 1
+    out = np.full((cap + 1, 2), -7, np.int32)
+    n = ctypes.c_int(0)
+    assert gpu._f["prior_vertices"](gpu._ctx, 1 if geom_rule else 0, out.ctypes.data, cap, ctypes.byref(n)) == 0
+    assert n.value == len(want) and np.array_equal(out[:cap], want[:cap]) and (out[cap] == -7).all()
 
 
 def test_device_raster_planes_mask_equal_fixtures(pm, engine, gold):
