@@ -416,6 +416,39 @@ int mpmvs_undistort_u8(int device, const unsigned char* src, int channels, int w
 /* device time (ms, HIP events) of the kernel of the calling thread's last successful mpmvs_undistort_u8 call */
 float mpmvs_undistort_kernel_ms(void);
 
+/* ---- point clouds: exact capped nearest neighbour (mp-mvs_amd/cloud.py, tools/eval_ply.py) --- */
+/* A target cloud on one device and, per query point, its nearest target point within a radius: what the accuracy /
+ * completeness / F1 score of a fused cloud against a ground-truth scan needs.
+ * DEFINED BY EQUIVALENCE with the brute-force statement, bit for bit and independent of scheduling:
+ *   r2 = radius * radius in fp32.
+ *   For query q and target p: dx = qx - px, likewise dy, dz, all in fp32; d2 = (dx*dx + dy*dy) + dz*dz in fp32, no contraction.
+ *   p is a candidate iff all its coordinates are finite and d2 <= r2.
+ *   out_d2 = the smallest candidate d2; out_idx = the smallest index among the candidates that attain it (duplicates and the
+ *   order in which the device handles the points do not show in the result).
+ *   No candidate, or a query with a non-finite coordinate: out_d2 = +inf, out_idx = -1.
+ * The search structure is a sparse uniform grid of cell edge max(radius, 2^-60) * (1 + 2^-10) addressed through a hash table
+ * (mp-mvs_amd/csrc/pm_cloud.hpp); it is built by the first call with a radius and cached in the handle per radius: a later call
+ * with the same radius reuses it, another radius builds its own (a handle keeps up to 8 grids; one more radius takes over the
+ * buffers of the least recently used one).
+ * Errors (text through mpmvs_last_error with a NULL context, per host thread): -2 = a NULL xyz with n > 0, a negative count, a radius
+ * that is not finite or <= 0, a NULL cloud or out_d2; -3 = n or n_q above 2^31 - 1, more than 2^29 finite target points (the
+ * table's slot count, a power of two of at least twice the finite points, is held to 2^30), or a target whose finite bounding box
+ * spans more than 2^21 cells along an axis at this radius (the text names the axis and the ratio; the handle stays usable);
+ * -100 = HIP failure, a bad device included.  All but -100 are found before the device is touched.  n == 0 and n_q == 0 are legal. */
+typedef struct mpmvs_cloud mpmvs_cloud;
+/* target cloud: n points, xyz = n x 3 fp32 (what a PLY holds); uploaded once, stays in HBM.  *cloud is NULL after a failure,
+ * which leaves no allocation behind. */
+int mpmvs_cloud_create(int device, long long n, const float* xyz, mpmvs_cloud** cloud);
+/* per query point: squared distance to, and index of, its nearest target point within `radius`; host buffers, blocks until
+ * done; n_q == 0 returns 0 and touches no output */
+int mpmvs_cloud_nearest(mpmvs_cloud* cloud, float radius, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx /* may be NULL */);
+/* stats of the grid of the last call: [0] finite target points, [1] occupied cells, [2] points in the fullest cell, [3] table slots */
+int mpmvs_cloud_stats(const mpmvs_cloud* cloud, long long stats[4]);
+/* device ms (HIP events) of the last call's query passes (the binning of the queries and the query kernel); *build_ms (may be
+ * NULL) of the grid build it needed (0 if reused) */
+float mpmvs_cloud_kernel_ms(const mpmvs_cloud* cloud, float* build_ms);
+void mpmvs_cloud_destroy(mpmvs_cloud* cloud);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

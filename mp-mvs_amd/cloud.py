@@ -1,0 +1,265 @@
+"""Point clouds: reading PLY files, the exact capped nearest-neighbour search on the GPU (mpmvs_cloud_*, csrc/pm_cloud.hpp)
+and the accuracy / completeness / F1 score of a fused cloud against a ground-truth scan.
+
+The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
+voxelises both clouds and masks the space the scanner did not observe, so the numbers here are comparable between our own
+builds and settings, and not to the ETH3D leaderboard.  The search runs on the GPU; there is no CPU path."""
+import ctypes as C
+
+import numpy as np
+
+from . import engine
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
+              "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def read_ply(path):
+    """The `vertex` element of a binary_little_endian or ascii PLY file -> {"xyz": float32 [n, 3]} plus "normals" (float32
+    [n, 3], from nx ny nz) and "colors" (uint8 [n, 3], from red green blue) when the file has them.  Other properties and
+    other elements are skipped by their declared sizes; list properties inside `vertex` and big-endian files are refused
+    (ValueError).  Reads back what hostlib.write_ply writes (the reference's 27-byte records)."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"{path}: not a PLY file (no 'ply' ... 'end_header' header)")
+    fmt, elements = None, []   # elements: [name, count, [(type, name) or ("list", count type, item type, name)]]
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append([w[1], int(w[2]), []])
+        elif w[0] == "property":
+            if not elements:
+                raise ValueError(f"{path}: property before any element")
+            if w[1] == "list":
+                elements[-1][2].append(("list", w[2], w[3], w[4]))
+            else:
+                elements[-1][2].append((w[1], w[2]))
+        else:
+            raise ValueError(f"{path}: unknown header line {line!r}")
+    if fmt == "binary_big_endian":
+        raise ValueError(f"{path}: big-endian PLY files are not supported")
+    if fmt not in ("binary_little_endian", "ascii"):
+        raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+    for e in elements:
+        for p in e[2]:
+            if p[0] != "list" and p[0] not in _PLY_TYPES or p[0] == "list" and (p[1] not in _PLY_TYPES or p[2] not in _PLY_TYPES):
+                raise ValueError(f"{path}: unknown property type in {p}")
+    body = nl + 1
+    vertex = None
+    if fmt == "ascii":
+        lines = data[body:].decode("ascii", "replace").split("\n")
+        lines = [ln for ln in lines if ln.strip()]
+        at = 0
+        for name, count, props in elements:
+            if name == "vertex":
+                if any(p[0] == "list" for p in props):
+                    raise ValueError(f"{path}: list properties inside the vertex element are not supported")
+                if at + count > len(lines):
+                    raise ValueError(f"{path}: truncated body: {len(lines) - at} of {count} vertex lines")
+                try:
+                    tab = np.array([ln.split() for ln in lines[at:at + count]], dtype=np.float64).reshape(count, -1)
+                except ValueError:
+                    raise ValueError(f"{path}: a vertex line does not hold numbers, or the lines differ in length") from None
+                if tab.shape[1] != len(props) and count:
+                    raise ValueError(f"{path}: vertex lines hold {tab.shape[1]} values, the header declares {len(props)}")
+                vertex = {p[1]: tab[:, k].astype(_PLY_TYPES[p[0]]) for k, p in enumerate(props)}
+                break
+            at += count   # one line per entry of any other element, lists included
+        if vertex is None and any(e[0] == "vertex" for e in elements):
+            raise ValueError(f"{path}: truncated body")
+    else:
+        at = body
+        for name, count, props in elements:
+            if name == "vertex":
+                if any(p[0] == "list" for p in props):
+                    raise ValueError(f"{path}: list properties inside the vertex element are not supported")
+                dt = np.dtype([(p[1], "<" + _PLY_TYPES[p[0]]) for p in props])
+                if at + count * dt.itemsize > len(data):
+                    raise ValueError(f"{path}: truncated body: {len(data) - at} bytes for {count} vertices of {dt.itemsize} bytes")
+                rec = np.frombuffer(data, dt, count, at)
+                vertex = {p[1]: rec[p[1]] for p in props}
+                break
+            if any(p[0] == "list" for p in props):   # entries of varying size: walk them
+                for _ in range(count):
+                    for p in props:
+                        if p[0] == "list":
+                            cdt, idt = np.dtype("<" + _PLY_TYPES[p[1]]), np.dtype("<" + _PLY_TYPES[p[2]])
+                            if at + cdt.itemsize > len(data):
+                                raise ValueError(f"{path}: truncated body in element {name}")
+                            at += cdt.itemsize + int(np.frombuffer(data, cdt, 1, at)[0]) * idt.itemsize
+                        else:
+                            at += np.dtype(_PLY_TYPES[p[0]]).itemsize
+            else:
+                at += count * sum(np.dtype(_PLY_TYPES[p[0]]).itemsize for p in props)
+            if at > len(data):
+                raise ValueError(f"{path}: truncated body in element {name}")
+    if vertex is None:
+        raise ValueError(f"{path}: no vertex element")
+    if not all(k in vertex for k in "xyz"):
+        raise ValueError(f"{path}: the vertex element has no x y z")
+    out = {"xyz": np.stack([np.asarray(vertex[k], np.float32) for k in "xyz"], 1)}
+    if all(k in vertex for k in ("nx", "ny", "nz")):
+        out["normals"] = np.stack([np.asarray(vertex[k], np.float32) for k in ("nx", "ny", "nz")], 1)
+    if all(k in vertex for k in ("red", "green", "blue")):
+        out["colors"] = np.stack([np.asarray(vertex[k], np.uint8) for k in ("red", "green", "blue")], 1)
+    return out
+
+
+def _xyz(a):
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"need an [n, 3] array of points, got {a.shape}")
+    return a
+
+
+class Cloud:
+    """A target cloud in the HBM of one MI355X (mpmvs_cloud_create); a context manager around the handle."""
+
+    def __init__(self, xyz, device=0):
+        _, self._f = engine.load()
+        a = _xyz(xyz)
+        self.n = len(a)
+        self._h = None
+        h = C.c_void_p(None)
+        rc = self._f["cloud_create"](int(device), self.n, a.ctypes.data, C.byref(h))
+        if rc != 0:
+            self._raise("cloud_create", rc)
+        self._h = h
+
+    def _raise(self, what, rc):
+        msg = self._f["last_error"](None)
+        text = f"mpmvs_{what} failed ({rc}): " + (msg.decode() if msg else "")
+        raise (ValueError if rc in (-2, -3) else RuntimeError)(text)
+
+    def close(self):
+        if self._h:
+            self._f["cloud_destroy"](self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def nearest(self, q, radius, want_idx=True):
+        """(d2 float32 [n_q], idx int32 [n_q]) of mpmvs_cloud_nearest: the squared distance to, and the index of, the nearest
+        target within `radius` (inf / -1 where there is none); idx is None with want_idx=False"""
+        a = _xyz(q)
+        d2 = np.empty(len(a), np.float32)
+        idx = np.empty(len(a), np.int32) if want_idx else None
+        rc = self._f["cloud_nearest"](self._h, float(radius), len(a), a.ctypes.data, d2.ctypes.data, idx.ctypes.data if want_idx else None)
+        if rc != 0:
+            self._raise("cloud_nearest", rc)
+        return d2, idx
+
+    def stats(self):
+        """grid of the last call: {"finite", "cells", "fullest", "slots"}"""
+        s = (C.c_longlong * 4)()
+        self._f["cloud_stats"](self._h, s)
+        return dict(zip(("finite", "cells", "fullest", "slots"), (int(v) for v in s)))
+
+    def kernel_ms(self):
+        """(query ms, build ms) of the last call, device time; build ms is 0 when the grid was reused"""
+        b = C.c_float(0.0)
+        q = self._f["cloud_kernel_ms"](self._h, C.byref(b))
+        return float(q), float(b.value)
+
+
+def distances(query, target_cloud, tolerances, on_level=None):
+    """float32 [n]: per query point the exact distance to its nearest point of `target_cloud` (a Cloud) where that is within
+    max(tolerances), else inf.
+
+    Computed as a cascade: tolerances ascending, one nearest() call per tolerance with radius = tolerance, and only the queries
+    still unresolved go on to the next one.  A query whose nearest d2 <= r2 at one level is final, because any nearer point
+    would also be within that radius.  The grid's cells are thus about tolerance-sized at every level, so a fine tolerance never
+    scans the population of coarse cells.  on_level(tolerance, n_queries, cloud), if given, is called after every level."""
+    q = _xyz(query)
+    out = np.full(len(q), np.inf, np.float32)
+    left = np.arange(len(q))
+    for t in sorted(set(float(t) for t in tolerances)):
+        if len(left) == 0:
+            break
+        d2, _ = target_cloud.nearest(q[left], t, want_idx=False)
+        if on_level:
+            on_level(t, len(left), target_cloud)
+        hit = np.isfinite(d2)
+        out[left[hit]] = np.sqrt(d2[hit])
+        left = left[~hit]
+    return out
+
+
+def score(d_recon, d_gt, tolerances, dropped=(0, 0)):
+    """the metric arithmetic of evaluate() on precomputed nearest distances (inf = none within the largest tolerance):
+    d_recon per reconstruction point to the ground truth, d_gt per ground-truth point to the reconstruction"""
+    d_recon, d_gt = np.asarray(d_recon, np.float32), np.asarray(d_gt, np.float32)
+    res = {"n_reconstruction": int(d_recon.size), "n_ground_truth": int(d_gt.size),
+           "dropped_reconstruction": int(dropped[0]), "dropped_ground_truth": int(dropped[1]), "tolerances": []}
+    for t in tolerances:
+        t32 = np.float32(t)
+        na, nc = int((d_recon <= t32).sum()), int((d_gt <= t32).sum())   # inclusive
+        acc = na / d_recon.size if d_recon.size else 0.0
+        com = nc / d_gt.size if d_gt.size else 0.0
+        res["tolerances"].append({"tolerance": float(t), "accuracy": acc, "completeness": com,
+                                  "f1": 2 * acc * com / (acc + com) if acc + com > 0 else 0.0, "n_accurate": na, "n_complete": nc})
+    for name, d in (("reconstruction_to_ground_truth", d_recon), ("ground_truth_to_reconstruction", d_gt)):
+        r = d[np.isfinite(d)].astype(np.float64)
+        res[name] = {"resolved": int(r.size), "mean": float(r.mean()) if r.size else None, "median": float(np.median(r)) if r.size else None}
+    return res
+
+
+def drop_nonfinite(xyz):
+    """(the points with finite coordinates, the number dropped)"""
+    a = _xyz(xyz)
+    ok = np.isfinite(a).all(1)
+    return (a if ok.all() else a[ok]), int((~ok).sum())
+
+
+def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None):
+    """Accuracy, completeness and F1 of a reconstructed cloud against a ground-truth cloud at every tolerance.
+
+    Per tolerance t: accuracy = the share of reconstruction points whose nearest ground-truth point is within t (inclusive),
+    completeness = the share of ground-truth points whose nearest reconstruction point is within t, f1 = their harmonic mean
+    (0 if both are 0); also the counts, the two point totals and the mean and median of the resolved distances each way.
+    Points with a non-finite coordinate are dropped and counted.
+
+    This is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
+    voxelises and masks the space the scanner did not observe: the numbers here are comparable between our own builds and
+    settings, and not to the ETH3D leaderboard.  timings (a dict, optional) receives seconds of upload + build and of query."""
+    import time
+    rec, drop_r = drop_nonfinite(recon_xyz)
+    gt, drop_g = drop_nonfinite(gt_xyz)
+    tol = [float(t) for t in tolerances]
+    if not tol or not all(np.isfinite(t) and t > 0 for t in tol):
+        raise ValueError("tolerances must be finite and positive")
+    t_build = [0.0]
+
+    def on_level(t, n, cloud):
+        t_build[0] += cloud.kernel_ms()[1] * 1e-3
+
+    t0 = time.perf_counter()
+    with Cloud(gt, device) as c_gt:
+        t1 = time.perf_counter()
+        d_rec = distances(rec, c_gt, tol, on_level)
+    t2 = time.perf_counter()
+    with Cloud(rec, device) as c_rec:
+        t3 = time.perf_counter()
+        d_gt = distances(gt, c_rec, tol, on_level)
+    t4 = time.perf_counter()
+    if timings is not None:
+        timings["upload_build_s"] = (t1 - t0) + (t3 - t2) + t_build[0]
+        timings["query_s"] = (t2 - t1) + (t4 - t3) - t_build[0]
+    return score(d_rec, d_gt, tol, (drop_r, drop_g))

@@ -1,7 +1,8 @@
 // mpmvs_api.hip -- host side of the C ABI declared in include/mpmvs.h: context
 // and HBM residency management, uploads (upload_views for both image entries; its host half, the staging
 // plan and the row work, is pm_stage.hpp), the Run() launch schedule (reference src/PatchMatch.cu:1188-1254),
-// the stateless calls (DeviceCall: fusion, sky mask, view selection, undistortion) and the probes used by the parity tests.
+// the stateless calls (DeviceCall: fusion, sky mask, view selection, undistortion), the point-cloud search handle (mpmvs_cloud)
+// and the probes used by the parity tests.
 //
 // HBM layout per context:
 //   reference image   (W+40) x (H+40) fp32, replicated apron 20  (window radius <= 20)
@@ -37,6 +38,7 @@
 #include "pm_kernels.hpp"
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
+#include "pm_cloud.hpp"
 #include "pm_ingest.hpp"
 #include "pm_undistort.hpp"
 #include "pm_skyseg.hpp"
@@ -2894,6 +2896,270 @@ float mpmvs_skyseg_ms(const mpmvs_skyseg* n, float* pre_ms) {
     if (!n) return 0.0f;
     if (pre_ms) *pre_ms = n->pre_ms;
     return n->net_ms;
+}
+
+// ---------------------------------------------------------------------------
+// capped nearest neighbour between point clouds (pm_cloud.hpp).  Errors of these entry points are
+// reported through mpmvs_last_error(NULL), per host thread.
+// ---------------------------------------------------------------------------
+// one grid of a cloud: the table and the cell runs for one radius
+struct CloudGridBuf {
+    float radius = 0.0f;
+    unsigned long long* d_keys = nullptr;
+    int* d_off = nullptr;
+    uint4* d_pts = nullptr;
+    long long occupied = 0, fullest = 0;
+    unsigned long long last_use = 0;
+};
+constexpr size_t kCloudMaxGrids = 8;   // per handle; the least recently used one gives its buffers to a new radius
+
+struct mpmvs_cloud {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin / end, query begin / end
+    long long n = 0, n_fin = 0;
+    float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // finite bounding box
+    int slots_log2 = 0;
+    float* d_xyz = nullptr;
+    int *d_cnt = nullptr, *d_tsum = nullptr, *d_slot_of = nullptr, *d_st = nullptr;   // scratch of a build
+    std::vector<CloudGridBuf> grids;   // every grid has the same sizes: they depend on the finite count only
+    unsigned long long use_clock = 0;
+    long long stats[4] = {0, 0, 0, 0};
+    float query_ms = 0.0f, build_ms = 0.0f;
+};
+
+static void cloud_free_grid(CloudGridBuf& g) {
+    for (void* p : {(void*)g.d_keys, (void*)g.d_off, (void*)g.d_pts})
+        if (p) (void)pool_free(p);
+    g = CloudGridBuf();
+}
+
+static void cloud_release(mpmvs_cloud* c) {
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (CloudGridBuf& g : c->grids) cloud_free_grid(g);
+    for (void* p : {(void*)c->d_xyz, (void*)c->d_cnt, (void*)c->d_tsum, (void*)c->d_slot_of, (void*)c->d_st})
+        if (p) (void)pool_free(p);
+    for (hipEvent_t e : c->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+
+static int cloud_create_device(mpmvs_cloud* c, const float* xyz) {
+    SEGCHK(enter_device(c->device));
+    SEGCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : c->ev) SEGCHK(hipEventCreate(&e));
+    if (c->n_fin == 0) return 0;   // nothing to search: every call answers on the host
+    const size_t n = (size_t)c->n, slots = (size_t)1 << c->slots_log2;
+    SEGCHK(pool_malloc(&c->d_xyz, n * 12));
+    SEGCHK(pool_malloc(&c->d_slot_of, n * 4));
+    SEGCHK(pool_malloc(&c->d_cnt, slots * 4));
+    SEGCHK(pool_malloc(&c->d_tsum, slots / kScanBlock * 4));
+    SEGCHK(pool_malloc(&c->d_st, 8));
+    SEGCHK(hipMemcpyAsync(c->d_xyz, xyz, n * 12, hipMemcpyHostToDevice, c->stream));
+    SEGCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mpmvs_cloud_create(int device, long long n, const float* xyz, mpmvs_cloud** cloud) {
+    if (!cloud) return seg_fail(-2, "cloud: bad argument");
+    *cloud = nullptr;
+    if (n < 0 || (n > 0 && !xyz)) return seg_fail(-2, "cloud: bad argument");
+    if (n > INT32_MAX) return seg_fail(-3, "cloud: more than 2^31 - 1 points");
+    mpmvs_cloud* c = new mpmvs_cloud;
+    c->device = device;
+    c->n = n;
+    for (long long i = 0; i < n; ++i) {
+        const float* p = xyz + 3 * i;
+        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
+        for (int a = 0; a < 3; ++a) {
+            c->mn[a] = c->n_fin ? std::min(c->mn[a], p[a]) : p[a];
+            c->mx[a] = c->n_fin ? std::max(c->mx[a], p[a]) : p[a];
+        }
+        ++c->n_fin;
+    }
+    c->slots_log2 = cloud_slots_log2(c->n_fin);
+    if (c->slots_log2 > kCloudMaxSlotsLog2) {
+        delete c;
+        return seg_fail(-3, "cloud: more than 2^29 finite points (the table would exceed 2^30 slots)");
+    }
+    const int rc = cloud_create_device(c, xyz);
+    if (rc) {
+        cloud_release(c);
+        return rc;
+    }
+    *cloud = c;
+    return 0;
+}
+
+void mpmvs_cloud_destroy(mpmvs_cloud* c) {
+    if (!c) return;
+    (void)enter_device(c->device);
+    cloud_release(c);
+}
+
+// slot counts -> offsets (off[n] = the total): the library's scan plus the add pass
+static void cloud_scan(hipStream_t st, const int* cnt, int n, int* off, int* tsum) {
+    const int ntiles = (n + kScanBlock - 1) / kScanBlock;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, st, cnt, n, off, tsum);
+    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, tsum, ntiles, 0, off + n);
+    hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kScanBlock), 0, st, off, n, tsum);
+}
+
+// builds the grid of `radius` into g, whose buffers exist
+static int cloud_build(mpmvs_cloud* c, CloudGridBuf& g, float radius) {
+    const hipStream_t st = c->stream;
+    const size_t slots = (size_t)1 << c->slots_log2;
+    const int n = (int)c->n;
+    const double edge = cloud_edge(radius);
+    SEGCHK(hipMemsetAsync(g.d_keys, 0xff, slots * 8, st));
+    SEGCHK(hipMemsetAsync(c->d_cnt, 0, slots * 4, st));
+    SEGCHK(hipMemsetAsync(c->d_st, 0, 8, st));
+    SEGCHK(hipEventRecord(c->ev[0], st));
+    const dim3 gp((n + 255) / 256), gs((unsigned)(slots / 256));
+    hipLaunchKernelGGL(k_cloud_insert, gp, dim3(256), 0, st, c->d_xyz, n, (double)c->mn[0], (double)c->mn[1], (double)c->mn[2], edge, (unsigned)(slots - 1),
+                       g.d_keys, c->d_cnt, c->d_slot_of);
+    hipLaunchKernelGGL(k_cloud_stats, gs, dim3(256), 0, st, c->d_cnt, (unsigned)slots, c->d_st);
+    cloud_scan(st, c->d_cnt, (int)slots, g.d_off, c->d_tsum);
+    hipLaunchKernelGGL(k_cloud_scatter, gp, dim3(256), 0, st, c->d_xyz, n, c->d_slot_of, g.d_off, c->d_cnt, g.d_pts);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[1], st));
+    int h_st[2] = {0, 0};
+    SEGCHK(hipMemcpyAsync(h_st, c->d_st, 8, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    SEGCHK(hipEventElapsedTime(&c->build_ms, c->ev[0], c->ev[1]));
+    g.occupied = h_st[0], g.fullest = h_st[1];
+    g.radius = radius;
+    return 0;
+}
+
+// the grid of `radius`: a cached one (build_ms = 0), or a new one in fresh buffers or in those of the least recently used grid
+static int cloud_grid(mpmvs_cloud* c, float radius, CloudGridBuf** out) {
+    CloudGridBuf* g = nullptr;
+    for (CloudGridBuf& k : c->grids)
+        if (std::memcmp(&k.radius, &radius, 4) == 0) g = &k;
+    if (g) {
+        c->build_ms = 0.0f;
+    } else {
+        if (c->grids.size() < kCloudMaxGrids) {
+            const size_t slots = (size_t)1 << c->slots_log2;
+            CloudGridBuf fresh;
+            if (pool_malloc(&fresh.d_keys, slots * 8) != hipSuccess || pool_malloc(&fresh.d_off, (slots + 1) * 4) != hipSuccess ||
+                pool_malloc(&fresh.d_pts, (size_t)c->n_fin * 16) != hipSuccess) {
+                (void)hipGetLastError();
+                cloud_free_grid(fresh);
+                if (c->grids.empty()) return seg_fail(-100, "cloud: no device memory for the grid");
+            } else {
+                c->grids.push_back(fresh);
+                g = &c->grids.back();
+            }
+        }
+        if (!g) {
+            g = &c->grids[0];
+            for (CloudGridBuf& k : c->grids)
+                if (k.last_use < g->last_use) g = &k;
+        }
+        const int rc = cloud_build(c, *g, radius);
+        if (rc) {   // what the buffers hold is not a grid of any radius
+            (void)hipStreamSynchronize(c->stream);
+            cloud_free_grid(*g);
+            c->grids.erase(c->grids.begin() + (g - c->grids.data()));
+            return rc;
+        }
+    }
+    g->last_use = ++c->use_clock;
+    c->stats[0] = c->n_fin, c->stats[1] = g->occupied, c->stats[2] = g->fullest, c->stats[3] = 1ll << c->slots_log2;
+    *out = g;
+    return 0;
+}
+
+static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, int nq, const float* q_xyz, float* out_d2, int32_t* out_idx) {
+    const hipStream_t st = c->stream;
+    static const bool bin = [] {
+        const char* e = std::getenv("MPMVS_CLOUD_BIN");
+        return !(e && e[0] == '0');
+    }();
+    CloudGrid g;
+    for (int a = 0; a < 3; ++a) g.mn[a] = (double)c->mn[a];
+    g.edge = cloud_edge(radius);
+    g.r2 = radius * radius;
+    g.mask = (unsigned)(((size_t)1 << c->slots_log2) - 1);
+    g.keys = grid.d_keys, g.off = grid.d_off, g.pts = grid.d_pts;
+    int bins_log2 = 8;
+    while (bins_log2 < kCloudMaxSlotsLog2 && (1ll << bins_log2) < nq) ++bins_log2;
+    const size_t bins = (size_t)1 << bins_log2, q = (size_t)nq;
+    Scratch d_q(st), d_d2(st), d_idx(st), d_qbin(st), d_order(st), d_qcnt(st), d_qoff(st), d_qtsum(st);
+    SEGCHK(d_q.alloc(q * 12));
+    SEGCHK(d_d2.alloc(q * 4));
+    if (out_idx) SEGCHK(d_idx.alloc(q * 4));
+    if (bin) {
+        SEGCHK(d_qbin.alloc(q * 4));
+        SEGCHK(d_order.alloc(q * 4));
+        SEGCHK(d_qcnt.alloc(bins * 4));
+        SEGCHK(d_qoff.alloc((bins + 1) * 4));
+        SEGCHK(d_qtsum.alloc(bins / kScanBlock * 4));
+        SEGCHK(hipMemsetAsync(d_qcnt.p, 0, bins * 4, st));
+    }
+    SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, q * 12, hipMemcpyHostToDevice, st));
+    SEGCHK(hipEventRecord(c->ev[2], st));
+    const dim3 gq((nq + 255) / 256);
+    if (bin) {
+        hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q.as<float>(), nq, g, (unsigned)(bins - 1), d_qcnt.as<int>(), d_qbin.as<int>());
+        cloud_scan(st, d_qcnt.as<int>(), (int)bins, d_qoff.as<int>(), d_qtsum.as<int>());
+        hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, d_qbin.as<int>(), d_qoff.as<int>(), d_qcnt.as<int>(), d_order.as<int>());
+    }
+    hipLaunchKernelGGL(k_cloud_query, gq, dim3(256), 0, st, d_q.as<float>(), nq, bin ? d_order.as<int>() : (const int*)nullptr, g, d_d2.as<float>(),
+                       out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    SEGCHK(hipMemcpyAsync(out_d2, d_d2.p, q * 4, hipMemcpyDeviceToHost, st));
+    if (out_idx) SEGCHK(hipMemcpyAsync(out_idx, d_idx.p, q * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    SEGCHK(hipEventElapsedTime(&c->query_ms, c->ev[2], c->ev[3]));
+    return 0;
+}
+
+int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx) {
+    if (!c || !out_d2 || n_q < 0 || (n_q > 0 && !q_xyz)) return seg_fail(-2, "cloud: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud: the radius must be finite and positive");
+    if (n_q > INT32_MAX) return seg_fail(-3, "cloud: more than 2^31 - 1 queries");
+    if (n_q == 0) return 0;
+    if (c->n_fin == 0) {   // no candidate anywhere
+        for (long long i = 0; i < n_q; ++i) {
+            out_d2[i] = INFINITY;
+            if (out_idx) out_idx[i] = -1;
+        }
+        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
+        c->query_ms = c->build_ms = 0.0f;
+        return 0;
+    }
+    const double edge = cloud_edge(radius);
+    for (int a = 0; a < 3; ++a) {
+        const double cells = std::floor(((double)c->mx[a] - (double)c->mn[a]) / edge) + 1.0;
+        if (cells > (double)kCloudAxisCells) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "cloud: the targets span %.6g cells of edge %.6g along %c, more than 2^21 (extent / radius = %.6g)", cells, edge,
+                          "xyz"[a], ((double)c->mx[a] - (double)c->mn[a]) / (double)radius);
+            return seg_fail(-3, msg);
+        }
+    }
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    const int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    return cloud_query(c, *grid, radius, (int)n_q, q_xyz, out_d2, out_idx);
+}
+
+int mpmvs_cloud_stats(const mpmvs_cloud* c, long long stats[4]) {
+    if (!c || !stats) return seg_fail(-2, "cloud: bad argument");
+    std::memcpy(stats, c->stats, sizeof c->stats);
+    return 0;
+}
+
+float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) {
+    if (!c) return 0.0f;
+    if (build_ms) *build_ms = c->build_ms;
+    return c->query_ms;
 }
 
 }  // extern "C"

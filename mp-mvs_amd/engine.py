@@ -59,6 +59,12 @@ _EXTRA = {
     "undistort_u8": (C.c_int, [C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
     "undistort_kernel_ms": (C.c_float, []),
     "eval_ncc_multi": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_float)]),
+    # point clouds (cloud.py)
+    "cloud_create": (C.c_int, [C.c_int, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
+    "cloud_nearest": (C.c_int, [_P, C.c_float, C.c_longlong, _P, _P, _P]),
+    "cloud_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "cloud_kernel_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "cloud_destroy": (None, [_P]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx"]
 

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Accuracy, completeness and F1 of a fused cloud against a ground-truth scan at a list of distance tolerances, on the GPU
+(mp-mvs_amd/cloud.py: evaluate).
+
+    python tools/eval_ply.py --reconstruction MPMVS_model.ply --ground_truth scan.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5]
+                             [--transform T.txt] [--crop xmin,ymin,zmin,xmax,ymax,zmax] [--device 0]
+
+--transform: a 4 x 4 text matrix that takes the reconstruction into the ground truth's frame; applied in fp64 and rounded to
+fp32.  --crop: an axis-aligned box (in the ground truth's frame, after the transform) applied to both clouds.
+This is the plain two-way nearest-neighbour measure (Tanks-and-Temples style); ETH3D's official program additionally voxelises
+and masks unobserved space, so the numbers compare our own builds and settings, not leaderboard entries.
+Prints one JSON line: the dictionary of evaluate() plus seconds per stage (read, upload + build, query)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: F401,E402
+
+cloud = importlib.import_module("mp-mvs_amd.cloud")
+
+
+def apply_transform(xyz, T):
+    T = np.asarray(T, np.float64)
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError(f"--transform needs a finite 4 x 4 matrix, got shape {T.shape}")
+    p = xyz.astype(np.float64)
+    h = p @ T[:3, :3].T + T[:3, 3]
+    w = p @ T[3, :3] + T[3, 3]
+    return (h / w[:, None]).astype(np.float32)
+
+
+def crop(xyz, box):
+    lo, hi = np.asarray(box[:3], np.float32), np.asarray(box[3:], np.float32)
+    with np.errstate(invalid="ignore"):
+        keep = ((xyz >= lo) & (xyz <= hi)).all(1) | ~np.isfinite(xyz).all(1)   # non-finite points stay, to be counted by evaluate
+    return xyz[keep]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--reconstruction", required=True)
+    ap.add_argument("--ground_truth", required=True)
+    ap.add_argument("--tolerances", default="0.01,0.02,0.05,0.1,0.2,0.5")
+    ap.add_argument("--transform")
+    ap.add_argument("--crop")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args()
+    tol = [float(t) for t in args.tolerances.split(",") if t.strip()]
+    t0 = time.perf_counter()
+    rec = cloud.read_ply(args.reconstruction)["xyz"]
+    gt = cloud.read_ply(args.ground_truth)["xyz"]
+    if args.transform:
+        rec = apply_transform(rec, np.loadtxt(args.transform))
+    if args.crop:
+        box = [float(v) for v in args.crop.split(",")]
+        if len(box) != 6:
+            raise SystemExit("--crop needs xmin,ymin,zmin,xmax,ymax,zmax")
+        rec, gt = crop(rec, box), crop(gt, box)
+    t1 = time.perf_counter()
+    timings = {}
+    res = cloud.evaluate(rec, gt, tol, device=args.device, timings=timings)
+    res["seconds"] = {"read": round(t1 - t0, 4), "upload_build": round(timings["upload_build_s"], 4), "query": round(timings["query_s"], 4)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
