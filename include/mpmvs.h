@@ -449,6 +449,41 @@ int mpmvs_cloud_stats(const mpmvs_cloud* cloud, long long stats[4]);
 float mpmvs_cloud_kernel_ms(const mpmvs_cloud* cloud, float* build_ms);
 void mpmvs_cloud_destroy(mpmvs_cloud* cloud);
 
+/* ---- point clouds: z-buffer render into cameras (mp-mvs_amd/cloud.py, tools/eval_depth.py) --- */
+/* The per-view ground-truth depth map of a scan: the handle's cloud rendered into n_views pinhole cameras with a visibility test,
+ * so that the back of the scene does not shine through the gaps between front points.
+ * DEFINED BY EQUIVALENCE with the plain-loop statement, bit for bit and independent of scheduling.  For view v with camera c
+ * (K, R, t row-major, W = c.width, H = c.height; depth_min / depth_max unused) and point i = (p0, p1, p2), everything in fp32, no
+ * contraction, correctly rounded quotients (project_depth of mp-mvs_amd/csrc/pm_fusion.hpp):
+ *   t0 = ((R0*p0 + R1*p1) + R2*p2) + t[0], t1 and t2 alike;  z = (K6*t0 + K7*t1) + K8*t2;
+ *   u = ((K0*t0 + K1*t1) + K2*t2) / z;  v = ((K3*t0 + K4*t1) + K5*t2) / z;  fu = u + 0.5f, fv = v + 0.5f (pixel centres at integers).
+ *   The point is IN VIEW iff its three coordinates are finite, z is finite and z > 0, fu >= 0, fu < (float)W, fv >= 0 and
+ *   fv < (float)H (a comparison with a NaN is false); then px = (int)fu, py = (int)fv.
+ *   Zc[y][x] = the smallest z of the in-view points with (px, py) = (x, y); +inf if there is none.
+ *   Z1[y][x] = the smallest Zc[y'][x'] over |x' - x| <= splat, |y' - y| <= splat inside the image.
+ *   m = 1.0f + occl_rel.
+ *   depth[y][x] = Zc[y][x] if it is finite and Zc[y][x] <= Z1[y][x] * m (an fp32 product), else 0.0f ("no depth").
+ *   idx[y][x] = the smallest i among the in-view points of that pixel whose z has the bits of Zc[y][x] where depth != 0, else -1.
+ * In point terms: a point is hidden if some point whose pixel lies within Chebyshev distance splat of its own is nearer by more
+ * than the factor m; the nearest visible point of a pixel wins, and if the nearest point of a pixel is hidden so are all its others.
+ * splat = 0 is the plain z-buffer.  THE SLOPE RULE: a slanted surface hides itself once occl_rel is below splat x the relative
+ * change of depth per pixel along the surface; raise occl_rel with splat on steep or close scenes.  The defaults of the Python
+ * layer (splat 1, occl_rel 0.02) are starting values from the synthetic scene only.
+ * Host buffers in and out: out_depth[v] holds H*W floats, out_idx (NULL, or NULL entries: not wanted) H*W int32.  Blocks until done.
+ * n_views == 0 returns 0 and touches nothing; a cloud without a finite point gives all 0.0f / -1 without touching the device.
+ * Views may differ in size; any n_views is served, a few views per launch.  The handle's search grids are not touched.
+ * Errors (text through the last-error call with a NULL context): -2 = a NULL cloud, n_views < 0, splat outside
+ * [0, MPMVS_RENDER_MAX_SPLAT], occl_rel not finite or < 0 (these four are checked first, also for n_views == 0), NULL cams or
+ * out_depth, a NULL out_depth[v], a non-positive width or height; -3 = a width or height above 2^24, a view of more than
+ * 2^31 - 1 pixels; -100 = HIP failure.  All but -100 are found before the device is touched. */
+#define MPMVS_RENDER_MAX_SPLAT 8
+int mpmvs_cloud_render_depth(mpmvs_cloud* cloud, int n_views, const mpmvs_camera* cams, int splat, float occl_rel, float* const* out_depth,
+                             int32_t* const* out_idx /* NULL, or NULL entries: not wanted */);
+/* device ms (HIP events) of the last render call's kernels, all chunks of views added up */
+float mpmvs_cloud_render_ms(const mpmvs_cloud* cloud);
+/* the same per pass: ms[0] z-min, ms[1] index (0 when no index map was wanted), ms[2] resolve */
+int mpmvs_cloud_render_pass_ms(const mpmvs_cloud* cloud, float ms[3]);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

@@ -1,5 +1,6 @@
-"""Point clouds: reading PLY files, the exact capped nearest-neighbour search on the GPU (mpmvs_cloud_*, csrc/pm_cloud.hpp)
-and the accuracy / completeness / F1 score of a fused cloud against a ground-truth scan.
+"""Point clouds: reading PLY files, the exact capped nearest-neighbour search on the GPU (mpmvs_cloud_*, csrc/pm_cloud.hpp),
+the accuracy / completeness / F1 score of a fused cloud against a ground-truth scan and the z-buffer
+render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
 voxelises both clouds and masks the space the scanner did not observe, so the numbers here are comparable between our own
@@ -8,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import engine
+from . import _abi, engine
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
@@ -177,6 +178,34 @@ class Cloud:
         b = C.c_float(0.0)
         q = self._f["cloud_kernel_ms"](self._h, C.byref(b))
         return float(q), float(b.value)
+
+    def render_depth(self, cams, splat=1, occl_rel=0.02, want_idx=False):
+        """mpmvs_cloud_render_depth: the cloud rendered into every camera of `cams` (_abi.Camera; width and height give the map's
+        size) -> a list of float32 [H, W] depth maps along the camera's z axis, 0 = no depth; with want_idx=True
+        (depths, idxs), idxs a list of int32 [H, W] maps of the point each pixel shows (-1 = none).
+
+        Per pixel the nearest point that lands in it (pixel centres at integers) stays unless a point within `splat` pixels
+        (Chebyshev) is nearer by more than the factor 1 + occl_rel: the back of the scene does not shine through the gaps
+        between front points.  splat=0 is the plain z-buffer.  The slope rule: a slanted surface hides itself once occl_rel is
+        below splat x the relative change of depth per pixel; raise occl_rel with splat on steep or close scenes.  The defaults
+        are starting values from the synthetic scene, not tuned on a real scan."""
+        cams = list(cams)
+        n = len(cams)
+        arr = (_abi.Camera * max(n, 1))(*cams)
+        depths = [np.empty((max(int(c.height), 0), max(int(c.width), 0)), np.float32) for c in cams]
+        idxs = [np.empty(d.shape, np.int32) for d in depths] if want_idx else None
+        dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in depths])
+        ip = (C.c_void_p * max(n, 1))(*[i.ctypes.data for i in idxs]) if want_idx else None
+        rc = self._f["cloud_render_depth"](self._h, n, arr, int(splat), float(occl_rel), dp, ip)
+        if rc != 0:
+            self._raise("cloud_render_depth", rc)
+        return (depths, idxs) if want_idx else depths
+
+    def render_ms(self):
+        """device ms of the last render_depth call's kernels: (total, {"zmin", "index", "resolve"})"""
+        ms = (C.c_float * 3)()
+        self._f["cloud_render_pass_ms"](self._h, ms)
+        return float(self._f["cloud_render_ms"](self._h)), {"zmin": float(ms[0]), "index": float(ms[1]), "resolve": float(ms[2])}
 
 
 def distances(query, target_cloud, tolerances, on_level=None):

@@ -39,6 +39,7 @@
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
 #include "pm_cloud.hpp"
+#include "pm_render.hpp"
 #include "pm_ingest.hpp"
 #include "pm_undistort.hpp"
 #include "pm_skyseg.hpp"
@@ -2916,7 +2917,7 @@ constexpr size_t kCloudMaxGrids = 8;   // per handle; the least recently used on
 struct mpmvs_cloud {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin / end, query begin / end
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin / end, query begin / end; a render: the borders of its three passes
     long long n = 0, n_fin = 0;
     float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // finite bounding box
     int slots_log2 = 0;
@@ -2926,6 +2927,7 @@ struct mpmvs_cloud {
     unsigned long long use_clock = 0;
     long long stats[4] = {0, 0, 0, 0};
     float query_ms = 0.0f, build_ms = 0.0f;
+    float render_pass_ms[3] = {0.0f, 0.0f, 0.0f};   // z-min, index, resolve of the last render call
 };
 
 static void cloud_free_grid(CloudGridBuf& g) {
@@ -3160,6 +3162,121 @@ float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) {
     if (!c) return 0.0f;
     if (build_ms) *build_ms = c->build_ms;
     return c->query_ms;
+}
+
+// ---------------------------------------------------------------------------
+// z-buffer render of the handle's cloud into cameras (pm_render.hpp).  The handle's grids are not touched.
+// ---------------------------------------------------------------------------
+static_assert(kRenderMaxSplat == MPMVS_RENDER_MAX_SPLAT, "splat bound");
+constexpr size_t kRenderChunkPixels = (size_t)1 << 27;   // a chunk of views ends before its buffers pass this many pixels (one view always fits)
+
+// views [v0, v1) in one launch of each point pass
+static int cloud_render_chunk(mpmvs_cloud* c, int v0, int v1, const mpmvs_camera* cams, int splat, float m, float* const* out_depth, int32_t* const* out_idx) {
+    const hipStream_t st = c->stream;
+    size_t total = 0;
+    bool any_idx = false;
+    for (int v = v0; v < v1; ++v) {
+        total += (size_t)cams[v].width * (size_t)cams[v].height;
+        any_idx = any_idx || (out_idx && out_idx[v]);
+    }
+    Scratch d_zc(st), d_depth(st), d_idx(st);
+    SEGCHK(d_zc.alloc(total * 4));
+    SEGCHK(d_depth.alloc(total * 4));
+    if (any_idx) SEGCHK(d_idx.alloc(total * 4));
+    RenderChunkArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.n = v1 - v0;
+    size_t at = 0;
+    for (int v = v0; v < v1; ++v) {
+        RenderView& V = A.v[v - v0];
+        cam_to_dev(cams[v], V.cam);
+        V.w = cams[v].width, V.h = cams[v].height;
+        V.zc = d_zc.as<uint32_t>() + at;
+        V.idx = (out_idx && out_idx[v]) ? d_idx.as<uint32_t>() + at : nullptr;
+        at += (size_t)V.w * (size_t)V.h;
+    }
+    SEGCHK(hipMemsetD32Async((hipDeviceptr_t)d_zc.p, (int)kRenderInfBits, total, st));
+    if (any_idx) SEGCHK(hipMemsetAsync(d_idx.p, 0xff, total * 4, st));
+    const int n = (int)c->n;
+    const dim3 gp((n + 255) / 256);
+    SEGCHK(hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(k_render_zmin, gp, dim3(256), 0, st, c->d_xyz, n, A);
+    SEGCHK(hipEventRecord(c->ev[1], st));
+    if (any_idx) hipLaunchKernelGGL(k_render_index, gp, dim3(256), 0, st, c->d_xyz, n, A);
+    SEGCHK(hipEventRecord(c->ev[2], st));
+    at = 0;
+    for (int k = 0; k < A.n; ++k) {
+        const RenderView& V = A.v[k];
+        const size_t npix = (size_t)V.w * (size_t)V.h;
+        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, V.zc, V.w, V.h, splat, m, d_depth.as<float>() + at, V.idx);
+        at += npix;
+    }
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    at = 0;
+    for (int k = 0; k < A.n; ++k) {
+        const RenderView& V = A.v[k];
+        const size_t npix = (size_t)V.w * (size_t)V.h;
+        SEGCHK(hipMemcpyAsync(out_depth[v0 + k], d_depth.as<float>() + at, npix * 4, hipMemcpyDeviceToHost, st));
+        if (V.idx) SEGCHK(hipMemcpyAsync(out_idx[v0 + k], V.idx, npix * 4, hipMemcpyDeviceToHost, st));
+        at += npix;
+    }
+    SEGCHK(hipStreamSynchronize(st));
+    for (int p = 0; p < 3; ++p) {
+        if (p == 1 && !any_idx) continue;   // no index pass: the gap between two event records is not its time
+        float ms = 0.0f;
+        SEGCHK(hipEventElapsedTime(&ms, c->ev[p], c->ev[p + 1]));
+        c->render_pass_ms[p] += ms;
+    }
+    return 0;
+}
+
+int mpmvs_cloud_render_depth(mpmvs_cloud* c, int n_views, const mpmvs_camera* cams, int splat, float occl_rel, float* const* out_depth, int32_t* const* out_idx) {
+    if (!c || n_views < 0) return seg_fail(-2, "cloud render: bad argument");
+    if (splat < 0 || splat > MPMVS_RENDER_MAX_SPLAT) return seg_fail(-2, "cloud render: splat must lie in [0, " + std::to_string(MPMVS_RENDER_MAX_SPLAT) + "]");
+    if (!std::isfinite(occl_rel) || !(occl_rel >= 0.0f)) return seg_fail(-2, "cloud render: occl_rel must be finite and not negative");
+    if (n_views == 0) return 0;
+    if (!cams || !out_depth) return seg_fail(-2, "cloud render: bad argument");
+    for (int v = 0; v < n_views; ++v) {
+        if (!out_depth[v]) return seg_fail(-2, "cloud render: view " + std::to_string(v) + " has no depth buffer");
+        if (cams[v].width <= 0 || cams[v].height <= 0) return seg_fail(-2, "cloud render: view " + std::to_string(v) + " has a non-positive width or height");
+    }
+    for (int v = 0; v < n_views; ++v) {
+        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return seg_fail(-3, "cloud render: view " + std::to_string(v) + " is wider or higher than 2^24");
+        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
+            return seg_fail(-3, "cloud render: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
+    }
+    c->render_pass_ms[0] = c->render_pass_ms[1] = c->render_pass_ms[2] = 0.0f;
+    if (c->n_fin == 0) {   // nothing lands anywhere
+        for (int v = 0; v < n_views; ++v) {
+            const size_t npix = (size_t)cams[v].width * (size_t)cams[v].height;
+            std::fill(out_depth[v], out_depth[v] + npix, 0.0f);
+            if (out_idx && out_idx[v]) std::fill(out_idx[v], out_idx[v] + npix, (int32_t)-1);
+        }
+        return 0;
+    }
+    SEGCHK(enter_device(c->device));
+    const float m = 1.0f + occl_rel;
+    for (int v0 = 0; v0 < n_views;) {
+        int v1 = v0 + 1;
+        size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
+        while (v1 < n_views && v1 - v0 < kRenderChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kRenderChunkPixels) {
+            pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
+            ++v1;
+        }
+        const int rc = cloud_render_chunk(c, v0, v1, cams, splat, m, out_depth, out_idx);
+        if (rc) return rc;
+        v0 = v1;
+    }
+    return 0;
+}
+
+float mpmvs_cloud_render_ms(const mpmvs_cloud* c) { return c ? (c->render_pass_ms[0] + c->render_pass_ms[1]) + c->render_pass_ms[2] : 0.0f; }
+
+int mpmvs_cloud_render_pass_ms(const mpmvs_cloud* c, float ms[3]) {
+    if (!c || !ms) return seg_fail(-2, "cloud render: bad argument");
+    std::memcpy(ms, c->render_pass_ms, sizeof c->render_pass_ms);
+    return 0;
 }
 
 }  // extern "C"
