@@ -296,6 +296,31 @@ long long mpmvs_fuse_ply_ctx(int device, int n, const mpmvs_camera* cams, const 
                              int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
                              int use_dynamic_consistency, unsigned char** records, unsigned char* const* out_masks);
 
+/* Tracks: which pixels of which images each fused point was averaged from.
+ * A point is produced by pixel t (raster index r * W_i + c) of image i, whose view list is src_ids[src_off[i] ..) with slot 0 =
+ * i itself.  Its TRACK is the sequence (i, t), followed in ascending slot order j = 1 .. num_ngb - 1 by (src_ids[j], q_j) for
+ * every slot whose source pixel q_j passed the consistency test against t in the evaluation that produced the point; q_j is the
+ * raster index sr * W_s + sc in source image s = src_ids[j], at THAT image's own width (the images of a call may differ in size).
+ *  - The track has num + 1 entries, the divisor of the point's averages: at least 2 with MPMVS_FUSE_DYNAMIC_CONSISTENCY, 3 without.
+ *  - Snapshot formulation: the entries after the first are exactly the pixels the point marks in out_masks.
+ *  - MPMVS_FUSE_REFERENCE_ORDER: the entries are the pixel's own consistent source pixels in the final fixpoint pass, not the
+ *    carried used_list entries, which only mask: there the marks are a superset of the tracks.
+ *  - DEFINING PROPERTY: the track alone reproduces the point bit for bit.  With X(s, q) the back-projection of pixel q of image s
+ *    at its depth (x = q % W_s, y = q / W_s;  ((depth * (x - K[2])) / K[0], (depth * (y - K[5])) / K[4], depth) rotated by R^T
+ *    and moved by C, fp32, as the fusion computes it), the position is ((X(i, t) + X(s_1, q_1)) + ...) / (float)length in fp32, in
+ *    track order; normal and colour are the same sums of normals[s][q] and colors[s][q] over the same divisor.
+ * mpmvs_fuse_ply_tracks is mpmvs_fuse_ply_ctx -- same arguments, flags, errors and records; ctxs may be NULL, which is
+ * mpmvs_fuse_ply -- and returns the tracks as CSR in the PLY's point order: *track_off has count + 1 entries, track_off[0] = 0,
+ * and point p owns entries track_off[p] .. track_off[p + 1) of *track_image (image index) and *track_pixel (raster index), which
+ * have track_off[count] entries each.  All four buffers are released with mpmvs_free; on failure none is allocated.  A NULL
+ * track_* pointer is -2; a view whose pixels x list length exceeds 2^31 - 1 is -3.  Device memory for the tracks is bounded by
+ * the largest view (pixels x list length), not by the dataset: every image's tracks go to the host before the next is fused. */
+long long mpmvs_fuse_ply_tracks(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs,
+                                const float* const* depths, const float* const* normals, const unsigned char* const* colors,
+                                int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
+                                int use_dynamic_consistency, unsigned char** records, long long** track_off, int32_t** track_image,
+                                int32_t** track_pixel, unsigned char* const* out_masks);
+
 /* device time (ms, HIP events) of the kernels of the last mpmvs_fuse / mpmvs_fuse_ply call */
 float mpmvs_fuse_kernel_ms(void);
 /* fixpoint passes of the last MPMVS_FUSE_REFERENCE_ORDER call: sum over the images and the largest count of one image */

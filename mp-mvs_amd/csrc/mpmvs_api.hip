@@ -45,6 +45,7 @@
 #include "pm_skyseg.hpp"
 #include "pm_skyseg_model.hpp"
 #include "pm_stage.hpp"
+#include "pm_tracks_host.hpp"
 
 using namespace pm;
 
@@ -1977,10 +1978,12 @@ void mpmvs_fuse_passes(int* total, int* max_per_image) {
 // Run() leaves in cudaPlaneHypotheses and the reference copies out (ref .cu:1246) and writes to depths.dmb / normals.dmb
 // (src/PatchMatch.cpp:610-633) for RunFusion to read back (:334-336).  For such an image nothing is uploaded: the planes are split
 // into the fusion's depth and normal arrays device to device (k_split_planes), or GPU to GPU when the context lives on another device.
+// tracks (nullable, with `records` only): receives per fused point the (image, pixel) pairs that were averaged (pm_fusion.hpp,
+// "Tracks").  The device holds one image's tracks at a time; they leave for the host at the image boundary.
 static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths, const float* const* normals,
                      const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
                      int flags, unsigned char* const* out_valid, float* const* out_points9, unsigned char* const* out_masks,
-                     unsigned char** records, long long* n_records) {
+                     unsigned char** records, long long* n_records, TrackSink* tracks = nullptr) {
     const int use_dynamic = flags & MPMVS_FUSE_DYNAMIC_CONSISTENCY;
     const bool exact = (flags & MPMVS_FUSE_REFERENCE_ORDER) != 0;
     g_fuse_passes_total = g_fuse_passes_max = 0;
@@ -2002,6 +2005,9 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
                 if (src_ids[k2] == src_ids[k]) return -2;
         }
     }
+    // a track's entries are addressed with int offsets inside one image
+    for (int i = 0; i < n && tracks; ++i)
+        if (estimate[i] && (long long)cams[i].width * cams[i].height * (src_off[i + 1] - src_off[i]) > 0x7fffffffLL) return -3;
     if (!call.ok()) return -100;
     const hipStream_t st = call.stream();
     std::vector<FuseView> hv(n);
@@ -2109,8 +2115,24 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     int* d_carry = nullptr;
     int* d_diff = nullptr;
     const size_t max_chunks = (max_wh + 255) / 256;
+    // tracks: one more row of consq for the slot bits; lengths, their in-tile scan and tile totals; one image's offsets and entries
+    int *d_len = nullptr, *d_excl = nullptr, *d_tiles = nullptr, *d_ent_image = nullptr, *d_ent_pixel = nullptr;
+    long long *d_ebase = nullptr, *d_point_off = nullptr;
+    if (!rc && tracks) {
+        d_consq = call.alloc<int>((size_t)max_ngb * max_wh * 4);
+        d_len = call.alloc<int>(max_wh * 4);
+        d_excl = call.alloc<int>(max_wh * 4);
+        d_tiles = call.alloc<int>(sizeof(int) * (max_blocks + 1));
+        d_ent_image = call.alloc<int>((size_t)max_ngb * max_wh * 4);
+        d_ent_pixel = call.alloc<int>((size_t)max_ngb * max_wh * 4);
+        d_point_off = call.alloc<long long>(max_wh * 8);
+        d_ebase = call.alloc<long long>(sizeof(long long));
+        if (!d_consq || !d_len || !d_excl || !d_tiles || !d_ent_image || !d_ent_pixel || !d_point_off || !d_ebase ||
+            hipMemsetAsync(d_ebase, 0, sizeof(long long), st) != hipSuccess)
+            rc = -100;
+    }
     if (!rc && exact) {
-        d_consq = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_wh * 4);
+        if (!tracks) d_consq = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_wh * 4);
         d_carry = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_chunks * 4);
         d_diff = call.alloc<int>(4);
         if (!d_consq || !d_carry || !d_diff) rc = -100;
@@ -2123,7 +2145,10 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
         const dim3 grid((hv[i].w + 31) / 32, (hv[i].h + 7) / 8);
         if (records && hipMemsetAsync(d_valid[i], 0, (size_t)hv[i].w * hv[i].h, st) != hipSuccess) { rc = -100; break; }
         if (!exact) {
-            hipLaunchKernelGGL(k_fuse<false>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], (int*)nullptr);
+            if (tracks)
+                hipLaunchKernelGGL((k_fuse<false, true>), grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
+            else
+                hipLaunchKernelGGL(k_fuse<false>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], (int*)nullptr);
             if (hipGetLastError() != hipSuccess) { rc = -100; break; }
             // the marks of image i become the masks the next image sees
             for (int j = 1; j < num_ngb; ++j) {
@@ -2145,7 +2170,10 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
                     const int s = src_ids[b + j], ns = hv[s].w * hv[s].h;
                     hipLaunchKernelGGL(k_fuse_tau_init, dim3((ns + 255) / 256), dim3(256), 0, st, d_mask[s], ns, hv[s].tau_new);
                 }
-                hipLaunchKernelGGL(k_fuse<true>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
+                if (tracks)
+                    hipLaunchKernelGGL((k_fuse<true, true>), grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
+                else
+                    hipLaunchKernelGGL(k_fuse<true>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
                 if (num_ngb > 1) {
                     hipLaunchKernelGGL(k_fuse_carry_local, dim3(nchunks, num_ngb - 1), dim3(256), 0, st, d_consq, npix, nchunks, d_carry);
                     hipLaunchKernelGGL(k_scan_totals<LastValid>, dim3(num_ngb - 1), dim3(256), 0, st, d_carry, nchunks, -1, (int*)nullptr);
@@ -2182,6 +2210,28 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
             hipLaunchKernelGGL(k_fuse_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_out[i], wh, d_blocks, d_base, d_records);
             hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, d_base, d_blocks + nb);
             if (hipGetLastError() != hipSuccess) rc = -100;
+            if (tracks && !rc) {
+                hipLaunchKernelGGL(k_fuse_track_len, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq + (size_t)(num_ngb - 1) * wh, wh, d_len);
+                hipLaunchKernelGGL(k_scan_tiles, dim3(nb), dim3(256), 0, st, d_len, wh, d_excl, d_tiles);
+                hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, d_tiles, nb, 0, d_tiles + nb);
+                hipLaunchKernelGGL(k_fuse_track_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq, wh, i, d_src + b, num_ngb, d_blocks, d_tiles, d_excl,
+                                   d_ebase, d_point_off, d_ent_image, d_ent_pixel);
+                hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, d_ebase, d_tiles + nb);
+                // the image's tracks leave before the next image reuses the buffers: its two counts first, then what they size
+                int got[2] = {0, 0};
+                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&got[0], d_blocks + nb, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipMemcpyAsync(&got[1], d_tiles + nb, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+                    rc = -100;
+                if (!rc && (got[0] < 0 || got[0] > wh || got[1] < got[0] || (long long)got[1] > (long long)wh * num_ngb)) rc = -100;
+                if (!rc && !tracks->reserve((size_t)got[0], (size_t)got[1])) rc = -101;
+                if (!rc && got[0] > 0 &&
+                    (hipMemcpyAsync(tracks->off_tail(), d_point_off, (size_t)got[0] * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                     hipMemcpyAsync(tracks->image_tail(), d_ent_image, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                     hipMemcpyAsync(tracks->pixel_tail(), d_ent_pixel, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                     hipStreamSynchronize(st) != hipSuccess))
+                    rc = -100;
+                if (!rc && !tracks->commit((size_t)got[0], (size_t)got[1])) rc = -100;
+            }
         }
     }
     (void)call.end();
@@ -2203,6 +2253,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
             if (!host) rc = -101;
         }
         if (!rc && count > 0 && hipMemcpyAsync(host, d_records, (size_t)count * kPlyRecord, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
+        if (!rc && tracks && (long long)tracks->points() != count) rc = -100;
         if (rc) {
             std::free(host);
         } else {
@@ -2250,6 +2301,30 @@ long long mpmvs_fuse_ply_ctx(int device, int n, const mpmvs_camera* cams, const 
     const int rc = fuse_impl(device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr,
                              out_masks, records, &count);
     return rc ? rc : count;
+}
+
+// mpmvs_fuse_ply_ctx that also returns every point's track (include/mpmvs.h); ctxs may be NULL
+long long mpmvs_fuse_ply_tracks(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths,
+                                const float* const* normals, const unsigned char* const* colors, int color_channels, const unsigned char* const* sky,
+                                const int* src_off, const int* src_ids, int use_dynamic, unsigned char** records, long long** track_off,
+                                int32_t** track_image, int32_t** track_pixel, unsigned char* const* out_masks) {
+    if (!records) return -1;
+    if (!track_off || !track_image || !track_pixel) return -2;
+    long long count = 0;
+    unsigned char* rec = nullptr;
+    TrackSink sink;
+    const int rc = fuse_impl(device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr,
+                             out_masks, &rec, &count, &sink);
+    if (rc) {
+        std::free(rec);   // nothing is handed over on failure
+        return rc;
+    }
+    if (!sink.finish(track_off, track_image, track_pixel)) {
+        std::free(rec);
+        return -101;
+    }
+    *records = rec;
+    return count;
 }
 
 void mpmvs_free(void* p) { std::free(p); }

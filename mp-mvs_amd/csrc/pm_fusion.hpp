@@ -86,8 +86,12 @@ PM_DEV void load_color(const FuseView& V, size_t idx, float& c0, float& c1, floa
 }
 
 // EXACT: consq[(j - 1) * N + t] receives, for every pixel t of the image and source slot j, the source pixel that was
-// consistent with t (or -1); out_valid is written for every pixel (0 / 1)
-template <bool EXACT>
+// consistent with t (or -1); out_valid is written for every pixel (0 / 1).
+// TRACKS (include/mpmvs.h, "tracks"): an accepted pixel also leaves which slots entered its averages -- one u32, bit j - 1 for
+// slot j, in row num_ngb - 1 of consq (the row after the last slot's) -- and, in the snapshot formulation, the source pixel
+// of each such slot in consq as EXACT writes it.  Rows of slots without a bit, and everything at pixels that are not
+// accepted, are not defined in the snapshot formulation; nothing reads them.  consq then has num_ngb rows.
+template <bool EXACT, bool TRACKS = false>
 __global__ __launch_bounds__(256) void k_fuse(const FuseView* __restrict__ views, int i, const int* __restrict__ src_ids, int num_ngb,
                                               int use_dynamic, unsigned char* __restrict__ out_valid, float* __restrict__ out9,
                                               int* __restrict__ consq) {
@@ -116,6 +120,7 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseView* __restrict__ views
     load_color(R, pix, sc0, sc1, sc2);
     int num = 0;
     float dyn = 0.0f;
+    unsigned bits = 0;  // TRACKS: the slots that entered the sums
     int used[kMaxFuseNgb];
     for (int j = 0; j < num_ngb; ++j) used[j] = -1;
     for (int j = 1; j < num_ngb; ++j) {
@@ -147,6 +152,7 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseView* __restrict__ views
         if (angle < 0.174533f) {
             used[j] = (int)sidx;
             if (EXACT) consq[(size_t)(j - 1) * npix + pix] = (int)sidx;
+            if (TRACKS) bits |= 1u << (j - 1);
             sp0 += T0;
             sp1 += T1;
             sp2 += T2;
@@ -180,6 +186,12 @@ __global__ __launch_bounds__(256) void k_fuse(const FuseView* __restrict__ views
     if (!EXACT)
         for (int j = 1; j < num_ngb; ++j)
             if (used[j] != -1) views[src_ids[j]].mask_next[used[j]] = 1;  // idempotent
+    if (TRACKS) {
+        if (!EXACT)
+            for (int j = 1; j < num_ngb; ++j)
+                if (used[j] != -1) consq[(size_t)(j - 1) * npix + pix] = used[j];
+        consq[(size_t)(num_ngb - 1) * npix + pix] = (int)bits;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -269,5 +281,44 @@ __global__ __launch_bounds__(kScanBlock) void k_fuse_scatter(const unsigned char
 
 // *base += count of the image just scattered (block_counts[nb] from k_scan_totals)
 __global__ void k_fuse_advance(long long* __restrict__ base, const int* __restrict__ image_count) { *base += *image_count; }
+
+// ---------------------------------------------------------------------------
+// Tracks: per fused point the (image, pixel) pairs that were averaged, as CSR in the PLY's point order.  Per image: the
+// length of every pixel's track (0 where there is no point) -> k_scan_tiles -> k_scan_totals<Sum> -> k_fuse_track_scatter,
+// which writes into buffers of ONE image's size: the point's offset at the point's rank within the image (the rank of
+// k_fuse_scatter), its entries at tile offset + exclusive.  The host takes both before the next image reuses the buffers;
+// *entry_base, advanced by k_fuse_advance, makes the offsets absolute.  consq is the scratch k_fuse<., true> wrote and, in
+// reference order, k_fuse_carry_local scanned in place: an entry of the pixel's own survives an inclusive LastValid scan,
+// so the bits select exactly the entries of the evaluation that produced the point.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fuse_track_len(const unsigned char* __restrict__ valid, const int* __restrict__ bits, int n,
+                                                        int* __restrict__ len) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n) len[t] = valid[t] ? __popc((unsigned)bits[t]) + 1 : 0;
+}
+
+__global__ __launch_bounds__(kScanBlock) void k_fuse_track_scatter(const unsigned char* __restrict__ valid, const int* __restrict__ consq, int n, int image,
+                                                                   const int* __restrict__ src_ids, int num_ngb,
+                                                                   const int* __restrict__ block_offsets, const int* __restrict__ tile_offsets,
+                                                                   const int* __restrict__ excl, const long long* __restrict__ entry_base,
+                                                                   long long* __restrict__ point_off, int* __restrict__ ent_image,
+                                                                   int* __restrict__ ent_pixel) {
+    const int t = blockIdx.x * kScanBlock + threadIdx.x;
+    const int v = (t < n && valid[t]) ? 1 : 0;
+    int total;
+    const int rank = block_excl_scan<Sum>(v, 0, total);
+    if (!v) return;
+    int e = tile_offsets[blockIdx.x] + excl[t];
+    point_off[block_offsets[blockIdx.x] + rank] = *entry_base + e;
+    ent_image[e] = image;
+    ent_pixel[e] = t;
+    const unsigned bits = (unsigned)consq[(size_t)(num_ngb - 1) * n + t];
+    for (int j = 1; j < num_ngb; ++j)
+        if (bits >> (j - 1) & 1u) {
+            ++e;
+            ent_image[e] = src_ids[j];
+            ent_pixel[e] = consq[(size_t)(j - 1) * n + t];
+        }
+}
 
 }  // namespace pm

@@ -69,7 +69,7 @@ _EXTRA = {
     "cloud_render_ms": (C.c_float, [_P]),
     "cloud_render_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
 }
-ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx"]
+ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 
 _cache = {}
 

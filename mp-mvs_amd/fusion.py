@@ -140,6 +140,87 @@ def fuse_ply(cams, estimate, depths, normals, colors, sources, use_dynamic=True,
     return out["records"], masks
 
 
+def fuse_ply_tracks(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, ctxs=None):
+    """mpmvs_fuse_ply_tracks: fuse_ply that also returns every point's track (include/mpmvs.h) as CSR in the point order of the
+    records: (records [M, 27] uint8, track_off [M + 1] int64, track_image [E] int32, track_pixel [E] int32, masks list).  Point p was
+    averaged from pixels track_pixel[track_off[p]:track_off[p + 1]] (raster index, at each image's own width) of images
+    track_image[...]; the first entry is the pixel that produced it.  ctxs as in fuse_ply (None: host arrays only)."""
+    from . import engine
+    lib, _ = engine.load()
+    fn = lib.mpmvs_fuse_ply_tracks
+    fn.argtypes = [C.c_int] + FUSE_ARGTYPES_TAIL[:3] + [C.POINTER(C.c_void_p)] + FUSE_ARGTYPES_TAIL[3:-3] + [
+        C.POINTER(C.POINTER(C.c_ubyte)), C.POINTER(C.POINTER(C.c_longlong)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int32)), _PP_U8]
+    fn.restype = C.c_longlong
+    lib.mpmvs_free.argtypes = [C.c_void_p]
+    lib.mpmvs_free.restype = None
+    out = {}
+
+    def call(*args):
+        # args from call_fuse: (device, n, cams, estimate, [ctxs,] depths, ..., dyn, valid, points9, masks); the entry always takes ctxs
+        head = args[:-3] if ctxs is not None else args[:4] + (None,) + args[4:-3]
+        rec, off = C.POINTER(C.c_ubyte)(), C.POINTER(C.c_longlong)()
+        img, pix = C.POINTER(C.c_int32)(), C.POINTER(C.c_int32)()
+        count = fn(*head, C.byref(rec), C.byref(off), C.byref(img), C.byref(pix), args[-1])
+        if count < 0:
+            return int(count)
+        out["records"] = np.ctypeslib.as_array(rec, shape=(count, 27)).copy() if count else np.zeros((0, 27), np.uint8)
+        out["off"] = np.ctypeslib.as_array(off, shape=(count + 1,)).astype(np.int64)
+        entries = int(out["off"][-1])
+        out["image"] = np.ctypeslib.as_array(img, shape=(entries,)).copy() if entries else np.zeros(0, np.int32)
+        out["pixel"] = np.ctypeslib.as_array(pix, shape=(entries,)).copy() if entries else np.zeros(0, np.int32)
+        for p in (rec, off, img, pix):
+            lib.mpmvs_free(p)
+        return 0
+
+    _, _, masks = call_fuse(call, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs)
+    return out["records"], out["off"], out["image"], out["pixel"], masks
+
+
+def write_vis(path, track_off, track_image, image_ids=None):
+    """COLMAP's point-visibility file (fused.ply.vis, read by its Delaunay mesher beside fused.ply), little endian: uint64 number of
+    points, then per point uint32 k and k x uint32 image index -- here the images of the point's track, in track order.
+    image_ids (optional): image_ids[our index] is the number written; default the index itself."""
+    off = np.asarray(track_off, np.int64)
+    img = np.asarray(track_image, np.int64)
+    if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(img) or (np.diff(off) < 0).any():
+        raise ValueError("track_off must be non-decreasing offsets from 0 to len(track_image)")
+    if image_ids is not None:
+        img = np.asarray(image_ids, np.int64)[img]
+    if len(img) and (img.min() < 0 or img.max() > 0xffffffff):
+        raise ValueError("image indices must fit uint32")
+    n = len(off) - 1
+    body = np.empty(n + len(img), "<u4")
+    at = off[:-1] + np.arange(n)                      # where each point's count goes
+    body[at] = np.diff(off)
+    keep = np.ones(len(body), bool)
+    keep[at] = False
+    body[keep] = img
+    with open(path, "wb") as f:
+        f.write(np.uint64(n).astype("<u8").tobytes())
+        f.write(body.tobytes())
+
+
+def read_vis(path):
+    """the file write_vis writes -> (track_off [M + 1] int64, image indices [E] int32 as stored)"""
+    raw = open(path, "rb").read()
+    if len(raw) < 8 or (len(raw) - 8) % 4:
+        raise ValueError("not a point-visibility file")
+    n = int(np.frombuffer(raw, "<u8", 1)[0])
+    body = np.frombuffer(raw, "<u4", offset=8).astype(np.int64)
+    off = np.zeros(n + 1, np.int64)
+    at = 0
+    for p in range(n):                                # the counts are only reachable one after the other
+        if at >= len(body):
+            raise ValueError("truncated point-visibility file")
+        off[p + 1] = off[p] + body[at]
+        at += 1 + int(body[at])
+    if at != len(body):
+        raise ValueError("point-visibility file has the wrong length")
+    keep = np.ones(len(body), bool)
+    keep[off[:-1] + np.arange(n)] = False
+    return off, body[keep].astype(np.int32)
+
+
 def last_kernel_ms():
     from . import engine
     lib, _ = engine.load()

@@ -458,7 +458,7 @@ int RunFolderJacobi(const std::string& input_folder, int max_src, int max_image_
     for (int i : todo) Scenes[i].device_depth = Scenes[i].device_depth_next = Scene::DeviceDepth();
     for (const auto& b : exchange_buffers) mpmvs_device_free(b.first, b.second);
     // the final maps are still in the Problems' contexts (Release() left them with the Scenes): fuse them from there
-    if (fuse) fuse->points = RunFusion(input_folder, out, Scenes, fuse->use_dynamic_consistency, fuse->device, fuse->sky_seg, true);
+    if (fuse) fuse->points = RunFusion(input_folder, out, Scenes, fuse->use_dynamic_consistency, fuse->device, fuse->sky_seg, true, fuse->write_vis);
     if (in_memory) {
         in_memory->assign(n, ProblemResult());
         for (int i : todo) {
@@ -671,8 +671,26 @@ static bool fuse_reference_order() {
     return e && std::string(e) == "reference";
 }
 
+// COLMAP's point-visibility file (little endian: uint64 number of points, per point uint32 k and k x uint32 image id) from the
+// tracks of mpmvs_fuse_ply_tracks; the id written for image index i is Scenes[i].refID, the number pair.txt gives the image
+static bool write_vis_file(const std::string& path, long long count, const long long* off, const int32_t* image, const std::vector<Scene>& Scenes) {
+    FILE* out = fopen(path.c_str(), "wb");
+    if (!out) return false;
+    auto put32 = [&](uint32_t v) {
+        const unsigned char b[4] = {(unsigned char)v, (unsigned char)(v >> 8), (unsigned char)(v >> 16), (unsigned char)(v >> 24)};
+        return fwrite(b, 1, 4, out) == 4;
+    };
+    const uint64_t n = (uint64_t)count;
+    bool ok = put32((uint32_t)n) && put32((uint32_t)(n >> 32));
+    for (long long p = 0; p < count && ok; ++p) {
+        ok = put32((uint32_t)(off[p + 1] - off[p]));
+        for (long long e = off[p]; e < off[p + 1] && ok; ++e) ok = put32((uint32_t)Scenes[(size_t)image[e]].refID);
+    }
+    return (fclose(out) == 0) && ok;
+}
+
 long RunFusion(const std::string& input_folder, const std::string& output_folder, std::vector<Scene>& Scenes, bool use_dynamic_consistency, int device,
-               bool sky_seg, bool resident) {
+               bool sky_seg, bool resident, bool write_vis) {
     const int n = (int)Scenes.size();
     std::vector<Camera> cams(n);
     std::vector<int> estimate(n, 0), src_off(1, 0), src_ids;
@@ -743,7 +761,12 @@ long RunFusion(const std::string& input_folder, const std::string& output_folder
     // reference's PointCloud vector): only they cross PCIe
     unsigned char* records = nullptr;
     const int fuse_flags = (use_dynamic_consistency ? MPMVS_FUSE_DYNAMIC_CONSISTENCY : 0) | (fuse_reference_order() ? MPMVS_FUSE_REFERENCE_ORDER : 0);
-    const long long count = resident ? mpmvs_fuse_ply_ctx(device, n, cams.data(), estimate.data(), ctxs.data(), dp.data(), np_.data(), gp.data(), 3,
+    long long* track_off = nullptr;
+    int32_t *track_image = nullptr, *track_pixel = nullptr;
+    const long long count = write_vis ? mpmvs_fuse_ply_tracks(device, n, cams.data(), estimate.data(), resident ? ctxs.data() : nullptr, dp.data(), np_.data(),
+                                                              gp.data(), 3, sky_seg ? sp.data() : nullptr, src_off.data(), src_ids.data(), fuse_flags, &records,
+                                                              &track_off, &track_image, &track_pixel, nullptr)
+                            : resident ? mpmvs_fuse_ply_ctx(device, n, cams.data(), estimate.data(), ctxs.data(), dp.data(), np_.data(), gp.data(), 3,
                                                           sky_seg ? sp.data() : nullptr, src_off.data(), src_ids.data(), fuse_flags, &records, nullptr)
                                       : mpmvs_fuse_ply(device, n, cams.data(), estimate.data(), dp.data(), np_.data(), gp.data(), 3, sky_seg ? sp.data() : nullptr,
                                                        src_off.data(), src_ids.data(), fuse_flags, &records, nullptr);
@@ -754,12 +777,21 @@ long RunFusion(const std::string& input_folder, const std::string& output_folder
     if (!out) {
         std::cout << "Error opening file " << ply << std::endl;
         mpmvs_free(records);
+        mpmvs_free(track_off);
+        mpmvs_free(track_image);
+        mpmvs_free(track_pixel);
         return -1;
     }
     WritePlyHeader(out, (size_t)count);
-    const bool ok = fwrite(records, 27, (size_t)count, out) == (size_t)count;
+    bool ok = fwrite(records, 27, (size_t)count, out) == (size_t)count;
     fclose(out);
     mpmvs_free(records);
+    if (write_vis) {
+        ok = ok && write_vis_file(ply + ".vis", count, track_off, track_image, Scenes);
+        mpmvs_free(track_off);
+        mpmvs_free(track_image);
+        mpmvs_free(track_pixel);
+    }
     return ok ? (long)count : -1;
 }
 
@@ -840,6 +872,13 @@ long mpmvs_host_fuse_folder(const char* input_folder, int device, int max_src, i
     GenerateSampleList(input_folder, max_src, 3200, Scenes);  // RunFusion does not use the image-size limit
     const std::string in = input_folder;
     return RunFusion(in, in + "/MPMVS", Scenes, use_dynamic_consistency != 0, device, sky_seg != 0);
+}
+// the same, and with write_vis != 0 the points' visibility beside the PLY: <folder>/MPMVS/MPMVS_model.ply.vis (scene_io.h)
+long mpmvs_host_fuse_folder_vis(const char* input_folder, int device, int max_src, int use_dynamic_consistency, int sky_seg, int write_vis) {
+    std::vector<Scene> Scenes;
+    GenerateSampleList(input_folder, max_src, 3200, Scenes);
+    const std::string in = input_folder;
+    return RunFusion(in, in + "/MPMVS", Scenes, use_dynamic_consistency != 0, device, sky_seg != 0, false, write_vis != 0);
 }
 int mpmvs_host_refine_sky_masks(const char* input_folder, int device, int max_src, int max_image_size) {
     std::vector<Scene> Scenes;

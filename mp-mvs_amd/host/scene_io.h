@@ -27,8 +27,11 @@ void StoreColorPlyFileBinaryPointCloud(const std::string& plyFilePath, const std
 // resident = true (no counterpart in the reference, whose passes hand over through files): the maps are Scenes[i].depth / .normal as the
 // pass schedule left them in memory, and where a Problem's context still holds them in HBM (ResidentResultContext) they are fused from
 // there without an upload (mpmvs_fuse_ply_ctx); cameras, colour images and sky masks are read as before.  Same PLY, byte for byte.
+// write_vis = true: the fusion also returns every point's track (mpmvs_fuse_ply_tracks) and <output>/MPMVS_model.ply.vis is written
+// beside the same PLY -- COLMAP's point-visibility file: uint64 number of points, per point uint32 k and k x uint32 image id, little
+// endian, the images of the point's track in track order, numbered as pair.txt numbers them (Scene::refID).
 long RunFusion(const std::string& input_folder, const std::string& output_folder, std::vector<Scene>& Scenes, bool use_dynamic_consistency, int device = 0,
-               bool sky_seg = false, bool resident = false);
+               bool sky_seg = false, bool resident = false, bool write_vis = false);
 // cv::imread(path, IMREAD_GRAYSCALE) + convertTo(CV_32F) (reference src/PatchMatch.cpp:877-882): JPEG (own decoder,
 // jpeg_decode.h), binary PGM (P5) or PPM (P6, converted with OpenCV's fixed-point BGR2GRAY weights); format by content
 bool readGrayImage(const std::string& path, Image& img);
@@ -88,6 +91,7 @@ int GenerateSkyRegionMask(const std::string& input_folder, const std::vector<Sce
 struct FuseAtEnd {
     bool use_dynamic_consistency = true;
     bool sky_seg = false;
+    bool write_vis = false;   // also write MPMVS_model.ply.vis (RunFusion)
     int device = 0;
     long points = -1;   // out: number of fused points (-1: fusion failed)
 };

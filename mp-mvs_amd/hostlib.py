@@ -15,7 +15,7 @@ SYMBOLS = ["mpmvs_host_triangulate_vertices", "mpmvs_host_delaunay", "mpmvs_host
            "mpmvs_host_run_folder", "mpmvs_host_resize_linear", "mpmvs_host_write_ply", "mpmvs_host_fuse_folder", "mpmvs_host_read_image",
            "mpmvs_host_decode_jpeg", "mpmvs_host_refine_sky_masks", "mpmvs_host_run_folder_jacobi", "mpmvs_host_prior_from_triangles", "mpmvs_host_run_folder_jacobi_fused",
            "mpmvs_host_generate_sky_masks", "mpmvs_host_sky_preprocess", "mpmvs_host_pyrdown8", "mpmvs_host_undistort_u8", "mpmvs_host_undistort_atan",
-           "mpmvs_host_undistort_forward", "mpmvs_host_undistort_inverse", "mpmvs_host_undistort_threads"]
+           "mpmvs_host_undistort_forward", "mpmvs_host_undistort_inverse", "mpmvs_host_undistort_threads", "mpmvs_host_fuse_folder_vis"]
 _cache = {}
 
 
@@ -55,6 +55,8 @@ def load():
                                                            C.c_int, C.c_int, C.c_int]
         lib.mpmvs_host_fuse_folder.restype = C.c_long
         lib.mpmvs_host_fuse_folder.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.mpmvs_host_fuse_folder_vis.restype = C.c_long
+        lib.mpmvs_host_fuse_folder_vis.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.mpmvs_host_refine_sky_masks.restype = C.c_int
         lib.mpmvs_host_refine_sky_masks.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int]
         lib.mpmvs_host_read_image.restype = C.c_int
@@ -426,9 +428,13 @@ def undistort_inverse(model_id, params, xy):
     return _undistort_points(load().mpmvs_host_undistort_inverse, model_id, params, xy)
 
 
-def fuse_folder(folder, device=0, max_src=20, use_dynamic=True, sky_seg=False):
-    """RunFusion over a processed dataset folder -> <folder>/MPMVS/MPMVS_model.ply; returns the point count"""
-    n = load().mpmvs_host_fuse_folder(str(folder).encode(), device, max_src, 1 if use_dynamic else 0, 1 if sky_seg else 0)
+def fuse_folder(folder, device=0, max_src=20, use_dynamic=True, sky_seg=False, write_vis=False):
+    """RunFusion over a processed dataset folder -> <folder>/MPMVS/MPMVS_model.ply; returns the point count.
+    write_vis: also <folder>/MPMVS/MPMVS_model.ply.vis, per point the images of its track (COLMAP's point-visibility format; ids as in pair.txt)"""
+    if write_vis:
+        n = load().mpmvs_host_fuse_folder_vis(str(folder).encode(), device, max_src, 1 if use_dynamic else 0, 1 if sky_seg else 0, 1)
+    else:
+        n = load().mpmvs_host_fuse_folder(str(folder).encode(), device, max_src, 1 if use_dynamic else 0, 1 if sky_seg else 0)
     if n < 0:
         raise RuntimeError("fuse_folder failed")
     return int(n)
