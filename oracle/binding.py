@@ -104,6 +104,44 @@ def eval_geom_literal(handle, params, planes_cam):
     return out
 
 
+def rng_table(seed, launch, npix, n):
+    """the first n uniforms of the streams (seed, pixel, launch) for pixel = 0 .. npix - 1, as an [npix][n] table, in one call"""
+    import numpy as np
+    l, _ = lib()
+    l.orc_rng_table.restype = C.c_int
+    l.orc_rng_table.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    out = np.empty((int(npix), int(n)), np.float32)
+    if l.orc_rng_table(int(seed), int(launch), int(npix), int(n), out.ctypes.data) != 0:
+        raise RuntimeError("orc_rng_table failed")
+    return out
+
+
+def homography_literal(handle, plane, v):
+    """ComputeHomography in the reference's literal operation order (the handle's literal mode; IEEE in canonical mode)"""
+    import numpy as np
+    l, _ = lib()
+    l.orc_homography_literal.restype = C.c_int
+    l.orc_homography_literal.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    p, out = np.ascontiguousarray(plane, np.float32).reshape(4), np.empty(9, np.float32)
+    if l.orc_homography_literal(handle._ctx, p.ctypes.data, int(v), out.ctypes.data) != 0:
+        raise RuntimeError("orc_homography_literal failed")
+    return out.reshape(3, 3)
+
+
+def eval_initial(handle, params, planes_cam, scale):
+    """ComputeMultiViewInitialCostandSelectedViews of per-pixel camera-frame planes in the handle's literal mode: (costs, selected views)"""
+    import numpy as np
+    l, _ = lib()
+    l.orc_eval_initial.restype = C.c_int
+    l.orc_eval_initial.argtypes = [C.c_void_p, C.POINTER(_abi.PatchMatchParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    p = np.ascontiguousarray(planes_cam, np.float32)
+    costs, sel = np.empty((handle.H, handle.W), np.float32), np.empty((handle.H, handle.W), np.uint32)
+    rc = l.orc_eval_initial(handle._ctx, C.byref(params), p.ctypes.data, int(scale), costs.ctypes.data, sel.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"orc_eval_initial failed ({rc})")
+    return costs, sel
+
+
 def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, sequential_literal=False, sky=None, reference_order=False):
     """oracle fusion: mode 0 = the snapshot formulation (the GPU's default), mode 1 = the reference's literal sequential
     order with libm (measurement only), mode 2 (reference_order) = the sequential order in the canonical arithmetic = what

@@ -5,10 +5,10 @@
 // "ref .cu:LINES").  Only tests/, __graft_entry__.smoke() and bench.py's
 // cpu_baseline leg may load this library; the product (mp-mvs_amd/) never does.
 //
-// PARITY UNPINNED: the reference ships no tests, golden vectors or fixtures
-//  and cannot be built in this image (nvcc, CUDA runtime,
-// cuRAND and OpenCV are absent; writing stand-ins for them is not allowed), so
-// nothing pins this restatement to reference outputs.  It follows the
+// PINNED THROUGH ITS LITERAL MODES: the reference ships no tests, golden vectors or fixtures and
+// its binary cannot be built in this image, but its device code compiles for the host against the stand-ins of
+// oracle/ref_shim/ (oracle/ref_driver.cpp), and the literal modes below equal it bit for bit, per function and per
+// launch (tests/test_reference_cpu.py).  The canonical mode follows the
 // reference's algorithm, including its bug-level quirks, under
 // the "canonical arithmetic" of DESIGN.md section 3: IEEE fp32 with explicit
 // fmaf, no libm transcendentals (own exp/sin/cos/acos/reciprocal, specified
@@ -1266,26 +1266,31 @@ int run(Ctx& c, const Params& prm, uint64_t seed) {
 // (tests/test_oracle_cpu.py::test_canonical_vs_literal_arithmetic); nothing else uses it.
 // ---------------------------------------------------------------------------
 float literal_tex(const Image& im, float x, float y, int quantize) {
-    // tex2D(t, x + 0.5, y + 0.5), linear filter, clamp addressing
-    const float xb = x, yb = y;
+    // tex2D(t, x + 0.5f, y + 0.5f), linear filter, clamp addressing.  The texture unit sees the fp32-ROUNDED sum x + 0.5f and
+    // subtracts 0.5 from that (CUDA C++ Programming Guide, "Texture Fetching": xB = x - 0.5), so the rounding of the sum is part
+    // of the reference's arithmetic (ref .cu:375-377): for |x| >= 1 the sum drops the last bit(s) of x.  Pinned bit for bit
+    // against the reference's own code compiled for the host (tests/test_reference_cpu.py).
+    const float xb = (x + 0.5f) - 0.5f, yb = (y + 0.5f) - 0.5f;
     const float fx = floorf(xb), fy = floorf(yb);
     float ax = xb - fx, ay = yb - fy;
     if (quantize) {
         ax = floorf(ax * 256.0f + 0.5f) / 256.0f;
         ay = floorf(ay * 256.0f + 0.5f) / 256.0f;
     }
-    const int ix = (int)fx, iy = (int)fy;
+    // coordinates far outside the image (a tap behind the plane's horizon) clamp like any other; NaN reads the first texel
+    auto index = [](float f, int size) { return !(f >= -1.0f) ? -1 : (f > (float)size ? size : (int)f); };
+    const int ix = index(fx, im.w), iy = index(fy, im.h);
     const float t00 = im.at(ix, iy), t10 = im.at(ix + 1, iy), t01 = im.at(ix, iy + 1), t11 = im.at(ix + 1, iy + 1);
     return (1.0f - ax) * (1.0f - ay) * t00 + ax * (1.0f - ay) * t10 + (1.0f - ax) * ay * t01 + ax * ay * t11;
 }
 
 // lm: 1 IEEE + libm; 2 the same with 8-bit texture fractions; 3 the fast-math model (m_div / m_exp, fused multiply-adds where
 // nvcc contracts a * b + c, 8-bit fractions); 4 = 3 without the 8-bit fractions
-float literal_ncc(const Ctx& c, const Params& prm, int px, int py, const F4& pl, int v, int scale, int lm) {
+// ComputeHomography (ref .cu:228-279) in the reference's operation order
+void literal_homography(const Ctx& c, const F4& pl, int v, int lm, float Hm[9]) {
     const Camera& rc = c.cams[0];
     const Camera& sc = c.cams[v + 1];
     const bool fast = lm >= 3;
-    const int quantize = lm == 2 || lm == 3;
     auto mad = [&](float a, float b, float acc) { return fast ? fmaf(a, b, acc) : acc + a * b; };
     // R_rel = R_s R_r^T, t_rel = R_s (C_r - C_s)
     float Rr[9], tr[3], Cd[3];
@@ -1293,7 +1298,7 @@ float literal_ncc(const Ctx& c, const Params& prm, int px, int py, const F4& pl,
         for (int j = 0; j < 3; ++j) Rr[i * 3 + j] = mad(sc.R[i * 3 + 2], rc.R[j * 3 + 2], mad(sc.R[i * 3 + 1], rc.R[j * 3 + 1], sc.R[i * 3] * rc.R[j * 3]));
     for (int k = 0; k < 3; ++k) Cd[k] = rc.C[k] - sc.C[k];
     for (int i = 0; i < 3; ++i) tr[i] = mad(sc.R[i * 3 + 2], Cd[2], mad(sc.R[i * 3 + 1], Cd[1], sc.R[i * 3] * Cd[0]));
-    float Hm[9], T[9];
+    float T[9];
     const float n3[3] = {pl.x, pl.y, pl.z};
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) Hm[i * 3 + j] = Rr[i * 3 + j] - m_div(lm, tr[i] * n3[j], pl.w);
@@ -1307,6 +1312,15 @@ float literal_ncc(const Ctx& c, const Params& prm, int px, int py, const F4& pl,
         Hm[3 + j] = mad(sc.K[5], T[6 + j], sc.K[4] * T[3 + j]);
         Hm[6 + j] = sc.K[8] * T[6 + j];
     }
+}
+
+float literal_ncc(const Ctx& c, const Params& prm, int px, int py, const F4& pl, int v, int scale, int lm) {
+    const Camera& sc = c.cams[v + 1];
+    const bool fast = lm >= 3;
+    const int quantize = lm == 2 || lm == 3;
+    auto mad = [&](float a, float b, float acc) { return fast ? fmaf(a, b, acc) : acc + a * b; };
+    float Hm[9];
+    literal_homography(c, pl, v, lm, Hm);
     auto warp = [&](int x, int y, float& u, float& w) {
         const float fx = (float)x, fy = (float)y;
         const float a = mad(Hm[1], fy, Hm[0] * fx) + Hm[2], b = mad(Hm[4], fy, Hm[3] * fx) + Hm[5], z = mad(Hm[7], fy, Hm[6] * fx) + Hm[8];
@@ -1566,6 +1580,38 @@ int orc_homography(orc_ctx* h, const float* plane4, int v, float* H9) {
     plane_to_m(c, pl, m);
     for (int r = 0; r < 3; ++r)
         for (int k = 0; k < 3; ++k) H9[r * 3 + k] = fmaf(-c.vc[v].b[r], m[k], c.vc[v].A[r * 3 + k]);
+    return 0;
+}
+// the same in the reference's literal operation order (literal_homography; IEEE when the context is in canonical mode)
+int orc_homography_literal(orc_ctx* h, const float* plane4, int v, float* H9) {
+    Ctx& c = h->c;
+    if (v < 0 || v >= (int)c.vc.size()) return -1;
+    literal_homography(c, F4{plane4[0], plane4[1], plane4[2], plane4[3]}, v, c.literal_mode ? c.literal_mode : 1, H9);
+    return 0;
+}
+// ComputeMultiViewInitialCostandSelectedViews (ref .cu:497-534) of per-pixel camera-frame planes in the context's literal mode;
+// costs and selected views are [H][W]
+int orc_eval_initial(orc_ctx* h, const void* params, const float* planes_cam4, int scale, float* costs, uint32_t* sel) {
+    Ctx& c = h->c;
+    const Params& prm = *(const Params*)params;
+    const int rc = check_ready(c, prm);
+    if (rc) return rc;
+#pragma omp parallel for schedule(dynamic, 2)
+    for (int y = 0; y < c.H; ++y)
+        for (int x = 0; x < c.W; ++x) {
+            const size_t idx = (size_t)y * c.W + x;
+            RefWin rw;
+            ref_window(c, prm, x, y, scale, rw);
+            costs[idx] = initial_cost(c, prm, rw, x, y, ((const F4*)planes_cam4)[idx], sel[idx]);
+        }
+    return 0;
+}
+// RNG table: the first n uniforms of the streams (seed, pix, launch) for pix = 0 .. npix - 1; out is [npix][n]
+int orc_rng_table(uint64_t seed, uint32_t launch, uint32_t npix, int n, float* out) {
+    for (uint32_t p = 0; p < npix; ++p) {
+        Rng g = rng_make(seed, p, launch);
+        for (int i = 0; i < n; ++i) out[(size_t)p * n + i] = rng_uniform(g);
+    }
     return 0;
 }
 // statistics hook (see g_stat_death): buffers of H*W*5 int8 and H*W uint32, or NULL to switch it off

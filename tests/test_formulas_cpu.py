@@ -6,9 +6,11 @@ oracle/pm_oracle.cpp or the HIP kernels.  The oracle (canonical mode, and its li
 fp32 accuracy on random evaluations of every kind the kernels meet: planes from the true surface to random, three window scales,
 windows that hang over the source border, out-of-view centres, flat windows.
 
-The reference holds no golden vectors for this path and cannot be built here, so this does not pin the oracle to
-the reference's OUTPUTS ("parity unpinned" stands); it pins it to the reference's published FORMULAS by a second, differently written
-evaluation of them."""
+This pins the oracle to the reference's published FORMULAS by a second, differently written evaluation of them; the reference's own
+device code, compiled for the host, pins the literal modes bit for bit (tests/test_reference_cpu.py).  It states the formulas and not the
+sampler's coordinate rounding: `u` goes straight into the bilinear fetch, whereas the reference's call rounds `u + 0.5f` to fp32 before
+the texture unit subtracts the 0.5 again (the literal modes reproduce that since the pinning; the canonical mode omits it by design).  The
+tolerances below are unchanged by that."""
 import numpy as np
 import pytest
 
