@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_prior_cells(const float* __restrict__ c
                 }
             }
         const float scaled = (float)((double)(sum / (float)(y1 * x1)) * 0.85);
-        const float limit = scaled > 0.2f ? scaled : 0.2f;
+        const float limit = scaled < 0.2f ? 0.2f : scaled;  // std::max(scaled, 0.2f) of ref :842: a NaN sum stays NaN, no vertex passes
         while (n < 3 && low[n] < limit) ++n;
     }
     cell_cnt[cell] = n;

@@ -11,8 +11,13 @@
 // triangulation is not unique and cv::Subdiv2D's choice, as well as its triangle
 // ORDER (which decides which triangle owns a shared border pixel), cannot be
 // reproduced without OpenCV: "parity unpinned" against the reference on those
-// two points.  Everything else is pinned by fixtures generated without this
-// repository (tests/golden/make_prior_golden.py: vertex selection and raster as
+// two points.  The vertex selection equals the reference's own
+// GetTriangulateVertices compiled for the host (oracle/ref_host_driver.cpp),
+// vertex for vertex under both rules: ties, partial cells, the never-assigned
+// (0, 0) points and a NaN cost in a cell included
+// (tests/test_reference_host_cpu.py).  The rest -- the raster, and the plane fit
+// behind cv::SVD -- is pinned by fixtures generated without this repository
+// (tests/golden/make_prior_golden.py: vertex selection and raster as
 // step-by-step restatements, Delaunay triangle sets from Qhull on
 // general-position points, planes from numpy's SVD;
 // tests/test_prior_golden_cpu.py), the device kernels (csrc/pm_prior.hpp) equal
@@ -119,7 +124,7 @@ struct CellPicker {
                 where[slot] = Point(x, y);
             }
         const float scaled = (float)((double)(sum / (float)(y1 * x1)) * 0.85);
-        const float limit = scaled > 0.2f ? scaled : 0.2f;
+        const float limit = scaled < 0.2f ? 0.2f : scaled;  // std::max(scaled, 0.2f) of ref :842: a NaN sum stays NaN, no vertex passes
         int n = 0;
         while (n < 3 && low[n] < limit) ++n;
         return n;

@@ -13,13 +13,19 @@
 //
 //  mode 1  literal sequential restatement of the reference: masks updated pixel by
 //          pixel in raster order, the used_list that is never reset between pixels
-//          (ref :382,:416,:470-495), libm acosf/exp.  Only used to MEASURE how far the
-//          snapshot formulation is from the reference's order-dependent result.
+//          (ref :382,:416,:470-495), libm acosf / expf, the reprojection error as the double sqrt of double pows,
+//          the dynamic-consistency threshold as a double product.  PINNED: it writes the file the reference's own
+//          RunFusion and PLY writer, compiled here (oracle/ref_host_driver.cpp), write -- point count, order and all 27
+//          bytes of every record (tests/test_reference_host_cpu.py).
 //
 //  mode 2  the same sequential order (in-place masks, persistent used_list) in the canonical arithmetic: what the GPU's
-//          MPMVS_FUSE_REFERENCE_ORDER mode must reproduce bit for bit (it computes it as a parallel fixpoint).
+//          MPMVS_FUSE_REFERENCE_ORDER mode must reproduce bit for bit (it computes it as a parallel fixpoint).  Measured
+//          against the compiled reference: no record differs on the cases of the tests.
 //
-// PARITY UNPINNED against reference outputs, like the rest of the oracle.
+// What the pinning does not cover: OpenCV's own `Vec3f /= float` (the averaged normal: a division here; the build of the
+// compiled reference that multiplies by the reciprocal differs by at most one ulp per component), and the reference's indexing
+// of depths / normals when a non-estimated image precedes an estimated one (it pushes those maps only for estimated images but
+// indexes them by image index: it reads the wrong maps; this file indexes by image, and the tests keep every image estimated).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -175,11 +181,15 @@ inline bool fuse_pixel(const Views& V, int i, int r, int c, unsigned char* const
             scol[1] += gs[1];
             scol[2] += gs[2];
             const float idx = (err + 200.0f * rel) + angle * 10.0f;
-            dyn += LITERAL ? (float)std::exp(-(double)idx) : det_exp(-idx);
+            dyn += LITERAL ? expf(-idx) : det_exp(-idx);  // ref :449: exp(float) is the float function
             num++;
         }
     }
-    const bool ok = use_dynamic ? (num >= 1 && dyn > 0.3f * (float)num) : (num >= 2);
+    // ref :455: `dynamic_consistency > 0.3 * num_consistent` is a double product compared in double: the literal mode follows it.
+    // The canonical modes keep the kernel's fp32 form, which decides differently only when dyn is the one fp32 value between the
+    // two thresholds
+    const bool above = LITERAL ? ((double)dyn > 0.3 * (double)num) : (dyn > 0.3f * (float)num);
+    const bool ok = use_dynamic ? (num >= 1 && above) : (num >= 2);
     if (!ok) return false;
     const float d = (float)num + 1.0f;
     for (int k = 0; k < 3; ++k) {

@@ -1,5 +1,7 @@
 """ctypes view of the reference's own device code compiled for the host (oracle/ref_driver.cpp, `make -C oracle ref`):
-oracle/_ref/libmpmvs_ref.so (IEEE operations as written) and libmpmvs_ref_fma.so (the same text with contracted multiply-adds).
+oracle/_ref/libmpmvs_ref.so (IEEE operations as written) and libmpmvs_ref_fma.so (the same text with contracted multiply-adds);
+and of its host code (oracle/ref_host_driver.cpp): libmpmvs_ref_host.so and libmpmvs_ref_host_rcp.so, RunFusion with its PLY
+writer and GetTriangulateVertices, the two differing only in the stand-in for OpenCV's `Vec3f /= float` (ref_fuse, ref_vertices).
 
 The libraries are build products of __graft_entry__.build() on a machine that holds the reference tree; they travel with the
 working tree to machines that do not.  A missing library is an error, never a skip.  Shared by tests/test_reference_cpu.py and
@@ -7,6 +9,7 @@ tests/test_reference_gpu.py, together with the scenes, plane sets and draw table
 import ctypes as C
 import importlib
 import os
+import tempfile
 
 import numpy as np
 
@@ -44,6 +47,75 @@ def lib(fma=False):
         l.ref_sky_bilateral.argtypes = [_P, _P, _P, C.c_int, C.c_int]
         _cache[name] = l
     return _cache[name]
+
+
+def host_lib(rcp=False):
+    """the reference's host code: RunFusion + PLY writer and GetTriangulateVertices; rcp: the build whose Vec3f `/=` multiplies
+    by the fp32 reciprocal instead of dividing"""
+    name = "libmpmvs_ref_host_rcp.so" if rcp else "libmpmvs_ref_host.so"
+    if name not in _cache:
+        path = os.path.join(ORACLE_DIR, "_ref", name)
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is missing: __graft_entry__.build() makes it where the reference tree is present (MPMVS_REFERENCE)")
+        l = C.CDLL(path)
+        pp_f, pp_u8 = C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_ubyte))
+        l.refh_fuse.restype = C.c_int
+        l.refh_fuse.argtypes = [C.c_int, C.POINTER(_abi.Camera), pp_f, pp_f, pp_u8, pp_u8, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_char_p]
+        l.refh_vertices.restype = C.c_int
+        l.refh_vertices.argtypes = [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int]
+        _cache[name] = l
+    return _cache[name]
+
+
+PLY_RECORD = 27      # 6 floats and 3 bytes per vertex
+
+
+def ref_fuse(cams, depths, normals, colours_bgr, sky_or_none, sources, use_dynamic, rcp=False):
+    """the reference's RunFusion and its own PLY writer over arrays: every image estimated, refID == index, image k's maps of the
+    size cams[k] states.  colours_bgr[k]: [h][w][3] uint8; sky_or_none: None (sky_seg off) or per image a [h][w] uint8 mask or
+    None (an all-zero mask on the reference's side); sources[k]: the source ids of image k without k itself.
+    Returns (header bytes, records [M, 27] uint8) of the file the reference wrote."""
+    n = len(cams)
+    shapes = [(cams[k].height, cams[k].width) for k in range(n)]
+    d = [np.ascontiguousarray(depths[k], np.float32) for k in range(n)]
+    nm = [np.ascontiguousarray(normals[k], np.float32) for k in range(n)]
+    g = [np.ascontiguousarray(colours_bgr[k], np.uint8) for k in range(n)]
+    for k in range(n):
+        assert d[k].shape == shapes[k] and nm[k].shape == shapes[k] + (3,) and g[k].shape == shapes[k] + (3,)
+        assert np.isfinite(d[k]).all(), "the reference's int() of a NaN coordinate is undefined: keep non-finite depths out"
+    sk = None
+    if sky_or_none is not None:
+        sk = [np.zeros(shapes[k], np.uint8) if m is None else np.ascontiguousarray(m, np.uint8) for k, m in enumerate(sky_or_none)]
+        assert all(m.shape == sh for m, sh in zip(sk, shapes))
+    ids, off = [], [0]
+    for k in range(n):
+        ids += [k] + [int(s) for s in sources[k]]
+        off.append(len(ids))
+    fp = lambda arrs: (C.POINTER(C.c_float) * n)(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrs])
+    up = lambda arrs: (C.POINTER(C.c_ubyte) * n)(*[a.ctypes.data_as(C.POINTER(C.c_ubyte)) for a in arrs])
+    with tempfile.TemporaryDirectory() as tmp:
+        rc_ = host_lib(rcp).refh_fuse(n, (_abi.Camera * n)(*cams), fp(d), fp(nm), up(g), None if sk is None else up(sk), (C.c_int * (n + 1))(*off),
+                                      (C.c_int * len(ids))(*ids), 1 if use_dynamic else 0, tmp.encode())
+        if rc_ != 0:
+            raise RuntimeError(f"refh_fuse failed ({rc_}): " + ("an image or mask would have been resampled" if rc_ == -1 else "unknown image number in a path"))
+        raw = open(os.path.join(tmp, "MPMVS_model.ply"), "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    body = np.frombuffer(raw, np.uint8, offset=end)
+    assert len(body) % PLY_RECORD == 0
+    return raw[:end], body.reshape(-1, PLY_RECORD).copy()
+
+
+def ref_vertices(costs, geom, geom_rule, rcp=False):
+    """the reference's GetTriangulateVertices over one cost map (and geometric cost map): [n, 2] int32 of x, y"""
+    c = _f32(costs)
+    g = _f32(geom if geom is not None else np.zeros_like(c))
+    assert c.ndim == 2 and g.shape == c.shape
+    h, w = c.shape
+    cap = 3 * ((w + 4) // 5) * ((h + 4) // 5)
+    out = np.zeros((cap, 2), np.int32)
+    n = host_lib(rcp).refh_vertices(c.ctypes.data, g.ctypes.data, w, h, 1 if geom_rule else 0, out.ctypes.data, cap)
+    assert 0 <= n <= cap
+    return out[:n].copy()
 
 
 def _f32(a):
@@ -360,3 +432,149 @@ def check_steps_direct(pm, oracle, d, handle, bars):
     for name, f_init, dmax, f_h, f_fma, f_q8, far, mh, ml in rows:
         assert far <= bars.T2_COST_FAR_SHARE and abs(mh / ml - 1.0) <= bars.T2_MEAN_COST_REL, (name, far, mh, ml)
     return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The cases of the fusion and vertex comparisons against the reference's compiled HOST code (tests/test_reference_host_cpu.py on
+# the CPU, tests/test_reference_gpu.py on the GPU).  Built once per session; the arrays are shared and nobody writes to them.
+# ---------------------------------------------------------------------------------------------------------------------------------
+MAX_FUSE_SOURCES = 32      # mpmvs_fuse takes an image and up to MPMVS_MAX_SRC_VIEWS sources (include/mpmvs.h)
+
+
+class FuseCase:
+    """one fusion input.  ours: the colours as the project's entry points get them (1 channel for the grey case);
+    bgr: the same as the 3-channel images the reference reads"""
+
+    def __init__(self, name, cams, depths, normals, ours, bgr, sky, sources, dynamic):
+        self.name, self.cams, self.depths, self.normals, self.ours, self.bgr, self.sky, self.sources, self.dynamic = name, cams, depths, normals, ours, bgr, sky, sources, dynamic
+        self.n = len(cams)
+        self._ref = {}
+
+    def reference(self, rcp=False):
+        """(header, records) of the file the reference writes for this case"""
+        if rcp not in self._ref:
+            self._ref[rcp] = ref_fuse(self.cams, self.depths, self.normals, self.bgr, self.sky, self.sources, self.dynamic, rcp=rcp)
+        return self._ref[rcp]
+
+    def oracle_records(self, oracle, fusion, mode):
+        """PLY records of oracle mode 1 (literal) or 2 (reference order, canonical arithmetic) or 0 (snapshot)"""
+        cloud, _, _ = oracle.fuse(self.cams, [True] * self.n, self.depths, self.normals, self.ours, self.sources, use_dynamic=self.dynamic,
+                                  sequential_literal=(mode == 1), sky=self.sky, reference_order=(mode == 2))
+        return fusion.ply_records(cloud)
+
+    def truncated_pixels(self):
+        """from a float64 projection of the inputs: how many (pixel, source slot) pairs land on a source coordinate with
+        coordinate + 0.5 in (-1, 0), which `int()` truncates to pixel 0 (the last slot is left out: it may not be visited)"""
+        count = 0
+        for i in range(self.n):
+            cam = self.cams[i]
+            K, R, Cc = (np.array(v, np.float64) for v in (cam.K, cam.R, cam.C))
+            h, w = cam.height, cam.width
+            u, v = np.meshgrid(np.arange(w, dtype=np.float64), np.arange(h, dtype=np.float64))
+            d = self.depths[i].astype(np.float64)
+            X = np.stack([d * (u - K[2]) / K[0], d * (v - K[5]) / K[4], d], -1)
+            P = X @ R.reshape(3, 3) + Cc                              # world = R^T X + C
+            for s in self.sources[i][:-1]:
+                sc = self.cams[s]
+                Ks, Rs, ts = (np.array(a, np.float64) for a in (sc.K, sc.R, sc.t))
+                Y = P @ Rs.reshape(3, 3).T + ts
+                q = Y @ Ks.reshape(3, 3).T
+                with np.errstate(all="ignore"):
+                    x, y = q[..., 0] / q[..., 2] + 0.5, q[..., 1] / q[..., 2] + 0.5
+                inside_x, inside_y = (x > -1) & (x < sc.width), (y > -1) & (y < sc.height)
+                count += int(((d > 0) & inside_x & inside_y & (((x > -1) & (x < 0)) | ((y > -1) & (y < 0)))).sum())
+        return count
+
+
+_fuse_cases = {}
+
+
+def fusion_cases(pm):
+    """name -> FuseCase, over the scenes of tests/test_fusion_cpu.py (3 x 2 camera grid, five sources per image)"""
+    if _fuse_cases:
+        return _fuse_cases
+    from test_fusion_cpu import _colours_and_sky, _scene
+
+    def scene(size):
+        sc, cams, depths, normals, grays, neigh = _scene(pm, size=size)
+        cols, sky = _colours_and_sky(grays)
+        return cams, depths, normals, grays, cols, sky, neigh
+
+    def add(name, cams, depths, normals, ours, bgr, sky, neigh, dynamic=True):
+        _fuse_cases[name] = FuseCase(name, cams, depths, normals, ours, bgr, sky, neigh, dynamic)
+
+    cams, depths, normals, grays, cols, sky, neigh = scene((96, 72))
+    add("96x72_dynamic", cams, depths, normals, cols, cols, None, neigh)
+    add("96x72_static", cams, depths, normals, cols, cols, None, neigh, dynamic=False)
+    g8 = [np.clip(np.rint(g), 0, 255).astype(np.uint8) for g in grays]
+    add("96x72_grey", cams, depths, normals, g8, [np.repeat(g[..., None], 3, -1) for g in g8], None, neigh)
+    add("96x72_colour_sky", cams, depths, normals, cols, cols, sky, neigh)
+    # the longest list mpmvs_fuse accepts: the five sources repeated (the same source in two slots is legal in the reference)
+    add("96x72_32_sources", cams, depths, normals, cols, cols, None, [[s[j % len(s)] for j in range(MAX_FUSE_SOURCES)] for s in neigh])
+    holes = [d.copy() for d in depths]
+    holes[0][30:50, 5:40] = 0.0
+    holes[2][10:30, 20:60] = 0.0
+    holes[3][40:60, 50:90] = -1.0
+    holes[5][0:20, 0:30] = -3.5
+    add("96x72_zero_and_negative_depth", cams, holes, normals, cols, cols, None, neigh)
+    # two sizes in one scene: views 1 and 4 at 64x48 -- the same cameras with K scaled by 2/3 (make_scene ties K to the size)
+    small = scene((64, 48))
+    mix = lambda a, b: [b[k] if k in (1, 4) else a[k] for k in range(len(a))]
+    add("96x72_and_64x48", mix(cams, small[0]), mix(depths, small[1]), mix(normals, small[2]), mix(cols, small[4]), mix(cols, small[4]), None, neigh)
+    for size in ((131, 97), (257, 256)):        # 257 x 256: 257 chunks of 256 pixels, the second round of k_scan_totals<LastValid>
+        cams, depths, normals, grays, cols, sky, neigh = scene(size)
+        add(f"{size[0]}x{size[1]}", cams, depths, normals, cols, cols, None, neigh)
+    return _fuse_cases
+
+
+def record_rows(rec):
+    """[M, 27] uint8 -> [M] of one 27-byte value each, for set operations"""
+    return np.ascontiguousarray(rec).view(np.dtype((np.void, PLY_RECORD))).ravel()
+
+
+def cloud_difference(got, want):
+    """(relative difference of the point counts, share of the records -- as 27-byte rows -- that one cloud has and the other
+    lacks, over the count of `want`)"""
+    a, b = np.unique(record_rows(got)), np.unique(record_rows(want))
+    only = len(np.setdiff1d(a, b, assume_unique=True)) + len(np.setdiff1d(b, a, assume_unique=True))
+    return abs(len(got) - len(want)) / len(want), only / len(want)
+
+
+VERTEX_SIZES = [(85, 75), (83, 71), (1285, 5), (7, 3)]      # 83x71: partial cells on both edges; 7x3: one partial row of cells
+VERTEX_INPUTS = ["random", "ties", "exact", "invalid_cells_and_origin", "nan", "all_invalid"]
+# 7x3 has two cells: the seed is the first for which every input leaves both rules a vertex count inside the bar of the tests
+# (at least one vertex: the second cell must hold a reliable pixel, since two inputs take the first cell out)
+VERTEX_SEEDS = {(7, 3): 9101}
+_vertex_inputs = {}
+
+
+def vertex_inputs(w, h, kind):
+    """(costs, geometric costs) of one vertex case; the base is _random_costs of tests/test_prior_gpu.py"""
+    key = (w, h, kind)
+    if key in _vertex_inputs:
+        return _vertex_inputs[key]
+    from test_prior_gpu import _random_costs
+    costs, geom = _random_costs(w, h, VERTEX_SEEDS.get((w, h), 9100 + w))
+    rng = np.random.default_rng(77 + w + h)
+    if kind == "ties":            # multiples of 1 / 64: cells hold ties for first, second and third place
+        costs = (np.floor(costs * 64.0) / 64.0).astype(np.float32)
+        geom = np.minimum(geom, np.float32(0.39))                   # every pixel a candidate of the geometric rule
+    elif kind == "exact":         # the constants of both rules, exactly
+        pick = rng.integers(0, 12, (h, w))
+        for k, val in enumerate((0.1, 0.2, 1.0, 2.0)):
+            costs[pick == k] = np.float32(val)
+        geom[rng.integers(0, 4, (h, w)) == 0] = np.float32(0.4)
+    elif kind == "invalid_cells_and_origin":
+        for cy in range(0, h, 5):                                    # a fifth of the cells: every cost at or above 2
+            for cx in range(0, w, 5):
+                if rng.random() < 0.2:
+                    costs[cy:cy + 5, cx:cx + 5] = rng.uniform(2.0, 2.6, costs[cy:cy + 5, cx:cx + 5].shape).astype(np.float32)
+        # the first cell's threshold 0.85 * sum / (x_end * y_end) exceeds 2.0: the reference pushes its never-assigned (0, 0)
+        costs[:5, :5] = np.float32(3.0)
+    elif kind == "nan":
+        costs[rng.random((h, w)) < 0.01] = np.nan
+        costs[min(2, h - 1), min(3, w - 1)] = np.nan
+    elif kind == "all_invalid":
+        costs = rng.uniform(2.0, 2.6, (h, w)).astype(np.float32)
+    _vertex_inputs[key] = (costs, geom)
+    return costs, geom

@@ -110,6 +110,16 @@ def test_colour_and_sky_mask(pm, oracle):
             assert valid_l[k][sky[k] > 0].sum() == 0 and masks_l[k][sky[k] > 0].all()
 
 
+# Oracle mode 2 (the reference's order in the canonical acos / exp / sqrtf: what the GPU's reference-order mode equals bit for bit)
+# against the reference's loop in libm arithmetic -- oracle mode 1 here, the reference's compiled RunFusion itself in
+# tests/test_reference_host_cpu.py and tests/test_reference_gpu.py.  Only a threshold decision that falls between a canonical
+# function and libm's can differ, and it would cascade through the masks.  Measured on the nine cases of
+# tests/ref_common.py::fusion_cases (8 000 to 80 000 points each) against the compiled reference: no point count differs and no
+# record differs, in any case.  The bars are twice the worst measured value, relative to the reference's count.
+REFERENCE_ORDER_COUNT_BAR = 2 * 0.0        # |M2 - M| / M
+REFERENCE_ORDER_RECORDS_BAR = 2 * 0.0      # share of the 27-byte records (here: of the per-pixel decisions) one side has and the other lacks
+
+
 def test_reference_order_in_canonical_arithmetic(pm, oracle):
     """oracle mode 2 = the reference's sequential order (in-place masks, persistent used_list) in the canonical arithmetic: what
     the GPU's MPMVS_FUSE_REFERENCE_ORDER mode reproduces.  Against the literal (libm) restatement of that loop only isolated
@@ -118,7 +128,7 @@ def test_reference_order_in_canonical_arithmetic(pm, oracle):
     c1, v1, m1 = oracle.fuse(cams, [True] * 6, depths, normals, grays, neigh, sequential_literal=True)
     c2, v2, m2 = oracle.fuse(cams, [True] * 6, depths, normals, grays, neigh, reference_order=True)
     c0, v0, m0 = oracle.fuse(cams, [True] * 6, depths, normals, grays, neigh)
-    assert abs(len(c2) - len(c1)) <= 0.002 * len(c1)
-    assert np.mean([np.mean(a == b) for a, b in zip(v1, v2)]) > 0.998
+    assert abs(len(c2) - len(c1)) <= REFERENCE_ORDER_COUNT_BAR * len(c1)
+    assert np.mean([np.mean(a == b) for a, b in zip(v1, v2)]) >= 1.0 - REFERENCE_ORDER_RECORDS_BAR
     assert len(c0) != len(c2)                      # the two formulations do differ on this scene
     assert np.array_equal(v0[0], v2[0]) is False or np.array_equal(m0[1], m2[1]) is False
