@@ -253,7 +253,9 @@ int mpmvs_rng(uint64_t seed, uint32_t pix, uint32_t launch_id, int n, void* out)
  * pixel, world frame), colors[k] (8-bit, color_channels = 3: interleaved B,G,R as the
  * reference's cv::Vec3b image, :324; or 1: grey, replicated), estimate[k] (0 = skip),
  * and the view list src_ids[src_off[k] .. src_off[k+1]) whose first entry is k itself
- * (Scene::srcID); a list that names a view twice, or image k among its own sources, is rejected (-2).  sky may be NULL, or hold per image NULL or an 8-bit mask of the map's
+ * (Scene::srcID); a list that names a view twice, or image k among its own sources, is rejected (-2), and so are, before
+ * anything is launched, a list whose first entry is not k, an estimated image with an empty list, and an estimated image with
+ * more than 1 + MPMVS_MAX_SRC_VIEWS entries.  A list that holds only k is legal and yields no point.  sky may be NULL, or hold per image NULL or an 8-bit mask of the map's
  * size: pixels with sky > 0 are masked when their image is fused (:385-388).
  * Outputs per image: out_valid (1 where a fused point was produced), out_points9
  * (x y z nx ny nz c0 c1 c2 per pixel, colour in the input channel order), out_masks

@@ -1996,8 +1996,14 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     // ... and lists that name a view twice or the image itself among its sources: the masks of a source are advanced once per
     // slot (a view named twice would be swapped back and the reference-order fixpoint would never settle), and the reference
     // masks the fused image's own pixels in place, which the per-image snapshot cannot express
+    // ... and lists that do not start with their own image (slot 0 is never read as a source: a list without it would lose its
+    // first source silently), an estimated image without a list (the scratch rows are addressed with num_ngb - 1), and an
+    // estimated image with more slots than a pixel's used-list holds
     for (int i = 0; i < n; ++i) {
         if (src_off[i + 1] < src_off[i]) return -2;
+        const int num_ngb = src_off[i + 1] - src_off[i];
+        if (num_ngb > 0 && src_ids[src_off[i]] != i) return -2;
+        if (estimate[i] && (num_ngb == 0 || num_ngb > kMaxFuseNgb)) return -2;
         for (int k = src_off[i]; k < src_off[i + 1]; ++k) {
             if (src_ids[k] < 0 || src_ids[k] >= n) return -2;
             if (k > src_off[i] && src_ids[k] == i) return -2;
@@ -2140,8 +2146,7 @@ static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* est
     (void)call.begin();
     for (int i = 0; i < n && !rc; ++i) {
         if (!estimate[i]) continue;
-        const int b = src_off[i], num_ngb = src_off[i + 1] - b;
-        if (num_ngb > kMaxFuseNgb) { rc = -2; break; }
+        const int b = src_off[i], num_ngb = src_off[i + 1] - b;   // 1 .. kMaxFuseNgb: checked above
         const dim3 grid((hv[i].w + 31) / 32, (hv[i].h + 7) / 8);
         if (records && hipMemsetAsync(d_valid[i], 0, (size_t)hv[i].w * hv[i].h, st) != hipSuccess) { rc = -100; break; }
         if (!exact) {

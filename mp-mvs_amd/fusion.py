@@ -22,11 +22,12 @@ def _as_u8(x):
 FUSE_DYNAMIC_CONSISTENCY, FUSE_REFERENCE_ORDER = 1, 2   # include/mpmvs.h
 
 
-def call_fuse(fn, lead_args, cams, estimate, depths, normals, colors, sources, use_dynamic=True, sky=None, reference_order=False, ctxs=None):
+def call_fuse(fn, lead_args, cams, estimate, depths, normals, colors, sources, use_dynamic=True, sky=None, reference_order=False, ctxs=None, lists=None):
     """fn(*lead_args, n, cams, estimate, [ctxs,] depths, normals, colors, channels, sky, src_off, src_ids, use_dynamic, valid, points9, masks)
     colors[k]: HxW grey or HxWx3 B,G,R (8 bit; floats are rounded); sky: None or per image None / HxW uint8 mask;
     sources[k] = source-view ids of image k (without k itself).  ctxs (the *_ctx entry points): per image None or the HipPatchMatch
-    handle whose last Run() estimated it -- depths[k] / normals[k] may then be None.  Returns
+    handle whose last Run() estimated it -- depths[k] / normals[k] may then be None.  lists: the complete view lists exactly as
+    the C entry takes them (own image included; `sources` is then not read) -- for callers that must hand over a malformed one.  Returns
     (points [M, 9] in image-then-raster order, valid list, masks list)."""
     n = len(cams)
     shapes = [(cams[k].height, cams[k].width) for k in range(n)]
@@ -46,7 +47,7 @@ def call_fuse(fn, lead_args, cams, estimate, depths, normals, colors, sources, u
         skyp = (C.POINTER(C.c_ubyte) * n)(*[None if m is None else m.ctypes.data_as(C.POINTER(C.c_ubyte)) for m in sk])
     ids, off = [], [0]
     for k in range(n):
-        ids += [k] + list(sources[k])
+        ids += [int(s) for s in lists[k]] if lists is not None else [k] + list(sources[k])
         off.append(len(ids))
     valid = [np.zeros(sh, np.uint8) for sh in shapes]
     pts = [np.zeros(sh + (9,), np.float32) for sh in shapes]
@@ -55,7 +56,7 @@ def call_fuse(fn, lead_args, cams, estimate, depths, normals, colors, sources, u
     up = lambda arrs: (C.POINTER(C.c_ubyte) * n)(*[a.ctypes.data_as(C.POINTER(C.c_ubyte)) for a in arrs])
     ctx_arg = () if ctxs is None else ((C.c_void_p * n)(*[None if c is None else c._ctx for c in ctxs]),)
     rc = fn(*lead_args, n, (Camera * n)(*cams), (C.c_int * n)(*[1 if e else 0 for e in estimate]), *ctx_arg, fp(d), fp(nm), up(g), cch, skyp,
-            (C.c_int * (n + 1))(*off), (C.c_int * len(ids))(*ids),
+            (C.c_int * (n + 1))(*off), (C.c_int * max(len(ids), 1))(*ids),
             (FUSE_DYNAMIC_CONSISTENCY if use_dynamic else 0) | (FUSE_REFERENCE_ORDER if reference_order else 0), up(valid), fp(pts), up(masks))
     if rc != 0:
         raise RuntimeError(f"fuse failed ({rc})")
@@ -63,17 +64,17 @@ def call_fuse(fn, lead_args, cams, estimate, depths, normals, colors, sources, u
     return cloud, valid, masks
 
 
-def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False):
+def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, lists=None):
     """fusion on the MI355X (mpmvs_fuse); reference_order: the reference's sequential masking order instead of the snapshot formulation"""
     from . import engine
     lib, _ = engine.load()
     fn = lib.mpmvs_fuse
     fn.restype = C.c_int
     fn.argtypes = [C.c_int] + FUSE_ARGTYPES_TAIL
-    return call_fuse(fn, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order)
+    return call_fuse(fn, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, lists=lists)
 
 
-def fuse_ctx(cams, estimate, ctxs, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False):
+def fuse_ctx(cams, estimate, ctxs, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, lists=None):
     """mpmvs_fuse_ctx: fusion of maps that are still resident in the contexts that estimated them (ctxs[k] a HipPatchMatch handle, or None
     and depths[k] / normals[k] host arrays)"""
     from . import engine
@@ -81,7 +82,7 @@ def fuse_ctx(cams, estimate, ctxs, depths, normals, colors, sources, use_dynamic
     fn = lib.mpmvs_fuse_ctx
     fn.restype = C.c_int
     fn.argtypes = [C.c_int] + FUSE_ARGTYPES_TAIL[:3] + [C.POINTER(C.c_void_p)] + FUSE_ARGTYPES_TAIL[3:]
-    return call_fuse(fn, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs)
+    return call_fuse(fn, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs, lists=lists)
 
 
 def fuse_passes():
@@ -110,7 +111,7 @@ def ply_records(cloud):
     return rec
 
 
-def fuse_ply(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, ctxs=None):
+def fuse_ply(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, ctxs=None, lists=None):
     """mpmvs_fuse_ply: fusion with device-side compaction; returns ([M, 27] uint8 PLY vertex records, masks list).
     With ctxs (per image a HipPatchMatch handle or None): mpmvs_fuse_ply_ctx, the resident maps are not uploaded"""
     from . import engine
@@ -136,11 +137,11 @@ def fuse_ply(cams, estimate, depths, normals, colors, sources, use_dynamic=True,
         lib.mpmvs_free(rec)
         return 0
 
-    _, _, masks = call_fuse(call, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs)
+    _, _, masks = call_fuse(call, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs, lists=lists)
     return out["records"], masks
 
 
-def fuse_ply_tracks(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, ctxs=None):
+def fuse_ply_tracks(cams, estimate, depths, normals, colors, sources, use_dynamic=True, device=0, sky=None, reference_order=False, ctxs=None, lists=None):
     """mpmvs_fuse_ply_tracks: fuse_ply that also returns every point's track (include/mpmvs.h) as CSR in the point order of the
     records: (records [M, 27] uint8, track_off [M + 1] int64, track_image [E] int32, track_pixel [E] int32, masks list).  Point p was
     averaged from pixels track_pixel[track_off[p]:track_off[p + 1]] (raster index, at each image's own width) of images
@@ -172,7 +173,7 @@ def fuse_ply_tracks(cams, estimate, depths, normals, colors, sources, use_dynami
             lib.mpmvs_free(p)
         return 0
 
-    _, _, masks = call_fuse(call, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs)
+    _, _, masks = call_fuse(call, (int(device),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, reference_order, ctxs=ctxs, lists=lists)
     return out["records"], out["off"], out["image"], out["pixel"], masks
 
 

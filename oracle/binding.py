@@ -142,7 +142,7 @@ def eval_initial(handle, params, planes_cam, scale):
     return costs, sel
 
 
-def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, sequential_literal=False, sky=None, reference_order=False):
+def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, sequential_literal=False, sky=None, reference_order=False, lists=None):
     """oracle fusion: mode 0 = the snapshot formulation (the GPU's default), mode 1 = the reference's literal sequential
     order with libm (measurement only), mode 2 (reference_order) = the sequential order in the canonical arithmetic = what
     the GPU's MPMVS_FUSE_REFERENCE_ORDER mode computes"""
@@ -151,7 +151,7 @@ def fuse(cams, estimate, depths, normals, colors, sources, use_dynamic=True, seq
     fn = l.orc_fuse
     fn.restype = C.c_int
     fn.argtypes = [C.c_int] + fusion.FUSE_ARGTYPES_TAIL
-    return fusion.call_fuse(fn, (1 if sequential_literal else (2 if reference_order else 0),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky)
+    return fusion.call_fuse(fn, (1 if sequential_literal else (2 if reference_order else 0),), cams, estimate, depths, normals, colors, sources, use_dynamic, sky, lists=lists)
 
 
 def sky_bilateral(bgr, mask, literal=False):

@@ -207,6 +207,11 @@ extern "C" int orc_fuse(int mode, int n, const void* cams_, const int* estimate,
                         const int* src_ids, int use_dynamic, unsigned char* const* out_valid, float* const* out_points9,
                         unsigned char* const* masks) {
     const Camera* cams = (const Camera*)cams_;
+    // the contract of include/mpmvs.h: a list starts with its own image, and an estimated image has one
+    for (int i = 0; i < n; ++i) {
+        const int num_ngb = src_off[i + 1] - src_off[i];
+        if (num_ngb < 0 || (num_ngb > 0 && src_ids[src_off[i]] != i) || (estimate[i] && num_ngb == 0)) return -2;
+    }
     Views V{n, cams, estimate, depths, normals, colors, color_channels, src_off, src_ids};
     for (int i = 0; i < n; ++i) {
         const size_t wh = (size_t)cams[i].width * cams[i].height;

@@ -3,26 +3,18 @@ against analytic ground truth and against the reference's literal sequential ord
 import numpy as np
 import pytest
 
+from fusion_fuzz_common import analytic_normals
+
 
 def _scene(pm, noise=0.002, n_grid=(3, 2), size=(96, 72), seed=0):
     sc, neigh = pm.synth.make_grid_scene(size[0], size[1], n_grid[0], n_grid[1], spacing=0.4, rot_deg=1.0, quantize=True)
     rng = np.random.default_rng(seed)
     cams = [v.cam for v in sc.views]
     depths, normals = [], []
-    eps = 1e-3
     for v in sc.views:
         d = v.gt_depth * (1.0 + noise * rng.standard_normal(v.gt_depth.shape)).astype(np.float32)
-        H, W = d.shape
-        # analytic world normal of the height field z = Z(x, y): (Zx, Zy, -1) / |.|
-        u, w = np.meshgrid(np.arange(W), np.arange(H))
-        ray = np.stack([(u - v.K[0, 2]) / v.K[0, 0], (w - v.K[1, 2]) / v.K[1, 1], np.ones_like(u, float)], -1) @ v.R
-        P = v.C + v.gt_depth[..., None] * ray
-        Zx = (pm.synth.height_field(P[..., 0] + eps, P[..., 1]) - pm.synth.height_field(P[..., 0] - eps, P[..., 1])) / (2 * eps)
-        Zy = (pm.synth.height_field(P[..., 0], P[..., 1] + eps) - pm.synth.height_field(P[..., 0], P[..., 1] - eps)) / (2 * eps)
-        n = np.stack([Zx, Zy, -np.ones_like(Zx)], -1)
-        n /= np.linalg.norm(n, axis=-1, keepdims=True)
         depths.append(d)
-        normals.append(n.astype(np.float32))
+        normals.append(analytic_normals(pm, v))
     grays = [v.image for v in sc.views]
     return sc, cams, depths, normals, grays, neigh
 

@@ -62,7 +62,12 @@ def test_records_and_masks_equal_fuse_ply(pm, engine, case):
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_track_structure(pm, engine, case):
-    r = _case(pm, case)
+    check_track_structure(_case(pm, case))
+
+
+def check_track_structure(r):
+    """r: the inputs (cams, depths, neigh, sky, dyn) and, of one call each, fuse_ply_tracks' rec / off / img / pix and fuse's valid;
+    shared with tests/test_fusion_fuzz_gpu.py"""
     off, img, pix = r["off"], r["img"], r["pix"]
     m = len(r["rec"])
     assert off.dtype == np.int64 and img.dtype == np.int32 and pix.dtype == np.int32
@@ -90,7 +95,7 @@ def test_track_structure(pm, engine, case):
     for s in range(n):
         assert (r["depths"][s].reshape(-1)[pix[img == s]] > 0).all()
     lo = 2 if r["dyn"] else 3
-    assert length.min() >= lo and length.max() <= max(len(x) for x in r["neigh"]) + 1
+    assert m == 0 or (length.min() >= lo and length.max() <= max(len(x) for x in r["neigh"]) + 1)
     if r["sky"] is not None:
         for i in range(n):
             if r["sky"][i] is not None:
@@ -125,18 +130,23 @@ def _nine(r, img, pix):
     return out
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_track_alone_reproduces_the_point_bit_for_bit(pm, engine, case):
-    """the defining property: sequential fp32 adds in track order and one division give all nine floats of fuse()'s out_points9"""
-    r = _case(pm, case)
+def points_from_tracks(r):
+    """sequential fp32 adds in track order and one division; shared with tests/test_fusion_fuzz_gpu.py"""
     off, img, pix = r["off"], r["img"], r["pix"]
     length = np.diff(off)
     terms = _nine(r, img, pix)
     acc = terms[off[:-1]].copy()
-    for k in range(1, int(length.max())):
+    for k in range(1, int(length.max()) if len(length) else 0):
         has = length > k
         acc[has] = acc[has] + terms[off[:-1][has] + k]
-    got = acc / length.astype(np.float32)[:, None]
+    return acc / length.astype(np.float32)[:, None]
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_track_alone_reproduces_the_point_bit_for_bit(pm, engine, case):
+    """the defining property: sequential fp32 adds in track order and one division give all nine floats of fuse()'s out_points9"""
+    r = _case(pm, case)
+    got = points_from_tracks(r)
     assert got.dtype == np.float32 and got.shape == r["cloud"].shape
     differ = (got.view(np.uint32) != np.ascontiguousarray(r["cloud"]).view(np.uint32)).any(1)
     print(f"{int(differ.sum())} of {len(got)} points differ")

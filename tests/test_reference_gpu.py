@@ -53,7 +53,7 @@ def test_init_and_one_black_update_vs_compiled_reference(pm, oracle, direct, gpu
 
 
 # ---- the reference's host code ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["96x72_colour_sky", "257x256"])
+@pytest.mark.parametrize("name", ["96x72_colour_sky", "257x256", "96x72_and_64x48", "96x72_zero_and_negative_depth", "96x72_grey", "96x72_static"])
 def test_fuse_ply_vs_compiled_reference(pm, oracle, engine, name):
     """the whole chain in one place: mpmvs_fuse_ply in reference order == oracle mode 2, every byte (as tests/test_fusion_gpu.py
     asserts on other scenes); against the file the reference's RunFusion writes, inside the named bars of tests/test_fusion_cpu.py;
