@@ -511,6 +511,54 @@ float mpmvs_cloud_render_ms(const mpmvs_cloud* cloud);
 /* the same per pass: ms[0] z-min, ms[1] index (0 when no index map was wanted), ms[2] resolve */
 int mpmvs_cloud_render_pass_ms(const mpmvs_cloud* cloud, float ms[3]);
 
+/* ---- point clouds: registration to a target handle, ICP on the device (mp-mvs_amd/cloud.py, tools/eval_ply.py --refine) --- */
+/* Point-to-point ICP with an optional scale, as the Tanks and Temples protocol refines a given alignment before it measures
+ * (DESIGN.md section 15).  The moving ("source") cloud is uploaded once per align handle; a PASS transforms it on the device by
+ * M (12 doubles, row-major 3 x 4: A = M[:, :3], t = M[:, 3]), takes every transformed point's nearest target within `radius`
+ * and reduces the matched pairs to 18 integers; per pass 12 doubles go up and 18 int64 come down.
+ * THE PASS IS DEFINED BY EQUIVALENCE with this plain loop, bit for bit and independent of scheduling:
+ *   frame (from the target's finite bounding box mn, mx and the radius, on the host, in fp64):
+ *     o[a] = 0.5 * ((double)mn[a] + (double)mx[a]);  h = 0.5 * max_a((double)mx[a] - (double)mn[a]) + 2.0 * (double)radius;
+ *     u = the smallest power of two >= h;  iu = 1 / u;  frame = {o[0], o[1], o[2], u}.
+ *   per source point s (fp64 unless stated, no contraction); it is skipped if one of its coordinates is not finite:
+ *     y_k = (float)(((A[k][0]*sx + A[k][1]*sy) + A[k][2]*sz) + t[k]),  k = 0, 1, 2;
+ *     (d2, j) = the answer of the nearest-neighbour statement above for the query y at this radius; no candidate: skipped;
+ *     a = ((double)y - o) * iu;  b = ((double)p_j - o) * iu   (every component is at most 1 in magnitude by the choice of u);
+ *   fix(x) = llrint(x * 2^30), round to nearest even; every matched source adds
+ *     1 to sums[0];  fix(a_k) to sums[1 + k];  fix(b_k) to sums[4 + k];  fix(a_i * b_j) to sums[7 + 3 i + j];
+ *     fix((a_x*a_x + a_y*a_y) + a_z*a_z) to sums[16];  fix((double)d2 * (iu * iu)) to sums[17].
+ *   Every |term| <= 3 and at most 2^31 - 1 sources add one, so every |sum| < 3 * 2^61: no overflow.  The sums are integers:
+ *   the order in which the device adds them never shows.
+ * THE SOLVE is host code and never touches a device: Umeyama's closed form in fp64 in the normalised frame (means, cross-
+ * covariance and source variance from the sums, rotation from a 3 x 3 Jacobi SVD with the determinant sign fix, scale 1 unless
+ * with_scale), mapped back to world units through o and u as an update D and composed as M_out = D * M_in.
+ * *rmse (may be NULL) = sqrt(sums[17] / 2^30 / n) * u: the RMS distance of the matched pairs BEFORE the update (0 if n = 0).
+ * It returns 1 and sets M_out = M_in when fewer than 3 pairs matched, when the source variance is <= 0 or when the largest
+ * singular value is 0; anything else is answered as the formula gives it.  Collinear pairs leave a rotation about their line
+ * open: they are the caller's problem.
+ * THE ICP CALL is this loop of the two calls above and nothing else: run a pass at M, solve; M = M_out; stop after the solve
+ * whose update D (what the solve returns for M_in = identity) moves none of the 8 corners o +- u of the frame's box by more than
+ * eps (x' = ((D[k][0]*x0 + D[k][1]*x1) + D[k][2]*x2) + D[k][3], distance = sqrt((dx*dx + dy*dy) + dz*dz), fp64), after
+ * max_iter passes, or at a solve that returns 1.  *iters = passes run, *inliers = sums[0] and *rmse of the last pass (each may
+ * be NULL).  Its M equals the caller's own loop over the two calls in every bit.  When a pass inside the loop fails (a HIP failure,
+ * or -2 because an update took M out of the finite numbers) the call returns that code at once: M_inout holds the transform
+ * that pass was given, and *iters, *inliers and *rmse are not written.
+ * The handle BORROWS the target: the target must outlive it, and calls on the two handles must not run concurrently.  A pass
+ * uses the target's grids and their per-radius cache (a radius used by a nearest-neighbour call before is not built again).
+ * Errors: -2 = NULL arguments, a negative count, a radius that is not finite or <= 0, a non-finite M, max_iter < 1, an eps that is
+ * negative or NaN; -3 = n_s above 2^31 - 1, or the cell-span limit of the nearest-neighbour call; -100 = HIP failure.  All but -100
+ * are found before the device is touched.  n_s == 0 gives all-zero sums, a target without a finite point all-zero sums and an
+ * all-zero frame; neither launches anything. */
+typedef struct mpmvs_align mpmvs_align;
+int mpmvs_align_create(mpmvs_cloud* target, long long n_s, const float* s_xyz, mpmvs_align** h);
+int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long sums[18], double frame[4]);
+int mpmvs_align_solve(const long long sums[18], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse);
+int mpmvs_align_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M_inout[12], long long* iters,
+                    long long* inliers, double* rmse);
+/* device ms (HIP events) of the last pass: binning + kernel; 0 when the pass launched nothing */
+float mpmvs_align_ms(const mpmvs_align* h);
+void mpmvs_align_destroy(mpmvs_align* h);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

@@ -1,11 +1,15 @@
 """Point clouds: reading PLY files, the exact capped nearest-neighbour search on the GPU (mpmvs_cloud_*, csrc/pm_cloud.hpp),
 the accuracy / completeness / F1 score of a fused cloud against a ground-truth scan and the z-buffer
-render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp).
+render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp), and the registration of a
+cloud to a target before it is scored: point-to-point ICP with a scale on the GPU (Aligner, solve, align; csrc/pm_align.hpp,
+DESIGN.md section 15).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
 voxelises both clouds and masks the space the scanner did not observe, so the numbers here are comparable between our own
 builds and settings, and not to the ETH3D leaderboard.  The search runs on the GPU; there is no CPU path."""
 import ctypes as C
+import math
+import weakref
 
 import numpy as np
 
@@ -128,6 +132,10 @@ class Cloud:
         a = _xyz(xyz)
         self.n = len(a)
         self._h = None
+        self._aligners = weakref.WeakSet()   # Aligner handles borrow this one: close() closes them first
+        ok = np.isfinite(a).all(1)
+        fin = a if ok.all() else a[ok]
+        self.bbox = (fin.min(0), fin.max(0)) if len(fin) else None   # finite bounding box, fp32 (what the handle keeps)
         h = C.c_void_p(None)
         rc = self._f["cloud_create"](int(device), self.n, a.ctypes.data, C.byref(h))
         if rc != 0:
@@ -141,6 +149,8 @@ class Cloud:
 
     def close(self):
         if self._h:
+            for al in list(self._aligners):
+                al.close()
             self._f["cloud_destroy"](self._h)
             self._h = None
 
@@ -155,6 +165,16 @@ class Cloud:
             self.close()
         except Exception:
             pass
+
+    def frame(self, radius):
+        """the frame of an align pass at `radius` (float64 [4]: o, u), in the arithmetic of include/mpmvs.h, on the host;
+        all zero for a cloud without a finite point"""
+        if self.bbox is None:
+            return np.zeros(4)
+        mn, mx = self.bbox[0].astype(np.float64), self.bbox[1].astype(np.float64)
+        h = 0.5 * float((mx - mn).max()) + 2.0 * float(np.float32(radius))
+        m, e = math.frexp(h)
+        return np.array([*(0.5 * (mn + mx)), h if m == 0.5 else math.ldexp(1.0, e)])
 
     def nearest(self, q, radius, want_idx=True):
         """(d2 float32 [n_q], idx int32 [n_q]) of mpmvs_cloud_nearest: the squared distance to, and the index of, the nearest
@@ -206,6 +226,153 @@ class Cloud:
         ms = (C.c_float * 3)()
         self._f["cloud_render_pass_ms"](self._h, ms)
         return float(self._f["cloud_render_ms"](self._h)), {"zmin": float(ms[0]), "index": float(ms[1]), "resolve": float(ms[2])}
+
+
+def _m12(M):
+    """a 3 x 4 or 4 x 4 (last row 0 0 0 1) matrix -> 12 contiguous doubles, row-major 3 x 4"""
+    a = np.asarray(M, np.float64)
+    if a.shape == (4, 4):
+        if not np.array_equal(a[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("the last row of a 4 x 4 transform must be 0 0 0 1")
+        a = a[:3]
+    if a.shape != (3, 4):
+        raise ValueError(f"need a 3 x 4 or 4 x 4 transform, got {a.shape}")
+    return np.ascontiguousarray(a).reshape(12)
+
+
+_PD = C.POINTER(C.c_double)
+_PL = C.POINTER(C.c_longlong)
+
+
+class Aligner:
+    """A moving ("source") cloud next to a target Cloud in HBM (mpmvs_align_create): uploaded once, transformed and matched on
+    the device per pass.  The handle borrows the target's: the Aligner keeps a reference to the Cloud, and closing the Cloud
+    closes its Aligners first."""
+
+    def __init__(self, target_cloud, source_xyz):
+        _, self._f = engine.load()
+        a = _xyz(source_xyz)
+        self.n = len(a)
+        self.target = target_cloud
+        self._h = None
+        h = C.c_void_p(None)
+        rc = self._f["align_create"](target_cloud._h, self.n, a.ctypes.data, C.byref(h))
+        if rc != 0:
+            target_cloud._raise("align_create", rc)
+        self._h = h
+        target_cloud._aligners.add(self)
+
+    def close(self):
+        if self._h:   # the target is still open: its close() comes here first
+            self._f["align_destroy"](self._h)
+            self._h = None
+            self.target._aligners.discard(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def sums(self, radius, M):
+        """one pass (mpmvs_align_sums) at the transform M (3 x 4 or 4 x 4): (sums int64 [18], frame float64 [4])"""
+        m = _m12(M)
+        sums, frame = np.zeros(18, np.int64), np.zeros(4, np.float64)
+        rc = self._f["align_sums"](self._h, float(radius), m.ctypes.data_as(_PD), sums.ctypes.data_as(_PL), frame.ctypes.data_as(_PD))
+        if rc != 0:
+            self.target._raise("align_sums", rc)
+        return sums, frame
+
+    def icp(self, radius, M, with_scale=True, max_iter=30, eps=0.0):
+        """mpmvs_align_icp from the transform M: (M float64 [3, 4], passes run, inliers and rmse of the last pass)"""
+        m = _m12(M).copy()
+        it, inl, rmse = C.c_longlong(0), C.c_longlong(0), C.c_double(0.0)
+        rc = self._f["align_icp"](self._h, float(radius), 1 if with_scale else 0, int(max_iter), float(eps), m.ctypes.data_as(_PD), C.byref(it),
+                                  C.byref(inl), C.byref(rmse))
+        if rc != 0:
+            self.target._raise("align_icp", rc)
+        return m.reshape(3, 4), int(it.value), int(inl.value), float(rmse.value)
+
+    def ms(self):
+        """device ms of the last pass: binning + kernel"""
+        return float(self._f["align_ms"](self._h))
+
+
+def solve(sums, frame, M, with_scale=True):
+    """mpmvs_align_solve (host code, no GPU): (status, M_out float64 [3, 4], rmse).  status 1: fewer than 3 pairs, no source
+    variance or no covariance; M_out is M then."""
+    _, f = engine.load()
+    s = np.ascontiguousarray(sums, np.int64)
+    fr = np.ascontiguousarray(frame, np.float64)
+    if s.shape != (18,) or fr.shape != (4,):
+        raise ValueError("need 18 sums and a frame of 4")
+    m, out, rmse = _m12(M), np.zeros(12, np.float64), C.c_double(0.0)
+    rc = f["align_solve"](s.ctypes.data_as(_PL), fr.ctypes.data_as(_PD), 1 if with_scale else 0, m.ctypes.data_as(_PD), out.ctypes.data_as(_PD), C.byref(rmse))
+    if rc < 0:
+        raise ValueError(f"mpmvs_align_solve failed ({rc})")
+    return rc, out.reshape(3, 4), float(rmse.value)
+
+
+def update_move(D, frame):
+    """the stop rule of mpmvs_align_icp in the header's arithmetic: the largest distance by which the update D (3 x 4) moves a
+    corner of the box frame[:3] +- frame[3]"""
+    D, fr = np.asarray(D, np.float64).reshape(3, 4), np.asarray(frame, np.float64)
+    worst = 0.0
+    for c in range(8):
+        x = [fr[k] + fr[3] if (c >> k) & 1 else fr[k] - fr[3] for k in range(3)]
+        d = [(((D[k, 0] * x[0] + D[k, 1] * x[1]) + D[k, 2] * x[2]) + D[k, 3]) - x[k] for k in range(3)]
+        worst = max(worst, float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])))
+    return worst
+
+
+IDENTITY34 = np.eye(4)[:3]
+
+
+def icp_loop(pass_fn, radius, M, with_scale=True, max_iter=30, eps=0.0):
+    """the loop mpmvs_align_icp is defined as, over the two public calls: pass_fn(radius, M) -> (sums, frame) is Aligner.sums
+    (or the numpy statement in the tests).  Returns what Aligner.icp returns, bit for bit."""
+    M = _m12(M).reshape(3, 4).copy()
+    passes, inliers, rmse = 0, 0, 0.0
+    for _ in range(int(max_iter)):
+        sums, frame = pass_fn(radius, M)
+        passes += 1
+        inliers = int(sums[0])
+        rc, M_out, rmse = solve(sums, frame, M, with_scale)
+        if rc == 1:
+            break
+        M = M_out
+        if update_move(solve(sums, frame, IDENTITY34, with_scale)[1], frame) <= eps:
+            break
+    return M, passes, inliers, rmse
+
+
+def align(source_xyz, target_cloud, T0=None, radii=None, with_scale=True, max_iter=30, eps=None):
+    """Refines the transform T0 (4 x 4, identity if None) that takes `source_xyz` into the frame of `target_cloud` (a Cloud) by
+    point-to-point ICP in coarse-to-fine rounds: one Aligner.icp per radius of `radii`, in descending order, each starting from
+    the result of the one before.  Returns (T float64 [4, 4], report), report = a list of {"radius", "passes", "inliers", "rmse"}
+    per round.  `radii` has no default: it is a property of the scene (tools/eval_ply.py derives it from its tolerances).
+    eps=None means 2^-20 of the frame's unit u, the power of two that covers half the target's bounding box plus two radii: a
+    round ends when an update moves no corner of that box by more than a millionth of its size."""
+    if radii is None or len(radii) == 0:
+        raise ValueError("align needs the radii of its rounds")
+    rad = sorted((float(r) for r in radii), reverse=True)
+    T = np.eye(4) if T0 is None else np.array(T0, np.float64)
+    M = _m12(T).reshape(3, 4)
+    report = []
+    with Aligner(target_cloud, source_xyz) as al:
+        for r in rad:
+            e = float(target_cloud.frame(r)[3]) * 2.0 ** -20 if eps is None else eps
+            M, passes, inliers, rmse = al.icp(r, M, with_scale, max_iter, e)
+            report.append({"radius": r, "passes": passes, "inliers": inliers, "rmse": rmse})
+    T = np.eye(4)
+    T[:3] = M
+    return T, report
 
 
 def distances(query, target_cloud, tolerances, on_level=None):

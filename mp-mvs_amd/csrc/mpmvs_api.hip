@@ -39,6 +39,8 @@
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
 #include "pm_cloud.hpp"
+#include "pm_align.hpp"
+#include "pm_align_host.hpp"
 #include "pm_render.hpp"
 #include "pm_ingest.hpp"
 #include "pm_undistort.hpp"
@@ -3155,18 +3157,30 @@ static int cloud_grid(mpmvs_cloud* c, float radius, CloudGridBuf** out) {
     return 0;
 }
 
-static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, int nq, const float* q_xyz, float* out_d2, int32_t* out_idx) {
-    const hipStream_t st = c->stream;
+// MPMVS_CLOUD_BIN=0: the queries (and the sources of an align pass) are served in caller order; read once per process
+static bool cloud_bin_queries() {
     static const bool bin = [] {
         const char* e = std::getenv("MPMVS_CLOUD_BIN");
         return !(e && e[0] == '0');
     }();
+    return bin;
+}
+
+// the kernels' view of a built grid
+static CloudGrid cloud_grid_args(const mpmvs_cloud* c, const CloudGridBuf& grid, float radius) {
     CloudGrid g;
     for (int a = 0; a < 3; ++a) g.mn[a] = (double)c->mn[a];
     g.edge = cloud_edge(radius);
     g.r2 = radius * radius;
     g.mask = (unsigned)(((size_t)1 << c->slots_log2) - 1);
     g.keys = grid.d_keys, g.off = grid.d_off, g.pts = grid.d_pts;
+    return g;
+}
+
+static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, int nq, const float* q_xyz, float* out_d2, int32_t* out_idx) {
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    const CloudGrid g = cloud_grid_args(c, grid, radius);
     int bins_log2 = 8;
     while (bins_log2 < kCloudMaxSlotsLog2 && (1ll << bins_log2) < nq) ++bins_log2;
     const size_t bins = (size_t)1 << bins_log2, q = (size_t)nq;
@@ -3201,6 +3215,21 @@ static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, i
     return 0;
 }
 
+// the cell-span limit of a grid of `radius` over the handle's finite bounding box (-3), found on the host
+static int cloud_span_check(const mpmvs_cloud* c, float radius) {
+    const double edge = cloud_edge(radius);
+    for (int a = 0; a < 3; ++a) {
+        const double cells = std::floor(((double)c->mx[a] - (double)c->mn[a]) / edge) + 1.0;
+        if (cells > (double)kCloudAxisCells) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "cloud: the targets span %.6g cells of edge %.6g along %c, more than 2^21 (extent / radius = %.6g)", cells, edge,
+                          "xyz"[a], ((double)c->mx[a] - (double)c->mn[a]) / (double)radius);
+            return seg_fail(-3, msg);
+        }
+    }
+    return 0;
+}
+
 int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx) {
     if (!c || !out_d2 || n_q < 0 || (n_q > 0 && !q_xyz)) return seg_fail(-2, "cloud: bad argument");
     if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud: the radius must be finite and positive");
@@ -3215,16 +3244,8 @@ int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float
         c->query_ms = c->build_ms = 0.0f;
         return 0;
     }
-    const double edge = cloud_edge(radius);
-    for (int a = 0; a < 3; ++a) {
-        const double cells = std::floor(((double)c->mx[a] - (double)c->mn[a]) / edge) + 1.0;
-        if (cells > (double)kCloudAxisCells) {
-            char msg[200];
-            std::snprintf(msg, sizeof msg, "cloud: the targets span %.6g cells of edge %.6g along %c, more than 2^21 (extent / radius = %.6g)", cells, edge,
-                          "xyz"[a], ((double)c->mx[a] - (double)c->mn[a]) / (double)radius);
-            return seg_fail(-3, msg);
-        }
-    }
+    const int span = cloud_span_check(c, radius);
+    if (span) return span;
     SEGCHK(enter_device(c->device));
     CloudGridBuf* grid = nullptr;
     const int rc = cloud_grid(c, radius, &grid);
@@ -3242,6 +3263,160 @@ float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) {
     if (!c) return 0.0f;
     if (build_ms) *build_ms = c->build_ms;
     return c->query_ms;
+}
+
+// ---------------------------------------------------------------------------
+// registration of a moving cloud to a target handle: the ICP pass and its closed-form solve (pm_align.hpp, pm_align_host.hpp;
+// DESIGN.md section 15).  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+struct mpmvs_align {
+    mpmvs_cloud* target = nullptr;   // borrowed: its stream, grids and points serve every pass
+    long long n = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float* d_src = nullptr;
+    int *d_qbin = nullptr, *d_order = nullptr, *d_qcnt = nullptr, *d_qoff = nullptr, *d_qtsum = nullptr;
+    unsigned long long* d_sums = nullptr;
+    size_t bins = 0;
+    float pass_ms = 0.0f;
+};
+
+static void align_release(mpmvs_align* h) {
+    if (h->target->stream) (void)hipStreamSynchronize(h->target->stream);
+    for (void* p : {(void*)h->d_src, (void*)h->d_qbin, (void*)h->d_order, (void*)h->d_qcnt, (void*)h->d_qoff, (void*)h->d_qtsum, (void*)h->d_sums})
+        if (p) (void)pool_free(p);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete h;
+}
+
+static int align_create_device(mpmvs_align* h, const float* s_xyz) {
+    const hipStream_t st = h->target->stream;
+    SEGCHK(enter_device(h->target->device));
+    for (hipEvent_t& e : h->ev) SEGCHK(hipEventCreate(&e));
+    if (h->n == 0) return 0;
+    const size_t n = (size_t)h->n;
+    SEGCHK(pool_malloc(&h->d_src, n * 12));
+    SEGCHK(pool_malloc(&h->d_qbin, n * 4));
+    SEGCHK(pool_malloc(&h->d_order, n * 4));
+    SEGCHK(pool_malloc(&h->d_qcnt, h->bins * 4));
+    SEGCHK(pool_malloc(&h->d_qoff, (h->bins + 1) * 4));
+    SEGCHK(pool_malloc(&h->d_qtsum, h->bins / kScanBlock * 4));
+    SEGCHK(pool_malloc(&h->d_sums, kAlignTerms * 8));
+    SEGCHK(hipMemcpyAsync(h->d_src, s_xyz, n * 12, hipMemcpyHostToDevice, st));
+    SEGCHK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int mpmvs_align_create(mpmvs_cloud* target, long long n_s, const float* s_xyz, mpmvs_align** out) {
+    if (!out) return seg_fail(-2, "align: bad argument");
+    *out = nullptr;
+    if (!target || n_s < 0 || (n_s > 0 && !s_xyz)) return seg_fail(-2, "align: bad argument");
+    if (n_s > INT32_MAX) return seg_fail(-3, "align: more than 2^31 - 1 source points");
+    mpmvs_align* h = new mpmvs_align;
+    h->target = target;
+    h->n = n_s;
+    int bins_log2 = 8;
+    while (bins_log2 < kCloudMaxSlotsLog2 && (1ll << bins_log2) < n_s) ++bins_log2;
+    h->bins = (size_t)1 << bins_log2;
+    const int rc = align_create_device(h, s_xyz);
+    if (rc) {
+        align_release(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+void mpmvs_align_destroy(mpmvs_align* h) {
+    if (!h) return;
+    (void)enter_device(h->target->device);
+    align_release(h);
+}
+
+float mpmvs_align_ms(const mpmvs_align* h) { return h ? h->pass_ms : 0.0f; }
+
+// the device half of a pass: the grid of `radius` (cached per radius in the target), the binning, the kernel, 18 integers back
+static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, long long sums[18]) {
+    mpmvs_cloud* c = h->target;
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    const int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    const CloudGrid g = cloud_grid_args(c, *grid, radius);
+    const int n = (int)h->n;
+    SEGCHK(hipMemsetAsync(h->d_sums, 0, kAlignTerms * 8, st));
+    if (bin) SEGCHK(hipMemsetAsync(h->d_qcnt, 0, h->bins * 4, st));
+    SEGCHK(hipEventRecord(h->ev[0], st));
+    const dim3 gq(((unsigned)n + 255u) / 256u);   // unsigned: n may be 2^31 - 1
+    if (bin) {
+        hipLaunchKernelGGL(k_align_qbin, gq, dim3(256), 0, st, h->d_src, n, f, g, (unsigned)(h->bins - 1), h->d_qcnt, h->d_qbin);
+        cloud_scan(st, h->d_qcnt, (int)h->bins, h->d_qoff, h->d_qtsum);
+        hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, n, h->d_qbin, h->d_qoff, h->d_qcnt, h->d_order);
+    }
+    hipLaunchKernelGGL(k_align_pass, gq, dim3(256), 0, st, h->d_src, n, bin ? h->d_order : (const int*)nullptr, f, g, c->d_xyz, h->d_sums);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(h->ev[1], st));
+    SEGCHK(hipMemcpyAsync(sums, h->d_sums, kAlignTerms * 8, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    SEGCHK(hipEventElapsedTime(&h->pass_ms, h->ev[0], h->ev[1]));
+    return 0;
+}
+
+static bool align_finite12(const double M[12]) {
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(M[k])) return false;
+    return true;
+}
+
+int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long sums[18], double frame[4]) {
+    if (!h || !M || !sums || !frame) return seg_fail(-2, "align: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
+    const mpmvs_cloud* c = h->target;
+    for (int k = 0; k < kAlignTerms; ++k) sums[k] = 0;
+    for (int k = 0; k < 4; ++k) frame[k] = 0.0;
+    h->pass_ms = 0.0f;
+    if (c->n_fin == 0) return 0;   // no candidate anywhere, and no bounding box to take a frame from
+    const int span = cloud_span_check(c, radius);
+    if (span) return span;
+    align_frame(c->mn, c->mx, radius, frame);
+    if (h->n == 0) return 0;
+    AlignXf f;
+    for (int k = 0; k < 12; ++k) f.m[k] = M[k];
+    for (int k = 0; k < 3; ++k) f.o[k] = frame[k];
+    f.iu = 1.0 / frame[3];
+    return align_pass(h, radius, f, sums);
+}
+
+int mpmvs_align_solve(const long long sums[18], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse) {
+    if (!sums || !frame || !M_in || !M_out) return seg_fail(-2, "align: bad argument");
+    return align_solve(sums, frame, with_scale, M_in, M_out, rmse);
+}
+
+int mpmvs_align_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M[12], long long* iters, long long* inliers, double* rmse) {
+    if (!h || !M) return seg_fail(-2, "align: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
+    if (max_iter < 1) return seg_fail(-2, "align: max_iter must be at least 1");
+    if (!(eps >= 0.0)) return seg_fail(-2, "align: eps must not be negative");
+    long long n_pass = 0, sums[18] = {0};
+    double frame[4], last_rmse = 0.0;
+    for (int it = 0; it < max_iter; ++it) {
+        const int rc = mpmvs_align_sums(h, radius, M, sums, frame);
+        if (rc < 0) return rc;
+        ++n_pass;
+        double D[12], next[12];
+        if (align_update(sums, frame, with_scale, D, &last_rmse)) break;
+        align_compose(D, M, next);
+        for (int k = 0; k < 12; ++k) M[k] = next[k];   // one that left the finite numbers is refused by the next pass, as in the caller's own loop
+        if (align_move(D, frame) <= eps) break;
+    }
+    if (iters) *iters = n_pass;
+    if (inliers) *inliers = sums[0];
+    if (rmse) *rmse = last_rmse;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

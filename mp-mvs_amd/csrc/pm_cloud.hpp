@@ -180,21 +180,27 @@ __global__ __launch_bounds__(256) void k_cloud_scatter(const float* __restrict__
 }
 
 // ---- query -----------------------------------------------------------------------------------------------------------
-__host__ __device__ inline bool cloud_query_cell(const float* __restrict__ q, size_t i, const CloudGrid& g, float& x, float& y, float& z, int& cx, int& cy,
-                                                 int& cz) {
-    x = q[3 * i], y = q[3 * i + 1], z = q[3 * i + 2];
+// the (clamped) cell of a query point; false, and no cell, if a coordinate is not finite
+__host__ __device__ inline bool cloud_point_cell(float x, float y, float z, const CloudGrid& g, int& cx, int& cy, int& cz) {
     if (!(cloud_finite(x) && cloud_finite(y) && cloud_finite(z))) return false;
     cx = cloud_cell(x, g.mn[0], g.edge), cy = cloud_cell(y, g.mn[1], g.edge), cz = cloud_cell(z, g.mn[2], g.edge);
     return true;
 }
+__host__ __device__ inline bool cloud_query_cell(const float* __restrict__ q, size_t i, const CloudGrid& g, float& x, float& y, float& z, int& cx, int& cy,
+                                                 int& cz) {
+    x = q[3 * i], y = q[3 * i + 1], z = q[3 * i + 2];
+    return cloud_point_cell(x, y, z, g, cx, cy, cz);
+}
 
 // bin of a query: the hash of its own (clamped) cell; a query without a cell goes to bin 0
+__host__ __device__ inline int cloud_cell_bin(int cx, int cy, int cz, unsigned bin_mask) {
+    return (int)((unsigned)cloud_mix(((unsigned long long)(cx + 2) | ((unsigned long long)(cy + 2) << 22)) ^ cloud_mix((unsigned long long)(cz + 2))) & bin_mask);
+}
 __host__ __device__ inline void cloud_qbin_one(size_t i, const float* __restrict__ q, const CloudGrid& g, unsigned bin_mask, int* __restrict__ qcnt,
                                                int* __restrict__ qbin) {
     float x, y, z;
     int cx, cy, cz, b = 0;
-    if (cloud_query_cell(q, i, g, x, y, z, cx, cy, cz))
-        b = (int)((unsigned)cloud_mix(((unsigned long long)(cx + 2) | ((unsigned long long)(cy + 2) << 22)) ^ cloud_mix((unsigned long long)(cz + 2))) & bin_mask);
+    if (cloud_query_cell(q, i, g, x, y, z, cx, cy, cz)) b = cloud_cell_bin(cx, cy, cz, bin_mask);
     qbin[i] = b;
     cloud_fetch_add(&qcnt[b], 1);
 }
@@ -217,44 +223,50 @@ __global__ __launch_bounds__(256) void k_cloud_qorder(int nq, const int* __restr
     if (i < (size_t)nq) cloud_qorder_one(i, qbin, qoff, qcnt, order);
 }
 
+// the 27-cell search for the query (x, y, z) of cell (cx, cy, cz): the minimum of (d2 bits << 32) | index over the candidates
+// (d2 >= +0, so its bits order as integers), ~0 if there is none.  Shared by k_cloud_query and k_align_pass (pm_align.hpp).
+__host__ __device__ inline unsigned long long cloud_search(float x, float y, float z, int cx, int cy, int cz, const CloudGrid& g) {
+    unsigned long long best = ~0ull;
+    for (int dz = -1; dz <= 1; ++dz) {
+        if (!cloud_cell_ok(cz + dz)) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            if (!cloud_cell_ok(cy + dy)) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!cloud_cell_ok(cx + dx)) continue;
+                const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
+                unsigned h = (unsigned)cloud_mix(key) & g.mask;
+                int s = -1;
+                for (unsigned probe = 0; probe <= g.mask; ++probe) {
+                    const unsigned long long cur = g.keys[h];
+                    if (cur == key) s = (int)h;
+                    if (cur == key || cur == kCloudEmpty) break;
+                    h = (h + 1) & g.mask;
+                }
+                if (s < 0) continue;
+                const int e = g.off[s + 1];
+                for (int p = g.off[s]; p < e; ++p) {
+                    const uint4 t = g.pts[p];
+                    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
+                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+                    if (d2 <= g.r2) {
+                        const unsigned long long cand = ((unsigned long long)cloud_bits(d2) << 32) | t.w;
+                        best = cand < best ? cand : best;
+                    }
+                }
+            }
+        }
+    }
+    return best;
+}
+
 // the query thread j serves is order[j] (order may be null: j itself)
 __host__ __device__ inline void cloud_query_one(size_t j, const float* __restrict__ q, const int* __restrict__ order, const CloudGrid& g,
                                                 float* __restrict__ out_d2, int32_t* __restrict__ out_idx) {
     const size_t i = order ? (size_t)order[j] : j;
     float x, y, z;
     int cx, cy, cz;
-    unsigned long long best = ~0ull;   // (d2 bits << 32) | index: d2 >= +0, so its bits order as integers
-    if (cloud_query_cell(q, i, g, x, y, z, cx, cy, cz)) {
-        for (int dz = -1; dz <= 1; ++dz) {
-            if (!cloud_cell_ok(cz + dz)) continue;
-            for (int dy = -1; dy <= 1; ++dy) {
-                if (!cloud_cell_ok(cy + dy)) continue;
-                for (int dx = -1; dx <= 1; ++dx) {
-                    if (!cloud_cell_ok(cx + dx)) continue;
-                    const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
-                    unsigned h = (unsigned)cloud_mix(key) & g.mask;
-                    int s = -1;
-                    for (unsigned probe = 0; probe <= g.mask; ++probe) {
-                        const unsigned long long cur = g.keys[h];
-                        if (cur == key) s = (int)h;
-                        if (cur == key || cur == kCloudEmpty) break;
-                        h = (h + 1) & g.mask;
-                    }
-                    if (s < 0) continue;
-                    const int e = g.off[s + 1];
-                    for (int p = g.off[s]; p < e; ++p) {
-                        const uint4 t = g.pts[p];
-                        const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
-                        const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                        if (d2 <= g.r2) {
-                            const unsigned long long cand = ((unsigned long long)cloud_bits(d2) << 32) | t.w;
-                            best = cand < best ? cand : best;
-                        }
-                    }
-                }
-            }
-        }
-    }
+    unsigned long long best = ~0ull;
+    if (cloud_query_cell(q, i, g, x, y, z, cx, cy, cz)) best = cloud_search(x, y, z, cx, cy, cz, g);
     const bool found = best != ~0ull;
     out_d2[i] = found ? cloud_float((uint32_t)(best >> 32)) : cloud_float(0x7f800000u);
     if (out_idx) out_idx[i] = found ? (int32_t)(uint32_t)(best & 0xffffffffull) : -1;

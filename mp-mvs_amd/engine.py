@@ -68,6 +68,13 @@ _EXTRA = {
     "cloud_render_depth": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, _P]),
     "cloud_render_ms": (C.c_float, [_P]),
     "cloud_render_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    # registration (cloud.py: Aligner, solve, align)
+    "align_create": (C.c_int, [_P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
+    "align_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "align_solve": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "align_icp": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "align_ms": (C.c_float, [_P]),
+    "align_destroy": (None, [_P]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

@@ -10,7 +10,9 @@ D holds cams/, images/ and pair.txt; the results are R/2333_<id>/<map> with R = 
 root.  Every view that has a result folder with the map is scored.  The ground truth is either
   * a scan (--ground_truth, a PLY file) rendered into every view's camera on the GPU (cloud.Cloud.render_depth): a z-buffer
     with a visibility test.  --transform: a 4 x 4 text matrix that takes the scan into the frame of the cameras (fp64, rounded
-    to fp32).  --splat / --occl: a point is hidden when a point within `splat` pixels is nearer by more than the factor
+    to fp32).  tools/eval_ply.py --refine --save_transform feeds it: that file takes the reconstruction (the cameras' frame)
+    into the scan's frame, so its inverse (numpy.linalg.inv of the loaded matrix) is what --transform expects here.
+    --splat / --occl: a point is hidden when a point within `splat` pixels is nearer by more than the factor
     1 + occl.  The slope rule: a slanted surface hides itself once occl is below splat x the relative change of depth per
     pixel, so raise --occl with --splat on steep or close scenes.  The defaults are starting values from the synthetic scene,
     not tuned on a real scan.  The map is rendered at the estimate's size with the camera rescaled as fusion does; or

@@ -4,9 +4,17 @@
 
     python tools/eval_ply.py --reconstruction MPMVS_model.ply --ground_truth scan.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5]
                              [--transform T.txt] [--crop xmin,ymin,zmin,xmax,ymax,zmax] [--device 0]
+                             [--refine [--refine_radii r1,r2,...] [--refine_no_scale] [--refine_iters 30] [--save_transform OUT.txt]]
 
 --transform: a 4 x 4 text matrix that takes the reconstruction into the ground truth's frame; applied in fp64 and rounded to
 fp32.  --crop: an axis-aligned box (in the ground truth's frame, after the transform) applied to both clouds.
+--refine: the transform (identity if absent) is only a starting guess and is refined before the score, as the Tanks and Temples
+protocol does: point-to-point ICP of the reconstruction to the ground truth on the GPU (mp-mvs_amd/cloud.py: align; DESIGN.md
+section 15), one round per radius of --refine_radii in descending order (default: 8, 4 and 2 times the largest tolerance), with
+a scale unless --refine_no_scale, at most --refine_iters passes per round.  The crop is applied after the refined transform,
+and the JSON line gains "refine": {"rounds": [{radius, passes, inliers, rmse}], "matrix": 4 x 4, "seconds"}.
+--save_transform writes the refined 4 x 4 matrix as text: a later run's --transform (tools/eval_depth.py takes its inverse: there
+the matrix carries the scan into the cameras' frame).
 This is the plain two-way nearest-neighbour measure (Tanks-and-Temples style); ETH3D's official program additionally voxelises
 and masks unobserved space, so the numbers compare our own builds and settings, not leaderboard entries.
 Prints one JSON line: the dictionary of evaluate() plus seconds per stage (read, upload + build, query)."""
@@ -51,12 +59,30 @@ def main():
     ap.add_argument("--transform")
     ap.add_argument("--crop")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--refine", action="store_true")
+    ap.add_argument("--refine_radii")
+    ap.add_argument("--refine_no_scale", action="store_true")
+    ap.add_argument("--refine_iters", type=int, default=30)
+    ap.add_argument("--save_transform")
     args = ap.parse_args()
+    if not args.refine and (args.refine_radii or args.refine_no_scale or args.save_transform):
+        raise SystemExit("--refine_radii, --refine_no_scale and --save_transform need --refine")
     tol = [float(t) for t in args.tolerances.split(",") if t.strip()]
     t0 = time.perf_counter()
     rec = cloud.read_ply(args.reconstruction)["xyz"]
     gt = cloud.read_ply(args.ground_truth)["xyz"]
-    if args.transform:
+    refine = None
+    if args.refine:
+        T0 = np.loadtxt(args.transform) if args.transform else np.eye(4)
+        radii = [float(r) for r in args.refine_radii.split(",") if r.strip()] if args.refine_radii else [8 * max(tol), 4 * max(tol), 2 * max(tol)]
+        t_r = time.perf_counter()
+        with cloud.Cloud(cloud.drop_nonfinite(gt)[0], args.device) as c_gt:
+            T, rounds = cloud.align(rec, c_gt, T0, radii=radii, with_scale=not args.refine_no_scale, max_iter=args.refine_iters)
+        refine = {"rounds": rounds, "matrix": T.tolist(), "seconds": round(time.perf_counter() - t_r, 4)}
+        if args.save_transform:
+            np.savetxt(args.save_transform, T, fmt="%.17g")
+        rec = apply_transform(rec, T)
+    elif args.transform:
         rec = apply_transform(rec, np.loadtxt(args.transform))
     if args.crop:
         box = [float(v) for v in args.crop.split(",")]
@@ -67,6 +93,8 @@ def main():
     timings = {}
     res = cloud.evaluate(rec, gt, tol, device=args.device, timings=timings)
     res["seconds"] = {"read": round(t1 - t0, 4), "upload_build": round(timings["upload_build_s"], 4), "query": round(timings["query_s"], 4)}
+    if refine is not None:
+        res["refine"] = refine
     print(json.dumps(res))
 
 
