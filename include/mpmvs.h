@@ -476,6 +476,45 @@ int mpmvs_cloud_stats(const mpmvs_cloud* cloud, long long stats[4]);
 float mpmvs_cloud_kernel_ms(const mpmvs_cloud* cloud, float* build_ms);
 void mpmvs_cloud_destroy(mpmvs_cloud* cloud);
 
+/* ---- point clouds: voxel-grid downsampling (mp-mvs_amd/cloud.py, tools/downsample_ply.py, tools/eval_ply.py --voxel) --- */
+/* One output point per occupied cell of a uniform grid of edge `voxel`: the mean position, the normalised sum of the normals and
+ * the rounded mean colour of the cell's members, as the Tanks and Temples and ETH3D protocols resample both clouds before they
+ * measure, so that a score does not weigh a surface by how densely it was sampled.  A stateless call:
+ * host buffers in and out, a stream of its own, blocks until done.  It returns the number m of occupied voxels, or a negative code.
+ * *out_xyz (m x 3), *out_normals (m x 3, iff normals), *out_rgb (m x 3, iff rgb), *out_count (m) and *out_first (m) receive
+ * buffers to release with mpmvs_free; on failure none is allocated and all are NULL; m == 0 (n == 0, or no point with three finite
+ * coordinates) sets them to NULL too and launches nothing.  out_voxel_of is the caller's, n entries, and may be NULL.
+ * DEFINED BY EQUIVALENCE with this plain loop, bit for bit and independent of scheduling (fp64 unless stated, no contraction):
+ *   A point TAKES PART iff its three coordinates are finite; otherwise out_voxel_of[i] = -1.
+ *   mn[a] = the minimum of the points that take part along axis a (fp32, found on the host as mpmvs_cloud_create finds it).
+ *   e = (double)voxel;  o[a] = (double)mn[a] - 0.5 * e   (the usual origin rule: the lowest point lies at a cell centre).
+ *   t_a = ((double)x_a - o[a]) / e;  c_a = floor(t_a): a point exactly on a cell border belongs to the upper cell.  o[a] <= mn[a],
+ *   so c_a >= 0; every c_a must be below 2^21 (-3 otherwise, found on the host from the maximum along the axis).
+ *   The voxels (occupied cells) are numbered in the order of their smallest member index, i.e. by first appearance in the input:
+ *   out_first[v] = that index, out_count[v] = the number of members, out_voxel_of[i] = v.
+ *   fix(x) = llrint(x * 2^30), round to nearest even.
+ *   Position: every member adds fix(t_a - c_a) to the int64 S[v][a]; each term is at most 2^30 and a voxel has at most 2^31 - 1
+ *     members: no overflow.  out_xyz[v][a] = (float)(o[a] + ((double)c_a + (double)S[v][a] / ((double)count * 2^30)) * e).
+ *   Normals: a member whose normal has a non-finite component adds nothing; any other adds fix(max(-1, min(1, (double)n_a))) to the
+ *     int64 N[v][a].  L = sqrt(((double)N0*N0 + (double)N1*N1) + (double)N2*N2);  out_normals[v][a] = (float)((double)N[v][a] / L),
+ *     and 0.0f on all three axes when L == 0.
+ *   Colour: C[v][k] = the integer sum of the members' bytes;  out_rgb[v][k] = (2 * C + count) / (2 * count) in integer division
+ *     (round half up).
+ * The sums are integers: the order in which the device adds them never shows.
+ * Errors (text through mpmvs_last_error with a NULL context, per host thread): -2 = a NULL xyz with n > 0, a negative n, a voxel
+ * that is not finite or <= 0, a NULL out_xyz, out_count or out_first, out_normals or out_rgb NULL while its input is given;
+ * -3 = n above 2^31 - 1, more than 2^29 finite points (the hash table's limit, as for mpmvs_cloud_create), or the cell-span limit
+ * above (the text names the axis and the ratio); -100 = HIP failure, a bad device included.  All but -100 are found before the
+ * device is touched. */
+long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz, const float* normals /* n x 3 or NULL */,
+                                       const unsigned char* rgb /* n x 3 or NULL */, float voxel, float** out_xyz,
+                                       float** out_normals /* NULL iff normals NULL */, unsigned char** out_rgb /* NULL iff rgb NULL */,
+                                       int32_t** out_count, int32_t** out_first, int32_t* out_voxel_of /* caller's, n entries, may be NULL */);
+/* device ms (HIP events) of the calling thread's last successful call, the sum of its passes; 0 when it launched nothing */
+float mpmvs_cloud_voxel_ms(void);
+/* the same per pass (mp-mvs_amd/csrc/pm_voxel.hpp): insert, first, flag + scan, number, accumulate, finish */
+void mpmvs_cloud_voxel_pass_ms(float ms[6]);
+
 /* ---- point clouds: z-buffer render into cameras (mp-mvs_amd/cloud.py, tools/eval_depth.py) --- */
 /* The per-view ground-truth depth map of a scan: the handle's cloud rendered into n_views pinhole cameras with a visibility test,
  * so that the back of the scene does not shine through the gaps between front points.

@@ -2,11 +2,13 @@
 the accuracy / completeness / F1 score of a fused cloud against a ground-truth scan and the z-buffer
 render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp), and the registration of a
 cloud to a target before it is scored: point-to-point ICP with a scale on the GPU (Aligner, solve, align; csrc/pm_align.hpp,
-DESIGN.md section 15).
+DESIGN.md section 15), and the voxel-grid downsampling of a cloud on the GPU (voxel_downsample; csrc/pm_voxel.hpp, DESIGN.md
+section 16).
 
-The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
-voxelises both clouds and masks the space the scanner did not observe, so the numbers here are comparable between our own
-builds and settings, and not to the ETH3D leaderboard.  The search runs on the GPU; there is no CPU path."""
+The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
+grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
+the space the scanner did not observe, which is not available here, so the numbers are comparable between our own builds and
+settings, and not to the ETH3D leaderboard.  The search runs on the GPU; there is no CPU path."""
 import ctypes as C
 import math
 import weakref
@@ -424,7 +426,69 @@ def drop_nonfinite(xyz):
     return (a if ok.all() else a[ok]), int((~ok).sum())
 
 
-def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None):
+def voxel_downsample(xyz, voxel, normals=None, colors=None, device=0, want_map=False):
+    """mpmvs_cloud_voxel_downsample: one point per occupied cell of a grid of edge `voxel` -> {"xyz": float32 [m, 3], "count":
+    int32 [m] members per voxel, "first": int32 [m] the smallest member index; "normals" float32 [m, 3] and "colors" uint8 [m, 3]
+    when given; "voxel_of": int32 [n], the voxel of every input point (-1: a non-finite coordinate), with want_map=True}.  The
+    voxels come in the order of their first member.  The arithmetic is that of include/mpmvs.h, bit for bit."""
+    lib, f = engine.load()
+    a = _xyz(xyz)
+    n = len(a)
+    nrm = col = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, np.float32)
+        if nrm.shape != a.shape:
+            raise ValueError(f"need {a.shape} normals, got {nrm.shape}")
+    if colors is not None:
+        col = np.ascontiguousarray(colors, np.uint8)
+        if col.shape != a.shape:
+            raise ValueError(f"need {a.shape} colours, got {col.shape}")
+    vmap = np.empty(n, np.int32) if want_map else None
+    p = [C.c_void_p(None) for _ in range(5)]   # xyz, normals, rgb, count, first
+    m = f["cloud_voxel_downsample"](int(device), n, a.ctypes.data if n else None, nrm.ctypes.data if nrm is not None and n else None,
+                                    col.ctypes.data if col is not None and n else None, float(voxel), C.byref(p[0]),
+                                    C.byref(p[1]) if nrm is not None else None, C.byref(p[2]) if col is not None else None, C.byref(p[3]), C.byref(p[4]),
+                                    vmap.ctypes.data if want_map and n else None)
+    if m < 0:
+        msg = f["last_error"](None)
+        text = f"mpmvs_cloud_voxel_downsample failed ({m}): " + (msg.decode() if msg else "")
+        raise (ValueError if m in (-2, -3) else RuntimeError)(text)
+    lib.mpmvs_free.argtypes = [C.c_void_p]
+    lib.mpmvs_free.restype = None
+
+    def take(ptr, dtype, cols):
+        shape = (m, cols) if cols else (m,)
+        if not m:
+            return np.empty(shape, dtype)
+        out = np.frombuffer((C.c_char * (m * max(cols, 1) * np.dtype(dtype).itemsize)).from_address(ptr.value), dtype).reshape(shape).copy()
+        lib.mpmvs_free(ptr)
+        return out
+
+    res = {"xyz": take(p[0], np.float32, 3)}
+    if nrm is not None:
+        res["normals"] = take(p[1], np.float32, 3)
+    if col is not None:
+        res["colors"] = take(p[2], np.uint8, 3)
+    res["count"] = take(p[3], np.int32, 0)
+    res["first"] = take(p[4], np.int32, 0)
+    if want_map:
+        res["voxel_of"] = vmap
+    return res
+
+
+def last_voxel_ms(passes=False):
+    """device ms of the calling thread's last voxel_downsample (mpmvs_cloud_voxel_ms); with passes=True (total, {"insert",
+    "first", "scan", "number", "accumulate", "finish"})"""
+    _, f = engine.load()
+    total = float(f["cloud_voxel_ms"]())
+    if not passes:
+        return total
+    ms = (C.c_float * 6)()
+    f["cloud_voxel_pass_ms"](ms)
+    return total, dict(zip(("insert", "first", "scan", "number", "accumulate", "finish"), (float(v) for v in ms)))
+
+
+def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None):
     """Accuracy, completeness and F1 of a reconstructed cloud against a ground-truth cloud at every tolerance.
 
     Per tolerance t: accuracy = the share of reconstruction points whose nearest ground-truth point is within t (inclusive),
@@ -432,15 +496,26 @@ def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None):
     (0 if both are 0); also the counts, the two point totals and the mean and median of the resolved distances each way.
     Points with a non-finite coordinate are dropped and counted.
 
+    voxel (None, or a positive edge length): both clouds are resampled on a voxel grid of that edge (voxel_downsample) after the
+    non-finite points are dropped and before anything else, so that a surface does not count by how densely it was sampled
+    (Tanks and Temples uses half its tolerance); the result then also holds "voxel" and the point counts before the resampling,
+    "n_reconstruction_in" and "n_ground_truth_in".  None leaves the clouds as they are.
+
     This is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
-    voxelises and masks the space the scanner did not observe: the numbers here are comparable between our own builds and
-    settings, and not to the ETH3D leaderboard.  timings (a dict, optional) receives seconds of upload + build and of query."""
+    masks the space the scanner did not observe, which is not available here: the numbers are comparable between our own builds
+    and settings, and not to the ETH3D leaderboard.  timings (a dict, optional) receives seconds of upload + build and of query."""
     import time
     rec, drop_r = drop_nonfinite(recon_xyz)
     gt, drop_g = drop_nonfinite(gt_xyz)
     tol = [float(t) for t in tolerances]
     if not tol or not all(np.isfinite(t) and t > 0 for t in tol):
         raise ValueError("tolerances must be finite and positive")
+    if voxel is not None:
+        if not (np.isfinite(voxel) and voxel > 0):
+            raise ValueError("voxel must be finite and positive")
+        n_in = (len(rec), len(gt))
+        rec = voxel_downsample(rec, voxel, device=device)["xyz"]
+        gt = voxel_downsample(gt, voxel, device=device)["xyz"]
     t_build = [0.0]
 
     def on_level(t, n, cloud):
@@ -458,4 +533,7 @@ def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None):
     if timings is not None:
         timings["upload_build_s"] = (t1 - t0) + (t3 - t2) + t_build[0]
         timings["query_s"] = (t2 - t1) + (t4 - t3) - t_build[0]
-    return score(d_rec, d_gt, tol, (drop_r, drop_g))
+    res = score(d_rec, d_gt, tol, (drop_r, drop_g))
+    if voxel is not None:
+        res["voxel"], res["n_reconstruction_in"], res["n_ground_truth_in"] = float(voxel), n_in[0], n_in[1]
+    return res

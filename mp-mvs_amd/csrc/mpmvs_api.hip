@@ -39,6 +39,7 @@
 #include "pm_prior.hpp"
 #include "pm_viewsel.hpp"
 #include "pm_cloud.hpp"
+#include "pm_voxel.hpp"
 #include "pm_align.hpp"
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
@@ -3263,6 +3264,176 @@ float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) {
     if (!c) return 0.0f;
     if (build_ms) *build_ms = c->build_ms;
     return c->query_ms;
+}
+
+// ---------------------------------------------------------------------------
+// voxel-grid downsampling of a cloud (pm_voxel.hpp).  A stateless call: host buffers in and out, a stream
+// of its own.  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+static thread_local float g_voxel_ms = 0.0f;   // per calling thread, as g_undistort_kernel_ms
+static thread_local float g_voxel_pass_ms[6] = {0, 0, 0, 0, 0, 0};
+float mpmvs_cloud_voxel_ms(void) { return g_voxel_ms; }
+void mpmvs_cloud_voxel_pass_ms(float ms[6]) {
+    if (ms) std::memcpy(ms, g_voxel_pass_ms, sizeof g_voxel_pass_ms);
+}
+
+namespace {
+// the borders of the six passes; destroyed after the DeviceCall declared below them has synchronised its stream
+struct VoxelEvents {
+    hipEvent_t e[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~VoxelEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+// the host buffers of the result: released unless the call succeeds
+struct VoxelOut {
+    void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool keep = false;
+    ~VoxelOut() {
+        if (!keep)
+            for (void* x : p) std::free(x);
+    }
+};
+}  // namespace
+
+long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz, const float* normals, const unsigned char* rgb, float voxel, float** out_xyz,
+                                       float** out_normals, unsigned char** out_rgb, int32_t** out_count, int32_t** out_first, int32_t* out_voxel_of) {
+    if (n < 0 || (n > 0 && !xyz) || !out_xyz || !out_count || !out_first || (normals && !out_normals) || (rgb && !out_rgb))
+        return seg_fail(-2, "voxel: bad argument");
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return seg_fail(-2, "voxel: the voxel size must be finite and positive");
+    *out_xyz = nullptr, *out_count = nullptr, *out_first = nullptr;
+    if (out_normals) *out_normals = nullptr;
+    if (out_rgb) *out_rgb = nullptr;
+    if (n > INT32_MAX) return seg_fail(-3, "voxel: more than 2^31 - 1 points");
+    float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+    long long n_fin = 0;
+    for (long long i = 0; i < n; ++i) {
+        const float* p = xyz + 3 * i;
+        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = n_fin ? std::min(mn[a], p[a]) : p[a];
+            mx[a] = n_fin ? std::max(mx[a], p[a]) : p[a];
+        }
+        ++n_fin;
+    }
+    const int slots_log2 = cloud_slots_log2(n_fin);
+    if (slots_log2 > kCloudMaxSlotsLog2) return seg_fail(-3, "voxel: more than 2^29 finite points (the table would exceed 2^30 slots)");
+    VoxelGrid g;
+    voxel_origin(mn, voxel, g);
+    if (n_fin > 0)
+        for (int a = 0; a < 3; ++a) {
+            const double top = std::floor(((double)mx[a] - g.o[a]) / g.e);   // the cell of the highest point: the cells are monotonic in x
+            if (!(top < (double)kCloudAxisCells)) {
+                char msg[200];
+                std::snprintf(msg, sizeof msg, "voxel: the points span %.6g cells of edge %.6g along %c, more than 2^21 (extent / voxel = %.6g)", top + 1.0, g.e,
+                              "xyz"[a], ((double)mx[a] - (double)mn[a]) / g.e);
+                return seg_fail(-3, msg);
+            }
+        }
+    if (n_fin == 0) {   // nothing occupies a voxel: answered on the host
+        if (out_voxel_of)
+            for (long long i = 0; i < n; ++i) out_voxel_of[i] = -1;
+        g_voxel_ms = 0.0f;
+        std::memset(g_voxel_pass_ms, 0, sizeof g_voxel_pass_ms);
+        return 0;
+    }
+
+    VoxelEvents ev;
+    VoxelOut out;
+    DeviceCall call(device);
+    if (!call.ok()) return seg_fail(-100, "voxel: the device could not be selected or gave no stream");
+    const hipStream_t st = call.stream();
+    for (hipEvent_t& e : ev.e) SEGCHK(hipEventCreate(&e));
+    const size_t np = (size_t)n, slots = (size_t)1 << slots_log2;
+    const int ni = (int)n, ntiles = (ni + kScanBlock - 1) / kScanBlock;
+    float* d_xyz = call.alloc<float>(np * 12);
+    int* d_slot_of = call.alloc<int>(np * 4);
+    int* d_flag = call.alloc<int>(np * 4);
+    int* d_num = call.alloc<int>(np * 4);
+    int* d_tsum = call.alloc<int>((size_t)ntiles * 4);
+    int* d_m = call.alloc<int>(4);
+    unsigned long long* d_keys = call.alloc<unsigned long long>(slots * 8);
+    int* d_cnt = call.alloc<int>(slots * 4);
+    unsigned* d_first = call.alloc<unsigned>(slots * 4);
+    int* d_vox_of_slot = call.alloc<int>(slots * 4);
+    float* d_nrm = normals ? call.alloc<float>(np * 12) : nullptr;
+    unsigned char* d_rgb = rgb ? call.alloc<unsigned char>(np * 3) : nullptr;
+    int32_t* d_voxel_of = out_voxel_of ? call.alloc<int32_t>(np * 4) : nullptr;
+    if (!d_xyz || !d_slot_of || !d_flag || !d_num || !d_tsum || !d_m || !d_keys || !d_cnt || !d_first || !d_vox_of_slot || (normals && !d_nrm) ||
+        (rgb && !d_rgb) || (out_voxel_of && !d_voxel_of))
+        return seg_fail(-100, "voxel: no device memory");
+    SEGCHK(hipMemcpyAsync(d_xyz, xyz, np * 12, hipMemcpyHostToDevice, st));
+    if (normals) SEGCHK(hipMemcpyAsync(d_nrm, normals, np * 12, hipMemcpyHostToDevice, st));
+    if (rgb) SEGCHK(hipMemcpyAsync(d_rgb, rgb, np * 3, hipMemcpyHostToDevice, st));
+    SEGCHK(hipMemsetAsync(d_keys, 0xff, slots * 8, st));
+    SEGCHK(hipMemsetAsync(d_cnt, 0, slots * 4, st));
+    SEGCHK(hipMemsetAsync(d_first, 0xff, slots * 4, st));
+    const dim3 gp((unsigned)ntiles), blk(256);
+    SEGCHK(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_cloud_insert, gp, blk, 0, st, d_xyz, ni, g.o[0], g.o[1], g.o[2], g.e, (unsigned)(slots - 1), d_keys, d_cnt, d_slot_of);
+    SEGCHK(hipEventRecord(ev.e[1], st));
+    hipLaunchKernelGGL(k_voxel_first, gp, blk, 0, st, ni, d_slot_of, d_first);
+    SEGCHK(hipEventRecord(ev.e[2], st));
+    hipLaunchKernelGGL(k_voxel_flag, gp, blk, 0, st, ni, d_slot_of, d_first, d_flag);
+    hipLaunchKernelGGL(k_scan_tiles, gp, dim3(kScanBlock), 0, st, d_flag, ni, d_num, d_tsum);
+    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_tsum, ntiles, 0, d_m);
+    hipLaunchKernelGGL(k_vs_scan_add, gp, dim3(kScanBlock), 0, st, d_num, ni, d_tsum);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(ev.e[3], st));
+    int m = 0;
+    SEGCHK(hipMemcpyAsync(&m, d_m, 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    if (m <= 0 || (long long)m > n_fin) return seg_fail(-100, "voxel: the device counted " + std::to_string(m) + " voxels for " + std::to_string(n_fin) + " finite points");
+
+    const size_t mv = (size_t)m;
+    int32_t* d_out_first = call.alloc<int32_t>(mv * 4);
+    int32_t* d_out_count = call.alloc<int32_t>(mv * 4);
+    float* d_out_xyz = call.alloc<float>(mv * 12);
+    float* d_out_nrm = normals ? call.alloc<float>(mv * 12) : nullptr;
+    unsigned char* d_out_rgb = rgb ? call.alloc<unsigned char>(mv * 3) : nullptr;
+    // S, then N, then C: 3 x 64 bits per voxel each
+    const size_t acc_parts = 1 + (normals ? 1 : 0) + (rgb ? 1 : 0);
+    unsigned long long* d_acc = call.alloc<unsigned long long>(acc_parts * mv * 24);
+    if (!d_out_first || !d_out_count || !d_out_xyz || (normals && !d_out_nrm) || (rgb && !d_out_rgb) || !d_acc) return seg_fail(-100, "voxel: no device memory");
+    unsigned long long* d_S = d_acc;
+    unsigned long long* d_N = normals ? d_acc + 3 * mv : nullptr;
+    unsigned long long* d_C = rgb ? d_acc + 3 * mv * (normals ? 2 : 1) : nullptr;
+    out.p[0] = std::malloc(mv * 12), out.p[1] = std::malloc(mv * 4), out.p[2] = std::malloc(mv * 4);
+    if (normals) out.p[3] = std::malloc(mv * 12);
+    if (rgb) out.p[4] = std::malloc(mv * 3);
+    if (!out.p[0] || !out.p[1] || !out.p[2] || (normals && !out.p[3]) || (rgb && !out.p[4])) return seg_fail(-100, "voxel: no host memory for the result");
+    SEGCHK(hipMemsetAsync(d_acc, 0, acc_parts * mv * 24, st));
+    SEGCHK(hipEventRecord(ev.e[4], st));   // pass 4 begins here: the wait for m is not device time
+    hipLaunchKernelGGL(k_voxel_number, gp, blk, 0, st, ni, d_flag, d_num, d_slot_of, d_cnt, d_vox_of_slot, d_out_first, d_out_count);
+    SEGCHK(hipEventRecord(ev.e[5], st));
+    hipLaunchKernelGGL(k_voxel_accumulate, gp, blk, 0, st, ni, d_xyz, d_nrm, d_rgb, g, d_slot_of, d_vox_of_slot, d_S, d_N, d_C, d_voxel_of);
+    SEGCHK(hipEventRecord(ev.e[6], st));
+    hipLaunchKernelGGL(k_voxel_finish, dim3((unsigned)((mv + 255) / 256)), blk, 0, st, m, d_xyz, d_out_first, d_out_count, g, d_S, d_N, d_C, d_out_xyz, d_out_nrm,
+                       d_out_rgb);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(ev.e[7], st));
+    SEGCHK(hipMemcpyAsync(out.p[0], d_out_xyz, mv * 12, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipMemcpyAsync(out.p[1], d_out_count, mv * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipMemcpyAsync(out.p[2], d_out_first, mv * 4, hipMemcpyDeviceToHost, st));
+    if (normals) SEGCHK(hipMemcpyAsync(out.p[3], d_out_nrm, mv * 12, hipMemcpyDeviceToHost, st));
+    if (rgb) SEGCHK(hipMemcpyAsync(out.p[4], d_out_rgb, mv * 3, hipMemcpyDeviceToHost, st));
+    if (out_voxel_of) SEGCHK(hipMemcpyAsync(out_voxel_of, d_voxel_of, np * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    float ms[6] = {0, 0, 0, 0, 0, 0};
+    SEGCHK(hipEventElapsedTime(&ms[0], ev.e[0], ev.e[1]));
+    SEGCHK(hipEventElapsedTime(&ms[1], ev.e[1], ev.e[2]));
+    SEGCHK(hipEventElapsedTime(&ms[2], ev.e[2], ev.e[3]));
+    SEGCHK(hipEventElapsedTime(&ms[3], ev.e[4], ev.e[5]));
+    SEGCHK(hipEventElapsedTime(&ms[4], ev.e[5], ev.e[6]));
+    SEGCHK(hipEventElapsedTime(&ms[5], ev.e[6], ev.e[7]));
+    std::memcpy(g_voxel_pass_ms, ms, sizeof ms);
+    g_voxel_ms = ((ms[0] + ms[1]) + (ms[2] + ms[3])) + (ms[4] + ms[5]);
+    *out_xyz = (float*)out.p[0], *out_count = (int32_t*)out.p[1], *out_first = (int32_t*)out.p[2];
+    if (normals) *out_normals = (float*)out.p[3];
+    if (rgb) *out_rgb = (unsigned char*)out.p[4];
+    out.keep = true;
+    return m;
 }
 
 // ---------------------------------------------------------------------------

@@ -68,6 +68,11 @@ _EXTRA = {
     "cloud_render_depth": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, _P]),
     "cloud_render_ms": (C.c_float, [_P]),
     "cloud_render_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    # voxel-grid downsampling (cloud.py: voxel_downsample)
+    "cloud_voxel_downsample": (C.c_longlong, [C.c_int, C.c_longlong, _P, _P, _P, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P]),
+    "cloud_voxel_ms": (C.c_float, []),
+    "cloud_voxel_pass_ms": (None, [C.POINTER(C.c_float)]),
     # registration (cloud.py: Aligner, solve, align)
     "align_create": (C.c_int, [_P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
     "align_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
