@@ -515,6 +515,55 @@ float mpmvs_cloud_voxel_ms(void);
 /* the same per pass (mp-mvs_amd/csrc/pm_voxel.hpp): insert, first, flag + scan, number, accumulate, finish */
 void mpmvs_cloud_voxel_pass_ms(float ms[6]);
 
+/* ---- point clouds: k nearest neighbours and outlier removal (mp-mvs_amd/cloud.py, tools/clean_ply.py) --- */
+/* The k nearest targets of every query within a radius (mp-mvs_amd/csrc/pm_knn.hpp).
+ * DEFINED BY EQUIVALENCE with brute force, bit for bit and independent of scheduling, on the candidate rule of mpmvs_cloud_nearest:
+ *   r2 = radius * radius in fp32;  d2 = (dx*dx + dy*dy) + dz*dz in fp32, no contraction;  a target is a candidate iff all its
+ *   coordinates are finite and d2 <= r2.
+ *   q_xyz == NULL: the queries are the handle's own n points (n_q must equal n), and target i is NOT a candidate of query i.  The
+ *   exclusion is by index, not by distance: an exact duplicate of point i is a neighbour at d2 = +0.
+ *   Row i of out_d2 / out_idx (k entries each) holds the min(k, candidates) lexicographically smallest pairs (d2 bits, index) in
+ *   ascending order, the rest of the row +inf / -1.  out_within[i] = the number of ALL candidates, not capped by k.
+ *   A query with a non-finite coordinate: a row of +inf / -1 and within = 0.
+ * The call uses the handle's grids and their per-radius cache: a radius built by mpmvs_cloud_nearest or an align pass is not built
+ * again.  The queries are served in chunks of 2^23 / k (2^18 at k = 32), so the device holds at most 2^23 list entries -- 64 MB
+ * with indices -- however many queries there are.
+ * Errors: -2 = a NULL cloud or out_d2, k outside [1, MPMVS_KNN_MAX_K], n_q < 0, a NULL q_xyz with n_q != n, a radius that is not
+ * finite or <= 0; -3 = the limits of mpmvs_cloud_nearest; -100 = HIP failure.  All but -100 are found before the device is touched.
+ * n_q == 0 returns 0 and writes nothing. */
+#define MPMVS_KNN_MAX_K 32
+int mpmvs_cloud_knn(mpmvs_cloud* cloud, float radius, int k, long long n_q, const float* q_xyz /* NULL: the cloud's own points */,
+                    float* out_d2 /* n_q x k */, int32_t* out_idx /* n_q x k, may be NULL */, int32_t* out_within /* n_q, may be NULL */);
+/* device ms (HIP events) of the last mpmvs_cloud_knn call's query passes, all chunks; *build_ms (may be NULL) of the grid build it
+ * needed (0 if reused) */
+float mpmvs_cloud_knn_ms(const mpmvs_cloud* cloud, float* build_ms);
+
+/* Statistical and radius outlier removal in one pass over the self-excluded k nearest neighbours.  A stateless call like
+ * mpmvs_cloud_voxel_downsample: host buffers in and out, a stream of its own, blocks until done.  It returns the number of points
+ * kept, or a negative code.  DEFINED BY this plain loop (fp64 unless stated, no contraction):
+ *   A point TAKES PART iff its three coordinates are finite.  For point i take the answer of mpmvs_cloud_knn with q_xyz == NULL at
+ *   `radius`.  Fewer than k candidates: mean[i] = +inf (fp32), the point is ISOLATED.  Otherwise s = sqrt((double)d2_0), then
+ *   s = s + sqrt((double)d2_j) for j = 1 .. k - 1 in ascending list order, mean[i] = (float)(s / (double)k) (IEEE sqrt and quotient).
+ *   A point that does not take part has mean = +inf and within = 0.
+ *   Over the c points with a finite mean: a_i = (double)mean[i] / (double)radius;  fix(x) = llrint(x * 2^30);
+ *   S1 = sum of fix(a_i), S2 = sum of fix(a_i * a_i) in int64 (a_i is at most slightly above 1 and c <= 2^31 - 1: no overflow; the
+ *   sums are integers, so their order never shows);  den = (double)c * 2^30;  mu = (double)S1 / den;
+ *   var = max(0, (double)S2 / den - mu * mu) (the population variance);  sigma = sqrt(var);
+ *   T = (mu + std_ratio * sigma) * (double)radius, and T = +inf outright when std_ratio is +inf;  c == 0: mu = sigma = T = 0.
+ *   keep[i] = 1 iff mean[i] is finite and (double)mean[i] <= T and within[i] >= min_within (min_within = 0 switches the radius
+ *   rule off), else 0.
+ *   counts = {points taking part, c, kept};  stats = {mu * radius, sigma * radius, T}.
+ * Errors: -2 = a NULL xyz or out_keep with n > 0, a negative n, a radius that is not finite or <= 0, k outside
+ * [1, MPMVS_KNN_MAX_K], a std_ratio that is negative or NaN, min_within < 0; -3 = the limits of mpmvs_cloud_create and of a grid:
+ * n above 2^31 - 1, more than 2^29 finite points, a finite bounding box of more than 2^21 cells along an axis at this radius (the
+ * text names the axis and the ratio); -100 = HIP failure, a bad device included.  All but -100 are found before the device is
+ * touched.  n == 0, or no point that takes part, returns 0, writes an all-zero keep and launches nothing. */
+long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float radius, int k, double std_ratio, int min_within,
+                               unsigned char* out_keep /* n */, float* out_mean /* n, may be NULL */, int32_t* out_within /* n, may be NULL */,
+                               long long counts[3] /* may be NULL */, double stats[3] /* may be NULL */);
+/* device ms (HIP events) of the calling thread's last successful call: the grid build and the query passes; 0 when it launched nothing */
+float mpmvs_cloud_outliers_ms(void);
+
 /* ---- point clouds: z-buffer render into cameras (mp-mvs_amd/cloud.py, tools/eval_depth.py) --- */
 /* The per-view ground-truth depth map of a scan: the handle's cloud rendered into n_views pinhole cameras with a visibility test,
  * so that the back of the scene does not shine through the gaps between front points.

@@ -3,7 +3,8 @@ the accuracy / completeness / F1 score of a fused cloud against a ground-truth s
 render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp), and the registration of a
 cloud to a target before it is scored: point-to-point ICP with a scale on the GPU (Aligner, solve, align; csrc/pm_align.hpp,
 DESIGN.md section 15), and the voxel-grid downsampling of a cloud on the GPU (voxel_downsample; csrc/pm_voxel.hpp, DESIGN.md
-section 16).
+section 16), and the k nearest neighbours within a cloud with the statistical / radius outlier filter on top of them (Cloud.knn,
+Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
 grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
@@ -199,6 +200,35 @@ class Cloud:
         """(query ms, build ms) of the last call, device time; build ms is 0 when the grid was reused"""
         b = C.c_float(0.0)
         q = self._f["cloud_kernel_ms"](self._h, C.byref(b))
+        return float(q), float(b.value)
+
+    def knn(self, q, radius, k, want_idx=True, want_within=False):
+        """mpmvs_cloud_knn: per query the k nearest targets within `radius` -> (d2 float32 [n_q, k] ascending, idx int32 [n_q, k]);
+        rows with fewer than k candidates end in inf / -1.  idx is None with want_idx=False; with want_within=True a third
+        entry, int32 [n_q]: the number of all targets within the radius, not capped by k"""
+        return self._knn(_xyz(q), radius, k, want_idx, want_within)
+
+    def knn_self(self, radius, k, want_idx=True, want_within=False):
+        """knn() of the cloud's own points among themselves: point i is not its own neighbour (the exclusion is by index: an
+        exact duplicate of it is a neighbour at d2 = 0)"""
+        return self._knn(None, radius, k, want_idx, want_within)
+
+    def _knn(self, a, radius, k, want_idx, want_within):
+        nq, k = (self.n if a is None else len(a)), int(k)
+        cols = k if 1 <= k <= 32 else 0   # a refused k writes nothing
+        d2 = np.empty((nq, cols), np.float32)
+        idx = np.empty((nq, cols), np.int32) if want_idx else None
+        within = np.empty(nq, np.int32) if want_within else None
+        rc = self._f["cloud_knn"](self._h, float(radius), k, nq, a.ctypes.data if a is not None else None, d2.ctypes.data,
+                                  idx.ctypes.data if want_idx else None, within.ctypes.data if want_within else None)
+        if rc != 0:
+            self._raise("cloud_knn", rc)
+        return (d2, idx, within) if want_within else (d2, idx)
+
+    def knn_ms(self):
+        """(query ms, build ms) of the last knn / knn_self call, device time; build ms is 0 when the grid was reused"""
+        b = C.c_float(0.0)
+        q = self._f["cloud_knn_ms"](self._h, C.byref(b))
         return float(q), float(b.value)
 
     def render_depth(self, cams, splat=1, occl_rel=0.02, want_idx=False):
@@ -486,6 +516,51 @@ def last_voxel_ms(passes=False):
     ms = (C.c_float * 6)()
     f["cloud_voxel_pass_ms"](ms)
     return total, dict(zip(("insert", "first", "scan", "number", "accumulate", "finish"), (float(v) for v in ms)))
+
+
+def remove_outliers(xyz, radius, k=16, std_ratio=2.0, min_within=0, device=0):
+    """mpmvs_cloud_outliers: the statistical and the radius outlier filter over the k nearest neighbours of every point within
+    `radius` -> {"keep": bool [n], "mean_dist": float32 [n] the mean distance to the k nearest (inf: fewer than k within the
+    radius, or a non-finite point), "within": int32 [n] the neighbours within the radius, "counts": int64 [3] (finite points,
+    points with a finite mean distance, points kept), "stats": float64 [3] (mean, sigma, threshold of the finite mean distances)}.
+    A point stays iff its mean distance is finite and at most mean + std_ratio x sigma
+    of all finite ones, and it has at least min_within neighbours.  std_ratio=inf switches the statistical test off, min_within=0
+    the radius rule.  The arithmetic is that of include/mpmvs.h, bit for bit."""
+    _, f = engine.load()
+    a = _xyz(xyz)
+    n = len(a)
+    keep = np.zeros(n, np.uint8)
+    mean = np.full(n, np.inf, np.float32)
+    within = np.zeros(n, np.int32)
+    counts, stats = (C.c_longlong * 3)(), (C.c_double * 3)()
+    rc = f["cloud_outliers"](int(device), n, a.ctypes.data if n else None, float(radius), int(k), float(std_ratio), int(min_within),
+                             keep.ctypes.data if n else None, mean.ctypes.data if n else None, within.ctypes.data if n else None, counts, stats)
+    if rc < 0:
+        msg = f["last_error"](None)
+        text = f"mpmvs_cloud_outliers failed ({rc}): " + (msg.decode() if msg else "")
+        raise (ValueError if rc in (-2, -3) else RuntimeError)(text)
+    return {"keep": keep.astype(bool), "mean_dist": mean, "within": within, "counts": np.array(list(counts), np.int64),
+            "stats": np.array(list(stats), np.float64)}
+
+
+def last_outliers_ms():
+    """device ms of the calling thread's last remove_outliers (mpmvs_cloud_outliers_ms): the grid build and the query passes"""
+    _, f = engine.load()
+    return float(f["cloud_outliers_ms"]())
+
+
+def write_ply(path, xyz, normals=None, colors=None):
+    """the reference's 27-byte records (hostlib.write_ply: x y z nx ny nz red green blue); normals or colours that are not given
+    are written as zeros"""
+    from . import hostlib
+    a = _xyz(xyz)
+    p9 = np.zeros((len(a), 9), np.float32)
+    p9[:, 0:3] = a
+    if normals is not None:
+        p9[:, 3:6] = normals
+    if colors is not None:
+        p9[:, 6:9] = np.asarray(colors)[:, ::-1]   # the record's colour triple is held blue, green, red and written red, green, blue
+    hostlib.write_ply(path, p9)
 
 
 def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None):

@@ -40,6 +40,7 @@
 #include "pm_viewsel.hpp"
 #include "pm_cloud.hpp"
 #include "pm_voxel.hpp"
+#include "pm_knn.hpp"
 #include "pm_align.hpp"
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
@@ -3011,6 +3012,7 @@ struct mpmvs_cloud {
     long long stats[4] = {0, 0, 0, 0};
     float query_ms = 0.0f, build_ms = 0.0f;
     float render_pass_ms[3] = {0.0f, 0.0f, 0.0f};   // z-min, index, resolve of the last render call
+    float knn_ms = 0.0f, knn_build_ms = 0.0f;       // the last mpmvs_cloud_knn call
 };
 
 static void cloud_free_grid(CloudGridBuf& g) {
@@ -3046,28 +3048,45 @@ static int cloud_create_device(mpmvs_cloud* c, const float* xyz) {
     return 0;
 }
 
+// the host's pass over a cloud, shared by every entry point that builds a grid: the number of points with three finite
+// coordinates and their bounding box (mn, mx untouched when there is none)
+static long long cloud_bbox(long long n, const float* xyz, float mn[3], float mx[3]) {
+    long long n_fin = 0;
+    for (long long i = 0; i < n; ++i) {
+        const float* p = xyz + 3 * i;
+        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = n_fin ? std::min(mn[a], p[a]) : p[a];
+            mx[a] = n_fin ? std::max(mx[a], p[a]) : p[a];
+        }
+        ++n_fin;
+    }
+    return n_fin;
+}
+
+// a handle on the host side only: the count, the bounding box and the table size of n points (n <= 2^31 - 1); nullptr, with the
+// -3 text under the name `who`, beyond 2^29 finite points
+static mpmvs_cloud* cloud_new(int device, long long n, const float* xyz, const char* who) {
+    mpmvs_cloud* c = new mpmvs_cloud;
+    c->device = device;
+    c->n = n;
+    c->n_fin = cloud_bbox(n, xyz, c->mn, c->mx);
+    c->slots_log2 = cloud_slots_log2(c->n_fin);
+    if (c->slots_log2 > kCloudMaxSlotsLog2) {
+        delete c;
+        (void)seg_fail(-3, std::string(who) + ": more than 2^29 finite points (the table would exceed 2^30 slots)");
+        return nullptr;
+    }
+    return c;
+}
+
 int mpmvs_cloud_create(int device, long long n, const float* xyz, mpmvs_cloud** cloud) {
     if (!cloud) return seg_fail(-2, "cloud: bad argument");
     *cloud = nullptr;
     if (n < 0 || (n > 0 && !xyz)) return seg_fail(-2, "cloud: bad argument");
     if (n > INT32_MAX) return seg_fail(-3, "cloud: more than 2^31 - 1 points");
-    mpmvs_cloud* c = new mpmvs_cloud;
-    c->device = device;
-    c->n = n;
-    for (long long i = 0; i < n; ++i) {
-        const float* p = xyz + 3 * i;
-        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
-        for (int a = 0; a < 3; ++a) {
-            c->mn[a] = c->n_fin ? std::min(c->mn[a], p[a]) : p[a];
-            c->mx[a] = c->n_fin ? std::max(c->mx[a], p[a]) : p[a];
-        }
-        ++c->n_fin;
-    }
-    c->slots_log2 = cloud_slots_log2(c->n_fin);
-    if (c->slots_log2 > kCloudMaxSlotsLog2) {
-        delete c;
-        return seg_fail(-3, "cloud: more than 2^29 finite points (the table would exceed 2^30 slots)");
-    }
+    mpmvs_cloud* c = cloud_new(device, n, xyz, "cloud");
+    if (!c) return -3;
     const int rc = cloud_create_device(c, xyz);
     if (rc) {
         cloud_release(c);
@@ -3216,14 +3235,14 @@ static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, i
     return 0;
 }
 
-// the cell-span limit of a grid of `radius` over the handle's finite bounding box (-3), found on the host
-static int cloud_span_check(const mpmvs_cloud* c, float radius) {
+// the cell-span limit of a grid of `radius` over the handle's finite bounding box (-3), found on the host; `who` opens the text
+static int cloud_span_check(const mpmvs_cloud* c, float radius, const char* who = "cloud: the targets") {
     const double edge = cloud_edge(radius);
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < 3 && c->n_fin > 0; ++a) {
         const double cells = std::floor(((double)c->mx[a] - (double)c->mn[a]) / edge) + 1.0;
         if (cells > (double)kCloudAxisCells) {
             char msg[200];
-            std::snprintf(msg, sizeof msg, "cloud: the targets span %.6g cells of edge %.6g along %c, more than 2^21 (extent / radius = %.6g)", cells, edge,
+            std::snprintf(msg, sizeof msg, "%s span %.6g cells of edge %.6g along %c, more than 2^21 (extent / radius = %.6g)", who, cells, edge,
                           "xyz"[a], ((double)c->mx[a] - (double)c->mn[a]) / (double)radius);
             return seg_fail(-3, msg);
         }
@@ -3307,16 +3326,7 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
     if (out_rgb) *out_rgb = nullptr;
     if (n > INT32_MAX) return seg_fail(-3, "voxel: more than 2^31 - 1 points");
     float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
-    long long n_fin = 0;
-    for (long long i = 0; i < n; ++i) {
-        const float* p = xyz + 3 * i;
-        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = n_fin ? std::min(mn[a], p[a]) : p[a];
-            mx[a] = n_fin ? std::max(mx[a], p[a]) : p[a];
-        }
-        ++n_fin;
-    }
+    const long long n_fin = cloud_bbox(n, xyz, mn, mx);
     const int slots_log2 = cloud_slots_log2(n_fin);
     if (slots_log2 > kCloudMaxSlotsLog2) return seg_fail(-3, "voxel: more than 2^29 finite points (the table would exceed 2^30 slots)");
     VoxelGrid g;
@@ -3434,6 +3444,242 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
     if (rgb) *out_rgb = (unsigned char*)out.p[4];
     out.keep = true;
     return m;
+}
+
+// ---------------------------------------------------------------------------
+// k nearest neighbours within a cloud handle, and the statistical / radius outlier filter on top of them (pm_knn.hpp; DESIGN.md
+// section 17).  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+constexpr size_t kKnnChunkEntries = (size_t)1 << 23;   // list entries per launch of the list variant: 2^23 / k queries (2^18 at k = 32), whatever n_q
+
+// the binning buffers of up to `cap` queries, on a stream that outlives the call
+struct KnnBins {
+    Scratch qbin, order, qcnt, qoff, qtsum;
+    size_t cap_bins = 0;
+    explicit KnnBins(hipStream_t st) : qbin(st), order(st), qcnt(st), qoff(st), qtsum(st) {}
+    hipError_t alloc(size_t cap) {
+        int lg = 8;
+        while (lg < kCloudMaxSlotsLog2 && (1ll << lg) < (long long)cap) ++lg;
+        cap_bins = (size_t)1 << lg;
+        hipError_t e;
+        if ((e = qbin.alloc(cap * 4)) != hipSuccess || (e = order.alloc(cap * 4)) != hipSuccess || (e = qcnt.alloc(cap_bins * 4)) != hipSuccess ||
+            (e = qoff.alloc((cap_bins + 1) * 4)) != hipSuccess || (e = qtsum.alloc(cap_bins / kScanBlock * 4)) != hipSuccess)
+            return e;
+        return hipSuccess;
+    }
+};
+
+// k_cloud_qbin / scan / k_cloud_qorder over the nq <= cap queries at q: bins.order then holds the serving order
+static int knn_bin(hipStream_t st, KnnBins& b, const float* d_q, int nq, const CloudGrid& g) {
+    int lg = 8;
+    while (lg < kCloudMaxSlotsLog2 && (1ll << lg) < nq) ++lg;
+    const size_t bins = (size_t)1 << lg;   // <= b.cap_bins
+    const dim3 gq((nq + 255) / 256);
+    SEGCHK(hipMemsetAsync(b.qcnt.p, 0, bins * 4, st));
+    hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q, nq, g, (unsigned)(bins - 1), b.qcnt.as<int>(), b.qbin.as<int>());
+    cloud_scan(st, b.qcnt.as<int>(), (int)bins, b.qoff.as<int>(), b.qtsum.as<int>());
+    hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, b.qbin.as<int>(), b.qoff.as<int>(), b.qcnt.as<int>(), b.order.as<int>());
+    return 0;
+}
+
+extern "C++" {
+template <int K>
+static void knn_launch_list(hipStream_t st, const float* d_q, int nq, const int* order, const CloudGrid& g, long long self_base, int k, float* d_d2, int32_t* d_idx,
+                            int32_t* d_within) {
+    hipLaunchKernelGGL(k_knn_list<K>, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, nq, order, g, self_base, k, d_d2, d_idx, d_within);
+}
+template <int K>
+static void knn_launch_reduce(hipStream_t st, const float* d_q, int nq, const int* order, const CloudGrid& g, long long self_base, int k, float* d_mean,
+                              int32_t* d_within) {
+    hipLaunchKernelGGL(k_knn_reduce<K>, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, nq, order, g, self_base, k, d_mean, d_within);
+}
+}  // extern "C++"
+
+int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx, int32_t* out_within) {
+    if (!c || !out_d2 || n_q < 0) return seg_fail(-2, "cloud knn: bad argument");
+    if (k < 1 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "cloud knn: k must lie in [1, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
+    if (!q_xyz && n_q != c->n) return seg_fail(-2, "cloud knn: without query points n_q must be the cloud's own count");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud knn: the radius must be finite and positive");
+    if (n_q > INT32_MAX) return seg_fail(-3, "cloud knn: more than 2^31 - 1 queries");
+    if (n_q == 0) return 0;
+    const size_t nq = (size_t)n_q, kk = (size_t)k;
+    if (c->n_fin == 0) {   // no candidate anywhere
+        for (size_t e = 0; e < nq * kk; ++e) {
+            out_d2[e] = INFINITY;
+            if (out_idx) out_idx[e] = -1;
+        }
+        if (out_within) std::memset(out_within, 0, nq * 4);
+        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
+        c->knn_ms = c->knn_build_ms = 0.0f;
+        return 0;
+    }
+    const int span = cloud_span_check(c, radius);
+    if (span) return span;
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    const int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    c->knn_build_ms = c->build_ms;
+    c->knn_ms = 0.0f;
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    const CloudGrid g = cloud_grid_args(c, *grid, radius);
+    const size_t chunk = std::min(nq, kKnnChunkEntries / kk);
+    Scratch d_q(st), d_d2(st), d_idx(st), d_within(st);
+    KnnBins bins(st);
+    if (q_xyz) {
+        SEGCHK(d_q.alloc(nq * 12));
+        SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, nq * 12, hipMemcpyHostToDevice, st));
+    }
+    SEGCHK(d_d2.alloc(chunk * kk * 4));
+    if (out_idx) SEGCHK(d_idx.alloc(chunk * kk * 4));
+    if (out_within) SEGCHK(d_within.alloc(chunk * 4));
+    if (bin) SEGCHK(bins.alloc(chunk));
+    const float* d_all = q_xyz ? d_q.as<float>() : c->d_xyz;
+    for (size_t i0 = 0; i0 < nq; i0 += chunk) {
+        const int cn = (int)std::min(chunk, nq - i0);
+        const float* d_qc = d_all + 3 * i0;
+        SEGCHK(hipEventRecord(c->ev[2], st));
+        if (bin) {
+            const int brc = knn_bin(st, bins, d_qc, cn, g);
+            if (brc) return brc;
+        }
+        const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
+        const long long self_base = q_xyz ? -1ll : (long long)i0;
+        int32_t* di = out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr;
+        int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
+        switch (knn_list_size(k)) {
+            case 4: knn_launch_list<4>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
+            case 8: knn_launch_list<8>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
+            case 16: knn_launch_list<16>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
+            default: knn_launch_list<32>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
+        }
+        SEGCHK(hipGetLastError());
+        SEGCHK(hipEventRecord(c->ev[3], st));
+        SEGCHK(hipMemcpyAsync(out_d2 + i0 * kk, d_d2.p, (size_t)cn * kk * 4, hipMemcpyDeviceToHost, st));
+        if (out_idx) SEGCHK(hipMemcpyAsync(out_idx + i0 * kk, d_idx.p, (size_t)cn * kk * 4, hipMemcpyDeviceToHost, st));
+        if (out_within) SEGCHK(hipMemcpyAsync(out_within + i0, d_within.p, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
+        SEGCHK(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        SEGCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        c->knn_ms += ms;
+    }
+    return 0;
+}
+
+float mpmvs_cloud_knn_ms(const mpmvs_cloud* c, float* build_ms) {
+    if (!c) return 0.0f;
+    if (build_ms) *build_ms = c->knn_build_ms;
+    return c->knn_ms;
+}
+
+static thread_local float g_outliers_ms = 0.0f;   // per calling thread, as g_voxel_ms
+float mpmvs_cloud_outliers_ms(void) { return g_outliers_ms; }
+
+// the device half of mpmvs_cloud_outliers: a handle of the call's own (its stream, its grid), the reducing kernel over every point
+static int outliers_device(mpmvs_cloud* c, const float* xyz, float radius, int k, float* mean, int32_t* within, float* ms) {
+    int rc = cloud_create_device(c, xyz);
+    if (rc) return rc;
+    CloudGridBuf* grid = nullptr;
+    if ((rc = cloud_grid(c, radius, &grid)) != 0) return rc;
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    const CloudGrid g = cloud_grid_args(c, *grid, radius);
+    const size_t n = (size_t)c->n;
+    const int ni = (int)c->n;
+    Scratch d_mean(st), d_within(st);
+    KnnBins bins(st);
+    SEGCHK(d_mean.alloc(n * 4));
+    SEGCHK(d_within.alloc(n * 4));
+    if (bin) SEGCHK(bins.alloc(n));
+    SEGCHK(hipEventRecord(c->ev[2], st));
+    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
+    switch (knn_list_size(k)) {
+        case 4: knn_launch_reduce<4>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
+        case 8: knn_launch_reduce<8>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
+        case 16: knn_launch_reduce<16>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
+        default: knn_launch_reduce<32>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
+    }
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    SEGCHK(hipMemcpyAsync(mean, d_mean.p, n * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipMemcpyAsync(within, d_within.p, n * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    float q_ms = 0.0f;
+    SEGCHK(hipEventElapsedTime(&q_ms, c->ev[2], c->ev[3]));
+    *ms = c->build_ms + q_ms;
+    return 0;
+}
+
+long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float radius, int k, double std_ratio, int min_within, unsigned char* out_keep,
+                               float* out_mean, int32_t* out_within, long long counts[3], double stats[3]) {
+    if (n < 0 || (n > 0 && (!xyz || !out_keep))) return seg_fail(-2, "outliers: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "outliers: the radius must be finite and positive");
+    if (k < 1 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "outliers: k must lie in [1, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
+    if (!(std_ratio >= 0.0)) return seg_fail(-2, "outliers: std_ratio must not be negative or NaN");
+    if (min_within < 0) return seg_fail(-2, "outliers: min_within must not be negative");
+    if (n > INT32_MAX) return seg_fail(-3, "outliers: more than 2^31 - 1 points");
+    mpmvs_cloud* c = cloud_new(device, n, xyz, "outliers");   // the limits of mpmvs_cloud_create and of a grid, in their one place
+    if (!c) return -3;
+    const long long n_fin = c->n_fin;
+    if (cloud_span_check(c, radius, "outliers: the points")) {
+        delete c;
+        return -3;
+    }
+    if (counts) counts[0] = n_fin, counts[1] = counts[2] = 0;
+    if (stats) stats[0] = stats[1] = stats[2] = 0.0;
+    if (n_fin == 0) {   // nothing to keep: answered on the host
+        delete c;
+        for (long long i = 0; i < n; ++i) {
+            out_keep[i] = 0;
+            if (out_mean) out_mean[i] = INFINITY;
+            if (out_within) out_within[i] = 0;
+        }
+        g_outliers_ms = 0.0f;
+        return 0;
+    }
+    const size_t np = (size_t)n;
+    std::vector<float> mean_own;
+    std::vector<int32_t> within_own;
+    if (!out_mean) mean_own.resize(np);
+    if (!out_within) within_own.resize(np);
+    float* mean = out_mean ? out_mean : mean_own.data();
+    int32_t* within = out_within ? out_within : within_own.data();
+    float ms = 0.0f;
+    const int rc = outliers_device(c, xyz, radius, k, mean, within, &ms);
+    (void)enter_device(c->device);
+    cloud_release(c);
+    if (rc) return rc;
+
+    // the statistics: integer sums, so their order never shows
+    const double rd = (double)radius;
+    long long cfin = 0, S1 = 0, S2 = 0;
+    for (size_t i = 0; i < np; ++i) {
+        if (!cloud_finite(mean[i])) continue;
+        const double a = (double)mean[i] / rd;
+        S1 += llrint(a * 0x1p30);
+        S2 += llrint((a * a) * 0x1p30);
+        ++cfin;
+    }
+    double mu = 0.0, sigma = 0.0, T = 0.0;
+    if (cfin > 0) {
+        const double den = (double)cfin * 0x1p30;
+        mu = (double)S1 / den;
+        const double var = (double)S2 / den - mu * mu;
+        sigma = std::sqrt(var > 0.0 ? var : 0.0);
+        T = std::isinf(std_ratio) ? (double)INFINITY : (mu + std_ratio * sigma) * rd;
+    }
+    long long kept = 0;
+    for (size_t i = 0; i < np; ++i) {
+        const bool keep = cloud_finite(mean[i]) && (double)mean[i] <= T && within[i] >= min_within;
+        out_keep[i] = keep ? 1 : 0;
+        kept += keep ? 1 : 0;
+    }
+    if (counts) counts[1] = cfin, counts[2] = kept;
+    if (stats) stats[0] = mu * rd, stats[1] = sigma * rd, stats[2] = T;
+    g_outliers_ms = ms;
+    return kept;
 }
 
 // ---------------------------------------------------------------------------

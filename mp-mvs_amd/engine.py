@@ -73,6 +73,12 @@ _EXTRA = {
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P]),
     "cloud_voxel_ms": (C.c_float, []),
     "cloud_voxel_pass_ms": (None, [C.POINTER(C.c_float)]),
+    # k nearest neighbours and outlier removal (cloud.py: Cloud.knn, remove_outliers)
+    "cloud_knn": (C.c_int, [_P, C.c_float, C.c_int, C.c_longlong, _P, _P, _P, _P]),
+    "cloud_knn_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "cloud_outliers": (C.c_longlong, [C.c_int, C.c_longlong, _P, C.c_float, C.c_int, C.c_double, C.c_int, _P, _P, _P, C.POINTER(C.c_longlong),
+                                      C.POINTER(C.c_double)]),
+    "cloud_outliers_ms": (C.c_float, []),
     # registration (cloud.py: Aligner, solve, align)
     "align_create": (C.c_int, [_P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
     "align_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),

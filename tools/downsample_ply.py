@@ -22,7 +22,6 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: F401,E402
 
 cloud = importlib.import_module("mp-mvs_amd.cloud")
-hostlib = importlib.import_module("mp-mvs_amd.hostlib")
 
 
 def main():
@@ -40,14 +39,8 @@ def main():
     res = cloud.voxel_downsample(src["xyz"], args.voxel, normals=src.get("normals"), colors=src.get("colors"), device=args.device)
     t2 = time.perf_counter()
     m = len(res["xyz"])
-    p9 = np.zeros((m, 9), np.float32)
-    p9[:, 0:3] = res["xyz"]
-    if "normals" in res:
-        p9[:, 3:6] = res["normals"]
-    if "colors" in res:
-        p9[:, 6:9] = res["colors"][:, ::-1]   # the record's colour triple is held blue, green, red and written red, green, blue
     sys.stdout.flush()
-    hostlib.write_ply(args.output, p9)
+    cloud.write_ply(args.output, res["xyz"], res.get("normals"), res.get("colors"))
     t3 = time.perf_counter()
     print(json.dumps({"n": int(len(src["xyz"])), "m": int(m), "voxel": args.voxel, "device_ms": round(cloud.last_voxel_ms(), 4),
                       "seconds": {"read": round(t1 - t0, 4), "downsample": round(t2 - t1, 4), "write": round(t3 - t2, 4), "total": round(t3 - t0, 4)}}),
