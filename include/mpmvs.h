@@ -564,6 +564,48 @@ long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float 
 /* device ms (HIP events) of the calling thread's last successful call: the grid build and the query passes; 0 when it launched nothing */
 float mpmvs_cloud_outliers_ms(void);
 
+/* ---- point clouds: normals from the k nearest neighbours (mp-mvs_amd/cloud.py, tools/normals_ply.py) --- */
+/* A surface normal and a curvature per point of the handle's cloud, fitted to its k nearest neighbours within a radius
+ * (mp-mvs_amd/csrc/pm_normals.hpp).  DEFINED BY EQUIVALENCE with this plain loop, bit for bit and independent
+ * of scheduling.  The arithmetic is fp64 unless stated, with no contraction, and uses only + - * / sqrt fabs and comparisons; -x
+ * changes the sign bit;  max0(x) = x > 0 ? x : +0.
+ *   NEIGHBOURHOOD.  For point i = (p_0, p_1, p_2) with finite coordinates take the answer of mpmvs_cloud_knn with q_xyz == NULL at
+ *   `radius` and `k` (point i is not its own neighbour; an exact duplicate of it is).  m = min(k, within[i]);  out_within[i] is that
+ *   call's within.  A point with a non-finite coordinate has m = 0 and within = 0.
+ *   SUMS over the m list entries j in ascending list order:  e_j[a] = (double)p_idx_j[a] - (double)p_i[a] (exact: both are fp32);
+ *   s_a = sum of e_j[a];  Q_ab = sum of e_j[a] * e_j[b] for the six a <= b; the first term initialises each sum and the others are
+ *   added in list order.  C_ab = Q_ab - (s_a * s_b) / (double)(m + 1): the scatter matrix of the m neighbours and the point itself
+ *   about their mean, written about p_i so that nothing large cancels.
+ *   EIGENVECTORS by cyclic Jacobi: A = C (symmetric), V = identity; exactly 8 sweeps over the pairs (p, q) = (0,1), (0,2), (1,2), r
+ *   the third index.  A pair with a_pq == 0 is skipped.  Otherwise
+ *     theta = (a_qq - a_pp) / (2.0 * a_pq);  t = (theta < 0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+ *     c = 1.0 / sqrt(t * t + 1.0);  s = t * c;
+ *     a_pp <- a_pp - t * a_pq;  a_qq <- a_qq + t * a_pq;  a_pq <- 0;
+ *     a_rp <- c * a_rp - s * a_rq;  a_rq <- s * a_rp + c * a_rq   (both from the old values);
+ *     for each row i of V:  v_ip <- c * v_ip - s * v_iq;  v_iq <- s * v_ip + c * v_iq   (both from the old values).
+ *   PICK.  d = (a_00, a_11, a_22);  i0 = the index of the smallest d, ties to the lowest index;  d_mid = the smaller of the other
+ *   two;  tr = (max0(d_0) + max0(d_1)) + max0(d_2).
+ *   The normal is DEFINED iff m >= 2 and d_mid > 0.  Undefined -- a non-finite point, fewer than two neighbours, all neighbours on the
+ *   point or on one exact line through it -- gives out_normals = 0 0 0 and out_curvature = +inf.  A neighbourhood that is collinear
+ *   only up to rounding can pass, with an arbitrary but still deterministic normal across the line; its curvature says so (the
+ *   surface variation of a line is that of a perfect plane, 0 up to rounding, and d_mid is at the rounding level of the largest d).
+ *   Defined: n = column i0 of V;  out_curvature[i] = (float)(max0(d_i0) / tr), the "surface variation", in [0, 1/3] up to rounding.
+ *   SIGN.  Canonical: if the component of n with the largest fabs (ties: the lowest index) is < 0, n <- -n.  orient == 0: that is
+ *   all.  orient == 1: w_a = view[a] - (double)p_i[a];  dot = (n_0 * w_0 + n_1 * w_1) + n_2 * w_2;  n <- -n iff dot < 0: the normal
+ *   looks at the scanner.  orient == 2: the same with w_a = (double)ref_normals[3 i + a].  A NaN or zero dot keeps the canonical sign.
+ *   out_normals[3 i + a] = (float)n_a.
+ * The call uses the handle's grids and their per-radius cache exactly as mpmvs_cloud_knn does.  One launch serves all n points (at
+ * most 20 bytes are written per point); the reference normals, when given, are uploaded once per call.
+ * Errors: -2 = a NULL cloud or out_normals, k outside [2, MPMVS_KNN_MAX_K], a radius that is not finite or <= 0, orient outside
+ * 0..2, orient == 1 with a NULL or non-finite view, orient == 2 with NULL ref_normals; -3 = the grid's limits, as for
+ * mpmvs_cloud_knn; -100 = HIP failure.  All but -100 are found before the device is touched.  n == 0 returns 0 and writes nothing. */
+int mpmvs_cloud_normals(mpmvs_cloud* cloud, float radius, int k, int orient, const double view[3] /* orient == 1 */,
+                        const float* ref_normals /* n x 3, orient == 2 */, float* out_normals /* n x 3 */,
+                        float* out_curvature /* n, may be NULL */, int32_t* out_within /* n, may be NULL */);
+/* device ms (HIP events) of the last mpmvs_cloud_normals call's query passes (binning and kernel); *build_ms (may be NULL) of the
+ * grid build it needed (0 if reused): what mpmvs_cloud_knn_ms reports of a knn call */
+float mpmvs_cloud_normals_ms(const mpmvs_cloud* cloud, float* build_ms);
+
 /* ---- point clouds: z-buffer render into cameras (mp-mvs_amd/cloud.py, tools/eval_depth.py) --- */
 /* The per-view ground-truth depth map of a scan: the handle's cloud rendered into n_views pinhole cameras with a visibility test,
  * so that the back of the scene does not shine through the gaps between front points.

@@ -4,7 +4,8 @@ render of a cloud into cameras (Cloud.render_depth, csrc/pm_render.hpp, DESIGN.m
 cloud to a target before it is scored: point-to-point ICP with a scale on the GPU (Aligner, solve, align; csrc/pm_align.hpp,
 DESIGN.md section 15), and the voxel-grid downsampling of a cloud on the GPU (voxel_downsample; csrc/pm_voxel.hpp, DESIGN.md
 section 16), and the k nearest neighbours within a cloud with the statistical / radius outlier filter on top of them (Cloud.knn,
-Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp).
+Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp), and a surface normal per point fitted to those neighbours
+(Cloud.normals, estimate_normals; csrc/pm_normals.hpp).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
 grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
@@ -229,6 +230,45 @@ class Cloud:
         """(query ms, build ms) of the last knn / knn_self call, device time; build ms is 0 when the grid was reused"""
         b = C.c_float(0.0)
         q = self._f["cloud_knn_ms"](self._h, C.byref(b))
+        return float(q), float(b.value)
+
+    def normals(self, radius, k=16, viewpoint=None, reference=None, want_curvature=True, want_within=False):
+        """mpmvs_cloud_normals: per point the normal of the plane fitted to its k nearest neighbours within `radius` (the point
+        itself is part of the fit) -> (normals float32 [n, 3] of unit length, curvature float32 [n] or None); with want_within=True
+        a third entry, int32 [n]: the neighbours within the radius, not capped by k.  The curvature is the surface variation, the
+        smallest eigenvalue of the neighbourhood's scatter matrix over the sum of all three: 0 on a plane, at most 1/3.  A point
+        with fewer than two neighbours, with all of them on itself or on one exact line, or with a non-finite coordinate has the
+        normal 0 0 0 and the curvature inf.
+        The sign: with `viewpoint` (3 numbers) every normal looks at that point; with `reference` (float32 [n, 3], e.g. the
+        PatchMatch normals of a fused cloud) it is the one with a positive dot product with the point's reference normal;
+        with neither, the component of the largest magnitude is positive.  The arithmetic is that of include/mpmvs.h, bit for bit."""
+        if viewpoint is not None and reference is not None:
+            raise ValueError("viewpoint and reference are mutually exclusive")
+        orient, view, ref = 0, None, None
+        if viewpoint is not None:
+            view = np.ascontiguousarray(viewpoint, np.float64)
+            if view.shape != (3,):
+                raise ValueError(f"need a viewpoint of 3 numbers, got {view.shape}")
+            orient = 1
+        if reference is not None:
+            ref = np.ascontiguousarray(reference, np.float32)
+            if ref.shape != (self.n, 3):
+                raise ValueError(f"need {(self.n, 3)} reference normals, got {ref.shape}")
+            orient = 2
+        nrm = np.empty((self.n, 3), np.float32)
+        curv = np.empty(self.n, np.float32) if want_curvature else None
+        within = np.empty(self.n, np.int32) if want_within else None
+        rc = self._f["cloud_normals"](self._h, float(radius), int(k), orient, view.ctypes.data_as(_PD) if view is not None else None,
+                                      ref.ctypes.data if ref is not None else None, nrm.ctypes.data, curv.ctypes.data if want_curvature else None,
+                                      within.ctypes.data if want_within else None)
+        if rc != 0:
+            self._raise("cloud_normals", rc)
+        return (nrm, curv, within) if want_within else (nrm, curv)
+
+    def normals_ms(self):
+        """(query ms, build ms) of the last normals call, device time; build ms is 0 when the grid was reused"""
+        b = C.c_float(0.0)
+        q = self._f["cloud_normals_ms"](self._h, C.byref(b))
         return float(q), float(b.value)
 
     def render_depth(self, cams, splat=1, occl_rel=0.02, want_idx=False):
@@ -547,6 +587,13 @@ def last_outliers_ms():
     """device ms of the calling thread's last remove_outliers (mpmvs_cloud_outliers_ms): the grid build and the query passes"""
     _, f = engine.load()
     return float(f["cloud_outliers_ms"]())
+
+
+def estimate_normals(xyz, radius, k=16, viewpoint=None, reference=None, device=0):
+    """Cloud.normals over a Cloud of the call's own -> {"normals": float32 [n, 3], "curvature": float32 [n], "within": int32 [n]}"""
+    with Cloud(xyz, device) as c:
+        nrm, curv, within = c.normals(radius, k, viewpoint, reference, want_within=True)
+    return {"normals": nrm, "curvature": curv, "within": within}
 
 
 def write_ply(path, xyz, normals=None, colors=None):

@@ -41,6 +41,7 @@
 #include "pm_cloud.hpp"
 #include "pm_voxel.hpp"
 #include "pm_knn.hpp"
+#include "pm_normals.hpp"
 #include "pm_align.hpp"
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
@@ -3013,6 +3014,7 @@ struct mpmvs_cloud {
     float query_ms = 0.0f, build_ms = 0.0f;
     float render_pass_ms[3] = {0.0f, 0.0f, 0.0f};   // z-min, index, resolve of the last render call
     float knn_ms = 0.0f, knn_build_ms = 0.0f;       // the last mpmvs_cloud_knn call
+    float normals_ms = 0.0f, normals_build_ms = 0.0f;   // the last mpmvs_cloud_normals call
 };
 
 static void cloud_free_grid(CloudGridBuf& g) {
@@ -3680,6 +3682,90 @@ long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float 
     if (stats) stats[0] = mu * rd, stats[1] = sigma * rd, stats[2] = T;
     g_outliers_ms = ms;
     return kept;
+}
+
+// ---------------------------------------------------------------------------
+// a normal per point from its k nearest neighbours (pm_normals.hpp): the reducing kernel k_knn_normal over
+// every point of the handle, in one launch, as outliers_device launches k_knn_reduce.  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+extern "C++" {
+template <int K>
+static void knn_launch_normal(hipStream_t st, const float* d_xyz, int n, const int* order, const CloudGrid& g, int k, int orient, const double view[3],
+                              const float* d_ref, float* d_n, float* d_curv, int32_t* d_within) {
+    hipLaunchKernelGGL(k_knn_normal<K>, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, n, order, g, k, orient, view[0], view[1], view[2], d_ref, d_n, d_curv,
+                       d_within);
+}
+}  // extern "C++"
+
+int mpmvs_cloud_normals(mpmvs_cloud* c, float radius, int k, int orient, const double view[3], const float* ref_normals, float* out_normals, float* out_curvature,
+                        int32_t* out_within) {
+    if (!c || !out_normals) return seg_fail(-2, "cloud normals: bad argument");
+    if (k < 2 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "cloud normals: k must lie in [2, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud normals: the radius must be finite and positive");
+    if (orient < 0 || orient > 2) return seg_fail(-2, "cloud normals: orient must be 0 (canonical), 1 (viewpoint) or 2 (reference normals)");
+    if (orient == 1 && !(view && std::isfinite(view[0]) && std::isfinite(view[1]) && std::isfinite(view[2])))
+        return seg_fail(-2, "cloud normals: orient 1 needs a finite viewpoint");
+    if (orient == 2 && !ref_normals) return seg_fail(-2, "cloud normals: orient 2 needs reference normals");
+    if (c->n == 0) return 0;
+    const size_t n = (size_t)c->n;
+    if (c->n_fin == 0) {   // no candidate anywhere: every normal is undefined
+        std::memset(out_normals, 0, n * 12);
+        for (size_t i = 0; i < n && out_curvature; ++i) out_curvature[i] = INFINITY;
+        if (out_within) std::memset(out_within, 0, n * 4);
+        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
+        c->normals_ms = c->normals_build_ms = 0.0f;
+        return 0;
+    }
+    const int span = cloud_span_check(c, radius);
+    if (span) return span;
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    c->normals_build_ms = c->build_ms;
+    c->normals_ms = 0.0f;
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    const CloudGrid g = cloud_grid_args(c, *grid, radius);
+    const int ni = (int)c->n;
+    const double no_view[3] = {0.0, 0.0, 0.0};
+    const double* v = orient == 1 ? view : no_view;
+    Scratch d_n(st), d_curv(st), d_within(st), d_ref(st);
+    KnnBins bins(st);
+    SEGCHK(d_n.alloc(n * 12));
+    if (out_curvature) SEGCHK(d_curv.alloc(n * 4));
+    if (out_within) SEGCHK(d_within.alloc(n * 4));
+    if (orient == 2) {
+        SEGCHK(d_ref.alloc(n * 12));
+        SEGCHK(hipMemcpyAsync(d_ref.p, ref_normals, n * 12, hipMemcpyHostToDevice, st));
+    }
+    if (bin) SEGCHK(bins.alloc(n));
+    SEGCHK(hipEventRecord(c->ev[2], st));
+    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
+    const float* dr = orient == 2 ? d_ref.as<float>() : (const float*)nullptr;
+    float* dc = out_curvature ? d_curv.as<float>() : (float*)nullptr;
+    int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
+    switch (knn_list_size(k)) {
+        case 4: knn_launch_normal<4>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
+        case 8: knn_launch_normal<8>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
+        case 16: knn_launch_normal<16>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
+        default: knn_launch_normal<32>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
+    }
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    SEGCHK(hipMemcpyAsync(out_normals, d_n.p, n * 12, hipMemcpyDeviceToHost, st));
+    if (out_curvature) SEGCHK(hipMemcpyAsync(out_curvature, d_curv.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_within) SEGCHK(hipMemcpyAsync(out_within, d_within.p, n * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    SEGCHK(hipEventElapsedTime(&c->normals_ms, c->ev[2], c->ev[3]));
+    return 0;
+}
+
+float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) {
+    if (!c) return 0.0f;
+    if (build_ms) *build_ms = c->normals_build_ms;
+    return c->normals_ms;
 }
 
 // ---------------------------------------------------------------------------

@@ -79,6 +79,9 @@ _EXTRA = {
     "cloud_outliers": (C.c_longlong, [C.c_int, C.c_longlong, _P, C.c_float, C.c_int, C.c_double, C.c_int, _P, _P, _P, C.POINTER(C.c_longlong),
                                       C.POINTER(C.c_double)]),
     "cloud_outliers_ms": (C.c_float, []),
+    # normals from the k nearest neighbours (cloud.py: Cloud.normals, estimate_normals)
+    "cloud_normals": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, _P, _P]),
+    "cloud_normals_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
     # registration (cloud.py: Aligner, solve, align)
     "align_create": (C.c_int, [_P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
     "align_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
