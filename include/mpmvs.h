@@ -685,9 +685,60 @@ int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long
 int mpmvs_align_solve(const long long sums[18], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse);
 int mpmvs_align_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M_inout[12], long long* iters,
                     long long* inliers, double* rmse);
-/* device ms (HIP events) of the last pass: binning + kernel; 0 when the pass launched nothing */
+/* device ms (HIP events) of the last pass of either kind (point-to-point or point-to-plane): binning + kernel; 0 when the pass
+ * launched nothing */
 float mpmvs_align_ms(const mpmvs_align* h);
 void mpmvs_align_destroy(mpmvs_align* h);
+
+/* Point-to-plane ICP on the same handle (mp-mvs_amd/csrc/pm_align_plane.hpp, pm_align_host.hpp): the
+ * residual of a pair is its distance along the TARGET's normal, so a source may slide along a surface whose samples are not its
+ * own -- what point-to-point ICP cannot do when the two clouds sample the same surfaces at different points.  The calls above
+ * are untouched by these: both kinds of pass may be mixed on one handle.
+ * TARGET NORMALS.  mpmvs_align_set_normals takes n_t x 3 floats in the target's caller order (n_t = the count the target handle
+ * was created with; e.g. the output of mpmvs_cloud_normals) and uploads them once onto the ALIGN handle, which owns the buffer; the
+ * target handle is untouched, so two align handles on one target may hold different normals.  A second call replaces them, NULL
+ * drops them.  Neither the sign nor the length of a normal matters.
+ * THE PASS IS DEFINED BY EQUIVALENCE with this plain loop, bit for bit and independent of scheduling.  The frame, y, (d2, j), a, b
+ * and iu are exactly those of mpmvs_align_sums, and a source is skipped for the same reasons as there.  It is also skipped when
+ * the normal of target j is unusable:  n = (double)nrm_j,  q = (n0*n0 + n1*n1) + n2*n2;  unusable iff q is not finite or q == 0
+ * (the undefined 0 0 0 of mpmvs_cloud_normals drops out here).  Otherwise, in fp64 without contraction, with + - * / sqrt only:
+ *     nh_k = n_k / sqrt(q);   e = a - b;   r = (e0*nh0 + e1*nh1) + e2*nh2;
+ *     c = a x nh:  c0 = a1*nh2 - a2*nh1,  c1 = a2*nh0 - a0*nh2,  c2 = a0*nh1 - a1*nh0;   g = (a0*nh0 + a1*nh1) + a2*nh2;
+ *     J = (c0, c1, c2, nh0, nh1, nh2, g)
+ *   and with fix as above the matched source adds
+ *     1 to sums[0];  fix(J_i * J_j) for i <= j, row by row (00 01 .. 06 11 12 .. 66), to sums[1..28];  fix(J_i * r) to sums[29 + i];
+ *     fix(r * r) to sums[36];  fix((double)d2 * (iu * iu)) to sums[37].
+ *   OVERFLOW.  |a_k| <= 1 as above and |nh_k| <= 1, so |c_k| <= sqrt 2 and |g| <= sqrt 3.  A matched y is within
+ *   radius (1 + 4 * 2^-24) of its target along every axis and u >= 2 radius, so |e_k| <= (1 + 4 * 2^-24) / 2 and |r| < 0.87.
+ *   Every |term| is at most 3 up to rounding and strictly below 4; at most 2^31 - 1 sources contribute, so every
+ *   |sum| <= 2^32 (2^31 - 1) < 2^63.
+ *   SIGN.  Negating a normal negates nh, c, g and r exactly, and every term is a product of two of them: flipping any or all of the
+ *   normals leaves all 38 sums unchanged in every bit.
+ * THE SOLVE is host code and never touches a device: one Gauss-Newton step in the normalised frame.  s = 2^-30;  H = J^T J (7 x 7,
+ * symmetric) from sums[1..28] * s and gvec = J^T r from sums[29..35] * s;  m = 7 with scale, else the leading 6;  H x = -gvec by
+ * LDL^T without pivoting, x = (omega[3], t[3], sigma);  pivot j is d_j = H_jj - sum over k < j of L_jk^2 d_k.  It returns 1 and sets
+ * M_out = M_in when fewer than m pairs matched, when a pivot is not finite, when a pivot is <= 2^-20 times the diagonal entry H_jj
+ * it started from (a direction the pairs do not observe: one plane, two parallel planes, the scale about the apex of a three-plane
+ * corner; the rounding of a sum is at most n 2^-31 against a diagonal of n mean(J_j^2), so a pivot that small is rounding), or when,
+ * with scale, 1 + sigma is not a positive finite number.  Otherwise R = the rotation of the unit quaternion
+ * (1, omega / 2) / |(1, omega / 2)| -- a proper rotation for every omega, with one sqrt --, c = 1 + sigma (1 without scale), and the
+ * update maps back and composes exactly as in mpmvs_align_solve:  D = [c R | o - c R o + u t],  M_out = D * M_in.
+ * *rmse_plane = sqrt(sums[36] / 2^30 / n) * u and *rmse_point = sqrt(sums[37] / 2^30 / n) * u: the RMS distance of the matched pairs
+ * along the normals, and between the points, BEFORE the update (0 if n = 0).  Either pointer may be NULL.
+ * THE ICP CALL is the loop of the two calls above and nothing else, with the stop rule and the failure semantics of mpmvs_align_icp
+ * word for word: it stops after the solve whose update D moves none of the 8 corners o +- u by more than eps, after max_iter passes,
+ * or at a solve that returns 1; *iters, *inliers (sums[0]), *rmse_plane and *rmse_point are those of the last pass (each may be
+ * NULL); its M equals the caller's own loop over the two calls in every bit; a pass that fails inside the loop returns its code at
+ * once, M_inout holds the transform that pass was given, and the four outputs are not written.
+ * Errors: as for the point-to-point calls; in addition a plane pass or plane ICP on a handle without normals returns -2 before the
+ * device is touched.  n_s == 0 gives all-zero sums, a target without a finite point all-zero sums and an all-zero frame; neither
+ * launches anything.  mpmvs_align_set_normals: -2 = a NULL handle, -100 = HIP failure. */
+int mpmvs_align_set_normals(mpmvs_align* h, const float* nrm /* n_t x 3, or NULL: drop them */);
+int mpmvs_align_plane_sums(mpmvs_align* h, float radius, const double M[12], long long sums[38], double frame[4]);
+int mpmvs_align_plane_solve(const long long sums[38], const double frame[4], int with_scale, const double M_in[12], double M_out[12],
+                            double* rmse_plane, double* rmse_point);
+int mpmvs_align_plane_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M_inout[12], long long* iters,
+                          long long* inliers, double* rmse_plane, double* rmse_point);
 
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and

@@ -5,7 +5,9 @@ cloud to a target before it is scored: point-to-point ICP with a scale on the GP
 DESIGN.md section 15), and the voxel-grid downsampling of a cloud on the GPU (voxel_downsample; csrc/pm_voxel.hpp, DESIGN.md
 section 16), and the k nearest neighbours within a cloud with the statistical / radius outlier filter on top of them (Cloud.knn,
 Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp), and a surface normal per point fitted to those neighbours
-(Cloud.normals, estimate_normals; csrc/pm_normals.hpp).
+(Cloud.normals, estimate_normals; csrc/pm_normals.hpp), and point-to-plane ICP on those normals beside the
+point-to-point one (Aligner.set_normals / plane_sums / plane_icp, plane_solve, align(method="plane"); csrc/pm_align_plane.hpp,
+DESIGN.md section 19).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
 grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
@@ -372,8 +374,41 @@ class Aligner:
         return m.reshape(3, 4), int(it.value), int(inl.value), float(rmse.value)
 
     def ms(self):
-        """device ms of the last pass: binning + kernel"""
+        """device ms of the last pass of either kind: binning + kernel"""
         return float(self._f["align_ms"](self._h))
+
+    def set_normals(self, normals):
+        """mpmvs_align_set_normals: one normal per target point (float32 [target.n, 3], the target's order; any sign, any
+        length; 0 0 0, NaN and inf mark a target that takes no part) for the point-to-plane pass, uploaded once onto this
+        handle.  None drops them."""
+        a = None
+        if normals is not None:
+            a = np.ascontiguousarray(normals, np.float32)
+            if a.shape != (self.target.n, 3):
+                raise ValueError(f"need {(self.target.n, 3)} target normals, got {a.shape}")
+        rc = self._f["align_set_normals"](self._h, a.ctypes.data if a is not None else None)
+        if rc != 0:
+            self.target._raise("align_set_normals", rc)
+
+    def plane_sums(self, radius, M):
+        """one point-to-plane pass (mpmvs_align_plane_sums) at the transform M: (sums int64 [38], frame float64 [4])"""
+        m = _m12(M)
+        sums, frame = np.zeros(38, np.int64), np.zeros(4, np.float64)
+        rc = self._f["align_plane_sums"](self._h, float(radius), m.ctypes.data_as(_PD), sums.ctypes.data_as(_PL), frame.ctypes.data_as(_PD))
+        if rc != 0:
+            self.target._raise("align_plane_sums", rc)
+        return sums, frame
+
+    def plane_icp(self, radius, M, with_scale=True, max_iter=30, eps=0.0):
+        """mpmvs_align_plane_icp from the transform M: (M float64 [3, 4], passes run, inliers, rmse_plane and rmse_point of the
+        last pass)"""
+        m = _m12(M).copy()
+        it, inl, rp, rq = C.c_longlong(0), C.c_longlong(0), C.c_double(0.0), C.c_double(0.0)
+        rc = self._f["align_plane_icp"](self._h, float(radius), 1 if with_scale else 0, int(max_iter), float(eps), m.ctypes.data_as(_PD), C.byref(it),
+                                        C.byref(inl), C.byref(rp), C.byref(rq))
+        if rc != 0:
+            self.target._raise("align_plane_icp", rc)
+        return m.reshape(3, 4), int(it.value), int(inl.value), float(rp.value), float(rq.value)
 
 
 def solve(sums, frame, M, with_scale=True):
@@ -424,22 +459,77 @@ def icp_loop(pass_fn, radius, M, with_scale=True, max_iter=30, eps=0.0):
     return M, passes, inliers, rmse
 
 
-def align(source_xyz, target_cloud, T0=None, radii=None, with_scale=True, max_iter=30, eps=None):
+def plane_solve(sums, frame, M, with_scale=True):
+    """mpmvs_align_plane_solve (host code, no GPU): (status, M_out float64 [3, 4], rmse_plane, rmse_point).  status 1: fewer pairs
+    than unknowns (7 with scale, 6 without), a direction the pairs do not observe (a pivot at or below 2^-20 of its diagonal
+    entry: one plane, parallel planes, the scale about the apex of a three-plane corner) or a scale that is not positive; M_out
+    is M then."""
+    _, f = engine.load()
+    s = np.ascontiguousarray(sums, np.int64)
+    fr = np.ascontiguousarray(frame, np.float64)
+    if s.shape != (38,) or fr.shape != (4,):
+        raise ValueError("need 38 sums and a frame of 4")
+    m, out, rp, rq = _m12(M), np.zeros(12, np.float64), C.c_double(0.0), C.c_double(0.0)
+    rc = f["align_plane_solve"](s.ctypes.data_as(_PL), fr.ctypes.data_as(_PD), 1 if with_scale else 0, m.ctypes.data_as(_PD), out.ctypes.data_as(_PD),
+                                C.byref(rp), C.byref(rq))
+    if rc < 0:
+        raise ValueError(f"mpmvs_align_plane_solve failed ({rc})")
+    return rc, out.reshape(3, 4), float(rp.value), float(rq.value)
+
+
+def plane_icp_loop(pass_fn, radius, M, with_scale=True, max_iter=30, eps=0.0):
+    """the loop mpmvs_align_plane_icp is defined as, over the two public calls: pass_fn(radius, M) -> (sums, frame) is
+    Aligner.plane_sums (or the numpy statement in the tests).  Returns what Aligner.plane_icp returns, bit for bit."""
+    M = _m12(M).reshape(3, 4).copy()
+    passes, inliers, rmse_plane, rmse_point = 0, 0, 0.0, 0.0
+    for _ in range(int(max_iter)):
+        sums, frame = pass_fn(radius, M)
+        passes += 1
+        inliers = int(sums[0])
+        rc, M_out, rmse_plane, rmse_point = plane_solve(sums, frame, M, with_scale)
+        if rc == 1:
+            break
+        M = M_out
+        if update_move(plane_solve(sums, frame, IDENTITY34, with_scale)[1], frame) <= eps:
+            break
+    return M, passes, inliers, rmse_plane, rmse_point
+
+
+def align(source_xyz, target_cloud, T0=None, radii=None, with_scale=True, max_iter=30, eps=None, method="point", target_normals=None,
+          normal_radius=None, normal_k=16):
     """Refines the transform T0 (4 x 4, identity if None) that takes `source_xyz` into the frame of `target_cloud` (a Cloud) by
-    point-to-point ICP in coarse-to-fine rounds: one Aligner.icp per radius of `radii`, in descending order, each starting from
+    ICP in coarse-to-fine rounds: one Aligner.icp per radius of `radii`, in descending order, each starting from
     the result of the one before.  Returns (T float64 [4, 4], report), report = a list of {"radius", "passes", "inliers", "rmse"}
     per round.  `radii` has no default: it is a property of the scene (tools/eval_ply.py derives it from its tolerances).
     eps=None means 2^-20 of the frame's unit u, the power of two that covers half the target's bounding box plus two radii: a
-    round ends when an update moves no corner of that box by more than a millionth of its size."""
+    round ends when an update moves no corner of that box by more than a millionth of its size.
+    method="point" is point-to-point ICP; method="plane" is point-to-plane ICP (Aligner.plane_icp, section
+    19), which measures each pair along the target's normal and so does not hold a source to samples that are not its own.  Its
+    normals are `target_normals` (float32 [target_cloud.n, 3]) or, if None, target_cloud.normals(normal_radius, normal_k);
+    normal_radius is then required.  Each report row gains "rmse_plane", and "rmse" stays the point-to-point figure."""
     if radii is None or len(radii) == 0:
         raise ValueError("align needs the radii of its rounds")
+    if method not in ("point", "plane"):
+        raise ValueError(f"align knows the methods 'point' and 'plane', not {method!r}")
+    if method == "point" and (target_normals is not None or normal_radius is not None):
+        raise ValueError("target_normals and normal_radius belong to method='plane'")
     rad = sorted((float(r) for r in radii), reverse=True)
     T = np.eye(4) if T0 is None else np.array(T0, np.float64)
     M = _m12(T).reshape(3, 4)
     report = []
+    if method == "plane" and target_normals is None:
+        if normal_radius is None:
+            raise ValueError("method='plane' needs target_normals or a normal_radius to estimate them with")
+        target_normals = target_cloud.normals(normal_radius, normal_k, want_curvature=False)[0]
     with Aligner(target_cloud, source_xyz) as al:
+        if method == "plane":
+            al.set_normals(target_normals)
         for r in rad:
             e = float(target_cloud.frame(r)[3]) * 2.0 ** -20 if eps is None else eps
+            if method == "plane":
+                M, passes, inliers, rmse_plane, rmse = al.plane_icp(r, M, with_scale, max_iter, e)
+                report.append({"radius": r, "passes": passes, "inliers": inliers, "rmse": rmse, "rmse_plane": rmse_plane})
+                continue
             M, passes, inliers, rmse = al.icp(r, M, with_scale, max_iter, e)
             report.append({"radius": r, "passes": passes, "inliers": inliers, "rmse": rmse})
     T = np.eye(4)

@@ -43,6 +43,7 @@
 #include "pm_knn.hpp"
 #include "pm_normals.hpp"
 #include "pm_align.hpp"
+#include "pm_align_plane.hpp"
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
 #include "pm_ingest.hpp"
@@ -3770,13 +3771,16 @@ float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) {
 
 // ---------------------------------------------------------------------------
 // registration of a moving cloud to a target handle: the ICP pass and its closed-form solve (pm_align.hpp, pm_align_host.hpp;
-// DESIGN.md section 15).  Errors are reported like those of mpmvs_cloud_*.
+// DESIGN.md section 15), and the point-to-plane pass and its Gauss-Newton step beside them (pm_align_plane.hpp; section 19).
+// Errors are reported like those of mpmvs_cloud_*.
 // ---------------------------------------------------------------------------
 struct mpmvs_align {
     mpmvs_cloud* target = nullptr;   // borrowed: its stream, grids and points serve every pass
     long long n = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     float* d_src = nullptr;
+    float* d_nrm = nullptr;   // a normal per target, caller order (mpmvs_align_set_normals); owned by this handle
+    bool has_nrm = false;     // also true for normals of a target without points
     int *d_qbin = nullptr, *d_order = nullptr, *d_qcnt = nullptr, *d_qoff = nullptr, *d_qtsum = nullptr;
     unsigned long long* d_sums = nullptr;
     size_t bins = 0;
@@ -3785,7 +3789,7 @@ struct mpmvs_align {
 
 static void align_release(mpmvs_align* h) {
     if (h->target->stream) (void)hipStreamSynchronize(h->target->stream);
-    for (void* p : {(void*)h->d_src, (void*)h->d_qbin, (void*)h->d_order, (void*)h->d_qcnt, (void*)h->d_qoff, (void*)h->d_qtsum, (void*)h->d_sums})
+    for (void* p : {(void*)h->d_src, (void*)h->d_nrm, (void*)h->d_qbin, (void*)h->d_order, (void*)h->d_qcnt, (void*)h->d_qoff, (void*)h->d_qtsum, (void*)h->d_sums})
         if (p) (void)pool_free(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3804,7 +3808,7 @@ static int align_create_device(mpmvs_align* h, const float* s_xyz) {
     SEGCHK(pool_malloc(&h->d_qcnt, h->bins * 4));
     SEGCHK(pool_malloc(&h->d_qoff, (h->bins + 1) * 4));
     SEGCHK(pool_malloc(&h->d_qtsum, h->bins / kScanBlock * 4));
-    SEGCHK(pool_malloc(&h->d_sums, kAlignTerms * 8));
+    SEGCHK(pool_malloc(&h->d_sums, kAlignPlaneTerms * 8));   // the larger of the two passes' sums
     SEGCHK(hipMemcpyAsync(h->d_src, s_xyz, n * 12, hipMemcpyHostToDevice, st));
     SEGCHK(hipStreamSynchronize(st));
     return 0;
@@ -3839,7 +3843,8 @@ void mpmvs_align_destroy(mpmvs_align* h) {
 float mpmvs_align_ms(const mpmvs_align* h) { return h ? h->pass_ms : 0.0f; }
 
 // the device half of a pass: the grid of `radius` (cached per radius in the target), the binning, the kernel, 18 integers back
-static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, long long sums[18]) {
+// (plane: the point-to-plane kernel, 38 integers)
+static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, bool plane, long long* sums) {
     mpmvs_cloud* c = h->target;
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries();
@@ -3849,7 +3854,8 @@ static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, long long 
     if (rc) return rc;
     const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const int n = (int)h->n;
-    SEGCHK(hipMemsetAsync(h->d_sums, 0, kAlignTerms * 8, st));
+    const size_t sums_bytes = (size_t)(plane ? kAlignPlaneTerms : kAlignTerms) * 8;
+    SEGCHK(hipMemsetAsync(h->d_sums, 0, sums_bytes, st));
     if (bin) SEGCHK(hipMemsetAsync(h->d_qcnt, 0, h->bins * 4, st));
     SEGCHK(hipEventRecord(h->ev[0], st));
     const dim3 gq(((unsigned)n + 255u) / 256u);   // unsigned: n may be 2^31 - 1
@@ -3858,10 +3864,14 @@ static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, long long 
         cloud_scan(st, h->d_qcnt, (int)h->bins, h->d_qoff, h->d_qtsum);
         hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, n, h->d_qbin, h->d_qoff, h->d_qcnt, h->d_order);
     }
-    hipLaunchKernelGGL(k_align_pass, gq, dim3(256), 0, st, h->d_src, n, bin ? h->d_order : (const int*)nullptr, f, g, c->d_xyz, h->d_sums);
+    const int* order = bin ? h->d_order : (const int*)nullptr;
+    if (plane)
+        hipLaunchKernelGGL(k_align_plane_pass, gq, dim3(256), 0, st, h->d_src, n, order, f, g, c->d_xyz, h->d_nrm, h->d_sums);
+    else
+        hipLaunchKernelGGL(k_align_pass, gq, dim3(256), 0, st, h->d_src, n, order, f, g, c->d_xyz, h->d_sums);
     SEGCHK(hipGetLastError());
     SEGCHK(hipEventRecord(h->ev[1], st));
-    SEGCHK(hipMemcpyAsync(sums, h->d_sums, kAlignTerms * 8, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipMemcpyAsync(sums, h->d_sums, sums_bytes, hipMemcpyDeviceToHost, st));
     SEGCHK(hipStreamSynchronize(st));
     SEGCHK(hipEventElapsedTime(&h->pass_ms, h->ev[0], h->ev[1]));
     return 0;
@@ -3873,12 +3883,14 @@ static bool align_finite12(const double M[12]) {
     return true;
 }
 
-int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long sums[18], double frame[4]) {
+// a pass of either kind: the checks, the frame, and the cases that launch nothing
+static int align_sums_any(mpmvs_align* h, float radius, const double M[12], bool plane, long long* sums, double frame[4]) {
     if (!h || !M || !sums || !frame) return seg_fail(-2, "align: bad argument");
     if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
     if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
+    if (plane && !h->has_nrm) return seg_fail(-2, "align: a point-to-plane pass needs mpmvs_align_set_normals first");
     const mpmvs_cloud* c = h->target;
-    for (int k = 0; k < kAlignTerms; ++k) sums[k] = 0;
+    for (int k = 0; k < (plane ? kAlignPlaneTerms : kAlignTerms); ++k) sums[k] = 0;
     for (int k = 0; k < 4; ++k) frame[k] = 0.0;
     h->pass_ms = 0.0f;
     if (c->n_fin == 0) return 0;   // no candidate anywhere, and no bounding box to take a frame from
@@ -3890,7 +3902,68 @@ int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long
     for (int k = 0; k < 12; ++k) f.m[k] = M[k];
     for (int k = 0; k < 3; ++k) f.o[k] = frame[k];
     f.iu = 1.0 / frame[3];
-    return align_pass(h, radius, f, sums);
+    return align_pass(h, radius, f, plane, sums);
+}
+
+int mpmvs_align_sums(mpmvs_align* h, float radius, const double M[12], long long sums[18], double frame[4]) {
+    return align_sums_any(h, radius, M, false, sums, frame);
+}
+
+int mpmvs_align_set_normals(mpmvs_align* h, const float* nrm) {
+    if (!h) return seg_fail(-2, "align: bad argument");
+    mpmvs_cloud* c = h->target;
+    SEGCHK(enter_device(c->device));
+    SEGCHK(hipStreamSynchronize(c->stream));   // no pass is reading the buffer that goes
+    h->has_nrm = false;
+    if (h->d_nrm) {
+        SEGCHK(pool_free(h->d_nrm));
+        h->d_nrm = nullptr;
+    }
+    if (!nrm) return 0;
+    if (c->n > 0) {
+        SEGCHK(pool_malloc(&h->d_nrm, (size_t)c->n * 12));
+        SEGCHK(hipMemcpyAsync(h->d_nrm, nrm, (size_t)c->n * 12, hipMemcpyHostToDevice, c->stream));
+        SEGCHK(hipStreamSynchronize(c->stream));
+    }
+    h->has_nrm = true;
+    return 0;
+}
+
+int mpmvs_align_plane_sums(mpmvs_align* h, float radius, const double M[12], long long sums[38], double frame[4]) {
+    return align_sums_any(h, radius, M, true, sums, frame);
+}
+
+int mpmvs_align_plane_solve(const long long sums[38], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse_plane,
+                            double* rmse_point) {
+    if (!sums || !frame || !M_in || !M_out) return seg_fail(-2, "align: bad argument");
+    return align_plane_solve(sums, frame, with_scale, M_in, M_out, rmse_plane, rmse_point);
+}
+
+int mpmvs_align_plane_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M[12], long long* iters, long long* inliers,
+                          double* rmse_plane, double* rmse_point) {
+    if (!h || !M) return seg_fail(-2, "align: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
+    if (max_iter < 1) return seg_fail(-2, "align: max_iter must be at least 1");
+    if (!(eps >= 0.0)) return seg_fail(-2, "align: eps must not be negative");
+    if (!h->has_nrm) return seg_fail(-2, "align: point-to-plane ICP needs mpmvs_align_set_normals first");
+    long long n_pass = 0, sums[kAlignPlaneTerms] = {0};
+    double frame[4], last_plane = 0.0, last_point = 0.0;
+    for (int it = 0; it < max_iter; ++it) {
+        const int rc = mpmvs_align_plane_sums(h, radius, M, sums, frame);
+        if (rc < 0) return rc;
+        ++n_pass;
+        double D[12], next[12];
+        if (align_plane_update(sums, frame, with_scale, D, &last_plane, &last_point)) break;
+        align_compose(D, M, next);
+        for (int k = 0; k < 12; ++k) M[k] = next[k];   // one that left the finite numbers is refused by the next pass, as in the caller's own loop
+        if (align_move(D, frame) <= eps) break;
+    }
+    if (iters) *iters = n_pass;
+    if (inliers) *inliers = sums[0];
+    if (rmse_plane) *rmse_plane = last_plane;
+    if (rmse_point) *rmse_point = last_point;
+    return 0;
 }
 
 int mpmvs_align_solve(const long long sums[18], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse) {

@@ -88,9 +88,10 @@ __global__ __launch_bounds__(256) void k_align_qbin(const float* __restrict__ sr
 }
 
 // the matched pair of the source thread j serves (order[j], or j itself when order is null) in the normalised frame: a, b and
-// dn = d2 / u^2; false for a skipped source.  txyz: the target's points in caller order (the index the search returns addresses them).
-__host__ __device__ inline bool align_pair_one(size_t j, const float* __restrict__ src, const int* __restrict__ order, const AlignXf& f, const CloudGrid& g,
-                                               const float* __restrict__ txyz, double a[3], double b[3], double& dn) {
+// dn = d2 / u^2; false for a skipped source.  txyz: the target's points in caller order (the index the search returns addresses them);
+// t: that index (the point-to-plane pass of pm_align_plane.hpp gathers the target's normal with it).
+__host__ __device__ inline bool align_match_one(size_t j, const float* __restrict__ src, const int* __restrict__ order, const AlignXf& f, const CloudGrid& g,
+                                                const float* __restrict__ txyz, double a[3], double b[3], double& dn, size_t& t) {
     const size_t i = order ? (size_t)order[j] : j;
     float x, y, z;
     int cx, cy, cz;
@@ -98,11 +99,16 @@ __host__ __device__ inline bool align_pair_one(size_t j, const float* __restrict
     const unsigned long long best = cloud_search(x, y, z, cx, cy, cz, g);
     if (best == ~0ull) return false;
     const float d2 = cloud_float((uint32_t)(best >> 32));
-    const size_t t = (size_t)(uint32_t)(best & 0xffffffffull);
+    t = (size_t)(uint32_t)(best & 0xffffffffull);
     a[0] = ((double)x - f.o[0]) * f.iu, a[1] = ((double)y - f.o[1]) * f.iu, a[2] = ((double)z - f.o[2]) * f.iu;
     b[0] = ((double)txyz[3 * t] - f.o[0]) * f.iu, b[1] = ((double)txyz[3 * t + 1] - f.o[1]) * f.iu, b[2] = ((double)txyz[3 * t + 2] - f.o[2]) * f.iu;
     dn = (double)d2 * (f.iu * f.iu);
     return true;
+}
+__host__ __device__ inline bool align_pair_one(size_t j, const float* __restrict__ src, const int* __restrict__ order, const AlignXf& f, const CloudGrid& g,
+                                               const float* __restrict__ txyz, double a[3], double b[3], double& dn) {
+    size_t t;
+    return align_match_one(j, src, order, f, g, txyz, a, b, dn, t);
 }
 
 // term k of a matched pair

@@ -9,6 +9,7 @@
 // distance of the matched pairs BEFORE the update.
 // Returns 1 with M_out = M_in when n < 3, var_a <= 0 or d0 == 0; anything else is answered as the formula gives it.  Collinear
 // pairs (d1 == 0) leave the rotation about their line open: some rotation of that family is returned, and telling is the caller's job.
+// Below it the step of point-to-plane ICP (mpmvs_align_plane_solve) on the 38 sums of pm_align_plane.hpp.
 // No device code and no HIP header: plain C++.
 #pragma once
 
@@ -141,6 +142,74 @@ inline double align_move(const double D[12], const double frame[4]) {
         worst = m > worst ? m : worst;
     }
     return worst;
+}
+
+// ---- point-to-plane (mpmvs_align_plane_solve) ----------------------------------------------------------
+// One Gauss-Newton step on the 38 integer sums of pm_align_plane.hpp, in their normalised frame:
+//   n = sums[0], s = 2^-30;  H = J^T J (7 x 7, symmetric, its upper triangle row by row in sums[1..28]) and gvec = J^T r
+//   (sums[29..35]), both times s;  m = 7 with scale, else the leading 6;  H x = -gvec by LDL^T without pivoting, x = (omega, t, sigma).
+//   Pivot j is d_j = H_jj - sum_k<j L_jk^2 d_k.  The step is refused -- 1 is returned -- for n < m, for a pivot that is not finite
+//   or is <= 2^-20 H_jj (a direction the pairs do not observe: the rounding of a sum is at most n 2^-31 against a diagonal of
+//   n mean(J_j^2)), and, with scale, for a 1 + sigma that is not a positive finite number.
+//   R = the rotation of the unit quaternion (1, omega / 2) / |.|: proper for every omega, and it needs one sqrt only.
+//   c = 1 + sigma with scale, else 1.  In world units the update is D = [c R | o - c R o + u t], as in align_update.
+// rmse_plane = sqrt(sums[36] s / n) u and rmse_point = sqrt(sums[37] s / n) u: the RMS point-to-plane and point-to-point
+// distance of the matched pairs BEFORE the update (0 for n = 0).
+inline int align_plane_update(const long long sums[38], const double frame[4], int with_scale, double D[12], double* rmse_plane, double* rmse_point) {
+    for (int k = 0; k < 12; ++k) D[k] = k % 5 == 0 ? 1.0 : 0.0;
+    const double n = (double)sums[0], s = 0x1p-30, u = frame[3];
+    if (rmse_plane) *rmse_plane = sums[0] > 0 ? std::sqrt((double)sums[36] * s / n) * u : 0.0;
+    if (rmse_point) *rmse_point = sums[0] > 0 ? std::sqrt((double)sums[37] * s / n) * u : 0.0;
+    const int m = with_scale ? 7 : 6;
+    if (sums[0] < m) return 1;
+    double H[7][7], L[7][7], d[7], x[7];
+    for (int i = 0, k = 1; i < 7; ++i)
+        for (int j = i; j < 7; ++j, ++k) H[i][j] = H[j][i] = (double)sums[k] * s;
+    for (int j = 0; j < m; ++j) {
+        double dj = H[j][j];
+        for (int k = 0; k < j; ++k) dj -= L[j][k] * L[j][k] * d[k];
+        if (!std::isfinite(dj) || !(dj > 0x1p-20 * H[j][j])) return 1;
+        d[j] = dj;
+        for (int i = j + 1; i < m; ++i) {
+            double v = H[i][j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k] * d[k];
+            L[i][j] = v / dj;
+        }
+    }
+    for (int i = 0; i < m; ++i) {   // L z = -gvec
+        double v = -((double)sums[29 + i] * s);
+        for (int k = 0; k < i; ++k) v -= L[i][k] * x[k];
+        x[i] = v;
+    }
+    for (int i = 0; i < m; ++i) x[i] /= d[i];
+    for (int i = m - 1; i >= 0; --i)   // L^T x = z / d
+        for (int k = i + 1; k < m; ++k) x[i] -= L[k][i] * x[k];
+    const double c = with_scale ? 1.0 + x[6] : 1.0;
+    if (!(c > 0.0) || !std::isfinite(c)) return 1;
+    const double qx = 0.5 * x[0], qy = 0.5 * x[1], qz = 0.5 * x[2];
+    const double qn = std::sqrt(1.0 + ((qx * qx + qy * qy) + qz * qz));
+    const double w = 1.0 / qn, a = qx / qn, b = qy / qn, e = qz / qn;
+    const double R[3][3] = {{1.0 - 2.0 * (b * b + e * e), 2.0 * (a * b - w * e), 2.0 * (a * e + w * b)},
+                            {2.0 * (a * b + w * e), 1.0 - 2.0 * (a * a + e * e), 2.0 * (b * e - w * a)},
+                            {2.0 * (a * e - w * b), 2.0 * (b * e + w * a), 1.0 - 2.0 * (a * a + b * b)}};
+    for (int r = 0; r < 3; ++r) {
+        const double cR[3] = {c * R[r][0], c * R[r][1], c * R[r][2]};
+        for (int k = 0; k < 3; ++k) D[4 * r + k] = cR[k];
+        D[4 * r + 3] = (frame[r] - ((cR[0] * frame[0] + cR[1] * frame[1]) + cR[2] * frame[2])) + u * x[3 + r];
+    }
+    return 0;
+}
+
+inline int align_plane_solve(const long long sums[38], const double frame[4], int with_scale, const double M_in[12], double M_out[12], double* rmse_plane,
+                             double* rmse_point) {
+    double D[12];
+    const int rc = align_plane_update(sums, frame, with_scale, D, rmse_plane, rmse_point);
+    if (rc) {
+        for (int k = 0; k < 12; ++k) M_out[k] = M_in[k];
+        return rc;
+    }
+    align_compose(D, M_in, M_out);
+    return 0;
 }
 
 }  // namespace pm

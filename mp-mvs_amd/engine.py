@@ -89,6 +89,13 @@ _EXTRA = {
     "align_icp": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "align_ms": (C.c_float, [_P]),
     "align_destroy": (None, [_P]),
+    # point-to-plane registration (cloud.py: Aligner.set_normals / plane_sums / plane_icp, plane_solve)
+    "align_set_normals": (C.c_int, [_P, _P]),
+    "align_plane_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "align_plane_solve": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double)]),
+    "align_plane_icp": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

@@ -4,7 +4,8 @@
 
     python tools/eval_ply.py --reconstruction MPMVS_model.ply --ground_truth scan.ply [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5]
                              [--transform T.txt] [--crop xmin,ymin,zmin,xmax,ymax,zmax] [--voxel V] [--device 0]
-                             [--refine [--refine_radii r1,r2,...] [--refine_no_scale] [--refine_iters 30] [--save_transform OUT.txt]]
+                             [--refine [--refine_radii r1,r2,...] [--refine_no_scale] [--refine_iters 30] [--save_transform OUT.txt]
+                                       [--refine_method point|plane [--refine_normal_radius R] [--refine_normal_k 16]]]
 
 --transform: a 4 x 4 text matrix that takes the reconstruction into the ground truth's frame; applied in fp64 and rounded to
 fp32.  --crop: an axis-aligned box (in the ground truth's frame, after the transform) applied to both clouds.
@@ -13,6 +14,14 @@ protocol does: point-to-point ICP of the reconstruction to the ground truth on t
 section 15), one round per radius of --refine_radii in descending order (default: 8, 4 and 2 times the largest tolerance), with
 a scale unless --refine_no_scale, at most --refine_iters passes per round.  The crop is applied after the refined transform,
 and the JSON line gains "refine": {"rounds": [{radius, passes, inliers, rmse}], "matrix": 4 x 4, "seconds"}.
+--refine_method plane: point-to-plane ICP instead: a pair counts by its distance along the ground truth's
+normal, so the reconstruction may slide along a surface that the scan sampled at other points -- the case of every real pair of
+clouds, where point-to-point ICP settles about a sample spacing off.  The normals are the ground-truth file's own (nx ny nz) when
+it has them and no --refine_normal_radius is given; otherwise they are estimated on the cloud that is registered against (after
+--voxel, if given) from the --refine_normal_k nearest neighbours within --refine_normal_radius (mp-mvs_amd/cloud.py:
+Cloud.normals).  Its default is the smallest refine radius: an untuned starting value; a good radius holds
+a dozen neighbours on one surface.  The rounds gain "rmse_plane" and "refine" gains "method" (also for point) and "normals".  The
+default method stays point.
 --save_transform writes the refined 4 x 4 matrix as text: a later run's --transform (tools/eval_depth.py takes its inverse: there
 the matrix carries the scan into the cameras' frame).
 --voxel V: both clouds are resampled on a voxel grid of edge V on the GPU (mp-mvs_amd/cloud.py: voxel_downsample; DESIGN.md
@@ -50,18 +59,40 @@ def apply_transform(xyz, T):
     return (h / w[:, None]).astype(np.float32)
 
 
-def crop(xyz, box):
+def crop_keep(xyz, box):
     lo, hi = np.asarray(box[:3], np.float32), np.asarray(box[3:], np.float32)
     with np.errstate(invalid="ignore"):
-        keep = ((xyz >= lo) & (xyz <= hi)).all(1) | ~np.isfinite(xyz).all(1)   # non-finite points stay, to be counted by evaluate
-    return xyz[keep]
+        return ((xyz >= lo) & (xyz <= hi)).all(1) | ~np.isfinite(xyz).all(1)   # non-finite points stay, to be counted by evaluate
+
+
+def crop(xyz, box):
+    return xyz[crop_keep(xyz, box)]
+
+
+def file_normals_wanted(args, gt):
+    """the ground-truth file's own normals serve --refine_method plane unless a radius asks for estimated ones"""
+    return args.refine and args.refine_method == "plane" and args.refine_normal_radius is None and "normals" in gt
+
+
+def refine_method(args, radii, normals):
+    """(the keyword arguments of cloud.align for --refine_method, what "refine" reports of them); normals: the file's, in the
+    order of the cloud that is registered against, or None"""
+    if args.refine_method == "point":
+        return {}, {"method": "point"}
+    if normals is not None:
+        return {"method": "plane", "target_normals": normals}, {"method": "plane", "normals": "ground truth file"}
+    r = args.refine_normal_radius if args.refine_normal_radius is not None else min(radii)
+    return ({"method": "plane", "normal_radius": r, "normal_k": args.refine_normal_k},
+            {"method": "plane", "normals": "estimated", "normal_radius": r, "normal_k": args.refine_normal_k})
 
 
 def main_voxel(args, tol):
     """the run with --voxel: transform, crop, resample both clouds, refine on the resampled clouds, score"""
     t0 = time.perf_counter()
     rec = cloud.read_ply(args.reconstruction)["xyz"]
-    gt = cloud.read_ply(args.ground_truth)["xyz"]
+    gt_file = cloud.read_ply(args.ground_truth)
+    gt = gt_file["xyz"]
+    gt_n = gt_file["normals"] if file_normals_wanted(args, gt_file) else None   # they follow their points through every step
     T0 = np.loadtxt(args.transform) if args.transform else np.eye(4)
     if args.transform:
         rec = apply_transform(rec, T0)
@@ -69,22 +100,26 @@ def main_voxel(args, tol):
         box = [float(v) for v in args.crop.split(",")]
         if len(box) != 6:
             raise SystemExit("--crop needs xmin,ymin,zmin,xmax,ymax,zmax")
+        gt_n = gt_n[crop_keep(gt, box)] if gt_n is not None else None
         rec, gt = crop(rec, box), crop(gt, box)
     t1 = time.perf_counter()
     rec, drop_r = cloud.drop_nonfinite(rec)
+    gt_n = gt_n[np.isfinite(gt).all(1)] if gt_n is not None else None
     gt, drop_g = cloud.drop_nonfinite(gt)
     n_in = (len(rec), len(gt))
     rec = cloud.voxel_downsample(rec, args.voxel, device=args.device)["xyz"]
-    gt = cloud.voxel_downsample(gt, args.voxel, device=args.device)["xyz"]
+    gt_v = cloud.voxel_downsample(gt, args.voxel, normals=gt_n, device=args.device)
+    gt, gt_n = gt_v["xyz"], gt_v.get("normals")
     t2 = time.perf_counter()
     refine = None
     if args.refine:
         radii = [float(r) for r in args.refine_radii.split(",") if r.strip()] if args.refine_radii else [8 * max(tol), 4 * max(tol), 2 * max(tol)]
+        how, said = refine_method(args, radii, gt_n)
         with cloud.Cloud(gt, args.device) as c_gt:
-            T, rounds = cloud.align(rec, c_gt, None, radii=radii, with_scale=not args.refine_no_scale, max_iter=args.refine_iters)
+            T, rounds = cloud.align(rec, c_gt, None, radii=radii, with_scale=not args.refine_no_scale, max_iter=args.refine_iters, **how)
         rec = apply_transform(rec, T)
         T = T @ np.asarray(T0, np.float64)
-        refine = {"rounds": rounds, "matrix": T.tolist(), "seconds": round(time.perf_counter() - t2, 4)}
+        refine = {"rounds": rounds, "matrix": T.tolist(), "seconds": round(time.perf_counter() - t2, 4), **said}
         if args.save_transform:
             np.savetxt(args.save_transform, T, fmt="%.17g")
     timings = {}
@@ -113,9 +148,15 @@ def main():
     ap.add_argument("--refine_no_scale", action="store_true")
     ap.add_argument("--refine_iters", type=int, default=30)
     ap.add_argument("--save_transform")
+    ap.add_argument("--refine_method", choices=("point", "plane"), default="point")
+    ap.add_argument("--refine_normal_radius", type=float, help="estimate the ground truth's normals within this radius (default: its file's own "
+                    "normals, else the smallest refine radius, an untuned starting value)")
+    ap.add_argument("--refine_normal_k", type=int, default=16)
     args = ap.parse_args()
-    if not args.refine and (args.refine_radii or args.refine_no_scale or args.save_transform):
-        raise SystemExit("--refine_radii, --refine_no_scale and --save_transform need --refine")
+    if not args.refine and (args.refine_radii or args.refine_no_scale or args.save_transform or args.refine_method != "point"):
+        raise SystemExit("--refine_radii, --refine_no_scale, --refine_method and --save_transform need --refine")
+    if args.refine_method != "plane" and (args.refine_normal_radius is not None or args.refine_normal_k != 16):
+        raise SystemExit("--refine_normal_radius and --refine_normal_k need --refine_method plane")
     if args.voxel is not None and not (np.isfinite(args.voxel) and args.voxel > 0):
         raise SystemExit("--voxel needs a finite positive edge length")
     tol = [float(t) for t in args.tolerances.split(",") if t.strip()]
@@ -123,15 +164,17 @@ def main():
         return main_voxel(args, tol)
     t0 = time.perf_counter()
     rec = cloud.read_ply(args.reconstruction)["xyz"]
-    gt = cloud.read_ply(args.ground_truth)["xyz"]
+    gt_file = cloud.read_ply(args.ground_truth)
+    gt = gt_file["xyz"]
     refine = None
     if args.refine:
         T0 = np.loadtxt(args.transform) if args.transform else np.eye(4)
         radii = [float(r) for r in args.refine_radii.split(",") if r.strip()] if args.refine_radii else [8 * max(tol), 4 * max(tol), 2 * max(tol)]
+        how, said = refine_method(args, radii, gt_file["normals"][np.isfinite(gt).all(1)] if file_normals_wanted(args, gt_file) else None)
         t_r = time.perf_counter()
         with cloud.Cloud(cloud.drop_nonfinite(gt)[0], args.device) as c_gt:
-            T, rounds = cloud.align(rec, c_gt, T0, radii=radii, with_scale=not args.refine_no_scale, max_iter=args.refine_iters)
-        refine = {"rounds": rounds, "matrix": T.tolist(), "seconds": round(time.perf_counter() - t_r, 4)}
+            T, rounds = cloud.align(rec, c_gt, T0, radii=radii, with_scale=not args.refine_no_scale, max_iter=args.refine_iters, **how)
+        refine = {"rounds": rounds, "matrix": T.tolist(), "seconds": round(time.perf_counter() - t_r, 4), **said}
         if args.save_transform:
             np.savetxt(args.save_transform, T, fmt="%.17g")
         rec = apply_transform(rec, T)
