@@ -606,6 +606,39 @@ int mpmvs_cloud_normals(mpmvs_cloud* cloud, float radius, int k, int orient, con
  * grid build it needed (0 if reused): what mpmvs_cloud_knn_ms reports of a knn call */
 float mpmvs_cloud_normals_ms(const mpmvs_cloud* cloud, float* build_ms);
 
+/* ---- point clouds: connected components within a radius (mp-mvs_amd/cloud.py, tools/clean_ply.py --cluster_radius) --- */
+/* Euclidean cluster extraction: the connected components of the graph "two points of the handle's cloud are neighbours iff they are
+ * within a radius" (mp-mvs_amd/csrc/pm_components.hpp), so that the small detached clusters of a fused cloud,
+ * which the outlier rules above keep because every point of such a cluster has close neighbours, can be told by their size.
+ * DEFINED BY EQUIVALENCE with this plain loop, bit for bit and independent of scheduling:
+ *   A point TAKES PART iff its three coordinates are finite.
+ *   Points i != j that both take part are ADJACENT iff d2 <= r2, on the candidate rule of mpmvs_cloud_nearest: r2 = radius * radius
+ *   in fp32;  dx = x_i - x_j, likewise dy, dz, in fp32;  d2 = (dx*dx + dy*dy) + dz*dz in fp32, no contraction; the comparison is
+ *   inclusive.  The rule is SYMMETRIC: x_i - x_j and x_j - x_i are exact negatives of each other (a correctly rounded difference
+ *   changes sign with its operands), the squares of exact negatives are equal, and the two sums add equal terms in the same order.
+ *   Adjacency is therefore an undirected graph, and its connected components are defined.
+ *   out_label[i] = the SMALLEST INDEX among the points of i's connected component; -1 for a point that does not take part.  An exact
+ *   duplicate of a point is adjacent to it at d2 = +0.  A point without a neighbour is a component of its own: out_label[i] = i.
+ *   out_size[i] = the number of points of that component; 0 for a point that does not take part.
+ *   counts = {points taking part, components, size of the largest component, label of the largest component}; among components of
+ *   equal size the smallest label counts as the largest.  No point taking part: counts = {0, 0, 0, -1}.
+ * The labels are what a union-find over all adjacent pairs gives, in any order of the pairs: the device unites them concurrently in
+ * one pass, without locks (DESIGN.md section 20 has the argument).  The call uses the handle's grids and their per-radius cache
+ * exactly as mpmvs_cloud_knn does: a radius built by mpmvs_cloud_nearest, mpmvs_cloud_knn, mpmvs_cloud_normals or an align pass is not
+ * built again.  The handle keeps n ints of scratch from the first call on, released with the handle.
+ * Errors: -2 = a NULL cloud, a NULL out_label with n > 0, a radius that is not finite or <= 0; -3 = the limits of
+ * mpmvs_cloud_nearest (the cell span at this radius; the text names the axis and the ratio); -100 = HIP failure.  All but -100 are
+ * found before the device is touched, and a refused call writes nothing.  n == 0, or no point that takes part, returns 0, writes
+ * -1 / 0 into the outputs and launches nothing. */
+int mpmvs_cloud_components(mpmvs_cloud* cloud, float radius, int32_t* out_label /* n */, int32_t* out_size /* n, may be NULL */,
+                           long long counts[4] /* may be NULL */);
+/* device ms (HIP events) of the last mpmvs_cloud_components call, the sum of its passes; *build_ms (may be NULL) of the grid build it
+ * needed (0 if reused) */
+float mpmvs_cloud_components_ms(const mpmvs_cloud* cloud, float* build_ms);
+/* the same per pass: hook (the initialisation, the binning and the union-find pass over the edges), flatten, size (0 when neither
+ * out_size nor counts was asked for) */
+int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* cloud, float ms[3]);
+
 /* ---- point clouds: z-buffer render into cameras (mp-mvs_amd/cloud.py, tools/eval_depth.py) --- */
 /* The per-view ground-truth depth map of a scan: the handle's cloud rendered into n_views pinhole cameras with a visibility test,
  * so that the back of the scene does not shine through the gaps between front points.

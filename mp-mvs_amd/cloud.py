@@ -7,7 +7,8 @@ section 16), and the k nearest neighbours within a cloud with the statistical / 
 Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp), and a surface normal per point fitted to those neighbours
 (Cloud.normals, estimate_normals; csrc/pm_normals.hpp), and point-to-plane ICP on those normals beside the
 point-to-point one (Aligner.set_normals / plane_sums / plane_icp, plane_solve, align(method="plane"); csrc/pm_align_plane.hpp,
-DESIGN.md section 19).
+DESIGN.md section 19), and the connected components of a cloud under "within a radius", with the filter that drops small detached
+clusters on top of them (Cloud.components, remove_small_clusters; csrc/pm_components.hpp).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
 grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
@@ -272,6 +273,31 @@ class Cloud:
         b = C.c_float(0.0)
         q = self._f["cloud_normals_ms"](self._h, C.byref(b))
         return float(q), float(b.value)
+
+    def components(self, radius, want_size=True):
+        """mpmvs_cloud_components: the connected components of the graph "two points are neighbours iff they are within `radius`"
+        (inclusive, the candidate rule of nearest()) -> (label int32 [n], size int32 [n] or None, counts int64 [4]).  label[i] is the
+        smallest index among the points of i's component (-1: a non-finite coordinate), size[i] the number of its points (0 likewise);
+        counts = (points taking part, components, size of the largest component, its label; ties go to the smallest label).  The
+        labels are a pure function of the point set, bit for bit those of include/mpmvs.h."""
+        label = np.empty(self.n, np.int32)
+        size = np.empty(self.n, np.int32) if want_size else None
+        counts = (C.c_longlong * 4)()
+        rc = self._f["cloud_components"](self._h, float(radius), label.ctypes.data, size.ctypes.data if want_size else None, counts)
+        if rc != 0:
+            self._raise("cloud_components", rc)
+        return label, size, np.array(list(counts), np.int64)
+
+    def components_ms(self, passes=False):
+        """(device ms, build ms) of the last components call; build ms is 0 when the grid was reused.  With passes=True a third
+        entry: {"hook", "flatten", "size"}, the device ms per pass (hook: initialisation, binning and the union-find pass)"""
+        b = C.c_float(0.0)
+        q = self._f["cloud_components_ms"](self._h, C.byref(b))
+        if not passes:
+            return float(q), float(b.value)
+        ms = (C.c_float * 3)()
+        self._f["cloud_components_pass_ms"](self._h, ms)
+        return float(q), float(b.value), dict(zip(("hook", "flatten", "size"), (float(v) for v in ms)))
 
     def render_depth(self, cams, splat=1, occl_rel=0.02, want_idx=False):
         """mpmvs_cloud_render_depth: the cloud rendered into every camera of `cams` (_abi.Camera; width and height give the map's
@@ -677,6 +703,50 @@ def last_outliers_ms():
     """device ms of the calling thread's last remove_outliers (mpmvs_cloud_outliers_ms): the grid build and the query passes"""
     _, f = engine.load()
     return float(f["cloud_outliers_ms"]())
+
+
+def cluster_keep(label, size, min_size=2, largest=None):
+    """the keep rule of remove_small_clusters, a few lines of numpy on the host: keep[i] iff size[i] >= min_size and, with
+    largest=K, i's component is among the K largest (by size descending, then label ascending)"""
+    keep = size >= min_size
+    if largest is not None:
+        roots = np.flatnonzero(label == np.arange(len(label)))          # one entry per component, labels ascending
+        top = roots[np.argsort(-size[roots].astype(np.int64), kind="stable")[:largest]]
+        keep &= np.isin(label, top)
+    return keep
+
+
+def remove_small_clusters(xyz, radius, min_size=2, largest=None, device=0):
+    """Euclidean cluster extraction: Cloud.components over a Cloud of the call's own -> {"keep": bool [n], "label": int32 [n],
+    "size": int32 [n], "counts": int64 [4]}.  keep[i] iff the connected component of point i (neighbours: within `radius`) has at
+    least min_size points; with largest=K a point stays only if its component is also among the K largest (by size descending,
+    then label ascending).  A point with a non-finite coordinate is never kept.  This drops the small detached clusters that
+    remove_outliers keeps, because inside such a cluster every point has close neighbours.  The components come from the GPU; the
+    keep rule is a few lines of numpy on the host (cluster_keep).  A cloud without a finite point is answered on the host."""
+    a = _xyz(xyz)
+    if not (np.isfinite(radius) and radius > 0):
+        raise ValueError("radius must be finite and positive")
+    if int(min_size) != min_size or min_size < 1:
+        raise ValueError("min_size must be an integer of at least 1")
+    if largest is not None and (int(largest) != largest or largest < 1):
+        raise ValueError("largest must be None or an integer of at least 1")
+    global _clusters_ms
+    _clusters_ms = 0.0
+    if not np.isfinite(a).all(1).any():
+        label, size, counts = np.full(len(a), -1, np.int32), np.zeros(len(a), np.int32), np.array([0, 0, 0, -1], np.int64)
+    else:
+        with Cloud(a, device) as c:
+            label, size, counts = c.components(radius)
+            _clusters_ms = sum(c.components_ms())
+    return {"keep": cluster_keep(label, size, int(min_size), None if largest is None else int(largest)), "label": label, "size": size, "counts": counts}
+
+
+_clusters_ms = 0.0
+
+
+def last_clusters_ms():
+    """device ms of the last remove_small_clusters of this process: the grid build and the three passes; 0 when it launched nothing"""
+    return _clusters_ms
 
 
 def estimate_normals(xyz, radius, k=16, viewpoint=None, reference=None, device=0):

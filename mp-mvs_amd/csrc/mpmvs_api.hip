@@ -42,6 +42,7 @@
 #include "pm_voxel.hpp"
 #include "pm_knn.hpp"
 #include "pm_normals.hpp"
+#include "pm_components.hpp"
 #include "pm_align.hpp"
 #include "pm_align_plane.hpp"
 #include "pm_align_host.hpp"
@@ -3016,6 +3017,9 @@ struct mpmvs_cloud {
     float render_pass_ms[3] = {0.0f, 0.0f, 0.0f};   // z-min, index, resolve of the last render call
     float knn_ms = 0.0f, knn_build_ms = 0.0f;       // the last mpmvs_cloud_knn call
     float normals_ms = 0.0f, normals_build_ms = 0.0f;   // the last mpmvs_cloud_normals call
+    int* d_cc = nullptr;                            // n ints of mpmvs_cloud_components (parent, then the sizes): allocated by its first call
+    float cc_ms = 0.0f, cc_build_ms = 0.0f;         // the last mpmvs_cloud_components call
+    float cc_pass_ms[3] = {0.0f, 0.0f, 0.0f};       // its hook (with init and binning), flatten and size passes
 };
 
 static void cloud_free_grid(CloudGridBuf& g) {
@@ -3027,7 +3031,7 @@ static void cloud_free_grid(CloudGridBuf& g) {
 static void cloud_release(mpmvs_cloud* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (CloudGridBuf& g : c->grids) cloud_free_grid(g);
-    for (void* p : {(void*)c->d_xyz, (void*)c->d_cnt, (void*)c->d_tsum, (void*)c->d_slot_of, (void*)c->d_st})
+    for (void* p : {(void*)c->d_xyz, (void*)c->d_cnt, (void*)c->d_tsum, (void*)c->d_slot_of, (void*)c->d_st, (void*)c->d_cc})
         if (p) (void)pool_free(p);
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);
@@ -3767,6 +3771,92 @@ float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) {
     if (!c) return 0.0f;
     if (build_ms) *build_ms = c->normals_build_ms;
     return c->normals_ms;
+}
+
+// ---------------------------------------------------------------------------
+// the connected components of the handle's cloud under "within a radius" (pm_components.hpp): a lock-free
+// union-find in one pass over the edges, a flatten pass and a size pass.  The four counts are taken on the host from the downloaded
+// labels and sizes.  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int32_t* out_size, long long counts[4]) {
+    if (!c || (c->n > 0 && !out_label)) return seg_fail(-2, "cloud components: bad argument");
+    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud components: the radius must be finite and positive");
+    const size_t n = (size_t)c->n;
+    if (c->n_fin == 0) {   // n == 0 included: nothing takes part
+        for (size_t i = 0; i < n; ++i) {
+            out_label[i] = -1;
+            if (out_size) out_size[i] = 0;
+        }
+        if (counts) counts[0] = counts[1] = counts[2] = 0, counts[3] = -1;
+        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
+        c->cc_ms = c->cc_build_ms = c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
+        return 0;
+    }
+    const int span = cloud_span_check(c, radius);
+    if (span) return span;
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    c->cc_build_ms = c->build_ms;
+    c->cc_ms = c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
+    if (!c->d_cc) SEGCHK(pool_malloc(&c->d_cc, n * 4));
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries(), want_size = out_size || counts;
+    const CloudGrid g = cloud_grid_args(c, *grid, radius);
+    const int ni = (int)c->n;
+    const dim3 gp((ni + 255) / 256);
+    Scratch d_label(st), d_size(st);
+    KnnBins bins(st);
+    SEGCHK(d_label.alloc(n * 4));
+    if (want_size) SEGCHK(d_size.alloc(n * 4));
+    if (bin) SEGCHK(bins.alloc(n));
+    std::vector<int32_t> size_own;
+    if (want_size && !out_size) size_own.resize(n);
+    int32_t* size = out_size ? out_size : size_own.data();
+    // the grid is built: its two events are free again, and the four borders of the three passes fit the handle's four
+    SEGCHK(hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(k_cc_init, gp, dim3(256), 0, st, c->d_xyz, ni, c->d_cc);
+    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    hipLaunchKernelGGL(k_cc_hook, gp, dim3(256), 0, st, c->d_xyz, ni, bin ? bins.order.as<int>() : (const int*)nullptr, g, c->d_cc);
+    SEGCHK(hipEventRecord(c->ev[1], st));
+    hipLaunchKernelGGL(k_cc_flatten, gp, dim3(256), 0, st, ni, c->d_cc, d_label.as<int32_t>());
+    SEGCHK(hipEventRecord(c->ev[2], st));
+    if (want_size) {   // the parents have served: the same ints count the members of every label
+        SEGCHK(hipMemsetAsync(c->d_cc, 0, n * 4, st));
+        hipLaunchKernelGGL(k_cc_count, gp, dim3(256), 0, st, ni, d_label.as<int32_t>(), c->d_cc);
+        hipLaunchKernelGGL(k_cc_gather, gp, dim3(256), 0, st, ni, d_label.as<int32_t>(), c->d_cc, d_size.as<int32_t>());
+    }
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    SEGCHK(hipMemcpyAsync(out_label, d_label.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (want_size) SEGCHK(hipMemcpyAsync(size, d_size.p, n * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    for (int p = 0; p < 3; ++p) SEGCHK(hipEventElapsedTime(&c->cc_pass_ms[p], c->ev[p], c->ev[p + 1]));
+    if (!want_size) c->cc_pass_ms[2] = 0.0f;   // two events with nothing between them
+    c->cc_ms = (c->cc_pass_ms[0] + c->cc_pass_ms[1]) + c->cc_pass_ms[2];
+    if (counts) {   // a component is counted at its label; the largest, ties to the smallest label
+        long long comps = 0, best = 0, best_label = -1;
+        for (size_t i = 0; i < n; ++i) {
+            if (out_label[i] != (int32_t)i) continue;
+            ++comps;
+            if (size[i] > best) best = size[i], best_label = (long long)i;
+        }
+        counts[0] = c->n_fin, counts[1] = comps, counts[2] = best, counts[3] = best_label;
+    }
+    return 0;
+}
+
+float mpmvs_cloud_components_ms(const mpmvs_cloud* c, float* build_ms) {
+    if (!c) return 0.0f;
+    if (build_ms) *build_ms = c->cc_build_ms;
+    return c->cc_ms;
+}
+
+int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* c, float ms[3]) {
+    if (!c || !ms) return seg_fail(-2, "cloud components: bad argument");
+    std::memcpy(ms, c->cc_pass_ms, sizeof c->cc_pass_ms);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

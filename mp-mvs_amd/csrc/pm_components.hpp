@@ -1,0 +1,194 @@
+// pm_components.hpp -- the connected components of a point cloud on the grids of pm_cloud.hpp (mpmvs_cloud_components; contract:
+// DESIGN.md section 20 and include/mpmvs.h).  Two finite points i != j are adjacent iff d2 = (dx*dx + dy*dy) + dz*dz <= r2 in fp32,
+// no contraction: the candidate rule of mpmvs_cloud_nearest, which is symmetric in its two points (x_i - x_j and x_j - x_i are exact
+// negatives, their squares are equal).  label[i] = the smallest index of i's component, size[i] = its number of points; -1 / 0 for a
+// point with a non-finite coordinate.  A pure function of the point set: bit for bit the plain union-find over brute-force
+// adjacency, independent of scheduling.
+//
+// A concurrent union-find in ONE pass over the edges (ECL-CC style: Jaiganesh and Burtscher, HPDC 2018), not label propagation: a
+// chain of n points costs one pass, not n.
+//   parent[]       an int per point of the cloud, indexed by the caller's index (pts[p].w): its own index at the start, -1 for a
+//                  point that does not take part (never read again).  Invariant: parent[x] <= x.  A root has parent[x] == x.
+//   k_cc_init      parent[i] = i or -1.
+//   k_cc_hook      one thread per point, in the binned order of k_cloud_qbin / k_cloud_qorder, walking the 27 cells as knn_search
+//                  does.  Only neighbours with an index BELOW its own are united with it: every edge is handled once, by its larger
+//                  end.  The thread carries its current root in a register and skips a neighbour whose root is that one.
+//   cc_find        follows parent to a root, halving the path on the way: parent[prev] is overwritten with parent[curr], a node
+//                  further down the same tree.  Such a store never touches a root (prev was seen with parent[prev] < prev, and a
+//                  node that has left the roots never returns: every value ever stored is below its index).
+//   cc_link        hooks the larger of two roots under the smaller with a compare-and-swap that expects the larger to be a root
+//                  still.  On a lost race it finds the root from the value the swap returned -- strictly below the index it tried
+//                  -- and tries again: the larger index of the pair falls with every retry, so the loop ends without any thread
+//                  waiting for another.  No lock, no flag, no barrier between blocks.
+//   k_cc_flatten   a launch of its own: label[i] = find(i).  All edges are united by then, so a tree is a component, and its root
+//                  is below every member and a member itself: the smallest index.
+//   k_cc_count     size[label[i]] += 1, an integer atomic, so the order never shows.  The lanes of a wave that share a label add
+//                  once, by their number: a cloud that is one component would otherwise send every point to one address.
+//   k_cc_gather    out_size[i] = size[label[i]].
+// Why stale reads do no harm: every value parent[x] has ever held is a node of x's tree (trees merge, never split) below or at x,
+// so a walk over old values still descends inside the tree; only the compare-and-swap decides a hook, and it is exact.  Reads of
+// parent inside the hook pass are relaxed atomic loads at agent scope, the halving stores relaxed atomic stores.
+// The four counts are taken on the host from the downloaded labels and sizes (mpmvs_api.hip).
+// The per-thread bodies are host and device code, so that tools/components_check.cpp can replay them thread by thread and edge by
+// edge under the sanitizers; there the atomics are plain reads and writes.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pm_cloud.hpp"
+
+namespace pm {
+
+__host__ __device__ inline int cc_load(const int* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    return *p;
+#endif
+}
+__host__ __device__ inline void cc_store(int* p, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    *p = v;
+#endif
+}
+__host__ __device__ inline int cc_cas(int* p, int expect, int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicCAS(p, expect, v);
+#else
+    const int old = *p;
+    if (old == expect) *p = v;
+    return old;
+#endif
+}
+
+// the root of x's tree; halves the path it walks.  x takes part (parent[x] >= 0).
+__host__ __device__ inline int cc_find(int* __restrict__ parent, int x) {
+    int curr = cc_load(&parent[x]);
+    if (curr != x) {
+        int prev = x, next;
+        while (curr > (next = cc_load(&parent[curr]))) {   // parent[curr] < curr: curr is no root
+            cc_store(&parent[prev], next);                 // prev is no root either; next lies further down its tree
+            prev = curr;
+            curr = next;
+        }
+    }
+    return curr;
+}
+
+// unites the trees of ra and rb, two roots that may have been hooked since they were found; returns the root of the united tree
+// as of the hook
+__host__ __device__ inline int cc_link(int* __restrict__ parent, int ra, int rb) {
+    while (ra != rb) {
+        const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+        const int old = cc_cas(&parent[hi], hi, lo);
+        if (old == hi) return lo;          // hi was a root and hangs under lo now
+        ra = cc_find(parent, old);         // hi had been hooked: old < hi is on its tree; max(ra, rb) falls with every retry
+        rb = lo;
+    }
+    return ra;
+}
+
+__host__ __device__ inline int cc_union(int* __restrict__ parent, int a, int b) {
+    return cc_link(parent, cc_find(parent, a), cc_find(parent, b));
+}
+
+// ---- init ----------------------------------------------------------------------------------------------------------------------
+__host__ __device__ inline void cc_init_one(size_t i, const float* __restrict__ xyz, int* __restrict__ parent) {
+    parent[i] = cloud_finite(xyz[3 * i]) && cloud_finite(xyz[3 * i + 1]) && cloud_finite(xyz[3 * i + 2]) ? (int)i : -1;
+}
+__global__ __launch_bounds__(256) void k_cc_init(const float* __restrict__ xyz, int n, int* __restrict__ parent) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) cc_init_one(i, xyz, parent);
+}
+
+// ---- hook: thread j serves point order[j] (order may be null: j itself) -----------------------------------------------------------
+__host__ __device__ inline void cc_hook_one(size_t j, const float* __restrict__ xyz, const int* __restrict__ order, const CloudGrid& g, int* __restrict__ parent) {
+    const size_t i = order ? (size_t)order[j] : j;
+    float x, y, z;
+    int cx, cy, cz;
+    if (!cloud_query_cell(xyz, i, g, x, y, z, cx, cy, cz)) return;
+    const unsigned self = (unsigned)i;
+    int root = cc_find(parent, (int)self);
+    for (int dz = -1; dz <= 1; ++dz) {
+        if (!cloud_cell_ok(cz + dz)) continue;
+        for (int dy = -1; dy <= 1; ++dy) {
+            if (!cloud_cell_ok(cy + dy)) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                if (!cloud_cell_ok(cx + dx)) continue;
+                const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
+                unsigned h = (unsigned)cloud_mix(key) & g.mask;
+                int s = -1;
+                for (unsigned probe = 0; probe <= g.mask; ++probe) {
+                    const unsigned long long cur = g.keys[h];
+                    if (cur == key) s = (int)h;
+                    if (cur == key || cur == kCloudEmpty) break;
+                    h = (h + 1) & g.mask;
+                }
+                if (s < 0) continue;
+                const int e = g.off[s + 1];
+                for (int p = g.off[s]; p < e; ++p) {
+                    const uint4 t = g.pts[p];
+                    if (t.w >= self) continue;   // the edge belongs to its larger end
+                    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
+                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+                    if (d2 <= g.r2) {
+                        const int other = cc_find(parent, (int)t.w);
+                        if (other != root) root = cc_link(parent, root, other);
+                    }
+                }
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_cc_hook(const float* __restrict__ xyz, int n, const int* __restrict__ order, CloudGrid g, int* __restrict__ parent) {
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < (size_t)n) cc_hook_one(j, xyz, order, g, parent);
+}
+
+// ---- flatten ---------------------------------------------------------------------------------------------------------------------
+__host__ __device__ inline void cc_flatten_one(size_t i, int* __restrict__ parent, int32_t* __restrict__ label) {
+    label[i] = cc_load(&parent[i]) < 0 ? -1 : cc_find(parent, (int)i);
+}
+__global__ __launch_bounds__(256) void k_cc_flatten(int n, int* __restrict__ parent, int32_t* __restrict__ label) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) cc_flatten_one(i, parent, label);
+}
+
+// ---- sizes: cnt[] is zero at the start ---------------------------------------------------------------------------------------------
+__host__ __device__ inline void cc_count_one(size_t i, const int32_t* __restrict__ label, int* __restrict__ cnt) {
+    const int l = label[i];
+    if (l >= 0) cloud_fetch_add(&cnt[l], 1);
+}
+// the same sums with one add per distinct label of a wave: the lanes that share the label of the first lane still waiting are
+// counted by a ballot, that lane adds their number, and they leave; a wave makes at most as many rounds as it holds labels
+__global__ __launch_bounds__(256) void k_cc_count(int n, const int32_t* __restrict__ label, int* __restrict__ cnt) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const int l = i < (size_t)n ? label[i] : -1;
+    const int lane = (int)(threadIdx.x & 63);
+    bool waiting = l >= 0;
+    unsigned long long todo = __ballot(waiting);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int ll = __shfl(l, lead, 64);
+        const unsigned long long same = __ballot(waiting && l == ll);
+        if (lane == lead) atomicAdd(&cnt[ll], (int)__popcll(same));
+        waiting = waiting && l != ll;
+        todo &= ~same;
+    }
+#endif
+}
+
+__host__ __device__ inline void cc_gather_one(size_t i, const int32_t* __restrict__ label, const int* __restrict__ cnt, int32_t* __restrict__ size) {
+    const int l = label[i];
+    size[i] = l >= 0 ? cnt[l] : 0;
+}
+__global__ __launch_bounds__(256) void k_cc_gather(int n, const int32_t* __restrict__ label, const int* __restrict__ cnt, int32_t* __restrict__ size) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)n) cc_gather_one(i, label, cnt, size);
+}
+
+}  // namespace pm

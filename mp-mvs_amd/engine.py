@@ -82,6 +82,10 @@ _EXTRA = {
     # normals from the k nearest neighbours (cloud.py: Cloud.normals, estimate_normals)
     "cloud_normals": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_double), _P, _P, _P, _P]),
     "cloud_normals_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    # connected components within a radius (cloud.py: Cloud.components, remove_small_clusters)
+    "cloud_components": (C.c_int, [_P, C.c_float, _P, _P, C.POINTER(C.c_longlong)]),
+    "cloud_components_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "cloud_components_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     # registration (cloud.py: Aligner, solve, align)
     "align_create": (C.c_int, [_P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
     "align_sums": (C.c_int, [_P, C.c_float, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
