@@ -674,6 +674,59 @@ float mpmvs_cloud_render_ms(const mpmvs_cloud* cloud);
 /* the same per pass: ms[0] z-min, ms[1] index (0 when no index map was wanted), ms[2] resolve */
 int mpmvs_cloud_render_pass_ms(const mpmvs_cloud* cloud, float ms[3]);
 
+/* ---- point clouds: the space a scan's scanners observed (mp-mvs_amd/cloud.py: Observer, tools/eval_ply.py --scanners) --- */
+/* A terrestrial scanner observed the segment from its own position to every surface sample: that is free space.  A reconstruction
+ * point inside it and far from every scan point is certainly wrong; a point beyond the surface, or along a ray that returned
+ * nothing, lies in space nobody measured and says nothing about accuracy.  Per scanner position the handle keeps a range image
+ * over the full sphere, as a cube map of six R x R faces, made from a scan on the device; any number of query points are then
+ * classified per scanner as free, covered but not free, or not covered (mp-mvs_amd/csrc/pm_observe.hpp).
+ * This is the project's own formulation of observed-space masking, not a port of ETH3D's program and not verified against it.
+ * DEFINED BY EQUIVALENCE with this plain-loop statement, bit for bit and independent of scheduling; everything is fp32 without
+ * contraction and with correctly rounded quotients.  Scanner j sits at S_j (three finite numbers), R = face_size, w = window.
+ *   FACE AND PIXEL of a point p for scanner j:  d_a = p_a - S_j,a for each axis a (one subtraction), A_a = |d_a|;  m = the lowest
+ *   axis index that attains max(A_0, A_1, A_2);  z = A_m.  The point TAKES PART iff its three coordinates are finite, z is finite
+ *   and z > 0 (a difference that overflows, and the scanner's own position, take no part).  face f = 2 m + (d_m < 0 ? 1 : 0);
+ *   b = (m + 1) % 3, c = (m + 2) % 3;  h = (float)R * 0.5f;  x = h * (d_b / z) + h,  y = h * (d_c / z) + h: a quotient, a product
+ *   and a sum, each rounded.  |d_b| <= z and the quotient is correctly rounded, so 0 <= x <= R.
+ *   px = x >= (float)R ? R - 1 : (int)x, py alike: every point that takes part has exactly one face and one pixel per scanner.
+ *   MAPS.  Zc[j][f][py][px] = the smallest z of the scan points that take part for j and land in that pixel; +inf if none.
+ *   owner == NULL: every scan point takes part for every scanner.  owner given (int32 [n], n the count of the cloud handle): point i
+ *   enters the maps of scanner owner[i] only, and of none when owner[i] == -1.
+ *   Zn[j][f][y][x] = the smallest Zc[j][f][y'][x'] over |x' - x| <= w, |y' - y| <= w clipped to the same face.  The window does not
+ *   cross onto the neighbouring faces: a stated simplification, near a face edge the test is a little less conservative.
+ *   window == 0 gives Zn == Zc.
+ *   CLASSIFICATION of a query q for scanner j with the margins rel (finite, in [0, 1)) and abs_margin (finite, >= 0):
+ *   q is COVERED iff it takes part and Zn at its (face, pixel) is finite;  q is FREE iff it is covered and
+ *   z + abs_margin < Zn * (1.0f - rel): each side one rounded operation after the rounded 1.0f - rel.
+ *   out_free[q] = the number of scanners for which q is free, out_covered[q] (may be NULL) for which it is covered; a query with a
+ *   non-finite coordinate has 0 and 0.
+ * mpmvs_observer_create reads the resident points of the cloud handle (the scan is uploaded once for the searches and for this),
+ * during the call only: the observer keeps no reference, and destroying the cloud afterwards is legal.  The cloud's search grids and
+ * their cache are not touched.  Only Zn stays resident (scanners x 6 R^2 floats); Zc is scratch of the call, for a few scanners at a
+ * time.  *out is NULL after a failure, which leaves no allocation behind.  A scan without a finite point is legal: every pixel is
+ * +inf and nothing is covered.  Host buffers in and out; every call blocks until done; n_q == 0 is legal and writes nothing.
+ * Errors (text through mpmvs_last_error with a NULL context, per host thread): -2 = a NULL handle or required pointer, n_scanners
+ * outside [1, MPMVS_OBSERVE_MAX_SCANNERS], a non-finite scanner coordinate, face_size outside [1, MPMVS_OBSERVE_MAX_FACE], window
+ * outside [0, MPMVS_OBSERVE_MAX_WINDOW], an owner value that is neither -1 nor a scanner, rel or abs_margin out of range, a negative
+ * n_q, a scanner index out of range in mpmvs_observer_maps; -3 = n_scanners * 6 * face_size^2 above 2^31 pixels, n_q above 2^31 - 1;
+ * -100 = HIP failure.  All but -100 are found before the device is touched. */
+#define MPMVS_OBSERVE_MAX_SCANNERS 64
+#define MPMVS_OBSERVE_MAX_FACE 4096
+#define MPMVS_OBSERVE_MAX_WINDOW 8
+typedef struct mpmvs_observer mpmvs_observer;
+int mpmvs_observer_create(mpmvs_cloud* scan, int n_scanners, const float* scanners_xyz /* n_scanners x 3 */, const int* owner /* n, or NULL */,
+                          int face_size, int window, mpmvs_observer** out);
+int mpmvs_observer_classify(mpmvs_observer* obs, long long n_q, const float* q_xyz, float rel, float abs_margin, int* out_free /* n_q */,
+                            int* out_covered /* n_q, may be NULL */);
+/* Zn of one scanner: 6 * R * R floats, face-major, +inf = nothing */
+int mpmvs_observer_maps(mpmvs_observer* obs, int scanner, float* out_near);
+/* out[0] = the pixels with a finite Zn, out[1] = all pixels (n_scanners * 6 * R^2) */
+int mpmvs_observer_stats(mpmvs_observer* obs, long long out[2]);
+/* device ms (HIP events) of the last classify call's kernel, all launches; build_ms (may be NULL) receives those of the create's two
+ * passes, all chunks of scanners added up: [0] z-min, [1] window minimum */
+float mpmvs_observer_ms(mpmvs_observer* obs, float build_ms[2]);
+void mpmvs_observer_destroy(mpmvs_observer* obs);
+
 /* ---- point clouds: registration to a target handle, ICP on the device (mp-mvs_amd/cloud.py, tools/eval_ply.py --refine) --- */
 /* Point-to-point ICP with an optional scale, as the Tanks and Temples protocol refines a given alignment before it measures
  * (DESIGN.md section 15).  The moving ("source") cloud is uploaded once per align handle; a PASS transforms it on the device by

@@ -8,12 +8,15 @@ Cloud.knn_self, remove_outliers; csrc/pm_knn.hpp), and a s
 (Cloud.normals, estimate_normals; csrc/pm_normals.hpp), and point-to-plane ICP on those normals beside the
 point-to-point one (Aligner.set_normals / plane_sums / plane_icp, plane_solve, align(method="plane"); csrc/pm_align_plane.hpp,
 DESIGN.md section 19), and the connected components of a cloud under "within a radius", with the filter that drops small detached
-clusters on top of them (Cloud.components, remove_small_clusters; csrc/pm_components.hpp).
+clusters on top of them (Cloud.components, remove_small_clusters; csrc/pm_components.hpp), and the space the
+scanners of a scan observed, as a range cube map per scanner position against which points are classified (Observer,
+score_observed, evaluate(scanners=...), read_scan_alignment; csrc/pm_observe.hpp).
 
 The score is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  Both clouds can be resampled on a voxel
 grid first (evaluate(voxel=...)), as Tanks and Temples and ETH3D's official program do.  ETH3D's program additionally masks
-the space the scanner did not observe, which is not available here, so the numbers are comparable between our own builds and
-settings, and not to the ETH3D leaderboard.  The search runs on the GPU; there is no CPU path."""
+the space the scanner did not observe; evaluate(scanners=...) does observed-space masking in our own formulation, not verified
+against ETH3D's program, so the numbers are comparable between our own builds and settings, and not to the ETH3D leaderboard.
+The search runs on the GPU; there is no CPU path."""
 import ctypes as C
 import math
 import weakref
@@ -328,6 +331,117 @@ class Cloud:
         return float(self._f["cloud_render_ms"](self._h)), {"zmin": float(ms[0]), "index": float(ms[1]), "resolve": float(ms[2])}
 
 
+class Observer:
+    """The space the scanners of a scan observed (mpmvs_observer_create; csrc/pm_observe.hpp): per scanner
+    position a range cube map of six face_size x face_size faces in HBM, made on the device from the points of `scan_cloud` (a
+    Cloud; read during the constructor only, so the Cloud may be closed afterwards, and its search grids are not touched).
+
+    scanners: float32 [m, 3], 1 <= m <= 64, in the scan's frame.  owner (int32 [n], optional): the scanner that measured each scan
+    point, -1 for none; without it every point counts for every scanner, which is right only when the scanners saw the same
+    surfaces.  window: a pixel's range is the smallest of the (2 window + 1)^2 pixels around it on its face, so that a query
+    just beside a silhouette is not called free against the background.
+
+    The defaults (face_size 1024, window 1, and rel 0.02 / abs_margin 0 of classify) are starting values, not tuned on a real
+    scan.  This is observed-space masking in the project's own formulation, not verified against ETH3D's program."""
+
+    def __init__(self, scan_cloud, scanners, owner=None, face_size=1024, window=1):
+        _, self._f = engine.load()
+        s = _xyz(scanners)
+        self.n_scanners, self.face_size, self.window = len(s), int(face_size), int(window)
+        self._h = None
+        own = None
+        if owner is not None:
+            own = np.ascontiguousarray(owner, np.int32)
+            if own.shape != (scan_cloud.n,):
+                raise ValueError(f"owner needs one entry per scan point ({scan_cloud.n}), got shape {own.shape}")
+        h = C.c_void_p(None)
+        rc = self._f["observer_create"](scan_cloud._h, self.n_scanners, s.ctypes.data, own.ctypes.data if own is not None else None, self.face_size,
+                                        self.window, C.byref(h))
+        if rc != 0:
+            self._raise("observer_create", rc)
+        self._h = h
+
+    _raise = Cloud._raise
+
+    def close(self):
+        if self._h:
+            self._f["observer_destroy"](self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def classify(self, xyz, rel=0.02, abs_margin=0.0, want_covered=True):
+        """mpmvs_observer_classify -> (free int32 [n], covered int32 [n] or None): per point the number of scanners that saw
+        through it (its range plus abs_margin lies below the map's range times 1 - rel: observed free space), and the number
+        whose map holds any range in its direction.  free == 0 with covered > 0: at or behind a scanned surface; covered == 0:
+        no scanner looked there."""
+        a = _xyz(xyz)
+        free = np.empty(len(a), np.int32)
+        cov = np.empty(len(a), np.int32) if want_covered else None
+        rc = self._f["observer_classify"](self._h, len(a), a.ctypes.data, float(rel), float(abs_margin), free.ctypes.data,
+                                          cov.ctypes.data if want_covered else None)
+        if rc != 0:
+            self._raise("observer_classify", rc)
+        return free, cov
+
+    def near_map(self, j):
+        """float32 [6, R, R]: the windowed nearest range of scanner j per face (+x -x +y -y +z -z) and pixel, inf = nothing"""
+        out = np.empty((6, self.face_size, self.face_size), np.float32)
+        rc = self._f["observer_maps"](self._h, int(j), out.ctypes.data)
+        if rc != 0:
+            self._raise("observer_maps", rc)
+        return out
+
+    def stats(self):
+        """{"covered_pixels": pixels with a finite range, "pixels": all pixels of all scanners}"""
+        s = (C.c_longlong * 2)()
+        self._f["observer_stats"](self._h, s)
+        return {"covered_pixels": int(s[0]), "pixels": int(s[1])}
+
+    def ms(self):
+        """device ms: (the last classify call, {"zmin", "near"} of the constructor's two passes)"""
+        b = (C.c_float * 2)()
+        q = self._f["observer_ms"](self._h, b)
+        return float(q), {"zmin": float(b[0]), "near": float(b[1])}
+
+
+def read_scan_alignment(path):
+    """The MeshLab project file ETH3D ships with its scans (scan_alignment.mlp) -> [(filename, T float64 [4, 4])]: every MLMesh
+    element's `filename` attribute and the 16 numbers of its MLMatrix44 child, row-major.  T takes the scan into the common
+    frame, so T[:3, 3] is the scanner's position there.  Restated from the format's description; no real ETH3D file has been
+    read with it here.  A file that does not parse, or an MLMesh without a name or 16 numbers, raises ValueError."""
+    import xml.etree.ElementTree as ET
+    try:
+        root = ET.parse(path).getroot()
+    except ET.ParseError as e:
+        raise ValueError(f"{path}: not an XML file: {e}") from None
+    out = []
+    for mesh in root.iter("MLMesh"):
+        name, mat = mesh.get("filename"), mesh.find("MLMatrix44")
+        if not name or mat is None:
+            raise ValueError(f"{path}: an MLMesh element without a filename or an MLMatrix44")
+        try:
+            T = np.array((mat.text or "").split(), np.float64)
+        except ValueError:
+            raise ValueError(f"{path}: the matrix of {name} does not hold numbers") from None
+        if T.size != 16 or not np.isfinite(T).all():
+            raise ValueError(f"{path}: the matrix of {name} needs 16 finite numbers, got {T.size}")
+        out.append((name, T.reshape(4, 4)))
+    if not out:
+        raise ValueError(f"{path}: no MLMesh element")
+    return out
+
+
 def _m12(M):
     """a 3 x 4 or 4 x 4 (last row 0 0 0 1) matrix -> 12 contiguous doubles, row-major 3 x 4"""
     a = np.asarray(M, np.float64)
@@ -605,6 +719,26 @@ def score(d_recon, d_gt, tolerances, dropped=(0, 0)):
     return res
 
 
+def score_observed(d_recon, d_gt, free, tolerances, dropped=(0, 0)):
+    """score() plus the observed-space keys of evaluate(scanners=...): `free` holds, per reconstruction point, the number of
+    scanners that saw through it (Observer.classify).  Per tolerance t a point with d > t counts as "n_free_inaccurate" when
+    free >= 1 (it lies in space a scanner saw to be empty: certainly wrong) and as "n_unobserved" when free == 0 (nobody measured
+    there: it leaves the denominator);  accuracy_observed = n_accurate / (n_accurate + n_free_inaccurate), 0 for an empty
+    denominator;  f1_observed is the harmonic mean of accuracy_observed and the unchanged completeness."""
+    res = score(d_recon, d_gt, tolerances, dropped)
+    d, seen = np.asarray(d_recon, np.float32), np.asarray(free) >= 1
+    if seen.shape != d.shape:
+        raise ValueError(f"free needs one entry per reconstruction point ({d.size}), got shape {seen.shape}")
+    for row in res["tolerances"]:
+        far = d > np.float32(row["tolerance"])
+        nf, nu = int((far & seen).sum()), int((far & ~seen).sum())
+        den = row["n_accurate"] + nf
+        acc, com = (row["n_accurate"] / den if den else 0.0), row["completeness"]
+        row.update({"n_free_inaccurate": nf, "n_unobserved": nu, "accuracy_observed": acc,
+                    "f1_observed": 2 * acc * com / (acc + com) if acc + com > 0 else 0.0})
+    return res
+
+
 def drop_nonfinite(xyz):
     """(the points with finite coordinates, the number dropped)"""
     a = _xyz(xyz)
@@ -770,7 +904,8 @@ def write_ply(path, xyz, normals=None, colors=None):
     hostlib.write_ply(path, p9)
 
 
-def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None):
+def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None, scanners=None, owner=None, face_size=1024, window=1, free_rel=0.02,
+             free_abs=0.0):
     """Accuracy, completeness and F1 of a reconstructed cloud against a ground-truth cloud at every tolerance.
 
     Per tolerance t: accuracy = the share of reconstruction points whose nearest ground-truth point is within t (inclusive),
@@ -783,15 +918,40 @@ def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None):
     (Tanks and Temples uses half its tolerance); the result then also holds "voxel" and the point counts before the resampling,
     "n_reconstruction_in" and "n_ground_truth_in".  None leaves the clouds as they are.
 
-    This is the plain two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
-    masks the space the scanner did not observe, which is not available here: the numbers are comparable between our own builds
-    and settings, and not to the ETH3D leaderboard.  timings (a dict, optional) receives seconds of upload + build and of query."""
+    scanners (None, or float32 [m, 3] scanner positions in the ground truth's frame): the accuracy is also given over observed
+    space only (Observer).  The range cube maps are made from the ground truth after the non-finite points
+    are dropped and before any voxel resampling; owner (optional, one scanner index or -1 per ground-truth point as passed in) is
+    filtered with the points.  The reconstruction as scored (after the resampling) is classified with the margins free_rel and
+    free_abs, and every tolerance row gains "n_free_inaccurate", "n_unobserved", "accuracy_observed" and "f1_observed"
+    (score_observed), the result "observed": {"scanners", "face_size", "window", "free_rel", "free_abs", "covered_pixels",
+    "pixels"}.  A reconstruction point beyond the scanned surface, or in a direction that returned nothing, then no longer counts
+    as inaccurate.  face_size 1024, window 1, free_rel 0.02 and free_abs 0 are starting values, not tuned on a real scan.  An
+    Observer the caller made (of a scan that these clouds were resampled from, say) may be given in place of the positions: it is
+    used as it is and left open.  None changes nothing: the keys and values are those of the plain measure.
+
+    The plain keys are the two-way nearest-neighbour measure (Tanks-and-Temples style).  ETH3D's official program additionally
+    masks the space the scanner did not observe; the observed-space keys do that in our own formulation, not verified against
+    ETH3D's program: the numbers are comparable between our own builds and settings, and not to the ETH3D leaderboard.
+    timings (a dict, optional) receives seconds of upload + build and of query, and "observe_s" with scanners."""
     import time
     rec, drop_r = drop_nonfinite(recon_xyz)
     gt, drop_g = drop_nonfinite(gt_xyz)
     tol = [float(t) for t in tolerances]
     if not tol or not all(np.isfinite(t) and t > 0 for t in tol):
         raise ValueError("tolerances must be finite and positive")
+    obs, t_obs = None, 0.0
+    if isinstance(scanners, Observer):
+        obs = scanners
+    elif scanners is not None:
+        if owner is not None:
+            owner = np.asarray(owner, np.int32)
+            if owner.shape != (len(_xyz(gt_xyz)),):
+                raise ValueError(f"owner needs one entry per ground-truth point, got shape {owner.shape}")
+            owner = owner[np.isfinite(_xyz(gt_xyz)).all(1)]
+        t_o = time.perf_counter()
+        with Cloud(gt, device) as c_scan:
+            obs = Observer(c_scan, scanners, owner, face_size, window)
+        t_obs = time.perf_counter() - t_o
     if voxel is not None:
         if not (np.isfinite(voxel) and voxel > 0):
             raise ValueError("voxel must be finite and positive")
@@ -815,7 +975,20 @@ def evaluate(recon_xyz, gt_xyz, tolerances, device=0, timings=None, voxel=None):
     if timings is not None:
         timings["upload_build_s"] = (t1 - t0) + (t3 - t2) + t_build[0]
         timings["query_s"] = (t2 - t1) + (t4 - t3) - t_build[0]
-    res = score(d_rec, d_gt, tol, (drop_r, drop_g))
+    if obs is None:
+        res = score(d_rec, d_gt, tol, (drop_r, drop_g))
+    else:
+        t_o = time.perf_counter()
+        try:
+            free, _ = obs.classify(rec, free_rel, free_abs, want_covered=False)
+            res = score_observed(d_rec, d_gt, free, tol, (drop_r, drop_g))
+            res["observed"] = {"scanners": obs.n_scanners, "face_size": obs.face_size, "window": obs.window, "free_rel": float(free_rel),
+                               "free_abs": float(free_abs), **obs.stats()}
+        finally:
+            if obs is not scanners:
+                obs.close()
+        if timings is not None:
+            timings["observe_s"] = t_obs + (time.perf_counter() - t_o)
     if voxel is not None:
         res["voxel"], res["n_reconstruction_in"], res["n_ground_truth_in"] = float(voxel), n_in[0], n_in[1]
     return res

@@ -47,6 +47,7 @@
 #include "pm_align_plane.hpp"
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
+#include "pm_observe.hpp"
 #include "pm_ingest.hpp"
 #include "pm_undistort.hpp"
 #include "pm_skyseg.hpp"
@@ -4198,6 +4199,183 @@ int mpmvs_cloud_render_pass_ms(const mpmvs_cloud* c, float ms[3]) {
     if (!c || !ms) return seg_fail(-2, "cloud render: bad argument");
     std::memcpy(ms, c->render_pass_ms, sizeof c->render_pass_ms);
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// the space the scanners of a scan observed: a resident range cube map per scanner position and the classification of query points
+// against it (pm_observe.hpp).  Errors are reported like those of mpmvs_cloud_*.
+// ---------------------------------------------------------------------------
+static_assert(kObserveMaxScanners == MPMVS_OBSERVE_MAX_SCANNERS && kObserveMaxFace == MPMVS_OBSERVE_MAX_FACE && kObserveMaxWindow == MPMVS_OBSERVE_MAX_WINDOW,
+              "observer bounds");
+constexpr long long kObserveChunkQueries = 1ll << 24;       // queries per launch of the classify pass: 320 MB of device buffers at most
+
+struct mpmvs_observer {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // the borders of the two passes of a chunk; ev[0], ev[1]: of a classify launch
+    ObserveScanners sc;                               // all scanners, j0 = 0
+    int R = 0, w = 0;
+    float* d_zn = nullptr;                            // [n_scanners][6][R][R]
+    long long stats[2] = {0, 0};
+    float build_pass_ms[2] = {0.0f, 0.0f}, classify_ms = 0.0f;
+};
+
+static void observer_release(mpmvs_observer* h) {
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    if (h->d_zn) (void)pool_free(h->d_zn);
+    for (hipEvent_t e : h->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+// the device half of mpmvs_observer_create: Zc and Zn of one chunk of scanners after the other; the scan's points are read in place
+static int observer_create_device(mpmvs_observer* h, const mpmvs_cloud* scan, const int* owner) {
+    SEGCHK(enter_device(scan->device));
+    SEGCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->ev) SEGCHK(hipEventCreate(&e));
+    const hipStream_t st = h->stream;
+    const size_t map = (size_t)6 * (size_t)h->R * (size_t)h->R, total = map * (size_t)h->sc.n;
+    SEGCHK(pool_malloc(&h->d_zn, total * 4));
+    if (scan->n_fin == 0) {   // nothing lands anywhere
+        SEGCHK(hipMemsetD32Async((hipDeviceptr_t)h->d_zn, (int)kRenderInfBits, total, st));
+        SEGCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    const int per = (int)std::min<size_t>((size_t)kObserveChunk, std::max<size_t>(1, kObserveChunkPixels / map));
+    const int n = (int)scan->n;
+    Scratch d_zc(st), d_owner(st), d_cnt(st);
+    SEGCHK(d_zc.alloc(map * (size_t)std::min(per, h->sc.n) * 4));
+    SEGCHK(d_cnt.alloc(8));
+    SEGCHK(hipMemsetAsync(d_cnt.p, 0, 8, st));
+    if (owner) {
+        SEGCHK(d_owner.alloc((size_t)n * 4));
+        SEGCHK(hipMemcpyAsync(d_owner.p, owner, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    for (int j0 = 0; j0 < h->sc.n; j0 += per) {
+        ObserveScanners A = h->sc;
+        A.j0 = j0, A.n = std::min(per, h->sc.n - j0);
+        const size_t n_pix = map * (size_t)A.n;
+        SEGCHK(hipMemsetD32Async((hipDeviceptr_t)d_zc.p, (int)kRenderInfBits, n_pix, st));
+        SEGCHK(hipEventRecord(h->ev[0], st));
+        hipLaunchKernelGGL(k_observe_zmin, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, scan->d_xyz, n, owner ? d_owner.as<int>() : (const int*)nullptr, A,
+                           h->R, d_zc.as<uint32_t>());
+        SEGCHK(hipEventRecord(h->ev[1], st));
+        hipLaunchKernelGGL(k_observe_near, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, st, d_zc.as<uint32_t>(), n_pix, h->R, h->w,
+                           h->d_zn + map * (size_t)j0, d_cnt.as<unsigned long long>());
+        SEGCHK(hipGetLastError());
+        SEGCHK(hipEventRecord(h->ev[2], st));
+        SEGCHK(hipStreamSynchronize(st));
+        for (int p = 0; p < 2; ++p) {
+            float ms = 0.0f;
+            SEGCHK(hipEventElapsedTime(&ms, h->ev[p], h->ev[p + 1]));
+            h->build_pass_ms[p] += ms;
+        }
+    }
+    unsigned long long covered = 0;
+    SEGCHK(hipMemcpyAsync(&covered, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    h->stats[0] = (long long)covered;
+    return 0;
+}
+
+int mpmvs_observer_create(mpmvs_cloud* scan, int n_scanners, const float* scanners_xyz, const int* owner, int face_size, int window, mpmvs_observer** out) {
+    if (!out) return seg_fail(-2, "observer: bad argument");
+    *out = nullptr;
+    if (!scanners_xyz) return seg_fail(-2, "observer: bad argument");
+    if (n_scanners < 1 || n_scanners > MPMVS_OBSERVE_MAX_SCANNERS)
+        return seg_fail(-2, "observer: the number of scanners must lie in [1, " + std::to_string(MPMVS_OBSERVE_MAX_SCANNERS) + "]");
+    for (int k = 0; k < 3 * n_scanners; ++k)
+        if (!std::isfinite(scanners_xyz[k])) return seg_fail(-2, "observer: scanner " + std::to_string(k / 3) + " has a non-finite coordinate");
+    if (face_size < 1 || face_size > MPMVS_OBSERVE_MAX_FACE) return seg_fail(-2, "observer: face_size must lie in [1, " + std::to_string(MPMVS_OBSERVE_MAX_FACE) + "]");
+    if (window < 0 || window > MPMVS_OBSERVE_MAX_WINDOW) return seg_fail(-2, "observer: window must lie in [0, " + std::to_string(MPMVS_OBSERVE_MAX_WINDOW) + "]");
+    if ((long long)n_scanners * 6 * face_size * face_size > (1ll << 31)) return seg_fail(-3, "observer: more than 2^31 pixels (scanners x 6 x face_size^2)");
+    if (!scan) return seg_fail(-2, "observer: no scan");   // after the checks that need none
+    for (long long i = 0; owner && i < scan->n; ++i)
+        if (owner[i] < -1 || owner[i] >= n_scanners)
+            return seg_fail(-2, "observer: owner[" + std::to_string(i) + "] = " + std::to_string(owner[i]) + " is neither -1 nor a scanner");
+    mpmvs_observer* h = new mpmvs_observer;
+    h->device = scan->device;
+    std::memset(&h->sc, 0, sizeof h->sc);
+    h->sc.n = n_scanners;
+    std::memcpy(h->sc.s, scanners_xyz, (size_t)n_scanners * 12);
+    h->R = face_size, h->w = window;
+    h->stats[1] = (long long)n_scanners * 6 * face_size * face_size;
+    const int rc = observer_create_device(h, scan, owner);
+    if (rc) {
+        observer_release(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+void mpmvs_observer_destroy(mpmvs_observer* h) {
+    if (!h) return;
+    (void)enter_device(h->device);
+    observer_release(h);
+}
+
+// queries [0, n) of one launch
+static int observer_classify_chunk(mpmvs_observer* h, int n, const float* q_xyz, float m1, float abs_margin, int* out_free, int* out_covered) {
+    const hipStream_t st = h->stream;
+    Scratch d_q(st), d_free(st), d_cov(st);
+    SEGCHK(d_q.alloc((size_t)n * 12));
+    SEGCHK(d_free.alloc((size_t)n * 4));
+    if (out_covered) SEGCHK(d_cov.alloc((size_t)n * 4));
+    SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
+    SEGCHK(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(k_observe_classify, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, d_q.as<float>(), n, h->sc, h->R, h->d_zn, m1, abs_margin,
+                       d_free.as<int>(), out_covered ? d_cov.as<int>() : (int*)nullptr);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(h->ev[1], st));
+    SEGCHK(hipMemcpyAsync(out_free, d_free.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (out_covered) SEGCHK(hipMemcpyAsync(out_covered, d_cov.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    SEGCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->classify_ms += ms;
+    return 0;
+}
+
+int mpmvs_observer_classify(mpmvs_observer* h, long long n_q, const float* q_xyz, float rel, float abs_margin, int* out_free, int* out_covered) {
+    if (!std::isfinite(rel) || !(rel >= 0.0f && rel < 1.0f)) return seg_fail(-2, "observer: rel must lie in [0, 1)");
+    if (!std::isfinite(abs_margin) || !(abs_margin >= 0.0f)) return seg_fail(-2, "observer: abs_margin must be finite and not negative");
+    if (n_q < 0 || !out_free || (n_q > 0 && !q_xyz)) return seg_fail(-2, "observer: bad argument");
+    if (n_q > INT32_MAX) return seg_fail(-3, "observer: more than 2^31 - 1 queries");
+    if (!h) return seg_fail(-2, "observer: no handle");   // after the checks that need none
+    h->classify_ms = 0.0f;
+    if (n_q == 0) return 0;
+    SEGCHK(enter_device(h->device));
+    const float m1 = 1.0f - rel;
+    for (long long q0 = 0; q0 < n_q; q0 += kObserveChunkQueries) {
+        const int n = (int)std::min(kObserveChunkQueries, n_q - q0);
+        const int rc = observer_classify_chunk(h, n, q_xyz + 3 * q0, m1, abs_margin, out_free + q0, out_covered ? out_covered + q0 : nullptr);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int mpmvs_observer_maps(mpmvs_observer* h, int scanner, float* out_near) {
+    if (!h || !out_near) return seg_fail(-2, "observer: bad argument");
+    if (scanner < 0 || scanner >= h->sc.n) return seg_fail(-2, "observer: no scanner " + std::to_string(scanner));
+    SEGCHK(enter_device(h->device));
+    const size_t map = (size_t)6 * (size_t)h->R * (size_t)h->R;
+    SEGCHK(hipMemcpyAsync(out_near, h->d_zn + map * (size_t)scanner, map * 4, hipMemcpyDeviceToHost, h->stream));
+    SEGCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int mpmvs_observer_stats(mpmvs_observer* h, long long out[2]) {
+    if (!h || !out) return seg_fail(-2, "observer: bad argument");
+    out[0] = h->stats[0], out[1] = h->stats[1];
+    return 0;
+}
+
+float mpmvs_observer_ms(mpmvs_observer* h, float build_ms[2]) {
+    if (!h) return 0.0f;
+    if (build_ms) build_ms[0] = h->build_pass_ms[0], build_ms[1] = h->build_pass_ms[1];
+    return h->classify_ms;
 }
 
 }  // extern "C"

@@ -68,6 +68,13 @@ _EXTRA = {
     "cloud_render_depth": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_float, _P, _P]),
     "cloud_render_ms": (C.c_float, [_P]),
     "cloud_render_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    # the space a scan's scanners observed (cloud.py: Observer)
+    "observer_create": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "observer_classify": (C.c_int, [_P, C.c_longlong, _P, C.c_float, C.c_float, _P, _P]),
+    "observer_maps": (C.c_int, [_P, C.c_int, _P]),
+    "observer_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "observer_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "observer_destroy": (None, [_P]),
     # voxel-grid downsampling (cloud.py: voxel_downsample)
     "cloud_voxel_downsample": (C.c_longlong, [C.c_int, C.c_longlong, _P, _P, _P, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _P]),
