@@ -3002,6 +3002,15 @@ struct CloudGridBuf {
 };
 constexpr size_t kCloudMaxGrids = 8;   // per handle; the least recently used one gives its buffers to a new radius
 
+// device ms (HIP events) of an operation's last call on a handle: its own passes, and the grid build it needed (0 if reused)
+struct CloudOpMs {
+    float ms = 0.0f, build_ms = 0.0f;
+};
+static float cloud_op_ms(const CloudOpMs& t, float* build_ms) {
+    if (build_ms) *build_ms = t.build_ms;
+    return t.ms;
+}
+
 struct mpmvs_cloud {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -3014,13 +3023,13 @@ struct mpmvs_cloud {
     std::vector<CloudGridBuf> grids;   // every grid has the same sizes: they depend on the finite count only
     unsigned long long use_clock = 0;
     long long stats[4] = {0, 0, 0, 0};
-    float query_ms = 0.0f, build_ms = 0.0f;
+    // the last nearest, knn, normals and components call (cloud_enter fills build_ms).  query.build_ms is also where cloud_grid
+    // leaves the build time of the grid it was last asked for, whoever asked (0 = cached): mpmvs_cloud_kernel_ms reports an align
+    // pass's build through it
+    CloudOpMs query, knn, normals, cc;
     float render_pass_ms[3] = {0.0f, 0.0f, 0.0f};   // z-min, index, resolve of the last render call
-    float knn_ms = 0.0f, knn_build_ms = 0.0f;       // the last mpmvs_cloud_knn call
-    float normals_ms = 0.0f, normals_build_ms = 0.0f;   // the last mpmvs_cloud_normals call
     int* d_cc = nullptr;                            // n ints of mpmvs_cloud_components (parent, then the sizes): allocated by its first call
-    float cc_ms = 0.0f, cc_build_ms = 0.0f;         // the last mpmvs_cloud_components call
-    float cc_pass_ms[3] = {0.0f, 0.0f, 0.0f};       // its hook (with init and binning), flatten and size passes
+    float cc_pass_ms[3] = {0.0f, 0.0f, 0.0f};       // the components call's hook (with init and binning), flatten and size passes
 };
 
 static void cloud_free_grid(CloudGridBuf& g) {
@@ -3139,7 +3148,7 @@ static int cloud_build(mpmvs_cloud* c, CloudGridBuf& g, float radius) {
     int h_st[2] = {0, 0};
     SEGCHK(hipMemcpyAsync(h_st, c->d_st, 8, hipMemcpyDeviceToHost, st));
     SEGCHK(hipStreamSynchronize(st));
-    SEGCHK(hipEventElapsedTime(&c->build_ms, c->ev[0], c->ev[1]));
+    SEGCHK(hipEventElapsedTime(&c->query.build_ms, c->ev[0], c->ev[1]));
     g.occupied = h_st[0], g.fullest = h_st[1];
     g.radius = radius;
     return 0;
@@ -3151,7 +3160,7 @@ static int cloud_grid(mpmvs_cloud* c, float radius, CloudGridBuf** out) {
     for (CloudGridBuf& k : c->grids)
         if (std::memcmp(&k.radius, &radius, 4) == 0) g = &k;
     if (g) {
-        c->build_ms = 0.0f;
+        c->query.build_ms = 0.0f;
     } else {
         if (c->grids.size() < kCloudMaxGrids) {
             const size_t slots = (size_t)1 << c->slots_log2;
@@ -3205,43 +3214,60 @@ static CloudGrid cloud_grid_args(const mpmvs_cloud* c, const CloudGridBuf& grid,
     return g;
 }
 
-static int cloud_query(mpmvs_cloud* c, const CloudGridBuf& grid, float radius, int nq, const float* q_xyz, float* out_d2, int32_t* out_idx) {
-    const hipStream_t st = c->stream;
-    const bool bin = cloud_bin_queries();
-    const CloudGrid g = cloud_grid_args(c, grid, radius);
-    int bins_log2 = 8;
-    while (bins_log2 < kCloudMaxSlotsLog2 && (1ll << bins_log2) < nq) ++bins_log2;
-    const size_t bins = (size_t)1 << bins_log2, q = (size_t)nq;
-    Scratch d_q(st), d_d2(st), d_idx(st), d_qbin(st), d_order(st), d_qcnt(st), d_qoff(st), d_qtsum(st);
-    SEGCHK(d_q.alloc(q * 12));
-    SEGCHK(d_d2.alloc(q * 4));
-    if (out_idx) SEGCHK(d_idx.alloc(q * 4));
-    if (bin) {
-        SEGCHK(d_qbin.alloc(q * 4));
-        SEGCHK(d_order.alloc(q * 4));
-        SEGCHK(d_qcnt.alloc(bins * 4));
-        SEGCHK(d_qoff.alloc((bins + 1) * 4));
-        SEGCHK(d_qtsum.alloc(bins / kScanBlock * 4));
-        SEGCHK(hipMemsetAsync(d_qcnt.p, 0, bins * 4, st));
+// the binning of nq queries: a power of two of bins, at least 2^8 and at least nq
+static int cloud_bins_log2(long long nq) {
+    int lg = 8;
+    while (lg < kCloudMaxSlotsLog2 && (1ll << lg) < nq) ++lg;
+    return lg;
+}
+
+// the binning buffers of up to `cap` queries, on a stream that outlives them: those of one call, or of an aligner for all its passes
+struct CloudBins {
+    Scratch qbin, order, qcnt, qoff, qtsum;
+    explicit CloudBins(hipStream_t st) : qbin(st), order(st), qcnt(st), qoff(st), qtsum(st) {}
+    hipError_t alloc(size_t cap) {
+        const size_t bins = (size_t)1 << cloud_bins_log2((long long)cap);
+        hipError_t e;
+        if ((e = qbin.alloc(cap * 4)) != hipSuccess || (e = order.alloc(cap * 4)) != hipSuccess || (e = qcnt.alloc(bins * 4)) != hipSuccess ||
+            (e = qoff.alloc((bins + 1) * 4)) != hipSuccess || (e = qtsum.alloc(bins / kScanBlock * 4)) != hipSuccess)
+            return e;
+        return hipSuccess;
     }
-    SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, q * 12, hipMemcpyHostToDevice, st));
-    SEGCHK(hipEventRecord(c->ev[2], st));
-    const dim3 gq((nq + 255) / 256);
-    if (bin) {
-        hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q.as<float>(), nq, g, (unsigned)(bins - 1), d_qcnt.as<int>(), d_qbin.as<int>());
-        cloud_scan(st, d_qcnt.as<int>(), (int)bins, d_qoff.as<int>(), d_qtsum.as<int>());
-        hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, d_qbin.as<int>(), d_qoff.as<int>(), d_qcnt.as<int>(), d_order.as<int>());
-    }
-    hipLaunchKernelGGL(k_cloud_query, gq, dim3(256), 0, st, d_q.as<float>(), nq, bin ? d_order.as<int>() : (const int*)nullptr, g, d_d2.as<float>(),
-                       out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr);
-    SEGCHK(hipGetLastError());
-    SEGCHK(hipEventRecord(c->ev[3], st));
-    SEGCHK(hipMemcpyAsync(out_d2, d_d2.p, q * 4, hipMemcpyDeviceToHost, st));
-    if (out_idx) SEGCHK(hipMemcpyAsync(out_idx, d_idx.p, q * 4, hipMemcpyDeviceToHost, st));
-    SEGCHK(hipStreamSynchronize(st));
-    SEGCHK(hipEventElapsedTime(&c->query_ms, c->ev[2], c->ev[3]));
+};
+
+extern "C++" {
+// The one binning path: the serving order of nq <= cap queries into b.order.  The counts are cleared, `begin` (may be null) is
+// recorded -- the callers whose timed interval opens after the memset pass their begin event -- and then count / scan / order run.
+// count(grid, bin_mask, qcnt, qbin) launches the counting kernel, the only part that differs: k_cloud_qbin on raw queries,
+// k_align_qbin on transformed sources.
+template <typename Count>
+static int cloud_bin(hipStream_t st, CloudBins& b, int nq, hipEvent_t begin, Count&& count) {
+    const size_t bins = (size_t)1 << cloud_bins_log2(nq);   // <= what alloc sized
+    const dim3 gq(((unsigned)nq + 255u) / 256u);            // unsigned: nq may be 2^31 - 1
+    SEGCHK(hipMemsetAsync(b.qcnt.p, 0, bins * 4, st));
+    if (begin) SEGCHK(hipEventRecord(begin, st));
+    count(gq, (unsigned)(bins - 1), b.qcnt.as<int>(), b.qbin.as<int>());
+    cloud_scan(st, b.qcnt.as<int>(), (int)bins, b.qoff.as<int>(), b.qtsum.as<int>());
+    hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, b.qbin.as<int>(), b.qoff.as<int>(), b.qcnt.as<int>(), b.order.as<int>());
     return 0;
 }
+// the counting launch of raw queries
+static auto cloud_count_queries(hipStream_t st, const float* d_q, int nq, const CloudGrid& g) {
+    return [=](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) { hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q, nq, g, bin_mask, qcnt, qbin); };
+}
+
+// The one dispatch over the list sizes of the kNN family (pm_knn.hpp: knn_list_size): launch(std::integral_constant<int, K>) with
+// the K of 4, 8, 16 or 32 that serves k
+template <typename F>
+static void knn_dispatch(int k, F&& launch) {
+    switch (knn_list_size(k)) {
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        case 16: launch(std::integral_constant<int, 16>{}); break;
+        default: launch(std::integral_constant<int, 32>{}); break;
+    }
+}
+}  // extern "C++"
 
 // the cell-span limit of a grid of `radius` over the handle's finite bounding box (-3), found on the host; `who` opens the text
 static int cloud_span_check(const mpmvs_cloud* c, float radius, const char* who = "cloud: the targets") {
@@ -3258,9 +3284,35 @@ static int cloud_span_check(const mpmvs_cloud* c, float radius, const char* who 
     return 0;
 }
 
+// what every entry point with a radius asks of it; each keeps the text of its own refusal
+static bool cloud_radius_ok(float radius) { return std::isfinite(radius) && radius > 0.0f; }
+
+// The device half of the prologue of every operation on a handle with finite points: the device, the grid of `radius` (cached or
+// built now) and the kernels' view of it in g; the build time goes to t->build_ms and t->ms is cleared (t may be null: an align
+// pass and the outlier filter read query.build_ms themselves).
+static int cloud_open(mpmvs_cloud* c, float radius, CloudOpMs* t, CloudGrid& g) {
+    SEGCHK(enter_device(c->device));
+    CloudGridBuf* grid = nullptr;
+    const int rc = cloud_grid(c, radius, &grid);
+    if (rc) return rc;
+    if (t) *t = CloudOpMs{0.0f, c->query.build_ms};
+    g = cloud_grid_args(c, *grid, radius);
+    return 0;
+}
+// The whole prologue, after the entry point's own argument checks: the span limit first (-3 before the device is touched).
+static int cloud_enter(mpmvs_cloud* c, float radius, CloudOpMs* t, CloudGrid& g) {
+    const int span = cloud_span_check(c, radius);
+    return span ? span : cloud_open(c, radius, t, g);
+}
+// a handle without a finite point answers on the host: no grid, no time
+static void cloud_answered_on_host(mpmvs_cloud* c, CloudOpMs& t) {
+    c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
+    t = CloudOpMs();
+}
+
 int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx) {
     if (!c || !out_d2 || n_q < 0 || (n_q > 0 && !q_xyz)) return seg_fail(-2, "cloud: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "cloud: the radius must be finite and positive");
     if (n_q > INT32_MAX) return seg_fail(-3, "cloud: more than 2^31 - 1 queries");
     if (n_q == 0) return 0;
     if (c->n_fin == 0) {   // no candidate anywhere
@@ -3268,17 +3320,38 @@ int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float
             out_d2[i] = INFINITY;
             if (out_idx) out_idx[i] = -1;
         }
-        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
-        c->query_ms = c->build_ms = 0.0f;
+        cloud_answered_on_host(c, c->query);
         return 0;
     }
-    const int span = cloud_span_check(c, radius);
-    if (span) return span;
-    SEGCHK(enter_device(c->device));
-    CloudGridBuf* grid = nullptr;
-    const int rc = cloud_grid(c, radius, &grid);
+    CloudGrid g;
+    const int rc = cloud_enter(c, radius, &c->query, g);
     if (rc) return rc;
-    return cloud_query(c, *grid, radius, (int)n_q, q_xyz, out_d2, out_idx);
+    const hipStream_t st = c->stream;
+    const bool bin = cloud_bin_queries();
+    const int nq = (int)n_q;
+    const size_t q = (size_t)n_q;
+    Scratch d_q(st), d_d2(st), d_idx(st);
+    CloudBins bins(st);
+    SEGCHK(d_q.alloc(q * 12));
+    SEGCHK(d_d2.alloc(q * 4));
+    if (out_idx) SEGCHK(d_idx.alloc(q * 4));
+    if (bin) SEGCHK(bins.alloc(q));
+    SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, q * 12, hipMemcpyHostToDevice, st));
+    if (bin) {
+        const int brc = cloud_bin(st, bins, nq, c->ev[2], cloud_count_queries(st, d_q.as<float>(), nq, g));
+        if (brc) return brc;
+    } else {
+        SEGCHK(hipEventRecord(c->ev[2], st));
+    }
+    hipLaunchKernelGGL(k_cloud_query, dim3(((unsigned)nq + 255u) / 256u), dim3(256), 0, st, d_q.as<float>(), nq, bin ? bins.order.as<int>() : (const int*)nullptr, g,
+                       d_d2.as<float>(), out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr);
+    SEGCHK(hipGetLastError());
+    SEGCHK(hipEventRecord(c->ev[3], st));
+    SEGCHK(hipMemcpyAsync(out_d2, d_d2.p, q * 4, hipMemcpyDeviceToHost, st));
+    if (out_idx) SEGCHK(hipMemcpyAsync(out_idx, d_idx.p, q * 4, hipMemcpyDeviceToHost, st));
+    SEGCHK(hipStreamSynchronize(st));
+    SEGCHK(hipEventElapsedTime(&c->query.ms, c->ev[2], c->ev[3]));
+    return 0;
 }
 
 int mpmvs_cloud_stats(const mpmvs_cloud* c, long long stats[4]) {
@@ -3287,11 +3360,7 @@ int mpmvs_cloud_stats(const mpmvs_cloud* c, long long stats[4]) {
     return 0;
 }
 
-float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) {
-    if (!c) return 0.0f;
-    if (build_ms) *build_ms = c->build_ms;
-    return c->query_ms;
-}
+float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) { return c ? cloud_op_ms(c->query, build_ms) : 0.0f; }
 
 // ---------------------------------------------------------------------------
 // voxel-grid downsampling of a cloud (pm_voxel.hpp).  A stateless call: host buffers in and out, a stream
@@ -3460,54 +3529,11 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
 // ---------------------------------------------------------------------------
 constexpr size_t kKnnChunkEntries = (size_t)1 << 23;   // list entries per launch of the list variant: 2^23 / k queries (2^18 at k = 32), whatever n_q
 
-// the binning buffers of up to `cap` queries, on a stream that outlives the call
-struct KnnBins {
-    Scratch qbin, order, qcnt, qoff, qtsum;
-    size_t cap_bins = 0;
-    explicit KnnBins(hipStream_t st) : qbin(st), order(st), qcnt(st), qoff(st), qtsum(st) {}
-    hipError_t alloc(size_t cap) {
-        int lg = 8;
-        while (lg < kCloudMaxSlotsLog2 && (1ll << lg) < (long long)cap) ++lg;
-        cap_bins = (size_t)1 << lg;
-        hipError_t e;
-        if ((e = qbin.alloc(cap * 4)) != hipSuccess || (e = order.alloc(cap * 4)) != hipSuccess || (e = qcnt.alloc(cap_bins * 4)) != hipSuccess ||
-            (e = qoff.alloc((cap_bins + 1) * 4)) != hipSuccess || (e = qtsum.alloc(cap_bins / kScanBlock * 4)) != hipSuccess)
-            return e;
-        return hipSuccess;
-    }
-};
-
-// k_cloud_qbin / scan / k_cloud_qorder over the nq <= cap queries at q: bins.order then holds the serving order
-static int knn_bin(hipStream_t st, KnnBins& b, const float* d_q, int nq, const CloudGrid& g) {
-    int lg = 8;
-    while (lg < kCloudMaxSlotsLog2 && (1ll << lg) < nq) ++lg;
-    const size_t bins = (size_t)1 << lg;   // <= b.cap_bins
-    const dim3 gq((nq + 255) / 256);
-    SEGCHK(hipMemsetAsync(b.qcnt.p, 0, bins * 4, st));
-    hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q, nq, g, (unsigned)(bins - 1), b.qcnt.as<int>(), b.qbin.as<int>());
-    cloud_scan(st, b.qcnt.as<int>(), (int)bins, b.qoff.as<int>(), b.qtsum.as<int>());
-    hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, b.qbin.as<int>(), b.qoff.as<int>(), b.qcnt.as<int>(), b.order.as<int>());
-    return 0;
-}
-
-extern "C++" {
-template <int K>
-static void knn_launch_list(hipStream_t st, const float* d_q, int nq, const int* order, const CloudGrid& g, long long self_base, int k, float* d_d2, int32_t* d_idx,
-                            int32_t* d_within) {
-    hipLaunchKernelGGL(k_knn_list<K>, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, nq, order, g, self_base, k, d_d2, d_idx, d_within);
-}
-template <int K>
-static void knn_launch_reduce(hipStream_t st, const float* d_q, int nq, const int* order, const CloudGrid& g, long long self_base, int k, float* d_mean,
-                              int32_t* d_within) {
-    hipLaunchKernelGGL(k_knn_reduce<K>, dim3((nq + 255) / 256), dim3(256), 0, st, d_q, nq, order, g, self_base, k, d_mean, d_within);
-}
-}  // extern "C++"
-
 int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const float* q_xyz, float* out_d2, int32_t* out_idx, int32_t* out_within) {
     if (!c || !out_d2 || n_q < 0) return seg_fail(-2, "cloud knn: bad argument");
     if (k < 1 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "cloud knn: k must lie in [1, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
     if (!q_xyz && n_q != c->n) return seg_fail(-2, "cloud knn: without query points n_q must be the cloud's own count");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud knn: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "cloud knn: the radius must be finite and positive");
     if (n_q > INT32_MAX) return seg_fail(-3, "cloud knn: more than 2^31 - 1 queries");
     if (n_q == 0) return 0;
     const size_t nq = (size_t)n_q, kk = (size_t)k;
@@ -3517,24 +3543,17 @@ int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const fl
             if (out_idx) out_idx[e] = -1;
         }
         if (out_within) std::memset(out_within, 0, nq * 4);
-        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
-        c->knn_ms = c->knn_build_ms = 0.0f;
+        cloud_answered_on_host(c, c->knn);
         return 0;
     }
-    const int span = cloud_span_check(c, radius);
-    if (span) return span;
-    SEGCHK(enter_device(c->device));
-    CloudGridBuf* grid = nullptr;
-    const int rc = cloud_grid(c, radius, &grid);
+    CloudGrid g;
+    const int rc = cloud_enter(c, radius, &c->knn, g);
     if (rc) return rc;
-    c->knn_build_ms = c->build_ms;
-    c->knn_ms = 0.0f;
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries();
-    const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const size_t chunk = std::min(nq, kKnnChunkEntries / kk);
     Scratch d_q(st), d_d2(st), d_idx(st), d_within(st);
-    KnnBins bins(st);
+    CloudBins bins(st);
     if (q_xyz) {
         SEGCHK(d_q.alloc(nq * 12));
         SEGCHK(hipMemcpyAsync(d_q.p, q_xyz, nq * 12, hipMemcpyHostToDevice, st));
@@ -3549,19 +3568,16 @@ int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const fl
         const float* d_qc = d_all + 3 * i0;
         SEGCHK(hipEventRecord(c->ev[2], st));
         if (bin) {
-            const int brc = knn_bin(st, bins, d_qc, cn, g);
+            const int brc = cloud_bin(st, bins, cn, nullptr, cloud_count_queries(st, d_qc, cn, g));
             if (brc) return brc;
         }
         const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
         const long long self_base = q_xyz ? -1ll : (long long)i0;
         int32_t* di = out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr;
         int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
-        switch (knn_list_size(k)) {
-            case 4: knn_launch_list<4>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
-            case 8: knn_launch_list<8>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
-            case 16: knn_launch_list<16>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
-            default: knn_launch_list<32>(st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw); break;
-        }
+        knn_dispatch(k, [&](auto K) {
+            hipLaunchKernelGGL(k_knn_list<K>, dim3((cn + 255) / 256), dim3(256), 0, st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw);
+        });
         SEGCHK(hipGetLastError());
         SEGCHK(hipEventRecord(c->ev[3], st));
         SEGCHK(hipMemcpyAsync(out_d2 + i0 * kk, d_d2.p, (size_t)cn * kk * 4, hipMemcpyDeviceToHost, st));
@@ -3570,16 +3586,12 @@ int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const fl
         SEGCHK(hipStreamSynchronize(st));
         float ms = 0.0f;
         SEGCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
-        c->knn_ms += ms;
+        c->knn.ms += ms;
     }
     return 0;
 }
 
-float mpmvs_cloud_knn_ms(const mpmvs_cloud* c, float* build_ms) {
-    if (!c) return 0.0f;
-    if (build_ms) *build_ms = c->knn_build_ms;
-    return c->knn_ms;
-}
+float mpmvs_cloud_knn_ms(const mpmvs_cloud* c, float* build_ms) { return c ? cloud_op_ms(c->knn, build_ms) : 0.0f; }
 
 static thread_local float g_outliers_ms = 0.0f;   // per calling thread, as g_voxel_ms
 float mpmvs_cloud_outliers_ms(void) { return g_outliers_ms; }
@@ -3588,27 +3600,23 @@ float mpmvs_cloud_outliers_ms(void) { return g_outliers_ms; }
 static int outliers_device(mpmvs_cloud* c, const float* xyz, float radius, int k, float* mean, int32_t* within, float* ms) {
     int rc = cloud_create_device(c, xyz);
     if (rc) return rc;
-    CloudGridBuf* grid = nullptr;
-    if ((rc = cloud_grid(c, radius, &grid)) != 0) return rc;
+    CloudGrid g;
+    if ((rc = cloud_open(c, radius, nullptr, g)) != 0) return rc;   // the caller has checked the span
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries();
-    const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const size_t n = (size_t)c->n;
     const int ni = (int)c->n;
     Scratch d_mean(st), d_within(st);
-    KnnBins bins(st);
+    CloudBins bins(st);
     SEGCHK(d_mean.alloc(n * 4));
     SEGCHK(d_within.alloc(n * 4));
     if (bin) SEGCHK(bins.alloc(n));
     SEGCHK(hipEventRecord(c->ev[2], st));
-    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
     const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
-    switch (knn_list_size(k)) {
-        case 4: knn_launch_reduce<4>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
-        case 8: knn_launch_reduce<8>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
-        case 16: knn_launch_reduce<16>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
-        default: knn_launch_reduce<32>(st, c->d_xyz, ni, order, g, 0, k, d_mean.as<float>(), d_within.as<int32_t>()); break;
-    }
+    knn_dispatch(k, [&](auto K) {
+        hipLaunchKernelGGL(k_knn_reduce<K>, dim3((ni + 255) / 256), dim3(256), 0, st, c->d_xyz, ni, order, g, 0ll, k, d_mean.as<float>(), d_within.as<int32_t>());
+    });
     SEGCHK(hipGetLastError());
     SEGCHK(hipEventRecord(c->ev[3], st));
     SEGCHK(hipMemcpyAsync(mean, d_mean.p, n * 4, hipMemcpyDeviceToHost, st));
@@ -3616,14 +3624,14 @@ static int outliers_device(mpmvs_cloud* c, const float* xyz, float radius, int k
     SEGCHK(hipStreamSynchronize(st));
     float q_ms = 0.0f;
     SEGCHK(hipEventElapsedTime(&q_ms, c->ev[2], c->ev[3]));
-    *ms = c->build_ms + q_ms;
+    *ms = c->query.build_ms + q_ms;
     return 0;
 }
 
 long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float radius, int k, double std_ratio, int min_within, unsigned char* out_keep,
                                float* out_mean, int32_t* out_within, long long counts[3], double stats[3]) {
     if (n < 0 || (n > 0 && (!xyz || !out_keep))) return seg_fail(-2, "outliers: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "outliers: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "outliers: the radius must be finite and positive");
     if (k < 1 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "outliers: k must lie in [1, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
     if (!(std_ratio >= 0.0)) return seg_fail(-2, "outliers: std_ratio must not be negative or NaN");
     if (min_within < 0) return seg_fail(-2, "outliers: min_within must not be negative");
@@ -3694,20 +3702,11 @@ long long mpmvs_cloud_outliers(int device, long long n, const float* xyz, float 
 // a normal per point from its k nearest neighbours (pm_normals.hpp): the reducing kernel k_knn_normal over
 // every point of the handle, in one launch, as outliers_device launches k_knn_reduce.  Errors are reported like those of mpmvs_cloud_*.
 // ---------------------------------------------------------------------------
-extern "C++" {
-template <int K>
-static void knn_launch_normal(hipStream_t st, const float* d_xyz, int n, const int* order, const CloudGrid& g, int k, int orient, const double view[3],
-                              const float* d_ref, float* d_n, float* d_curv, int32_t* d_within) {
-    hipLaunchKernelGGL(k_knn_normal<K>, dim3((n + 255) / 256), dim3(256), 0, st, d_xyz, n, order, g, k, orient, view[0], view[1], view[2], d_ref, d_n, d_curv,
-                       d_within);
-}
-}  // extern "C++"
-
 int mpmvs_cloud_normals(mpmvs_cloud* c, float radius, int k, int orient, const double view[3], const float* ref_normals, float* out_normals, float* out_curvature,
                         int32_t* out_within) {
     if (!c || !out_normals) return seg_fail(-2, "cloud normals: bad argument");
     if (k < 2 || k > MPMVS_KNN_MAX_K) return seg_fail(-2, "cloud normals: k must lie in [2, " + std::to_string(MPMVS_KNN_MAX_K) + "]");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud normals: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "cloud normals: the radius must be finite and positive");
     if (orient < 0 || orient > 2) return seg_fail(-2, "cloud normals: orient must be 0 (canonical), 1 (viewpoint) or 2 (reference normals)");
     if (orient == 1 && !(view && std::isfinite(view[0]) && std::isfinite(view[1]) && std::isfinite(view[2])))
         return seg_fail(-2, "cloud normals: orient 1 needs a finite viewpoint");
@@ -3718,26 +3717,19 @@ int mpmvs_cloud_normals(mpmvs_cloud* c, float radius, int k, int orient, const d
         std::memset(out_normals, 0, n * 12);
         for (size_t i = 0; i < n && out_curvature; ++i) out_curvature[i] = INFINITY;
         if (out_within) std::memset(out_within, 0, n * 4);
-        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
-        c->normals_ms = c->normals_build_ms = 0.0f;
+        cloud_answered_on_host(c, c->normals);
         return 0;
     }
-    const int span = cloud_span_check(c, radius);
-    if (span) return span;
-    SEGCHK(enter_device(c->device));
-    CloudGridBuf* grid = nullptr;
-    int rc = cloud_grid(c, radius, &grid);
+    CloudGrid g;
+    int rc = cloud_enter(c, radius, &c->normals, g);
     if (rc) return rc;
-    c->normals_build_ms = c->build_ms;
-    c->normals_ms = 0.0f;
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries();
-    const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const int ni = (int)c->n;
     const double no_view[3] = {0.0, 0.0, 0.0};
     const double* v = orient == 1 ? view : no_view;
     Scratch d_n(st), d_curv(st), d_within(st), d_ref(st);
-    KnnBins bins(st);
+    CloudBins bins(st);
     SEGCHK(d_n.alloc(n * 12));
     if (out_curvature) SEGCHK(d_curv.alloc(n * 4));
     if (out_within) SEGCHK(d_within.alloc(n * 4));
@@ -3747,32 +3739,25 @@ int mpmvs_cloud_normals(mpmvs_cloud* c, float radius, int k, int orient, const d
     }
     if (bin) SEGCHK(bins.alloc(n));
     SEGCHK(hipEventRecord(c->ev[2], st));
-    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
     const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
     const float* dr = orient == 2 ? d_ref.as<float>() : (const float*)nullptr;
     float* dc = out_curvature ? d_curv.as<float>() : (float*)nullptr;
     int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
-    switch (knn_list_size(k)) {
-        case 4: knn_launch_normal<4>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
-        case 8: knn_launch_normal<8>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
-        case 16: knn_launch_normal<16>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
-        default: knn_launch_normal<32>(st, c->d_xyz, ni, order, g, k, orient, v, dr, d_n.as<float>(), dc, dw); break;
-    }
+    knn_dispatch(k, [&](auto K) {
+        hipLaunchKernelGGL(k_knn_normal<K>, dim3((ni + 255) / 256), dim3(256), 0, st, c->d_xyz, ni, order, g, k, orient, v[0], v[1], v[2], dr, d_n.as<float>(), dc, dw);
+    });
     SEGCHK(hipGetLastError());
     SEGCHK(hipEventRecord(c->ev[3], st));
     SEGCHK(hipMemcpyAsync(out_normals, d_n.p, n * 12, hipMemcpyDeviceToHost, st));
     if (out_curvature) SEGCHK(hipMemcpyAsync(out_curvature, d_curv.p, n * 4, hipMemcpyDeviceToHost, st));
     if (out_within) SEGCHK(hipMemcpyAsync(out_within, d_within.p, n * 4, hipMemcpyDeviceToHost, st));
     SEGCHK(hipStreamSynchronize(st));
-    SEGCHK(hipEventElapsedTime(&c->normals_ms, c->ev[2], c->ev[3]));
+    SEGCHK(hipEventElapsedTime(&c->normals.ms, c->ev[2], c->ev[3]));
     return 0;
 }
 
-float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) {
-    if (!c) return 0.0f;
-    if (build_ms) *build_ms = c->normals_build_ms;
-    return c->normals_ms;
-}
+float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) { return c ? cloud_op_ms(c->normals, build_ms) : 0.0f; }
 
 // ---------------------------------------------------------------------------
 // the connected components of the handle's cloud under "within a radius" (pm_components.hpp): a lock-free
@@ -3781,7 +3766,7 @@ float mpmvs_cloud_normals_ms(const mpmvs_cloud* c, float* build_ms) {
 // ---------------------------------------------------------------------------
 int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int32_t* out_size, long long counts[4]) {
     if (!c || (c->n > 0 && !out_label)) return seg_fail(-2, "cloud components: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "cloud components: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "cloud components: the radius must be finite and positive");
     const size_t n = (size_t)c->n;
     if (c->n_fin == 0) {   // n == 0 included: nothing takes part
         for (size_t i = 0; i < n; ++i) {
@@ -3789,26 +3774,21 @@ int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int
             if (out_size) out_size[i] = 0;
         }
         if (counts) counts[0] = counts[1] = counts[2] = 0, counts[3] = -1;
-        c->stats[0] = c->stats[1] = c->stats[2] = c->stats[3] = 0;
-        c->cc_ms = c->cc_build_ms = c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
+        cloud_answered_on_host(c, c->cc);
+        c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
         return 0;
     }
-    const int span = cloud_span_check(c, radius);
-    if (span) return span;
-    SEGCHK(enter_device(c->device));
-    CloudGridBuf* grid = nullptr;
-    int rc = cloud_grid(c, radius, &grid);
+    CloudGrid g;
+    int rc = cloud_enter(c, radius, &c->cc, g);
     if (rc) return rc;
-    c->cc_build_ms = c->build_ms;
-    c->cc_ms = c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
+    c->cc_pass_ms[0] = c->cc_pass_ms[1] = c->cc_pass_ms[2] = 0.0f;
     if (!c->d_cc) SEGCHK(pool_malloc(&c->d_cc, n * 4));
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries(), want_size = out_size || counts;
-    const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const int ni = (int)c->n;
     const dim3 gp((ni + 255) / 256);
     Scratch d_label(st), d_size(st);
-    KnnBins bins(st);
+    CloudBins bins(st);
     SEGCHK(d_label.alloc(n * 4));
     if (want_size) SEGCHK(d_size.alloc(n * 4));
     if (bin) SEGCHK(bins.alloc(n));
@@ -3818,7 +3798,7 @@ int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int
     // the grid is built: its two events are free again, and the four borders of the three passes fit the handle's four
     SEGCHK(hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(k_cc_init, gp, dim3(256), 0, st, c->d_xyz, ni, c->d_cc);
-    if (bin && (rc = knn_bin(st, bins, c->d_xyz, ni, g)) != 0) return rc;
+    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
     hipLaunchKernelGGL(k_cc_hook, gp, dim3(256), 0, st, c->d_xyz, ni, bin ? bins.order.as<int>() : (const int*)nullptr, g, c->d_cc);
     SEGCHK(hipEventRecord(c->ev[1], st));
     hipLaunchKernelGGL(k_cc_flatten, gp, dim3(256), 0, st, ni, c->d_cc, d_label.as<int32_t>());
@@ -3835,7 +3815,7 @@ int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int
     SEGCHK(hipStreamSynchronize(st));
     for (int p = 0; p < 3; ++p) SEGCHK(hipEventElapsedTime(&c->cc_pass_ms[p], c->ev[p], c->ev[p + 1]));
     if (!want_size) c->cc_pass_ms[2] = 0.0f;   // two events with nothing between them
-    c->cc_ms = (c->cc_pass_ms[0] + c->cc_pass_ms[1]) + c->cc_pass_ms[2];
+    c->cc.ms = (c->cc_pass_ms[0] + c->cc_pass_ms[1]) + c->cc_pass_ms[2];
     if (counts) {   // a component is counted at its label; the largest, ties to the smallest label
         long long comps = 0, best = 0, best_label = -1;
         for (size_t i = 0; i < n; ++i) {
@@ -3848,11 +3828,7 @@ int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int
     return 0;
 }
 
-float mpmvs_cloud_components_ms(const mpmvs_cloud* c, float* build_ms) {
-    if (!c) return 0.0f;
-    if (build_ms) *build_ms = c->cc_build_ms;
-    return c->cc_ms;
-}
+float mpmvs_cloud_components_ms(const mpmvs_cloud* c, float* build_ms) { return c ? cloud_op_ms(c->cc, build_ms) : 0.0f; }
 
 int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* c, float ms[3]) {
     if (!c || !ms) return seg_fail(-2, "cloud components: bad argument");
@@ -3866,25 +3842,25 @@ int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* c, float ms[3]) {
 // Errors are reported like those of mpmvs_cloud_*.
 // ---------------------------------------------------------------------------
 struct mpmvs_align {
-    mpmvs_cloud* target = nullptr;   // borrowed: its stream, grids and points serve every pass
+    mpmvs_cloud* target;   // borrowed: its stream, grids and points serve every pass
     long long n = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     float* d_src = nullptr;
     float* d_nrm = nullptr;   // a normal per target, caller order (mpmvs_align_set_normals); owned by this handle
     bool has_nrm = false;     // also true for normals of a target without points
-    int *d_qbin = nullptr, *d_order = nullptr, *d_qcnt = nullptr, *d_qoff = nullptr, *d_qtsum = nullptr;
+    CloudBins bins;           // of the n sources, allocated once: a pass allocates nothing
     unsigned long long* d_sums = nullptr;
-    size_t bins = 0;
     float pass_ms = 0.0f;
+    explicit mpmvs_align(mpmvs_cloud* t) : target(t), bins(t->stream) {}
 };
 
 static void align_release(mpmvs_align* h) {
     if (h->target->stream) (void)hipStreamSynchronize(h->target->stream);
-    for (void* p : {(void*)h->d_src, (void*)h->d_nrm, (void*)h->d_qbin, (void*)h->d_order, (void*)h->d_qcnt, (void*)h->d_qoff, (void*)h->d_qtsum, (void*)h->d_sums})
+    for (void* p : {(void*)h->d_src, (void*)h->d_nrm, (void*)h->d_sums})
         if (p) (void)pool_free(p);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
-    delete h;
+    delete h;   // the bins go back to the pool here
 }
 
 static int align_create_device(mpmvs_align* h, const float* s_xyz) {
@@ -3894,11 +3870,7 @@ static int align_create_device(mpmvs_align* h, const float* s_xyz) {
     if (h->n == 0) return 0;
     const size_t n = (size_t)h->n;
     SEGCHK(pool_malloc(&h->d_src, n * 12));
-    SEGCHK(pool_malloc(&h->d_qbin, n * 4));
-    SEGCHK(pool_malloc(&h->d_order, n * 4));
-    SEGCHK(pool_malloc(&h->d_qcnt, h->bins * 4));
-    SEGCHK(pool_malloc(&h->d_qoff, (h->bins + 1) * 4));
-    SEGCHK(pool_malloc(&h->d_qtsum, h->bins / kScanBlock * 4));
+    SEGCHK(h->bins.alloc(n));
     SEGCHK(pool_malloc(&h->d_sums, kAlignPlaneTerms * 8));   // the larger of the two passes' sums
     SEGCHK(hipMemcpyAsync(h->d_src, s_xyz, n * 12, hipMemcpyHostToDevice, st));
     SEGCHK(hipStreamSynchronize(st));
@@ -3910,12 +3882,8 @@ int mpmvs_align_create(mpmvs_cloud* target, long long n_s, const float* s_xyz, m
     *out = nullptr;
     if (!target || n_s < 0 || (n_s > 0 && !s_xyz)) return seg_fail(-2, "align: bad argument");
     if (n_s > INT32_MAX) return seg_fail(-3, "align: more than 2^31 - 1 source points");
-    mpmvs_align* h = new mpmvs_align;
-    h->target = target;
+    mpmvs_align* h = new mpmvs_align(target);
     h->n = n_s;
-    int bins_log2 = 8;
-    while (bins_log2 < kCloudMaxSlotsLog2 && (1ll << bins_log2) < n_s) ++bins_log2;
-    h->bins = (size_t)1 << bins_log2;
     const int rc = align_create_device(h, s_xyz);
     if (rc) {
         align_release(h);
@@ -3933,29 +3901,28 @@ void mpmvs_align_destroy(mpmvs_align* h) {
 
 float mpmvs_align_ms(const mpmvs_align* h) { return h ? h->pass_ms : 0.0f; }
 
-// the device half of a pass: the grid of `radius` (cached per radius in the target), the binning, the kernel, 18 integers back
-// (plane: the point-to-plane kernel, 38 integers)
+// the device half of a pass: the grid of `radius` (cached per radius in the target; the caller has checked the span), the binning,
+// the kernel, 18 integers back (plane: the point-to-plane kernel, 38 integers)
 static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, bool plane, long long* sums) {
     mpmvs_cloud* c = h->target;
     const hipStream_t st = c->stream;
     const bool bin = cloud_bin_queries();
-    SEGCHK(enter_device(c->device));
-    CloudGridBuf* grid = nullptr;
-    const int rc = cloud_grid(c, radius, &grid);
+    CloudGrid g;
+    const int rc = cloud_open(c, radius, nullptr, g);
     if (rc) return rc;
-    const CloudGrid g = cloud_grid_args(c, *grid, radius);
     const int n = (int)h->n;
     const size_t sums_bytes = (size_t)(plane ? kAlignPlaneTerms : kAlignTerms) * 8;
     SEGCHK(hipMemsetAsync(h->d_sums, 0, sums_bytes, st));
-    if (bin) SEGCHK(hipMemsetAsync(h->d_qcnt, 0, h->bins * 4, st));
-    SEGCHK(hipEventRecord(h->ev[0], st));
-    const dim3 gq(((unsigned)n + 255u) / 256u);   // unsigned: n may be 2^31 - 1
-    if (bin) {
-        hipLaunchKernelGGL(k_align_qbin, gq, dim3(256), 0, st, h->d_src, n, f, g, (unsigned)(h->bins - 1), h->d_qcnt, h->d_qbin);
-        cloud_scan(st, h->d_qcnt, (int)h->bins, h->d_qoff, h->d_qtsum);
-        hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, n, h->d_qbin, h->d_qoff, h->d_qcnt, h->d_order);
+    if (bin) {   // by the cell of the transformed source
+        const int brc = cloud_bin(st, h->bins, n, h->ev[0], [&](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) {
+            hipLaunchKernelGGL(k_align_qbin, gq, dim3(256), 0, st, h->d_src, n, f, g, bin_mask, qcnt, qbin);
+        });
+        if (brc) return brc;
+    } else {
+        SEGCHK(hipEventRecord(h->ev[0], st));
     }
-    const int* order = bin ? h->d_order : (const int*)nullptr;
+    const dim3 gq(((unsigned)n + 255u) / 256u);   // unsigned: n may be 2^31 - 1
+    const int* order = bin ? h->bins.order.as<int>() : (const int*)nullptr;
     if (plane)
         hipLaunchKernelGGL(k_align_plane_pass, gq, dim3(256), 0, st, h->d_src, n, order, f, g, c->d_xyz, h->d_nrm, h->d_sums);
     else
@@ -3977,7 +3944,7 @@ static bool align_finite12(const double M[12]) {
 // a pass of either kind: the checks, the frame, and the cases that launch nothing
 static int align_sums_any(mpmvs_align* h, float radius, const double M[12], bool plane, long long* sums, double frame[4]) {
     if (!h || !M || !sums || !frame) return seg_fail(-2, "align: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "align: the radius must be finite and positive");
     if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
     if (plane && !h->has_nrm) return seg_fail(-2, "align: a point-to-plane pass needs mpmvs_align_set_normals first");
     const mpmvs_cloud* c = h->target;
@@ -4033,7 +4000,7 @@ int mpmvs_align_plane_solve(const long long sums[38], const double frame[4], int
 int mpmvs_align_plane_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M[12], long long* iters, long long* inliers,
                           double* rmse_plane, double* rmse_point) {
     if (!h || !M) return seg_fail(-2, "align: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "align: the radius must be finite and positive");
     if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
     if (max_iter < 1) return seg_fail(-2, "align: max_iter must be at least 1");
     if (!(eps >= 0.0)) return seg_fail(-2, "align: eps must not be negative");
@@ -4064,7 +4031,7 @@ int mpmvs_align_solve(const long long sums[18], const double frame[4], int with_
 
 int mpmvs_align_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M[12], long long* iters, long long* inliers, double* rmse) {
     if (!h || !M) return seg_fail(-2, "align: bad argument");
-    if (!std::isfinite(radius) || !(radius > 0.0f)) return seg_fail(-2, "align: the radius must be finite and positive");
+    if (!cloud_radius_ok(radius)) return seg_fail(-2, "align: the radius must be finite and positive");
     if (!align_finite12(M)) return seg_fail(-2, "align: the transform must be finite");
     if (max_iter < 1) return seg_fail(-2, "align: max_iter must be at least 1");
     if (!(eps >= 0.0)) return seg_fail(-2, "align: eps must not be negative");

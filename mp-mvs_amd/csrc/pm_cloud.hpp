@@ -5,11 +5,9 @@
 //
 // Structure: a sparse uniform grid of cell edge `edge` > radius addressed through an open-addressing hash table; no sort and no
 // dense cell array.  Cell coordinate per axis: floor(((double)x - min) / edge) with min the finite bounding-box minimum, three
-// coordinates of 21 bits packed into a u64 key.  edge = max(radius, 2^-60) * (1 + 2^-10): a candidate is at most
-// radius * (1 + 4 * 2^-24) away along an axis (one rounding in the difference, one in the square, two in the sums), the fp64
-// coordinate carries an error below 2^21 * 2^-51, so the coordinates of a query and of a candidate differ by less than
-// (1 + 2.4e-7) / (1 + 9.77e-4) + 1e-9 < 1 before the floor: by at most one after it.  The 3 x 3 x 3 cells around the query's
-// hold every candidate.  (The 2^-60 floor keeps the bound where radius * radius underflows in fp32.)
+// coordinates of 21 bits packed into a u64 key.  edge = max(radius, 2^-60) * (1 + 2^-10), so that the 3 x 3 x 3 cells around a
+// query's cell hold every candidate: the argument stands at cloud_walk below, the one walk over them that every search of the
+// library (nearest, align, kNN, normals, components) goes through.
 //
 // Passes of a grid build (integer bookkeeping only; what depends on scheduling -- the slot a key lands in, the order inside a
 // cell -- never reaches a result, because a query takes the minimum of (d2, index) over whole cells):
@@ -22,7 +20,7 @@
 // Passes of a query call:
 //   5. k_cloud_qbin / scan / k_cloud_qorder   the queries binned by the hash of their own cell, so that the 64 queries of a
 //                       wave sit in few cells and read the same target runs out of L1 / L2 (MPMVS_CLOUD_BIN=0: caller order).
-//   6. k_cloud_query    one thread per query: the 27 keys looked up, every found cell walked, results stored in caller order.
+//   6. k_cloud_query    one thread per query: cloud_walk with the minimum of (d2, index) as its visitor, results in caller order.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -223,39 +221,73 @@ __global__ __launch_bounds__(256) void k_cloud_qorder(int nq, const int* __restr
     if (i < (size_t)nq) cloud_qorder_one(i, qbin, qoff, qcnt, order);
 }
 
-// the 27-cell search for the query (x, y, z) of cell (cx, cy, cz): the minimum of (d2 bits << 32) | index over the candidates
-// (d2 >= +0, so its bits order as integers), ~0 if there is none.  Shared by k_cloud_query and k_align_pass (pm_align.hpp).
-__host__ __device__ inline unsigned long long cloud_search(float x, float y, float z, int cx, int cy, int cz, const CloudGrid& g) {
-    unsigned long long best = ~0ull;
+// the slot that holds `key`, -1 if the table has none: the probe walks from the key's hash to the key or to the first empty slot
+// (an insert never leaves a gap before its key), and the table is never full, so it ends within the table's size
+__host__ __device__ inline int cloud_lookup(unsigned long long key, const CloudGrid& g) {
+    unsigned h = (unsigned)cloud_mix(key) & g.mask;
+    int s = -1;
+    for (unsigned probe = 0; probe <= g.mask; ++probe) {
+        const unsigned long long cur = g.keys[h];
+        if (cur == key) s = (int)h;
+        if (cur == key || cur == kCloudEmpty) break;
+        h = (h + 1) & g.mask;
+    }
+    return s;
+}
+
+// THE CANDIDATE WALK, the only one: the 3 x 3 x 3 cells around the query's cell (cx, cy, cz), less those outside [0, cells); each
+// one looked up, and every record t of a found cell's run (x, y, z bits and the caller's index in t.w) handed to visit(t).
+// Why 27 cells suffice: a candidate is at most radius * (1 + 4 * 2^-24) away along an axis (one rounding in the difference, one
+// in the square, two in the sums), the fp64 cell coordinate carries an error below 2^21 * 2^-51, and edge = max(radius, 2^-60) *
+// (1 + 2^-10), so the coordinates of a query and of a candidate differ by less than (1 + 2.4e-7) / (1 + 9.77e-4) + 1e-9 < 1
+// before the floor: by at most one after it.  (The 2^-60 floor keeps the bound where radius * radius underflows in fp32.)
+// The visitor decides what a candidate is and in which order it tests: the walk computes no distance.  Always inlined, host and
+// device: a visitor's state stays in the caller's registers.
+// kUnroll is the unroll count of the dy and dx loops, so that what the code looks like does not hang on the compiler's size
+// threshold: 3 writes the nine cells of a layer out (the nearest search: its kernels always were compiled so), 1 keeps them
+// rolled (the list kernels, 22 and 50 registers lighter at K = 4 and 8 than with nine copies; the hook pass: never unrolled).
+// Figures: DESIGN.md section 13.8.
+template <int kUnroll, typename Visit>
+__host__ __device__ __attribute__((always_inline)) inline void cloud_walk(int cx, int cy, int cz, const CloudGrid& g, Visit&& visit) {
     for (int dz = -1; dz <= 1; ++dz) {
         if (!cloud_cell_ok(cz + dz)) continue;
+#pragma unroll kUnroll
         for (int dy = -1; dy <= 1; ++dy) {
             if (!cloud_cell_ok(cy + dy)) continue;
+#pragma unroll kUnroll
             for (int dx = -1; dx <= 1; ++dx) {
                 if (!cloud_cell_ok(cx + dx)) continue;
-                const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
-                unsigned h = (unsigned)cloud_mix(key) & g.mask;
-                int s = -1;
-                for (unsigned probe = 0; probe <= g.mask; ++probe) {
-                    const unsigned long long cur = g.keys[h];
-                    if (cur == key) s = (int)h;
-                    if (cur == key || cur == kCloudEmpty) break;
-                    h = (h + 1) & g.mask;
-                }
+                const int s = cloud_lookup(cloud_key(cx + dx, cy + dy, cz + dz), g);
                 if (s < 0) continue;
                 const int e = g.off[s + 1];
                 for (int p = g.off[s]; p < e; ++p) {
-                    const uint4 t = g.pts[p];
-                    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
-                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                    if (d2 <= g.r2) {
-                        const unsigned long long cand = ((unsigned long long)cloud_bits(d2) << 32) | t.w;
-                        best = cand < best ? cand : best;
-                    }
+                    const uint4 t = g.pts[p];   // a copy: one 16-byte load, whatever fields the visitor reads
+                    visit(t);
                 }
             }
         }
     }
+}
+
+// the squared distance of the query (x, y, z) to the record t, in fp32: the one expression every result is stated in
+__host__ __device__ inline float cloud_d2(float x, float y, float z, const uint4& t) {
+    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
+    return (ddx * ddx + ddy * ddy) + ddz * ddz;
+}
+// the key of a candidate: (d2 bits << 32) | index; d2 >= +0, so its bits order as integers
+__host__ __device__ inline unsigned long long cloud_cand(float d2, const uint4& t) { return ((unsigned long long)cloud_bits(d2) << 32) | t.w; }
+
+// the search for the query (x, y, z) of cell (cx, cy, cz): the minimum key over the candidates, ~0 if there is none.  Shared by
+// k_cloud_query and k_align_pass (pm_align.hpp).
+__host__ __device__ inline unsigned long long cloud_search(float x, float y, float z, int cx, int cy, int cz, const CloudGrid& g) {
+    unsigned long long best = ~0ull;
+    cloud_walk<3>(cx, cy, cz, g, [&](const uint4& t) {
+        // no branch (& and a select): the index is then needed whatever d2 is, and the record stays one 16-byte load; behind a
+        // branch the compiler fetches the index in a second, dependent load per candidate (query time + 35 %)
+        const float d2 = cloud_d2(x, y, z, t);
+        const unsigned long long cand = cloud_cand(d2, t);
+        best = ((d2 <= g.r2) & (cand < best)) ? cand : best;
+    });
     return best;
 }
 

@@ -10,8 +10,8 @@
 //   parent[]       an int per point of the cloud, indexed by the caller's index (pts[p].w): its own index at the start, -1 for a
 //                  point that does not take part (never read again).  Invariant: parent[x] <= x.  A root has parent[x] == x.
 //   k_cc_init      parent[i] = i or -1.
-//   k_cc_hook      one thread per point, in the binned order of k_cloud_qbin / k_cloud_qorder, walking the 27 cells as knn_search
-//                  does.  Only neighbours with an index BELOW its own are united with it: every edge is handled once, by its larger
+//   k_cc_hook      one thread per point, in the binned order of k_cloud_qbin / k_cloud_qorder, its neighbours handed over by
+//                  cloud_walk (pm_cloud.hpp).  Only those with an index BELOW its own are united with it: every edge is handled once, by its larger
 //                  end.  The thread carries its current root in a register and skips a neighbour whose root is that one.
 //   cc_find        follows parent to a root, halving the path on the way: parent[prev] is overwritten with parent[curr], a node
 //                  further down the same tree.  Such a store never touches a root (prev was seen with parent[prev] < prev, and a
@@ -112,36 +112,13 @@ __host__ __device__ inline void cc_hook_one(size_t j, const float* __restrict__ 
     if (!cloud_query_cell(xyz, i, g, x, y, z, cx, cy, cz)) return;
     const unsigned self = (unsigned)i;
     int root = cc_find(parent, (int)self);
-    for (int dz = -1; dz <= 1; ++dz) {
-        if (!cloud_cell_ok(cz + dz)) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            if (!cloud_cell_ok(cy + dy)) continue;
-            for (int dx = -1; dx <= 1; ++dx) {
-                if (!cloud_cell_ok(cx + dx)) continue;
-                const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
-                unsigned h = (unsigned)cloud_mix(key) & g.mask;
-                int s = -1;
-                for (unsigned probe = 0; probe <= g.mask; ++probe) {
-                    const unsigned long long cur = g.keys[h];
-                    if (cur == key) s = (int)h;
-                    if (cur == key || cur == kCloudEmpty) break;
-                    h = (h + 1) & g.mask;
-                }
-                if (s < 0) continue;
-                const int e = g.off[s + 1];
-                for (int p = g.off[s]; p < e; ++p) {
-                    const uint4 t = g.pts[p];
-                    if (t.w >= self) continue;   // the edge belongs to its larger end
-                    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
-                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                    if (d2 <= g.r2) {
-                        const int other = cc_find(parent, (int)t.w);
-                        if (other != root) root = cc_link(parent, root, other);
-                    }
-                }
-            }
+    cloud_walk<1>(cx, cy, cz, g, [&](const uint4& t) {
+        if (t.w >= self) return;   // the edge belongs to its larger end: no distance is taken for the others
+        if (cloud_d2(x, y, z, t) <= g.r2) {
+            const int other = cc_find(parent, (int)t.w);
+            if (other != root) root = cc_link(parent, root, other);
         }
-    }
+    });
 }
 __global__ __launch_bounds__(256) void k_cc_hook(const float* __restrict__ xyz, int n, const int* __restrict__ order, CloudGrid g, int* __restrict__ parent) {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;

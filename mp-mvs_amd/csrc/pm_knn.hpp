@@ -6,8 +6,8 @@
 // statement; independent of scheduling, because the order in which a cell's run is walked never shows in a sorted list of
 // distinct keys.
 //
-// One thread per query, binned by k_cloud_qbin / k_cloud_qorder (pm_cloud.hpp), walking the 27 cells of cloud_search.  The list is
-// K sorted 64-bit keys, (d2 bits << 32) | index, the key cloud_search forms; ~0 marks a free entry and is above every key
+// One thread per query, binned by k_cloud_qbin / k_cloud_qorder (pm_cloud.hpp), its candidates handed over by cloud_walk (there:
+// why 27 cells hold them all).  The list is K sorted 64-bit keys, cloud_cand's (d2 bits << 32) | index; ~0 marks a free entry and is above every key
 // (d2 <= r2 is finite).  A candidate below the worst key replaces it and sinks through one fully unrolled chain of K - 1
 // compare-exchanges: every index is a constant, so the list stays in registers.  K is a template parameter of 4, 8, 16 or 32, the
 // caller's k rounded up; only the first k entries are reported.
@@ -59,40 +59,18 @@ __host__ __device__ __attribute__((always_inline)) inline void knn_push(KnnList<
     }
 }
 
-// cloud_search's walk with a list in place of the minimum; returns the number of candidates
+// cloud_walk (pm_cloud.hpp) with a list as its visitor; returns the number of candidates
 template <int K>
 __host__ __device__ __attribute__((always_inline)) inline int knn_search(float x, float y, float z, int cx, int cy, int cz, const CloudGrid& g, unsigned self,
                                                                          KnnList<K>& l) {
     int within = 0;
-    for (int dz = -1; dz <= 1; ++dz) {
-        if (!cloud_cell_ok(cz + dz)) continue;
-        for (int dy = -1; dy <= 1; ++dy) {
-            if (!cloud_cell_ok(cy + dy)) continue;
-            for (int dx = -1; dx <= 1; ++dx) {
-                if (!cloud_cell_ok(cx + dx)) continue;
-                const unsigned long long key = cloud_key(cx + dx, cy + dy, cz + dz);
-                unsigned h = (unsigned)cloud_mix(key) & g.mask;
-                int s = -1;
-                for (unsigned probe = 0; probe <= g.mask; ++probe) {
-                    const unsigned long long cur = g.keys[h];
-                    if (cur == key) s = (int)h;
-                    if (cur == key || cur == kCloudEmpty) break;
-                    h = (h + 1) & g.mask;
-                }
-                if (s < 0) continue;
-                const int e = g.off[s + 1];
-                for (int p = g.off[s]; p < e; ++p) {
-                    const uint4 t = g.pts[p];
-                    const float ddx = x - cloud_float(t.x), ddy = y - cloud_float(t.y), ddz = z - cloud_float(t.z);
-                    const float d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                    if (d2 <= g.r2 && t.w != self) {
-                        ++within;
-                        knn_push(l, ((unsigned long long)cloud_bits(d2) << 32) | t.w);
-                    }
-                }
-            }
+    cloud_walk<1>(cx, cy, cz, g, [&](const uint4& t) {
+        const float d2 = cloud_d2(x, y, z, t);
+        if (d2 <= g.r2 && t.w != self) {
+            ++within;
+            knn_push(l, cloud_cand(d2, t));
         }
-    }
+    });
     return within;
 }
 

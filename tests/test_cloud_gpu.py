@@ -41,6 +41,23 @@ def test_random(cloud, radius):
         assert 0 < np.isinf(d2).sum() < len(q)
 
 
+@pytest.mark.parametrize("n_q", [1, 256, 257, 513])
+def test_query_counts_around_the_bin_floor(cloud, n_q):
+    """the queries are binned into max(2^8, the power of two >= n_q) bins: one query, the floor itself, one above it (2^9 bins) and
+    one power further (2^10); some queries without a cell, which go to bin 0"""
+    rng = np.random.default_rng(100 + n_q)
+    t = rng.random((300, 3), dtype=np.float32)
+    q = rng.random((n_q, 3), dtype=np.float32)
+    bad = [np.nan, np.inf, -np.inf]
+    for j, i in enumerate(range(3, n_q, 50)):
+        q[i, j % 3] = bad[j % 3]
+    for radius in (0.05, 0.3):
+        (d2, idx), st = check(cloud, t, q, radius)
+        assert st["finite"] == 300
+        assert np.isinf(d2[3::50]).all() and (idx[3::50] == -1).all()
+    assert np.isfinite(d2).sum() == n_q - len(range(3, n_q, 50))   # at 0.3 every finite query has a candidate among 300 in the unit cube
+
+
 @pytest.mark.parametrize("shift", [0.0, 1000.25])
 def test_lattice_cell_borders(cloud, shift):
     r = np.float32(0.25)
