@@ -380,6 +380,33 @@ PM_DEV void load_ref_tile(const ProblemDev& P, float* tile, int x0, int y0, int 
     }
 }
 
+// The same tile in two halves, for the update kernel: all loads of a thread go out together and are stored afterwards, where the
+// loop above pays one memory round trip per element of a thread (8 in a one-wave block).  N = ceil(tile / NT).
+template <int NT, int BW, int BH, int RADIUS, int N>
+PM_DEV void load_ref_tile_values(const ProblemDev& P, int x0, int y0, float (&v)[N]) {
+    constexpr int tw = BW + 2 * RADIUS, th = BH + 2 * RADIUS;
+    static_assert(N * NT >= tw * th, "every tile element has a thread");
+    const int xmin = -kRefApron, xmax = P.W + kRefApron - 1, ymin = -kRefApron, ymax = P.H + kRefApron - 1;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const int i = min((int)threadIdx.x + k * NT, tw * th - 1);   // (the spare threads of the last round repeat the last element and drop it)
+        const int ty = i / tw, tx = i - ty * tw;
+        int gx = x0 - RADIUS + tx, gy = y0 - RADIUS + ty;
+        gx = gx < xmin ? xmin : (gx > xmax ? xmax : gx);
+        gy = gy < ymin ? ymin : (gy > ymax ? ymax : gy);
+        v[k] = P.ref_img[(long)gy * P.ref_pitch + gx];
+    }
+}
+template <int NT, int BW, int BH, int RADIUS, int N>
+PM_DEV void store_ref_tile_values(float* tile, const float (&v)[N]) {
+    constexpr int tw = BW + 2 * RADIUS, th = BH + 2 * RADIUS;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const int i = (int)threadIdx.x + k * NT;
+        if (i < tw * th) tile[i] = v[k];
+    }
+}
+
 // weights of one pixel -> LDS column `lw`.  tap(dx, dy) reads the reference image at the pixel + (dx, dy): from the block's
 // LDS tile, or from the apron-padded image in global memory (see Win).
 template <int SCALE, int NT, class TAP>
@@ -423,23 +450,32 @@ PM_DEV void ref_window(float4* lw, TAP tap, const float (&spatial)[36], float tw
     rw.var_r = __builtin_fmaf(-rw.mean_r, rw.mean_r, mrr);
 }
 
-// stages the block's reference tile if it is to live in LDS and fills the pixel's weight column
+// fills the pixel's weight column from the block's staged reference tile (Win::tile_in_lds: the tile is in LDS behind a barrier) or,
+// where the tile is not staged, from the apron-padded image
 template <int SCALE, int BW, int BH, int NT = kBlockThreads, int TILE_MAX = 2048>
-PM_DEV void ref_window_of_pixel(const ProblemDev& P, int x, int y, int x0, int y0, bool valid, const float (&spatial)[36], float two_sc, RefWin& rw) {
+PM_DEV void ref_window_at_pixel(const ProblemDev& P, int x, int y, int x0, int y0, const float (&spatial)[36], float two_sc, RefWin& rw) {
     typedef Win<SCALE, BW, BH, TILE_MAX> Wn;
     float4* lw = (float4*)pm_lds + threadIdx.x;
     if constexpr (Wn::tile_in_lds) {
-        load_ref_tile<NT>(P, pm_lds + kLdsWeightFloatsOf<NT>, x0, y0, BW, BH, Wn::radius);
-        __syncthreads();
-        if (!valid) return;
         const int ctr = kLdsWeightFloatsOf<NT> + (y - y0 + Wn::radius) * Wn::pitch + (x - x0 + Wn::radius);
         ref_window<SCALE, NT>(lw, [&](int dx, int dy) { return pm_lds[ctr + dy * Wn::pitch + dx]; }, spatial, two_sc, rw);
     } else {
-        if (!valid) return;
         const float* ctr = P.ref_img + (long)y * P.ref_pitch + x;
         const int pitch = P.ref_pitch;
         ref_window<SCALE, NT>(lw, [&](int dx, int dy) { return ctr[dy * pitch + dx]; }, spatial, two_sc, rw);
     }
+}
+
+// stages the block's reference tile if it is to live in LDS and fills the pixel's weight column
+template <int SCALE, int BW, int BH, int NT = kBlockThreads, int TILE_MAX = 2048>
+PM_DEV void ref_window_of_pixel(const ProblemDev& P, int x, int y, int x0, int y0, bool valid, const float (&spatial)[36], float two_sc, RefWin& rw) {
+    typedef Win<SCALE, BW, BH, TILE_MAX> Wn;
+    if constexpr (Wn::tile_in_lds) {
+        load_ref_tile<NT>(P, pm_lds + kLdsWeightFloatsOf<NT>, x0, y0, BW, BH, Wn::radius);
+        __syncthreads();
+    }
+    if (!valid) return;
+    ref_window_at_pixel<SCALE, BW, BH, NT, TILE_MAX>(P, x, y, x0, y0, spatial, two_sc, rw);
 }
 
 // the tap-pair arithmetic is written on float2 vectors (v_pk_fma/mul_f32)

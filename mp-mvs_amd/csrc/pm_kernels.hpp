@@ -10,6 +10,7 @@
 // MFMA is not used: there is no dense contraction on this path.
 #pragma once
 
+#include "pm_cand_tile.hpp"
 #include "pm_device.hpp"
 
 // waves per SIMD the NCC kernels are compiled for (2: the 72 KB of LDS weight records per block allow no more, and the update
@@ -38,20 +39,7 @@ struct LaunchArgs {
     int use_prior;         // params.planar_prior
 };
 
-// sampling regions of the checkerboard propagation, ref .cu:769-779
-struct Off {
-    signed char x, y;
-};
-__device__ constexpr Off kDirs[8][12] = {
-    {{-5, -6}, {5, -6}, {-6, -7}, {6, -7}, {-7, -8}, {7, -8}, {-8, -9}, {8, -9}, {-9, -10}, {9, -10}, {-10, -11}, {10, -11}},
-    {{-5, 6}, {5, 6}, {-6, 7}, {6, 7}, {-7, 8}, {7, 8}, {-8, 9}, {8, 9}, {-9, 10}, {9, 10}, {-10, 11}, {10, 11}},
-    {{-6, -5}, {-6, 5}, {-7, -6}, {-7, 6}, {-8, -7}, {-8, 7}, {-9, -8}, {-9, 8}, {-10, -9}, {-10, 9}, {-11, -10}, {-11, 10}},
-    {{6, -5}, {6, 5}, {7, -6}, {7, 6}, {8, -7}, {8, 7}, {9, -8}, {9, 8}, {10, -9}, {10, 9}, {11, -10}, {11, 10}},
-    {{0, -5}, {0, -7}, {0, -9}, {0, -11}, {0, -13}, {0, -15}, {0, -17}, {0, -19}, {0, -21}, {0, -23}, {0, 0}, {0, 0}},
-    {{0, 5}, {0, 7}, {0, 9}, {0, 11}, {0, 13}, {0, 15}, {0, 17}, {0, 19}, {0, 21}, {0, 23}, {0, 0}, {0, 0}},
-    {{-5, 0}, {-7, 0}, {-9, 0}, {-11, 0}, {-13, 0}, {-15, 0}, {-17, 0}, {-19, 0}, {-21, 0}, {-23, 0}, {0, 0}, {0, 0}},
-    {{5, 0}, {7, 0}, {9, 0}, {11, 0}, {13, 0}, {15, 0}, {17, 0}, {19, 0}, {21, 0}, {23, 0}, {0, 0}, {0, 0}}};
-__device__ constexpr int kNumDirs[8] = {12, 12, 12, 12, 10, 10, 10, 10};
+// (the sampling regions of the checkerboard propagation, kDirs / kNumDirs: pm_cand_tile.hpp)
 
 // Wave shape of the checkerboard launches: 8 rows of 8 same-colour pixels, for both texel formats; a block stacks its waves
 // vertically (2x2 or 4x1 arrangements of four waves: 3.52 / 3.61 against 3.45 ms, round 2, profiles/EXPERIMENTS.md 12).  Compact
@@ -205,6 +193,13 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_init(const ProblemDev* _
 // promoted to registers: its address is shown to an empty asm statement.
 PM_DEV void keep_in_memory(float* p) { asm volatile("" : : "v"(p)); }
 
+// A loaded value that has to be loaded where the source says, whatever is done with it afterwards: without this a load whose
+// value is used under a condition is moved under that condition, into a branch of its own.
+PM_DEV float loaded_here(float v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
 // An index whose address arithmetic has to stay where it is used: without this the 64-bit addresses of the eight neighbour
 // planes are formed once, ahead of the slot loop, and then spilled around the evaluations.
 PM_DEV int pinned_here(int i) {
@@ -242,12 +237,14 @@ PM_DEV float prior_term(float depth_diff, float angle_cos, float two_ds2, float 
 
 #ifdef PM_DBG_WAVETIME
 // Measurement builds only: every wave of the update kernel records when it entered the kernel, when its block's dependencies were met
-// and when it ended (s_memrealtime, 100 MHz) and where it ran (HW_ID: SIMD / CU / SH / SE, XCC_ID), 4 x u64 per wave at
+// (ready), when it started its first phase-A evaluation (first_eval: ready .. first_eval is the block's prologue -- reference tile,
+// candidate tile, search, weight records) and when it ended (s_memrealtime, 100 MHz) and where it ran (HW_ID: SIMD / CU / SH / SE, XCC_ID), 4 x u64 per wave at
 // [launch id % 16][raster block][wave]; tools/wave_timeline.py turns the records into the slot occupancy over time.
 struct WaveTimer {
-    unsigned long long t_enter, t_ready;
-    PM_DEV WaveTimer() { t_enter = t_ready = __builtin_amdgcn_s_memrealtime(); }
-    PM_DEV void ready() { t_ready = __builtin_amdgcn_s_memrealtime(); }   // the block's dependencies are met: the update itself starts
+    unsigned long long t_enter, t_ready, t_eval;
+    PM_DEV WaveTimer() { t_enter = t_ready = t_eval = __builtin_amdgcn_s_memrealtime(); }
+    PM_DEV void ready() { t_ready = t_eval = __builtin_amdgcn_s_memrealtime(); }   // the block's dependencies are met: the update itself starts
+    PM_DEV void first_eval() { t_eval = __builtin_amdgcn_s_memrealtime(); }        // the prologue is over: the first NCC evaluation of phase A starts
     PM_DEV void finish(unsigned long long* base, uint32_t launch, int b, int n_blocks) const {
         const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
         uint32_t hw, xcc;
@@ -258,7 +255,9 @@ struct WaveTimer {
             unsigned long long* rec = base + ((size_t)(launch & 15u) * waves + (unsigned)b * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 4;
             rec[0] = t_enter;
             rec[1] = t_end;
-            rec[2] = ((unsigned long long)(xcc & 0xfu) << 32) | hw;
+            unsigned long long prologue = t_eval - t_ready;   // ticks of 10 ns between "ready" and the first evaluation (0 for a wave without a pixel)
+            prologue = prologue > 0xffffffull ? 0xffffffull : prologue;
+            rec[2] = (prologue << 36) | ((unsigned long long)(xcc & 0xfu) << 32) | hw;
             unsigned long long waited = t_ready - t_enter;   // ticks of 10 ns between kernel entry and the start of the update (ticket, wait for the neighbours, barriers)
             waited = waited > 0xffffffull ? 0xffffffull : waited;
             rec[3] = ((unsigned long long)(unsigned)b << 32) | (waited << 8) | (threadIdx.x >> 6);
@@ -278,8 +277,10 @@ struct WaveTimer {
 // holds that plane's photometric cost per view at this window scale -- phase B reads them instead of evaluating the plane again.
 // (At window scales 1 and 2 the reference tile could be staged as a compact half tile of the pass's colour: built in round 6, bit-exact,
 // 0-0.7 % on the scale-2 passes -- the prologue's 37 reads per pixel are not what scale 2 pays for, profiles/EXPERIMENTS.md 52.)
-template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE>
-PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr, bool use_own) {
+// `wait_for_neighbours` is called before the block's first load, `first_evaluation` when the prologue is over (the stamp of the measurement builds, empty otherwise).
+template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE, class WAIT, class STAMP>
+PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr, bool use_own, WAIT wait_for_neighbours,
+                        STAMP first_evaluation) {
     constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
     // gathers of two window columns ahead (ncc_core): always with the 8-byte texels; with the 16-byte ones where the variant
     // still has the 24 registers of a third column (8 views; more views spill 4 .. 81 registers around the evaluations)
@@ -291,45 +292,106 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     constexpr bool kPark = !U8 && (PRIOR || (GEOM && MAXV > 16));
     // ... and the candidates' m vectors of phase A (see there)
     constexpr bool kParkM = !U8 && ((PRIOR && MAXV == 8) || (GEOM && MAXV == 32));
+    // Where the loads of the candidates' planes are issued: right after the search, ahead of the weight records, or where the planes
+    // are consumed.  In time the two are not told apart (2.280 against 2.269 ms per pass on cfg 1, 0.005 between runs of one build:
+    // profiles/EXPERIMENTS.md 65), so registers decide, per variant: issued late, <photometric, 8 views, fp16 texels, scale 2> takes 239
+    // registers instead of 215 and <geometric, 24 views, fp32 texels> spills 33 instead of 13; issued early, <geometric, 8 views, fp32
+    // texels> spills 21 instead of 15.  Everywhere else the two orders allocate alike and the planes are loaded where they are used.
+    constexpr bool kPlanesEarly = (U8 && SCALE == 2) || (GEOM && !U8 && MAXV > 8);
+    typedef Win<SCALE, BW, BH, kLdsXchgFloats<NT>> Wn;
+    typedef CandTile<BW, BH> CT;
+    static_assert(CT::floats <= kLdsWeightFloatsOf<NT>, "the candidate tile lives in the weight records' area until they are written");
     int x, y, x0, y0;
     const bool valid = checker_pixel<NT>(P, a, b, parity, x, y, x0, y0);
-    RefWin rw;
-    ref_window_of_pixel<SCALE, BW, BH, NT, kLdsXchgFloats<NT>>(P, x, y, x0, y0, valid, a.spatial, a.two_sc, rw);
-    // the tile region becomes the exchange area of the refinement: every wave must be done reading the tile first
-    if constexpr (Win<SCALE, BW, BH, kLdsXchgFloats<NT>>::tile_in_lds) __syncthreads();
-    if (!valid) return;
     const int W = P.W, Hh = P.H, V = P.V;
-    const int idx = y * W + x;
-    Rng g = rng_make(a.seed, (uint32_t)idx, launch);
 
-    // -- 8 sampling regions: position of the lowest stored cost (ref .cu:798-816)
+    // ---- the block's prologue.  Its round trips, in the order they are issued:
+    //   wait for the neighbours, acquire  ->  reference tile (loads, into LDS)  ->  stored costs around the block (loads, into LDS)
+    //   ->  search  ->  weight records  ->  the eight candidate planes (loads; ahead of the weight records where kPlanesEarly)  ->  phase A
+    // Threads without a pixel take part in everything up to the last barrier of the prologue.
+    wait_for_neighbours();
+    __syncthreads();   // the acquire of the waiting wave stands before every load of the block that reads what a pass before wrote
+    // the reference tile: all its loads first, then the stores (a loop of load-and-store pays one round trip per element), and into
+    // LDS before the next loads go out (stored between them, its wait would split their batch)
+    if constexpr (Wn::tile_in_lds) {
+        float ref_v[(Wn::pitch * Wn::rows + NT - 1) / NT];
+        load_ref_tile_values<NT, BW, BH, Wn::radius>(P, x0, y0, ref_v);
+        store_ref_tile_values<NT, BW, BH, Wn::radius>(pm_lds + kLdsWeightFloatsOf<NT>, ref_v);
+    }
+    // -- the stored costs the block's searches can ask for, once per block (CandTile, pm_cand_tile.hpp).  Read UNCONDITIONALLY at
+    // the position clamped into the image and replaced afterwards where the position lies outside: the loads sit in
+    // straight-line code and go out back to back.
+    // (loaded_here: left to itself the compiler moves each load under the test of its position, one branch and one s_waitcnt
+    // vmcnt(0) per load -- 18 serialised round trips in the one-wave block)
+    constexpr int kCostN = (CT::items + NT - 1) / NT;
+    static_assert(kCostN <= 32, "one bit of `outside` per cell of a thread");
+    const int tid = (int)threadIdx.x;
+    __builtin_assume(tid >= 0 && tid < NT);
+    const float* const costs = S.costs;
+    float cost_v[kCostN];
+    uint32_t outside = 0;   // bit k: the position of this thread's k-th cell lies outside the image
+#pragma unroll
+    for (int k = 0; k < kCostN; ++k) {
+        int r, c, nx, ny;
+        cand_tile_cell<BW, BH>(min(tid + k * NT, CT::items - 1), r, c);
+        cand_tile_position<BW, BH>(r, c, x0, y0, parity, nx, ny);
+        const int cx = nx < 0 ? 0 : (nx > W - 1 ? W - 1 : nx), cy = ny < 0 ? 0 : (ny > Hh - 1 ? Hh - 1 : ny);
+        cost_v[k] = costs[__umul24((unsigned)cy, (unsigned)W) + (unsigned)cx];   // (one v_mad_u32_u24; rows and widths are far below 2^24)
+        outside |= (((cx ^ nx) | (cy ^ ny)) != 0 ? 1u : 0u) << k;
+    }
+#pragma unroll
+    for (int k = 0; k < kCostN; ++k) cost_v[k] = loaded_here(cost_v[k]);
+#pragma unroll
+    for (int k = 0; k < kCostN; ++k) {
+        if (tid + k * NT < CT::items) {
+            int r, c;
+            cand_tile_cell<BW, BH>(tid + k * NT, r, c);
+            pm_lds[r * CT::pitch + c] = ((outside >> k) & 1u) ? kCandNone : cost_v[k];
+        }
+    }
+    __syncthreads();
+
+    // -- 8 sampling regions: position of the lowest stored cost (ref .cu:798-816).  A position outside the image holds kCandNone
+    // in the tile and the comparison is strict, so it is never chosen and never sets its region's flag.
     int pos[8];
     uint32_t flags = 0;
-    // The 88 stored costs are read UNCONDITIONALLY, at the position clamped into the image, and a position outside the image is
-    // ignored afterwards: the loads of a region then sit in straight-line code and go out back to back.  (Loaded under their
-    // bounds test, each was its own branch with its own s_waitcnt vmcnt(0): 88 serialised round trips per pixel and launch.)
+    {
+        int te, to;
+        cand_tile_bases<BW, BH>(x, y, x0, y0, te, to);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        float nc[12];
+        for (int k = 0; k < 8; ++k) {
+            float nc[12];
 #pragma unroll
-        for (int d = 0; d < kNumDirs[k]; ++d) {
-            const int nx = x + kDirs[k][d].x, ny = y + kDirs[k][d].y;
-            const int cx = nx < 0 ? 0 : (nx > W - 1 ? W - 1 : nx), cy = ny < 0 ? 0 : (ny > Hh - 1 ? Hh - 1 : ny);
-            nc[d] = S.costs[cy * W + cx];
-        }
-        float best = 3.402823466e+38f;
-        int bpos = 0;
+            for (int d = 0; d < kNumDirs[k]; ++d) nc[d] = pm_lds[cand_tile_index<BW, BH>(te, to, kDirs[k][d].x, kDirs[k][d].y)];
+            float best = kCandNone;
+            int bpos = 0;
 #pragma unroll
-        for (int d = 0; d < kNumDirs[k]; ++d) {
-            const int nx = x + kDirs[k][d].x, ny = y + kDirs[k][d].y;
-            if (nx >= 0 && ny >= 0 && nx < W && ny < Hh && best > nc[d]) {
-                best = nc[d];
-                bpos = ny * W + nx;
+            for (int d = 0; d < kNumDirs[k]; ++d) {
+                if (best > nc[d]) {
+                    best = nc[d];
+                    bpos = (y + kDirs[k][d].y) * W + (x + kDirs[k][d].x);
+                }
             }
+            pos[k] = bpos;
+            if (best < kCandNone) flags |= (1u << k);
         }
-        pos[k] = bpos;
-        if (best < 3.402823466e+38f) flags |= (1u << k);
     }
+    // (pos is 0 where a region has no candidate, and a position in the image otherwise, also for a thread without a pixel: the eight
+    // loads are unconditional and in flight together)
+    float4 cand_pl[8];
+    if constexpr (kPlanesEarly) {
+#pragma unroll
+        for (int slot = 0; slot < 8; ++slot) cand_pl[slot] = S.planes[pos[slot]];
+    }
+    __syncthreads();   // the candidate tile is dead: its area takes the weight records
+
+    RefWin rw;
+    if (valid) ref_window_at_pixel<SCALE, BW, BH, NT, kLdsXchgFloats<NT>>(P, x, y, x0, y0, a.spatial, a.two_sc, rw);
+    // the tile region becomes the exchange area of the refinement: every wave must be done reading the tile first
+    if constexpr (Wn::tile_in_lds) __syncthreads();
+    if (!valid) return;
+    const int idx = y * W + x;
+    Rng g = rng_make(a.seed, (uint32_t)idx, launch);
 
     float cost_arr[8 * MAXV];
     int cnt[MAXV];       // good count | bad count << 8   (ref .cu:834-845)
@@ -380,13 +442,14 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     // of the launch.  Parked in private memory only in the two variants that would otherwise spill around the evaluations.
     float cand_m[8 * 3];
     if (kParkM) keep_in_memory(cand_m);
-    // (read unconditionally as well -- pos is 0 where a region has no candidate -- so that the eight loads are in flight together)
 #pragma unroll
     for (int slot = 0; slot < 8; ++slot) {
         float m0, m1, m2;
-        plane_to_m(P, S.planes[pos[slot]], m0, m1, m2);
+        if constexpr (!kPlanesEarly) cand_pl[slot] = S.planes[pos[slot]];
+        plane_to_m(P, cand_pl[slot], m0, m1, m2);
         cand_m[3 * slot] = m0, cand_m[3 * slot + 1] = m1, cand_m[3 * slot + 2] = m2;
     }
+    first_evaluation();
     for (int v = 0; v < V; ++v) {
         int cn = 0;       // good count | bad count << 8   (ref .cu:834-845)
         float tw = 0.0f;
@@ -904,15 +967,25 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
 #ifdef PM_DBG_WAVETIME
     WaveTimer wave_timer;
 #endif
-    // two spare words of wave 0's exchange area (the tile / exchange region is not in use yet; two barriers fence the hand-over)
-    int* const bcast = reinterpret_cast<int*>(reinterpret_cast<char*>(pm_lds + kLdsWeightFloatsOf<NT>) + 1664);
-    if (threadIdx.x < 64) {
+    // The ticket.  A four-wave block passes it on through two spare words of wave 0's exchange area (the tile / exchange region is not
+    // in use yet: this barrier and the one behind the wait fence the hand-over); a one-wave block has it in its own registers.
+    int pass, b;
+    {
         int t = 0;
         if (threadIdx.x == 0) t = __hip_atomic_fetch_add(&ch.sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kWaves > 1) {
+            int* const bcast = reinterpret_cast<int*>(reinterpret_cast<char*>(pm_lds + kLdsWeightFloatsOf<NT>) + 1664);
+            if (threadIdx.x == 0) bcast[0] = t;
+            __syncthreads();
+            t = bcast[0];
+        }
         t = __builtin_amdgcn_readfirstlane(t);
-        const int pass = t / ch.nb;
-        const int b = t - pass * ch.nb;
-        if (pass > 0) {
+        pass = t / ch.nb;
+        b = t - pass * ch.nb;
+    }
+    // What the block waits for, called by update_body ahead of its loads: the positions around its own have completed the pass before.  Wave 0 polls, acquires and waits for the acquire; update_body's barrier comes next.
+    const auto wait_for_neighbours = [&]() {
+        if (threadIdx.x < 64 && pass > 0) {
             const int by = b / ch.nbx, bx = b - by * ch.nbx;
             int nbid = -1;
             if ((int)threadIdx.x < NN) {
@@ -943,21 +1016,19 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (threadIdx.x == 0) {
-            bcast[0] = pass;
-            bcast[1] = b;
-        }
-    }
-    __syncthreads();
-    const int pass = __builtin_amdgcn_readfirstlane(bcast[0]), b = __builtin_amdgcn_readfirstlane(bcast[1]);
-    __syncthreads();
 #ifdef PM_DBG_WAVETIME
-    wave_timer.ready();
+        wave_timer.ready();
 #endif
+    };
+    const auto first_evaluation = [&]() {
+#ifdef PM_DBG_WAVETIME
+        wave_timer.first_eval();
+#endif
+    };
     {
         const int k = a.parity + pass;
         const bool use_own = pass < 2 && ((ch.own_mask >> (k & 1)) & 1) != 0;
-        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0], use_own);
+        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0], use_own, wait_for_neighbours, first_evaluation);
     }
     // completion: this wave's stores have left (write-through) before it counts itself done
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

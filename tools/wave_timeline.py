@@ -2,7 +2,7 @@
 """Slot occupancy of the update launches over time, from per-wave start / end stamps.
 
 Needs a measurement build of the HIP library with -DPM_DBG_WAVETIME (pm_kernels.hpp, WaveTimer: every wave of k_update records
-s_memrealtime at its start and end, HW_ID and XCC_ID):
+s_memrealtime at its start, when its block may go on, at its first NCC evaluation and at its end, HW_ID and XCC_ID):
     make -C mp-mvs_amd/csrc EXTRA=-DPM_DBG_WAVETIME ... -o build/libmpmvs_hip_wt.so      (tools/build_variants.sh wt)
     MPMVS_HIP_LIB=$PWD/build/libmpmvs_hip_wt.so python tools/wave_timeline.py [--out profiles/r05_wave_timeline.txt]
 
@@ -31,7 +31,7 @@ TICK_NS = 10.0   # s_memrealtime: 100 MHz
 
 
 def analyse(rec, waves_per_block, out):
-    """rec: [n_waves][4] u64 (start, end, hw | xcc << 32, wave | block << 32) of ONE launch (rows of waves that never ran are zero)"""
+    """rec: [n_waves][4] u64 (start, end, hw | xcc << 32 | prologue << 36, wave | waited << 8 | block << 32) of ONE launch (rows of waves that never ran are zero)"""
     ran = rec[:, 0] != 0
     rec = rec[ran]
     start, end = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64)
@@ -92,6 +92,13 @@ def analyse(rec, waves_per_block, out):
     out.append(f"  kernel entry -> start of the update (ticket, wait for the neighbouring blocks of the pass before, barriers): mean {waited.mean() * TICK_NS / 1e3:.2f} us, "
                f"p50 {np.percentile(waited, 50) * TICK_NS / 1e3:.2f}, p95 {np.percentile(waited, 95) * TICK_NS / 1e3:.2f}, max {waited.max() * TICK_NS / 1e3:.1f}; "
                f"{100.0 * waited.sum() / (span * slots):.2f} % of the launch's slot-time")
+    prologue = ((rec[:, 2] >> 36) & 0xffffff).astype(np.float64)   # ticks between that start and the wave's first phase-A evaluation (0: stamp missing)
+    has = prologue > 0
+    if has.any():
+        pr, du, wa = prologue[has], dur[has], waited[has]
+        out.append(f"  prologue (start of the update -> first NCC evaluation: reference tile, candidate search, weight records): mean {pr.mean() * TICK_NS / 1e3:.2f} us, "
+                   f"p50 {np.percentile(pr, 50) * TICK_NS / 1e3:.2f}, p95 {np.percentile(pr, 95) * TICK_NS / 1e3:.2f}; {100.0 * pr.sum() / du.sum():.2f} % of the waves' lifetime; "
+                   f"kernel entry -> first evaluation: mean {(pr + wa).mean() * TICK_NS / 1e3:.2f} us, {100.0 * (pr + wa).sum() / du.sum():.2f} % of the lifetime")
     full = b_cnt == waves_per_block
     if waves_per_block > 1 and full.any():
         # slowest wave of a block against the mean of its waves
