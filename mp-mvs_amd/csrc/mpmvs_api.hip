@@ -1,7 +1,7 @@
 // mpmvs_api.hip -- host side of the C ABI declared in include/mpmvs.h: context
 // and HBM residency management, uploads (upload_views for both image entries; its host half, the staging
 // plan and the row work, is pm_stage.hpp), the Run() launch schedule (reference src/PatchMatch.cu:1188-1254),
-// the stateless calls (DeviceCall: fusion, sky mask, view selection, undistortion), the point-cloud search handle (mpmvs_cloud)
+// the stateless calls (DeviceCall: fusion -- FuseRun, on the request and rules of pm_fusion_host.hpp --, sky mask, view selection, undistortion), the point-cloud search handle (mpmvs_cloud)
 // and the probes used by the parity tests.
 //
 // HBM layout per context:
@@ -26,6 +26,7 @@
 #include <thread>
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <type_traits>
@@ -54,6 +55,7 @@
 #include "pm_skyseg_model.hpp"
 #include "pm_stage.hpp"
 #include "pm_tracks_host.hpp"
+#include "pm_fusion_host.hpp"
 
 using namespace pm;
 
@@ -318,6 +320,11 @@ class DeviceCall {
         if (pool_malloc_bytes(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
         bufs.push_back(p);
         return (T*)p;
+    }
+    // the same for `count` elements of T
+    template <typename T>
+    T* alloc_n(size_t count) {
+        return alloc<T>(count * sizeof(T));
     }
     // begin() ... end() around the kernels; once the stream is synchronised, elapsed() is their device time
     bool begin() { return hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventRecord(ev[0], st) == hipSuccess; }
@@ -1980,340 +1987,334 @@ void mpmvs_fuse_passes(int* total, int* max_per_image) {
     if (max_per_image) *max_per_image = g_fuse_passes_max;
 }
 
-// depth-map fusion, snapshot formulation (pm_fusion.hpp); host buffers in and out.  With `records` the fused points are
-// compacted on the device into PLY vertex records (reference PointCloud order) and only those cross PCIe.
+// a failed HIP call ends a fusion call with -100 (no error text); FuseRun's DeviceCall synchronises and frees on the way out
+#define FUSECHK(expr) do { if ((expr) != hipSuccess) return -100; } while (0)
+
+extern "C++" {
+namespace {
+// depth-map fusion, snapshot formulation (pm_fusion.hpp); host buffers in and out (FuseRequest, pm_fusion_host.hpp).  With
+// `records` the fused points are compacted on the device into PLY vertex records (reference PointCloud order) and only those cross PCIe.
 // ctxs (nullable): per image the PatchMatch context whose device state holds its final maps -- (world normal, depth) per pixel, what
 // Run() leaves in cudaPlaneHypotheses and the reference copies out (ref .cu:1246) and writes to depths.dmb / normals.dmb
 // (src/PatchMatch.cpp:610-633) for RunFusion to read back (:334-336).  For such an image nothing is uploaded: the planes are split
 // into the fusion's depth and normal arrays device to device (k_split_planes), or GPU to GPU when the context lives on another device.
 // tracks (nullable, with `records` only): receives per fused point the (image, pixel) pairs that were averaged (pm_fusion.hpp,
 // "Tracks").  The device holds one image's tracks at a time; they leave for the host at the image boundary.
-static int fuse_impl(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths, const float* const* normals,
-                     const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
-                     int flags, unsigned char* const* out_valid, float* const* out_points9, unsigned char* const* out_masks,
-                     unsigned char** records, long long* n_records, TrackSink* tracks = nullptr) {
-    const int use_dynamic = flags & MPMVS_FUSE_DYNAMIC_CONSISTENCY;
-    const bool exact = (flags & MPMVS_FUSE_REFERENCE_ORDER) != 0;
-    g_fuse_passes_total = g_fuse_passes_max = 0;
-    // own stream: a fusion call must not stall the PatchMatch contexts other host threads drive on this device
-    DeviceCall call(device);
-    if (n <= 0 || (color_channels != 1 && color_channels != 3) || !call.entered()) return -1;
-    // every view id is used as an index below (host vectors, FuseView table, masks): reject lists that name images that do
-    // not exist before anything is launched (the reference looks ids up in a map, src/PatchMatch.cpp:306-312)
-    if (!src_off || !src_ids || src_off[0] != 0) return -2;
-    // ... and lists that name a view twice or the image itself among its sources: the masks of a source are advanced once per
-    // slot (a view named twice would be swapped back and the reference-order fixpoint would never settle), and the reference
-    // masks the fused image's own pixels in place, which the per-image snapshot cannot express
-    // ... and lists that do not start with their own image (slot 0 is never read as a source: a list without it would lose its
-    // first source silently), an estimated image without a list (the scratch rows are addressed with num_ngb - 1), and an
-    // estimated image with more slots than a pixel's used-list holds
-    for (int i = 0; i < n; ++i) {
-        if (src_off[i + 1] < src_off[i]) return -2;
-        const int num_ngb = src_off[i + 1] - src_off[i];
-        if (num_ngb > 0 && src_ids[src_off[i]] != i) return -2;
-        if (estimate[i] && (num_ngb == 0 || num_ngb > kMaxFuseNgb)) return -2;
-        for (int k = src_off[i]; k < src_off[i + 1]; ++k) {
-            if (src_ids[k] < 0 || src_ids[k] >= n) return -2;
-            if (k > src_off[i] && src_ids[k] == i) return -2;
-            for (int k2 = src_off[i]; k2 < k; ++k2)
-                if (src_ids[k2] == src_ids[k]) return -2;
-        }
-    }
-    // a track's entries are addressed with int offsets inside one image
-    for (int i = 0; i < n && tracks; ++i)
-        if (estimate[i] && (long long)cams[i].width * cams[i].height * (src_off[i + 1] - src_off[i]) > 0x7fffffffLL) return -3;
-    if (!call.ok()) return -100;
-    const hipStream_t st = call.stream();
-    std::vector<FuseView> hv(n);
-    int rc = 0;
-    std::vector<unsigned char*> d_valid(n, nullptr);
-    std::vector<float*> d_out(n, nullptr);
-    std::vector<unsigned char*> d_mask(n, nullptr), d_next(n, nullptr);
-    size_t total_px = 0, max_blocks = 0, max_wh = 0;
-    int max_ngb = 1;
-    for (int i = 0; i < n; ++i)
-        if (estimate[i]) {
-            max_wh = std::max(max_wh, (size_t)cams[i].width * cams[i].height);
-            max_ngb = std::max(max_ngb, src_off[i + 1] - src_off[i]);
-        }
-    // with `records` the per-pixel outputs of an image are consumed (compacted) before the next image is fused: one buffer
-    // of the largest size serves all images (the per-image form would be 37 B per pixel of the whole dataset)
-    unsigned char* shared_valid = records ? call.alloc<unsigned char>(max_wh) : nullptr;
-    float* shared_out = records ? call.alloc<float>(max_wh * 36) : nullptr;
-    if (records && (!shared_valid || !shared_out)) rc = -100;
-    for (int i = 0; i < n && !rc; ++i) {
-        const size_t wh = (size_t)cams[i].width * cams[i].height;
-        if (estimate[i]) {
-            total_px += wh;
-            max_blocks = std::max(max_blocks, (wh + 255) / 256);
-        }
-        FuseView& v = hv[i];
-        cam_to_dev(cams[i], v.cam);
-        v.w = cams[i].width;
-        v.h = cams[i].height;
-        float* dd = call.alloc<float>(wh * 4);
-        float* dn = call.alloc<float>(wh * 12);
-        unsigned char* dg = call.alloc<unsigned char>(wh * color_channels);
-        unsigned char* dsky = (sky && sky[i]) ? call.alloc<unsigned char>(wh) : nullptr;
-        d_mask[i] = call.alloc<unsigned char>(wh);
-        d_next[i] = call.alloc<unsigned char>(wh);
-        d_valid[i] = records ? shared_valid : call.alloc<unsigned char>(wh);
-        d_out[i] = records ? shared_out : call.alloc<float>(wh * 36);
-        int* dtau = exact ? call.alloc<int>(wh * 4) : nullptr;
-        int* dtau_new = exact ? call.alloc<int>(wh * 4) : nullptr;
-        if (exact && (!dtau || !dtau_new)) { rc = -100; break; }
-        v.tau = dtau;
-        v.tau_new = dtau_new;
-        if (!dd || !dn || !dg || (sky && sky[i] && !dsky) || !d_mask[i] || !d_next[i] || !d_valid[i] || !d_out[i]) { rc = -100; break; }
-        mpmvs_ctx* const cx = ctxs ? ctxs[i] : nullptr;
-        if (cx) {
-            // the maps of this image are resident: no upload
-            if (cx->W != v.w || cx->H != v.h || !cx->S.planes || !cx->depth_plane_valid || cx->async_outstanding) { rc = -2; break; }   // no finished Run() of that size behind it
-            const float4* planes = cx->S.planes;
-            if (cx->device == device) {
-                if (hipStreamSynchronize(cx->stream) != hipSuccess) { rc = -100; break; }
-            } else {
-                // another GPU of the node: its stream is drained there, the planes cross xGMI into a scratch buffer here
-                float4* tmp = call.alloc<float4>(wh * 16);
-                if (!tmp || hipSetDevice(cx->device) != hipSuccess || hipStreamSynchronize(cx->stream) != hipSuccess || hipSetDevice(device) != hipSuccess ||
-                    hipMemcpyPeerAsync(tmp, device, cx->S.planes, cx->device, wh * 16, st) != hipSuccess) {
-                    (void)hipSetDevice(device);
-                    rc = -100;
-                    break;
-                }
-                planes = tmp;
-            }
-            hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((wh + 255) / 256)), dim3(256), 0, st, planes, dd, dn, wh);
-            if (hipGetLastError() != hipSuccess) { rc = -100; break; }
-        } else if (!depths || !normals || !depths[i] || !normals[i]) {
-            rc = -2;
-            break;
-        } else if (hipMemcpyAsync(dd, depths[i], wh * 4, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(dn, normals[i], wh * 12, hipMemcpyHostToDevice, st) != hipSuccess) {
-            rc = -100;
-            break;
-        }
-        if (
-            hipMemcpyAsync(dg, colors[i], wh * color_channels, hipMemcpyHostToDevice, st) != hipSuccess || (dsky && hipMemcpyAsync(dsky, sky[i], wh, hipMemcpyHostToDevice, st) != hipSuccess) ||
-            hipMemsetAsync(d_mask[i], 0, wh, st) != hipSuccess ||
-            hipMemsetAsync(d_next[i], 0, wh, st) != hipSuccess || (!records && hipMemsetAsync(d_valid[i], 0, wh, st) != hipSuccess) ||
-            (!records && hipMemsetAsync(d_out[i], 0, wh * 36, st) != hipSuccess))
-            rc = -100;
-        v.depth = dd;
-        v.normal = dn;
-        v.color = dg;
-        v.cch = color_channels;
-        v.sky = dsky;
-        v.mask = d_mask[i];
-        v.mask_next = d_next[i];
-    }
+// One call is one FuseRun: run() checks the request, stages the views and the tables, fuses image by image in index order
+// (fuse_image) and downloads.  Every stage returns 0 or the code the call ends with.
+class FuseRun {
+    const FuseRequest& q;
+    const bool exact;
+    DeviceCall call;   // own stream: a fusion call must not stall the PatchMatch contexts other host threads drive on this device
+    hipStream_t st = nullptr;
+    std::vector<FuseView> hv;   // host mirror of d_views; .mask / .mask_next: the masks the next image sees, the marks of the one being fused
+    std::vector<unsigned char*> d_valid;   // per image the per-pixel outputs
+    std::vector<float*> d_out;
+    size_t total_px = 0, max_blocks = 0, max_wh = 0;   // over the estimated images: pixels, 256-pixel blocks and pixels of the largest
+    int max_ngb = 1;                                   // ... and the longest view list
     FuseView* d_views = nullptr;
     int* d_src = nullptr;
-    int* d_blocks = nullptr;
-    long long* d_base = nullptr;
-    unsigned char* d_records = nullptr;
-    if (!rc) {
-        d_views = call.alloc<FuseView>(sizeof(FuseView) * n);
-        d_src = call.alloc<int>(sizeof(int) * (src_off[n] > 0 ? src_off[n] : 1));
-        if (!d_views || !d_src || hipMemcpyAsync(d_views, hv.data(), sizeof(FuseView) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(d_src, src_ids, sizeof(int) * src_off[n], hipMemcpyHostToDevice, st) != hipSuccess)
-            rc = -100;
-    }
-    if (!rc && records) {
-        d_blocks = call.alloc<int>(sizeof(int) * (max_blocks + 1));
-        d_base = call.alloc<long long>(sizeof(long long));
-        d_records = call.alloc<unsigned char>(total_px * kPlyRecord);  // upper bound: every pixel a point
-        if (!d_blocks || !d_base || !d_records || hipMemsetAsync(d_base, 0, sizeof(long long), st) != hipSuccess) rc = -100;
-    }
-    // exact mode scratch: per source slot the consistent source pixel of every pixel, the chunk carries of the scan, a counter
+    // per source slot the consistent source pixel of every pixel (exact mode), with tracks one more row for the slot bits
     int* d_consq = nullptr;
-    int* d_carry = nullptr;
-    int* d_diff = nullptr;
-    const size_t max_chunks = (max_wh + 255) / 256;
-    // tracks: one more row of consq for the slot bits; lengths, their in-tile scan and tile totals; one image's offsets and entries
-    int *d_len = nullptr, *d_excl = nullptr, *d_tiles = nullptr, *d_ent_image = nullptr, *d_ent_pixel = nullptr;
-    long long *d_ebase = nullptr, *d_point_off = nullptr;
-    if (!rc && tracks) {
-        d_consq = call.alloc<int>((size_t)max_ngb * max_wh * 4);
-        d_len = call.alloc<int>(max_wh * 4);
-        d_excl = call.alloc<int>(max_wh * 4);
-        d_tiles = call.alloc<int>(sizeof(int) * (max_blocks + 1));
-        d_ent_image = call.alloc<int>((size_t)max_ngb * max_wh * 4);
-        d_ent_pixel = call.alloc<int>((size_t)max_ngb * max_wh * 4);
-        d_point_off = call.alloc<long long>(max_wh * 8);
-        d_ebase = call.alloc<long long>(sizeof(long long));
-        if (!d_consq || !d_len || !d_excl || !d_tiles || !d_ent_image || !d_ent_pixel || !d_point_off || !d_ebase ||
-            hipMemsetAsync(d_ebase, 0, sizeof(long long), st) != hipSuccess)
-            rc = -100;
+    struct {   // compaction: per-block counts and their total, the running base, the records of all images
+        int* blocks = nullptr;
+        long long* base = nullptr;
+        unsigned char* out = nullptr;
+    } rec;
+    struct {   // tracks: lengths, their in-tile scan and tile totals; one image's offsets and entries; the running entry base
+        int *len = nullptr, *excl = nullptr, *tiles = nullptr, *ent_image = nullptr, *ent_pixel = nullptr;
+        long long *ebase = nullptr, *point_off = nullptr;
+    } trk;
+    struct { int *carry = nullptr, *diff = nullptr; } ex;   // exact mode: the chunk carries of the scan, the counter of changed marking times
+    size_t pixels(int i) const { return (size_t)hv[i].w * hv[i].h; }
+    static int launched() { return hipGetLastError() == hipSuccess ? 0 : -100; }   // after the last launch of a stage
+    // f(view, ns, blocks) for every source of image i (slots 1 .. num_ngb - 1 of its list; slot 0 is the image itself):
+    // ns its pixels, blocks the grid of a one-thread-per-pixel kernel over them
+    template <typename F>
+    void each_source(int i, F&& f) {
+        for (int k = q.src_off[i] + 1; k < q.src_off[i + 1]; ++k) {
+            FuseView& v = hv[q.src_ids[k]];
+            f(v, v.w * v.h, dim3((v.w * v.h + 255) / 256));
+        }
     }
-    if (!rc && exact) {
-        if (!tracks) d_consq = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_wh * 4);
-        d_carry = call.alloc<int>((size_t)(max_ngb - 1 > 0 ? max_ngb - 1 : 1) * max_chunks * 4);
-        d_diff = call.alloc<int>(4);
-        if (!d_consq || !d_carry || !d_diff) rc = -100;
-    }
-    (void)call.begin();
-    for (int i = 0; i < n && !rc; ++i) {
-        if (!estimate[i]) continue;
-        const int b = src_off[i], num_ngb = src_off[i + 1] - b;   // 1 .. kMaxFuseNgb: checked above
+    // k_fuse<EXACT, TRACKS> over image i.  d_consq is null exactly for <false, false>, the one form that writes no row of it.
+    void launch_fuse(int i) {
+        const int b = q.src_off[i], num_ngb = q.src_off[i + 1] - b;   // 1 .. kMaxFuseNgb: fuse_check_request
         const dim3 grid((hv[i].w + 31) / 32, (hv[i].h + 7) / 8);
-        if (records && hipMemsetAsync(d_valid[i], 0, (size_t)hv[i].w * hv[i].h, st) != hipSuccess) { rc = -100; break; }
-        if (!exact) {
-            if (tracks)
-                hipLaunchKernelGGL((k_fuse<false, true>), grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
-            else
-                hipLaunchKernelGGL(k_fuse<false>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], (int*)nullptr);
-            if (hipGetLastError() != hipSuccess) { rc = -100; break; }
-            // the marks of image i become the masks the next image sees
-            for (int j = 1; j < num_ngb; ++j) {
-                const int s = src_ids[b + j];
-                if (hipMemcpyAsync(d_mask[s], d_next[s], (size_t)hv[s].w * hv[s].h, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = -100;
-            }
+        auto launch = [&](auto ex_, auto tr_) {
+            hipLaunchKernelGGL((k_fuse<decltype(ex_)::value, decltype(tr_)::value>), grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb,
+                               q.flags & MPMVS_FUSE_DYNAMIC_CONSISTENCY, d_valid[i], d_out[i], d_consq);
+        };
+        if (!exact)
+            q.tracks ? launch(std::false_type{}, std::true_type{}) : launch(std::false_type{}, std::false_type{});
+        else
+            q.tracks ? launch(std::true_type{}, std::true_type{}) : launch(std::true_type{}, std::false_type{});
+    }
+    // Stage a view, the resident case: the maps of image i are in context cx, no upload
+    int split_resident(int i, const mpmvs_ctx* cx, float* dd, float* dn) {
+        const size_t wh = pixels(i);
+        if (cx->W != hv[i].w || cx->H != hv[i].h || !cx->S.planes || !cx->depth_plane_valid || cx->async_outstanding) return -2;   // no finished Run() of that size behind it
+        const float4* planes = cx->S.planes;
+        if (cx->device == q.device) {
+            FUSECHK(hipStreamSynchronize(cx->stream));
         } else {
-            // fixpoint over tau (pm_fusion.hpp): every pass re-evaluates all pixels of the image against the marking times of the
-            // previous pass; ends when the marking times repeat
-            const int npix = hv[i].w * hv[i].h, nchunks = (npix + 255) / 256;
-            for (int j = 1; j < num_ngb; ++j) {
-                const int s = src_ids[b + j], ns = hv[s].w * hv[s].h;
-                hipLaunchKernelGGL(k_fuse_tau_init, dim3((ns + 255) / 256), dim3(256), 0, st, d_mask[s], ns, hv[s].tau);
+            // another GPU of the node: its stream is drained there, the planes cross xGMI into a scratch buffer here
+            float4* tmp = call.alloc_n<float4>(wh);
+            if (!tmp || hipSetDevice(cx->device) != hipSuccess || hipStreamSynchronize(cx->stream) != hipSuccess || hipSetDevice(q.device) != hipSuccess ||
+                hipMemcpyPeerAsync(tmp, q.device, cx->S.planes, cx->device, wh * 16, st) != hipSuccess) {
+                (void)hipSetDevice(q.device);
+                return -100;
             }
-            int passes = 0;
-            for (;;) {
-                ++passes;
-                for (int j = 1; j < num_ngb; ++j) {
-                    const int s = src_ids[b + j], ns = hv[s].w * hv[s].h;
-                    hipLaunchKernelGGL(k_fuse_tau_init, dim3((ns + 255) / 256), dim3(256), 0, st, d_mask[s], ns, hv[s].tau_new);
-                }
-                if (tracks)
-                    hipLaunchKernelGGL((k_fuse<true, true>), grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
-                else
-                    hipLaunchKernelGGL(k_fuse<true>, grid, dim3(256), 0, st, d_views, i, d_src + b, num_ngb, use_dynamic, d_valid[i], d_out[i], d_consq);
-                if (num_ngb > 1) {
-                    hipLaunchKernelGGL(k_fuse_carry_local, dim3(nchunks, num_ngb - 1), dim3(256), 0, st, d_consq, npix, nchunks, d_carry);
-                    hipLaunchKernelGGL(k_scan_totals<LastValid>, dim3(num_ngb - 1), dim3(256), 0, st, d_carry, nchunks, -1, (int*)nullptr);
-                    hipLaunchKernelGGL(k_fuse_mark, dim3(nchunks), dim3(256), 0, st, d_views, d_src + b, num_ngb, d_valid[i], d_consq, d_carry, npix, nchunks);
-                }
-                if (hipMemsetAsync(d_diff, 0, 4, st) != hipSuccess) rc = -100;
-                for (int j = 1; j < num_ngb; ++j) {
-                    const int s = src_ids[b + j], ns = hv[s].w * hv[s].h;
-                    hipLaunchKernelGGL(k_fuse_tau_diff, dim3((ns + 255) / 256), dim3(256), 0, st, hv[s].tau, hv[s].tau_new, ns, d_diff);
-                }
-                int changed = 0;
-                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&changed, d_diff, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess)
-                    rc = -100;
-                if (rc) break;
-                for (int j = 1; j < num_ngb; ++j) std::swap(hv[src_ids[b + j]].tau, hv[src_ids[b + j]].tau_new);
-                if (hipMemcpyAsync(d_views, hv.data(), sizeof(FuseView) * n, hipMemcpyHostToDevice, st) != hipSuccess) { rc = -100; break; }
-                if (changed == 0) break;   // tau (now in .tau) reproduces itself: the sequential result
-                if (passes > npix || passes > 4096) { rc = -3; break; }   // every pass fixes at least one more pixel; measured <= 7 per image
-            }
-            g_fuse_passes_total += passes;
+            planes = tmp;
+        }
+        hipLaunchKernelGGL(k_split_planes, dim3((unsigned)((wh + 255) / 256)), dim3(256), 0, st, planes, dd, dn, wh);
+        return launched();
+    }
+    // Stage a view: the buffers of image i, its maps (uploaded, or split from resident planes), colours and sky mask; masks cleared.
+    // With `records` the per-pixel outputs of an image are consumed (compacted) before the next image is fused: one buffer
+    // of the largest size serves all images (the per-image form would be 37 B per pixel of the whole dataset)
+    int stage_view(int i, unsigned char* shared_valid, float* shared_out) {
+        FuseView& v = hv[i];
+        cam_to_dev(q.cams[i], v.cam);
+        v.w = q.cams[i].width, v.h = q.cams[i].height, v.cch = q.color_channels;
+        const size_t wh = pixels(i);
+        const bool has_sky = q.sky && q.sky[i];
+        float *dd = call.alloc_n<float>(wh), *dn = call.alloc_n<float>(wh * 3);
+        unsigned char* dg = call.alloc_n<unsigned char>(wh * q.color_channels);
+        unsigned char* dsky = has_sky ? call.alloc_n<unsigned char>(wh) : nullptr;
+        v.mask = call.alloc_n<unsigned char>(wh), v.mask_next = call.alloc_n<unsigned char>(wh);
+        d_valid[i] = q.records ? shared_valid : call.alloc_n<unsigned char>(wh);
+        d_out[i] = q.records ? shared_out : call.alloc_n<float>(wh * 9);
+        v.tau = exact ? call.alloc_n<int>(wh) : nullptr, v.tau_new = exact ? call.alloc_n<int>(wh) : nullptr;
+        if (!dd || !dn || !dg || (has_sky && !dsky) || !v.mask || !v.mask_next || !d_valid[i] || !d_out[i] || (exact && (!v.tau || !v.tau_new))) return -100;
+        v.depth = dd, v.normal = dn, v.color = dg, v.sky = dsky;
+        if (mpmvs_ctx* const cx = q.ctxs ? q.ctxs[i] : nullptr) {
+            if (const int rc = split_resident(i, cx, dd, dn)) return rc;
+        } else if (!q.depths || !q.normals || !q.depths[i] || !q.normals[i]) {
+            return -2;
+        } else {
+            FUSECHK(hipMemcpyAsync(dd, q.depths[i], wh * 4, hipMemcpyHostToDevice, st));
+            FUSECHK(hipMemcpyAsync(dn, q.normals[i], wh * 12, hipMemcpyHostToDevice, st));
+        }
+        FUSECHK(hipMemcpyAsync(dg, q.colors[i], wh * q.color_channels, hipMemcpyHostToDevice, st));
+        if (dsky) FUSECHK(hipMemcpyAsync(dsky, q.sky[i], wh, hipMemcpyHostToDevice, st));
+        FUSECHK(hipMemsetAsync(v.mask, 0, wh, st));
+        FUSECHK(hipMemsetAsync(v.mask_next, 0, wh, st));
+        if (!q.records) FUSECHK(hipMemsetAsync(d_valid[i], 0, wh, st));
+        if (!q.records) FUSECHK(hipMemsetAsync(d_out[i], 0, wh * 36, st));
+        return 0;
+    }
+    // Stage the tables: the views and the source ids, then the scratch of compaction, tracks and exact mode
+    int stage_tables() {
+        const int n = q.n, n_ids = q.src_off[n];
+        d_views = call.alloc_n<FuseView>(n);
+        d_src = call.alloc_n<int>(n_ids > 0 ? n_ids : 1);
+        if (!d_views || !d_src) return -100;
+        FUSECHK(hipMemcpyAsync(d_views, hv.data(), sizeof(FuseView) * n, hipMemcpyHostToDevice, st));
+        FUSECHK(hipMemcpyAsync(d_src, q.src_ids, sizeof(int) * n_ids, hipMemcpyHostToDevice, st));
+        if (q.records) {
+            rec.blocks = call.alloc_n<int>(max_blocks + 1);
+            rec.base = call.alloc_n<long long>(1);
+            rec.out = call.alloc_n<unsigned char>(total_px * kPlyRecord);  // upper bound: every pixel a point
+            if (!rec.blocks || !rec.base || !rec.out) return -100;
+            FUSECHK(hipMemsetAsync(rec.base, 0, sizeof(long long), st));
+        }
+        // rows of max_wh: tracks read every slot's row and one of slot bits, exact mode alone the source slots', the plain snapshot none
+        const size_t consq_rows = q.tracks ? (size_t)max_ngb : exact ? (size_t)std::max(max_ngb - 1, 1) : 0;
+        if (consq_rows && !(d_consq = call.alloc_n<int>(consq_rows * max_wh))) return -100;
+        if (q.tracks) {
+            trk.len = call.alloc_n<int>(max_wh), trk.excl = call.alloc_n<int>(max_wh), trk.tiles = call.alloc_n<int>(max_blocks + 1);
+            trk.ent_image = call.alloc_n<int>((size_t)max_ngb * max_wh), trk.ent_pixel = call.alloc_n<int>((size_t)max_ngb * max_wh);
+            trk.point_off = call.alloc_n<long long>(max_wh), trk.ebase = call.alloc_n<long long>(1);
+            if (!trk.len || !trk.excl || !trk.tiles || !trk.ent_image || !trk.ent_pixel || !trk.point_off || !trk.ebase) return -100;
+            FUSECHK(hipMemsetAsync(trk.ebase, 0, sizeof(long long), st));
+        }
+        if (exact) {
+            ex.carry = call.alloc_n<int>((size_t)std::max(max_ngb - 1, 1) * ((max_wh + 255) / 256));
+            ex.diff = call.alloc_n<int>(1);
+            if (!ex.carry || !ex.diff) return -100;
+        }
+        return 0;
+    }
+    // Fuse one image by snapshot: all its pixels read the masks as they were when the image started
+    int fuse_snapshot(int i) {
+        launch_fuse(i);
+        FUSECHK(hipGetLastError());
+        // the marks of image i become the masks the next image sees
+        bool ok = true;
+        each_source(i, [&](FuseView& v, int ns, dim3) { ok &= hipMemcpyAsync(v.mask, v.mask_next, (size_t)ns, hipMemcpyDeviceToDevice, st) == hipSuccess; });
+        return ok ? 0 : -100;
+    }
+    // Fuse one image by fixpoint over tau (pm_fusion.hpp), the reference's sequential masking order: every pass re-evaluates all
+    // pixels of the image against the marking times of the previous pass; ends when the marking times repeat.  A pass counts
+    // for mpmvs_fuse_passes once it is started, also when it fails
+    int fuse_fixpoint(int i) {
+        const int b = q.src_off[i], num_ngb = q.src_off[i + 1] - b;
+        const int npix = hv[i].w * hv[i].h, nchunks = (npix + 255) / 256;
+        each_source(i, [&](FuseView& v, int ns, dim3 blocks) { hipLaunchKernelGGL(k_fuse_tau_init, blocks, dim3(256), 0, st, v.mask, ns, v.tau); });
+        for (int passes = 1, changed = 1; changed; ++passes) {
+            ++g_fuse_passes_total;
             g_fuse_passes_max = std::max(g_fuse_passes_max, passes);
-            if (rc) break;
-            for (int j = 1; j < num_ngb; ++j) {
-                const int s = src_ids[b + j], ns = hv[s].w * hv[s].h;
-                hipLaunchKernelGGL(k_fuse_tau_to_mask, dim3((ns + 255) / 256), dim3(256), 0, st, hv[s].tau, ns, d_mask[s]);
+            each_source(i, [&](FuseView& v, int ns, dim3 blocks) { hipLaunchKernelGGL(k_fuse_tau_init, blocks, dim3(256), 0, st, v.mask, ns, v.tau_new); });
+            launch_fuse(i);
+            if (num_ngb > 1) {
+                hipLaunchKernelGGL(k_fuse_carry_local, dim3(nchunks, num_ngb - 1), dim3(256), 0, st, d_consq, npix, nchunks, ex.carry);
+                hipLaunchKernelGGL(k_scan_totals<LastValid>, dim3(num_ngb - 1), dim3(256), 0, st, ex.carry, nchunks, -1, (int*)nullptr);
+                hipLaunchKernelGGL(k_fuse_mark, dim3(nchunks), dim3(256), 0, st, d_views, d_src + b, num_ngb, d_valid[i], d_consq, ex.carry, npix, nchunks);
             }
-            if (hipGetLastError() != hipSuccess) { rc = -100; break; }
+            FUSECHK(hipMemsetAsync(ex.diff, 0, 4, st));
+            each_source(i, [&](FuseView& v, int ns, dim3 blocks) { hipLaunchKernelGGL(k_fuse_tau_diff, blocks, dim3(256), 0, st, v.tau, v.tau_new, ns, ex.diff); });
+            FUSECHK(hipGetLastError());
+            FUSECHK(hipMemcpyAsync(&changed, ex.diff, 4, hipMemcpyDeviceToHost, st));
+            FUSECHK(hipStreamSynchronize(st));
+            each_source(i, [&](FuseView& v, int, dim3) { std::swap(v.tau, v.tau_new); });
+            FUSECHK(hipMemcpyAsync(d_views, hv.data(), sizeof(FuseView) * q.n, hipMemcpyHostToDevice, st));
+            // changed == 0: tau (now in .tau) reproduces itself, the sequential result.  Every pass fixes at least one more pixel; measured <= 7 per image
+            if (changed && (passes > npix || passes > 4096)) return -3;
         }
-        if (records && !rc) {
-            const int wh = hv[i].w * hv[i].h, nb = (wh + 255) / 256;
-            hipLaunchKernelGGL(k_fuse_count, dim3(nb), dim3(256), 0, st, d_valid[i], wh, d_blocks);
-            hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, d_blocks, nb, 0, d_blocks + nb);
-            hipLaunchKernelGGL(k_fuse_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_out[i], wh, d_blocks, d_base, d_records);
-            hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, d_base, d_blocks + nb);
-            if (hipGetLastError() != hipSuccess) rc = -100;
-            if (tracks && !rc) {
-                hipLaunchKernelGGL(k_fuse_track_len, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq + (size_t)(num_ngb - 1) * wh, wh, d_len);
-                hipLaunchKernelGGL(k_scan_tiles, dim3(nb), dim3(256), 0, st, d_len, wh, d_excl, d_tiles);
-                hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, d_tiles, nb, 0, d_tiles + nb);
-                hipLaunchKernelGGL(k_fuse_track_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq, wh, i, d_src + b, num_ngb, d_blocks, d_tiles, d_excl,
-                                   d_ebase, d_point_off, d_ent_image, d_ent_pixel);
-                hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, d_ebase, d_tiles + nb);
-                // the image's tracks leave before the next image reuses the buffers: its two counts first, then what they size
-                int got[2] = {0, 0};
-                if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&got[0], d_blocks + nb, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipMemcpyAsync(&got[1], d_tiles + nb, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                    rc = -100;
-                if (!rc && (got[0] < 0 || got[0] > wh || got[1] < got[0] || (long long)got[1] > (long long)wh * num_ngb)) rc = -100;
-                if (!rc && !tracks->reserve((size_t)got[0], (size_t)got[1])) rc = -101;
-                if (!rc && got[0] > 0 &&
-                    (hipMemcpyAsync(tracks->off_tail(), d_point_off, (size_t)got[0] * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                     hipMemcpyAsync(tracks->image_tail(), d_ent_image, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                     hipMemcpyAsync(tracks->pixel_tail(), d_ent_pixel, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                     hipStreamSynchronize(st) != hipSuccess))
-                    rc = -100;
-                if (!rc && !tracks->commit((size_t)got[0], (size_t)got[1])) rc = -100;
-            }
+        each_source(i, [&](FuseView& v, int ns, dim3 blocks) { hipLaunchKernelGGL(k_fuse_tau_to_mask, blocks, dim3(256), 0, st, v.tau, ns, v.mask); });
+        return launched();
+    }
+    // Compact records: the valid pixels of image i, in raster order, behind those of the images before it
+    int compact_records(int i) {
+        const int wh = hv[i].w * hv[i].h, nb = (wh + 255) / 256;
+        hipLaunchKernelGGL(k_fuse_count, dim3(nb), dim3(256), 0, st, d_valid[i], wh, rec.blocks);
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, rec.blocks, nb, 0, rec.blocks + nb);
+        hipLaunchKernelGGL(k_fuse_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_out[i], wh, rec.blocks, rec.base, rec.out);
+        hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, rec.base, rec.blocks + nb);
+        return launched();
+    }
+    // Ship one image's tracks (after compact_records(i), whose block counts it reads): built on the device, appended to the host sink
+    int ship_tracks(int i) {
+        const int b = q.src_off[i], num_ngb = q.src_off[i + 1] - b;
+        const int wh = hv[i].w * hv[i].h, nb = (wh + 255) / 256;
+        hipLaunchKernelGGL(k_fuse_track_len, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq + (size_t)(num_ngb - 1) * wh, wh, trk.len);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nb), dim3(256), 0, st, trk.len, wh, trk.excl, trk.tiles);
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(256), 0, st, trk.tiles, nb, 0, trk.tiles + nb);
+        hipLaunchKernelGGL(k_fuse_track_scatter, dim3(nb), dim3(256), 0, st, d_valid[i], d_consq, wh, i, d_src + b, num_ngb, rec.blocks, trk.tiles, trk.excl,
+                           trk.ebase, trk.point_off, trk.ent_image, trk.ent_pixel);
+        hipLaunchKernelGGL(k_fuse_advance, dim3(1), dim3(1), 0, st, trk.ebase, trk.tiles + nb);
+        // the image's tracks leave before the next image reuses the buffers: its two counts first, then what they size
+        int got[2] = {0, 0};
+        FUSECHK(hipGetLastError());
+        FUSECHK(hipMemcpyAsync(&got[0], rec.blocks + nb, 4, hipMemcpyDeviceToHost, st));
+        FUSECHK(hipMemcpyAsync(&got[1], trk.tiles + nb, 4, hipMemcpyDeviceToHost, st));
+        FUSECHK(hipStreamSynchronize(st));
+        if (got[0] < 0 || got[0] > wh || got[1] < got[0] || (long long)got[1] > (long long)wh * num_ngb) return -100;
+        TrackSink& sink = *q.tracks;
+        if (!sink.reserve((size_t)got[0], (size_t)got[1])) return -101;
+        if (got[0] > 0) {
+            FUSECHK(hipMemcpyAsync(sink.off_tail(), trk.point_off, (size_t)got[0] * 8, hipMemcpyDeviceToHost, st));
+            FUSECHK(hipMemcpyAsync(sink.image_tail(), trk.ent_image, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st));
+            FUSECHK(hipMemcpyAsync(sink.pixel_tail(), trk.ent_pixel, (size_t)got[1] * 4, hipMemcpyDeviceToHost, st));
+            FUSECHK(hipStreamSynchronize(st));
         }
+        return sink.commit((size_t)got[0], (size_t)got[1]) ? 0 : -100;
     }
-    (void)call.end();
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;
-    if (!rc) (void)call.elapsed(&g_fuse_kernel_ms);
-    for (int i = 0; i < n && !rc; ++i) {
-        const size_t wh = (size_t)hv[i].w * hv[i].h;
-        if ((out_valid && hipMemcpyAsync(out_valid[i], d_valid[i], wh, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (out_points9 && hipMemcpyAsync(out_points9[i], d_out[i], wh * 36, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            (out_masks && hipMemcpyAsync(out_masks[i], d_mask[i], wh, hipMemcpyDeviceToHost, st) != hipSuccess))
-            rc = -100;
+    // one estimated image: fused, then (with `records`) compacted and its tracks shipped before the next image reuses the buffers
+    int fuse_image(int i) {
+        if (q.records) FUSECHK(hipMemsetAsync(d_valid[i], 0, pixels(i), st));
+        if (const int rc = exact ? fuse_fixpoint(i) : fuse_snapshot(i)) return rc;
+        if (!q.records) return 0;
+        if (const int rc = compact_records(i)) return rc;
+        return q.tracks ? ship_tracks(i) : 0;
     }
-    if (!rc && records) {
+    // Download: the per-pixel outputs and masks that were asked for, then the records; handed over once all have arrived
+    int download() {
+        for (int i = 0; i < q.n; ++i) {
+            const size_t wh = pixels(i);
+            if (q.out_valid) FUSECHK(hipMemcpyAsync(q.out_valid[i], d_valid[i], wh, hipMemcpyDeviceToHost, st));
+            if (q.out_points9) FUSECHK(hipMemcpyAsync(q.out_points9[i], d_out[i], wh * 36, hipMemcpyDeviceToHost, st));
+            if (q.out_masks) FUSECHK(hipMemcpyAsync(q.out_masks[i], hv[i].mask, wh, hipMemcpyDeviceToHost, st));
+        }
+        std::unique_ptr<unsigned char, void (*)(void*)> host(nullptr, std::free);   // released unless the records are handed over
         long long count = 0;
-        if ((hipMemcpyAsync(&count, d_base, sizeof(count), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st)) != hipSuccess) rc = -100;
-        unsigned char* host = nullptr;
-        if (!rc) {
-            host = (unsigned char*)std::malloc(count > 0 ? (size_t)count * kPlyRecord : 1);
-            if (!host) rc = -101;
+        if (q.records) {
+            FUSECHK(hipMemcpyAsync(&count, rec.base, sizeof(count), hipMemcpyDeviceToHost, st));
+            FUSECHK(hipStreamSynchronize(st));
+            host.reset((unsigned char*)std::malloc(count > 0 ? (size_t)count * kPlyRecord : 1));
+            if (!host) return -101;
+            if (count > 0) FUSECHK(hipMemcpyAsync(host.get(), rec.out, (size_t)count * kPlyRecord, hipMemcpyDeviceToHost, st));
+            if (q.tracks && (long long)q.tracks->points() != count) return -100;
         }
-        if (!rc && count > 0 && hipMemcpyAsync(host, d_records, (size_t)count * kPlyRecord, hipMemcpyDeviceToHost, st) != hipSuccess) rc = -100;
-        if (!rc && tracks && (long long)tracks->points() != count) rc = -100;
-        if (rc) {
-            std::free(host);
-        } else {
-            *records = host;
-            *n_records = count;
+        FUSECHK(hipStreamSynchronize(st));   // the outputs have arrived
+        if (q.records) {
+            *q.records = host.release();
+            *q.n_records = count;
         }
+        return 0;
     }
-    if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = -100;   // the outputs have arrived
-    return rc;
+   public:
+    explicit FuseRun(const FuseRequest& request) : q(request), exact((request.flags & MPMVS_FUSE_REFERENCE_ORDER) != 0), call(request.device) {}
+    int run() {
+        g_fuse_passes_total = g_fuse_passes_max = 0;
+        if (const int rc = fuse_check_request(q, call.entered(), kMaxFuseNgb)) return rc;
+        if (!call.ok()) return -100;
+        st = call.stream();
+        const int n = q.n;
+        hv.resize(n), d_valid.assign(n, nullptr), d_out.assign(n, nullptr);
+        for (int i = 0; i < n; ++i)
+            if (q.estimate[i]) {
+                const size_t wh = (size_t)q.cams[i].width * q.cams[i].height;
+                total_px += wh, max_wh = std::max(max_wh, wh), max_blocks = std::max(max_blocks, (wh + 255) / 256);
+                max_ngb = std::max(max_ngb, q.src_off[i + 1] - q.src_off[i]);
+            }
+        unsigned char* shared_valid = q.records ? call.alloc_n<unsigned char>(max_wh) : nullptr;
+        float* shared_out = q.records ? call.alloc_n<float>(max_wh * 9) : nullptr;
+        if (q.records && (!shared_valid || !shared_out)) return -100;
+        for (int i = 0; i < n; ++i)
+            if (const int rc = stage_view(i, shared_valid, shared_out)) return rc;
+        if (const int rc = stage_tables()) return rc;
+        (void)call.begin();
+        for (int i = 0; i < n; ++i)
+            if (q.estimate[i])
+                if (const int rc = fuse_image(i)) return rc;
+        (void)call.end();
+        FUSECHK(hipStreamSynchronize(st));
+        (void)call.elapsed(&g_fuse_kernel_ms);   // written on success only
+        return download();
+    }
+};
+}  // namespace
+}  // extern "C++"
+
+// the record forms: the count, or the code
+static long long fuse_run_records(FuseRequest q, unsigned char** records, TrackSink* tracks = nullptr) {
+    long long count = 0;
+    q.records = records, q.n_records = &count, q.tracks = tracks;
+    const int rc = FuseRun(q).run();
+    return rc ? rc : count;
+}
+
+// The ctx forms take maps that are still resident in the PatchMatch contexts that estimated them (ctxs[i] != NULL: depths[i] /
+// normals[i] are not read and may be NULL; depths / normals themselves may be NULL when every image has a context); ctxs NULL:
+// host arrays only, which is what the forms without ctxs are.
+int mpmvs_fuse_ctx(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths, const float* const* normals,
+                   const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
+                   int use_dynamic, unsigned char* const* out_valid, float* const* out_points9, unsigned char* const* out_masks) {
+    if (!out_valid || !out_points9 || !out_masks) return -1;
+    return FuseRun({device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, out_valid, out_points9, out_masks}).run();
 }
 
 int mpmvs_fuse(int device, int n, const mpmvs_camera* cams, const int* estimate, const float* const* depths, const float* const* normals,
                const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
                int use_dynamic, unsigned char* const* out_valid, float* const* out_points9, unsigned char* const* out_masks) {
-    if (!out_valid || !out_points9 || !out_masks) return -1;
-    return fuse_impl(device, n, cams, estimate, nullptr, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, out_valid, out_points9,
-                     out_masks, nullptr, nullptr);
-}
-
-long long mpmvs_fuse_ply(int device, int n, const mpmvs_camera* cams, const int* estimate, const float* const* depths, const float* const* normals,
-                         const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off,
-                         const int* src_ids, int use_dynamic, unsigned char** records, unsigned char* const* out_masks) {
-    if (!records) return -1;
-    long long count = 0;
-    const int rc = fuse_impl(device, n, cams, estimate, nullptr, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr,
-                             out_masks, records, &count);
-    return rc ? rc : count;
-}
-
-// The same two calls for maps that are still resident in the PatchMatch contexts that estimated them (ctxs[i] != NULL: depths[i] /
-// normals[i] are not read and may be NULL; depths / normals themselves may be NULL when every image has a context).
-int mpmvs_fuse_ctx(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths, const float* const* normals,
-                   const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off, const int* src_ids,
-                   int use_dynamic, unsigned char* const* out_valid, float* const* out_points9, unsigned char* const* out_masks) {
-    if (!out_valid || !out_points9 || !out_masks) return -1;
-    return fuse_impl(device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, out_valid, out_points9,
-                     out_masks, nullptr, nullptr);
+    return mpmvs_fuse_ctx(device, n, cams, estimate, nullptr, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, out_valid, out_points9,
+                          out_masks);
 }
 
 long long mpmvs_fuse_ply_ctx(int device, int n, const mpmvs_camera* cams, const int* estimate, mpmvs_ctx* const* ctxs, const float* const* depths,
                              const float* const* normals, const unsigned char* const* colors, int color_channels, const unsigned char* const* sky,
                              const int* src_off, const int* src_ids, int use_dynamic, unsigned char** records, unsigned char* const* out_masks) {
     if (!records) return -1;
-    long long count = 0;
-    const int rc = fuse_impl(device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr,
-                             out_masks, records, &count);
-    return rc ? rc : count;
+    return fuse_run_records({device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr, out_masks},
+                            records);
+}
+
+long long mpmvs_fuse_ply(int device, int n, const mpmvs_camera* cams, const int* estimate, const float* const* depths, const float* const* normals,
+                         const unsigned char* const* colors, int color_channels, const unsigned char* const* sky, const int* src_off,
+                         const int* src_ids, int use_dynamic, unsigned char** records, unsigned char* const* out_masks) {
+    return mpmvs_fuse_ply_ctx(device, n, cams, estimate, nullptr, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, records, out_masks);
 }
 
 // mpmvs_fuse_ply_ctx that also returns every point's track (include/mpmvs.h); ctxs may be NULL
@@ -2323,15 +2324,11 @@ long long mpmvs_fuse_ply_tracks(int device, int n, const mpmvs_camera* cams, con
                                 int32_t** track_image, int32_t** track_pixel, unsigned char* const* out_masks) {
     if (!records) return -1;
     if (!track_off || !track_image || !track_pixel) return -2;
-    long long count = 0;
     unsigned char* rec = nullptr;
     TrackSink sink;
-    const int rc = fuse_impl(device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr,
-                             out_masks, &rec, &count, &sink);
-    if (rc) {
-        std::free(rec);   // nothing is handed over on failure
-        return rc;
-    }
+    const long long count = fuse_run_records(
+        {device, n, cams, estimate, ctxs, depths, normals, colors, color_channels, sky, src_off, src_ids, use_dynamic, nullptr, nullptr, out_masks}, &rec, &sink);
+    if (count < 0) return count;   // nothing was handed over
     if (!sink.finish(track_off, track_image, track_pixel)) {
         std::free(rec);
         return -101;
