@@ -644,7 +644,7 @@ int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* cloud, float ms[3]);
  * so that the back of the scene does not shine through the gaps between front points.
  * DEFINED BY EQUIVALENCE with the plain-loop statement, bit for bit and independent of scheduling.  For view v with camera c
  * (K, R, t row-major, W = c.width, H = c.height; depth_min / depth_max unused) and point i = (p0, p1, p2), everything in fp32, no
- * contraction, correctly rounded quotients (project_depth of mp-mvs_amd/csrc/pm_fusion.hpp):
+ * contraction, correctly rounded quotients (project_depth of mp-mvs_amd/csrc/pm_device.hpp):
  *   t0 = ((R0*p0 + R1*p1) + R2*p2) + t[0], t1 and t2 alike;  z = (K6*t0 + K7*t1) + K8*t2;
  *   u = ((K0*t0 + K1*t1) + K2*t2) / z;  v = ((K3*t0 + K4*t1) + K5*t2) / z;  fu = u + 0.5f, fv = v + 0.5f (pixel centres at integers).
  *   The point is IN VIEW iff its three coordinates are finite, z is finite and z > 0, fu >= 0, fu < (float)W, fv >= 0 and

@@ -16,7 +16,7 @@
 // GRANULARITY: the grain is 2^-30 u.  An fp32 coordinate of magnitude up to u has a grain of 2^-24 u at worst, 64 times coarser.
 // ORDER: integer addition is associative and commutative: the order of the lanes, waves, blocks and atomics never shows.
 //
-// Passes of a call (mpmvs_api.hip: align_pass):
+// Passes of a call (mpmvs_cloud.hip: align_pass):
 //   1. k_align_qbin / scan / k_cloud_qorder   the sources binned by the cell of their TRANSFORMED point (MPMVS_CLOUD_BIN=0: caller order)
 //   2. k_align_pass   one thread per source: transform, search, the pair in the normalised frame; then term by term: the wave
 //                     adds it with __shfl_xor (a 64-bit value crosses lanes as two dwords and is put together again BEFORE the

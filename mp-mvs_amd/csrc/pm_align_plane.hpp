@@ -16,7 +16,7 @@
 // SIGN: -n gives -nh, hence -c, -g and -r, each exactly (a negated product is the product negated, a difference of two negated
 // products is the difference negated): J and r change sign together and every product of two of them keeps every bit.
 //
-// Passes of a call (mpmvs_api.hip: align_pass): the binning of pm_align.hpp as it is, then k_align_plane_pass instead of
+// Passes of a call (mpmvs_cloud.hip: align_pass): the binning of pm_align.hpp as it is, then k_align_plane_pass instead of
 // k_align_pass: one thread per source; the matched thread gathers the 12 bytes of its target's normal and forms J, r and dn
 // once -- nine doubles in named scalars -- and then goes term by term as k_align_pass does: one term formed, added across the
 // wave (align_shfl_xor), parked in LDS (4 x 38 x 8 = 1 216 bytes); threads 0..37 add the block's totals with one 64-bit

@@ -15,7 +15,7 @@
 //                       it claims the slot, finds its own key, or moves on; slots >= 2 x finite points, so the table cannot
 //                       fill and a probe sequence is bounded by the table size), count per slot with an integer atomic.
 //   2. k_cloud_stats    occupied slots and the fullest cell.
-//   3. scan             slot counts -> offsets: k_scan_tiles, k_scan_totals<Sum> (pm_scan.hpp) and k_vs_scan_add.
+//   3. scan             slot counts -> offsets: k_scan_tiles, k_scan_totals<Sum> and k_vs_scan_add (pm_scan.hpp).
 //   4. k_cloud_scatter  (x, y, z, original index) of every target into its cell's run: one 16-byte record per candidate.
 // Passes of a query call:
 //   5. k_cloud_qbin / scan / k_cloud_qorder   the queries binned by the hash of their own cell, so that the 64 queries of a
@@ -27,7 +27,6 @@
 #include <stdint.h>
 
 #include "pm_scan.hpp"
-#include "pm_viewsel.hpp"   // k_vs_scan_add
 
 namespace pm {
 

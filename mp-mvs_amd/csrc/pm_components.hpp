@@ -28,7 +28,7 @@
 // Why stale reads do no harm: every value parent[x] has ever held is a node of x's tree (trees merge, never split) below or at x,
 // so a walk over old values still descends inside the tree; only the compare-and-swap decides a hook, and it is exact.  Reads of
 // parent inside the hook pass are relaxed atomic loads at agent scope, the halving stores relaxed atomic stores.
-// The four counts are taken on the host from the downloaded labels and sizes (mpmvs_api.hip).
+// The four counts are taken on the host from the downloaded labels and sizes (mpmvs_cloud.hip).
 // The per-thread bodies are host and device code, so that tools/components_check.cpp can replay them thread by thread and edge by
 // edge under the sanitizers; there the atomics are plain reads and writes.
 #pragma once

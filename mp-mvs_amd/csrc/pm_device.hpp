@@ -839,6 +839,16 @@ PM_DEV void project(const CamDev& cam, float p0, float p1, float p2, float& u, f
     u = ((cam.K[0] * t0 + cam.K[1] * t1) + cam.K[2] * t2) / d;
     v = ((cam.K[3] * t0 + cam.K[4] * t1) + cam.K[5] * t2) / d;
 }
+// reference src/PatchMatch.cpp:251-261: the projection of the fusion (pm_fusion.hpp), of the depth render (pm_render.hpp) and of the
+// observer.  Host code too: the render passes are replayed on the host through it.
+__host__ PM_DEV void project_depth(const CamDev& cam, float p0, float p1, float p2, float& u, float& v, float& depth) {
+    const float t0 = ((cam.R[0] * p0 + cam.R[1] * p1) + cam.R[2] * p2) + cam.t[0];
+    const float t1 = ((cam.R[3] * p0 + cam.R[4] * p1) + cam.R[5] * p2) + cam.t[1];
+    const float t2 = ((cam.R[6] * p0 + cam.R[7] * p1) + cam.R[8] * p2) + cam.t[2];
+    depth = (cam.K[6] * t0 + cam.K[7] * t1) + cam.K[8] * t2;
+    u = ((cam.K[0] * t0 + cam.K[1] * t1) + cam.K[2] * t2) / depth;
+    v = ((cam.K[3] * t0 + cam.K[4] * t1) + cam.K[5] * t2) / depth;
+}
 // ComputeGeomConsistencyCost: forward-project the pixel at the hypothesis' depth into the source view, read the source depth
 // there (nearest texel, clamp), back-project and re-project into the reference view, cost = min(3, reprojection distance).
 // The reference walks through world coordinates with 9 divisions per check (BackProjectPoint2W, ProjectPoint twice each way);

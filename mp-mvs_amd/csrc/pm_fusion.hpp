@@ -45,15 +45,7 @@ struct FuseView {
 PM_DEV void point_on_world(const CamDev& cam, int x, int y, float depth, float& o0, float& o1, float& o2) {
     backproject(cam, (float)x, (float)y, depth, o0, o1, o2);
 }
-// reference src/PatchMatch.cpp:251-261.  Host code too: the render passes of pm_render.hpp are replayed on the host through it.
-__host__ PM_DEV void project_depth(const CamDev& cam, float p0, float p1, float p2, float& u, float& v, float& depth) {
-    const float t0 = ((cam.R[0] * p0 + cam.R[1] * p1) + cam.R[2] * p2) + cam.t[0];
-    const float t1 = ((cam.R[3] * p0 + cam.R[4] * p1) + cam.R[5] * p2) + cam.t[1];
-    const float t2 = ((cam.R[6] * p0 + cam.R[7] * p1) + cam.R[8] * p2) + cam.t[2];
-    depth = (cam.K[6] * t0 + cam.K[7] * t1) + cam.K[8] * t2;
-    u = ((cam.K[0] * t0 + cam.K[1] * t1) + cam.K[2] * t2) / depth;
-    v = ((cam.K[3] * t0 + cam.K[4] * t1) + cam.K[5] * t2) / depth;
-}
+// (its way back, project_depth, reference src/PatchMatch.cpp:251-261, is pm_device.hpp's: the depth render shares it)
 PM_DEV bool round_index(float v, int& out) {
     const float f = v + 0.5f;
     if (!(f > -1.0f && f < 1.0e8f)) return false;

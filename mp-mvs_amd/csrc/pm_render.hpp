@@ -1,6 +1,6 @@
 // pm_render.hpp -- z-buffer render of a point cloud into pinhole cameras with a splat visibility test (mpmvs_cloud_render_depth;
 // contract: DESIGN.md section 14 and include/mpmvs.h): the per-view ground-truth depth map of a scan.  Per view and pixel
-//   Zc = the smallest z of the in-view points that land in the pixel (+inf: none), z, u, v by project_depth (pm_fusion.hpp),
+//   Zc = the smallest z of the in-view points that land in the pixel (+inf: none), z, u, v by project_depth (pm_device.hpp),
 //        pixel = ((int)(u + 0.5f), (int)(v + 0.5f));
 //   Z1 = the smallest Zc of the (2 splat + 1)^2 window around the pixel, inside the image;
 //   depth = Zc if it is finite and Zc <= Z1 * (1 + occl_rel) in fp32, else 0;  idx = the smallest index of a point of the pixel
@@ -23,7 +23,7 @@
 #include <stdint.h>
 
 #include "pm_cloud.hpp"    // cloud_bits, cloud_float, cloud_finite
-#include "pm_fusion.hpp"   // project_depth
+#include "pm_device.hpp"   // CamDev, project_depth
 
 namespace pm {
 

@@ -7,10 +7,12 @@
 //   k_scan_tiles          per tile of kScanBlock elements: exclusive + scan in the tile (optional) and the tile's total
 //   k_scan_totals         one block per row: exclusive scan of the row's tile totals in place, in rounds of kScanBlock
 //                         with a running carry (any count), and the row's grand total
+//   k_vs_scan_add         adds the scanned tile totals to the in-tile scan: offsets over the whole array
 // Every thread of the block must reach a block scan (it synchronises); on return its LDS is free for the next call.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace pm {
 
@@ -66,8 +68,12 @@ __device__ __forceinline__ int block_excl_scan(int v, int identity, int& total) 
     return Op::apply(scan_wave_carry<Op>(inc, identity, total), (threadIdx.x & 63) ? up : identity);
 }
 
+// The two kernels that are no templates are `inline`: several translation units of the library include this header.  (nvcc would
+// ignore the keyword on a kernel, which is all -Wcuda-compat has to say about it; clang gives them the linkage asked for.)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
 // totals[b] = sum of v[b * kScanBlock ..); excl (if given) [k] = sum of the elements before k in k's tile
-__global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const int* __restrict__ v, int n, int* __restrict__ excl, int* __restrict__ totals) {
+inline __global__ __launch_bounds__(kScanBlock) void k_scan_tiles(const int* __restrict__ v, int n, int* __restrict__ excl, int* __restrict__ totals) {
     const size_t k = (size_t)blockIdx.x * kScanBlock + threadIdx.x;
     int total;
     const int r = block_excl_scan<Sum>(k < (size_t)n ? v[k] : 0, 0, total);
@@ -89,5 +95,13 @@ __global__ __launch_bounds__(kScanBlock) void k_scan_totals(int* __restrict__ to
     }
     if (grand && threadIdx.x == 0) grand[blockIdx.x] = carry;
 }
+
+// off[k] += the scanned total of k's tile (after k_scan_tiles and k_scan_totals<Sum>): the add pass of the view selection's track
+// offsets, the cloud grid's slot offsets and the voxel numbering, named after its first user
+inline __global__ __launch_bounds__(kScanBlock) void k_vs_scan_add(int* __restrict__ off, int n, const int* __restrict__ tsum) {
+    const int64_t k = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
+    if (k < n) off[k] += tsum[blockIdx.x];
+}
+#pragma clang diagnostic pop
 
 }  // namespace pm

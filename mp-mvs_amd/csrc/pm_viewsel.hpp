@@ -8,7 +8,7 @@
 // Passes (all integer bookkeeping; the results do not depend on scheduling):
 //   1. k_vs_count / scan / k_vs_scatter: per-image observations -> point-major tracks (the image of
 //      every observation, in scatter order).  The scan of the per-point counts into track offsets is
-//      the shared one of pm_scan.hpp (k_scan_tiles, k_scan_totals<Sum>) followed by k_vs_scan_add.
+//      the shared one of pm_scan.hpp (k_scan_tiles, k_scan_totals<Sum>, k_vs_scan_add).
 //   2. k_vs_mult: per track slot, whether it is the first slot of its image in the track (scanning
 //      the track) and, if so, the image's multiplicity in it; other slots get 0.  "First" depends on
 //      scatter order, the multiplicity it carries does not, so no per-track sort is needed.
@@ -37,12 +37,6 @@ __global__ __launch_bounds__(256) void k_vs_count(const int64_t* __restrict__ ob
         const int p = obs_pt[k];
         if (p >= 0) atomicAdd(&cnt[p], 1);
     }
-}
-
-// off[k] += the scanned total of k's tile (after k_scan_tiles and k_scan_totals<Sum>, pm_scan.hpp)
-__global__ __launch_bounds__(kScanBlock) void k_vs_scan_add(int* __restrict__ off, int n, const int* __restrict__ tsum) {
-    const int64_t k = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    if (k < n) off[k] += tsum[blockIdx.x];
 }
 
 // one block per image: every observation goes to the next free slot of its point's track

@@ -1,6 +1,6 @@
 """Seeded random programs of operations on one long-lived mpmvs_cloud handle, shared by tests/test_cloud_seq_cpu.py (what the
 sweep covers, on the statements alone) and tests/test_cloud_seq_gpu.py (the sweep on the MI355X); a plain model of the handle's
-grid cache (cloud_grid in csrc/mpmvs_api.hip); and the expected result of every step from the statements the
+grid cache (cloud_grid in csrc/mpmvs_cloud.hip); and the expected result of every step from the statements the
 operations already have.  case(k) is a pure function of k.
 
 What a case varies: a target of 1..400 points (weight on 1, 2, 255, 256, 257: the edges of the 256-thread blocks of insert,

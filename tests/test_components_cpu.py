@@ -43,7 +43,11 @@ def test_symbols_declared_exported_and_bound(eng):
     assert f.restype is C.c_float and f.argtypes == [C.c_void_p, C.POINTER(C.c_float)]
     f = fns["cloud_components_pass_ms"]
     assert f.restype is C.c_int and f.argtypes == [C.c_void_p, C.POINTER(C.c_float)]
-    assert "pm_components.hpp" in open(os.path.join(ROOT, "mp-mvs_amd", "csrc", "Makefile")).read()
+    # the library follows the header: the cloud unit includes it, and the objects depend on what they include (generated dependencies)
+    csrc = os.path.join(ROOT, "mp-mvs_amd", "csrc")
+    assert '#include "pm_components.hpp"' in open(os.path.join(csrc, "mpmvs_cloud.hip")).read()
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert "mpmvs_cloud" in makefile and "-MMD" in makefile and "-include $(OBJS:.o=.d)" in makefile
     assert os.path.exists(os.path.join(ROOT, "mp-mvs_amd", "csrc", "pm_components.hpp"))
 
 

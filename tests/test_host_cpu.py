@@ -582,3 +582,85 @@ def test_bench_quotes_pmc_figures_only_for_this_build_and_this_run(tmp_path, mon
     lib.write_bytes(b"binary two")                           # another build of the kernels
     stale = bench.profile_counters(2.70)
     assert stale["traffic"] is None and "another kernel build" in stale["reason"]
+
+
+def _own_handle(path):
+    """a CDLL object of our own on the library: its function objects (and their argtypes) are not the bound ones of engine.load()"""
+    lib = ctypes.CDLL(path)
+    lib.mpmvs_last_error.restype = ctypes.c_char_p
+    lib.mpmvs_last_error.argtypes = [ctypes.c_void_p]
+    return lib
+
+
+def test_one_error_channel_across_translation_units_per_thread(pm):
+    """The calls without a PatchMatch context live in several translation units of the HIP library and report through ONE
+    per-thread text, mpmvs_last_error(NULL).  Four calls from four families, each refused by an argument check before any device is
+    selected: each returns -2 and leaves its own text, and a failing call of another thread does not change what this thread reads."""
+    import threading
+    C = ctypes
+    engine = importlib.import_module("mp-mvs_amd.engine")
+    lib = _own_handle(engine.load()[0]._name)
+    P, F, I, LL = C.c_void_p, C.c_float, C.c_int, C.c_longlong
+    lib.mpmvs_cloud_knn.restype, lib.mpmvs_cloud_knn.argtypes = I, [P, F, I, LL, P, P, P, P]
+    lib.mpmvs_skyseg_inspect.restype, lib.mpmvs_skyseg_inspect.argtypes = I, [C.c_char_p, C.c_char_p, I, I, C.c_char_p, P]
+    lib.mpmvs_cloud_voxel_downsample.restype, lib.mpmvs_cloud_voxel_downsample.argtypes = LL, [I, LL, P, P, P, F, P, P, P, P, P, P]
+    lib.mpmvs_observer_classify.restype, lib.mpmvs_observer_classify.argtypes = I, [P, LL, P, F, F, P, P]
+    lib.mpmvs_cloud_nearest.restype, lib.mpmvs_cloud_nearest.argtypes = I, [P, F, LL, P, P, P]
+    d2 = (C.c_float * 4)()
+    out = [C.c_void_p() for _ in range(3)]
+    free = (C.c_int * 1)()
+    calls = [
+        (lambda: lib.mpmvs_cloud_knn(None, 1.0, 1, 1, None, d2, None, None), b"cloud knn: bad argument"),
+        (lambda: lib.mpmvs_skyseg_inspect(b"none.param", b"none.bin", 8, 8, None, None), b"skyseg: bad argument"),
+        (lambda: lib.mpmvs_cloud_voxel_downsample(0, 0, None, None, None, 0.0, C.byref(out[0]), None, None, C.byref(out[1]), C.byref(out[2]), None),
+         b"voxel: the voxel size must be finite and positive"),
+        (lambda: lib.mpmvs_observer_classify(None, 0, None, 0.1, 0.0, free, None), b"observer: no handle"),
+    ]
+    other = {}
+
+    def other_thread():
+        other["rc"] = lib.mpmvs_cloud_nearest(None, 1.0, 0, None, None, None)
+        other["text"] = lib.mpmvs_last_error(None)
+
+    for call, text in calls:
+        assert call() == -2
+        assert lib.mpmvs_last_error(None) == text
+        t = threading.Thread(target=other_thread)
+        t.start()
+        t.join()
+        assert other == {"rc": -2, "text": b"cloud: bad argument"}
+        assert lib.mpmvs_last_error(None) == text, "another thread's failing call changed this thread's text"
+
+
+def _defined_dynamic_symbols(path):
+    """names (as the linker sees them) of the defined entries of a library's dynamic symbol table, read with the ROCm tree's LLVM tools:
+    llvm-nm -D --defined-only, or llvm-readelf --dyn-syms where the tree ships no llvm-nm.  No tool is a failure, not a skip."""
+    import subprocess
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    found = [os.path.join(rocm, d, t) for t in ("llvm-nm", "llvm-readelf") for d in ("llvm/bin", "lib/llvm/bin")]
+    found = [t for t in found if os.path.exists(t)]
+    assert found, f"neither llvm-nm nor llvm-readelf under {rocm}"
+    if found[0].endswith("llvm-nm"):
+        text = subprocess.run([found[0], "-D", "--defined-only", path], check=True, capture_output=True, text=True).stdout
+        return [f[2] for f in (line.split(None, 2) for line in text.splitlines()) if len(f) == 3]
+    text = subprocess.run([found[0], "--dyn-syms", "--wide", path], check=True, capture_output=True, text=True).stdout
+    # Num: Value Size Type Bind Vis Ndx Name
+    rows = [f for f in (line.split(None, 7) for line in text.splitlines()) if len(f) == 8 and f[0].rstrip(":").isdigit()]
+    return [f[7].split("@")[0] for f in rows if f[6] != "UND"]
+
+
+def test_export_list_is_the_header_and_hides_the_shared_helpers(pm):
+    """The dynamic symbol table of the HIP library, both builds: the defined mpmvs_* names are exactly the functions include/mpmvs.h
+    declares, and no helper that the translation units share (pm_host.hpp) is exported."""
+    header = open(os.path.join(ROOT, "include", "mpmvs.h")).read()
+    declared = set(re.findall(r"\b(mpmvs_[a-z0-9_]+)\s*\(", header))
+    engine = importlib.import_module("mp-mvs_amd.engine")
+    hidden = ("pool_malloc", "pool_free", "call_fail", "call_error", "enter_device", "ctx_resident_planes", "cam_to_dev", "DeviceCall", "Scratch", "PinnedBuf")
+    for path in (engine.load()[0]._name, engine.LIB_Q8_PATH):
+        names = _defined_dynamic_symbols(path)
+        assert len(names) >= len(declared)
+        exported = {n for n in names if n.startswith("mpmvs_")}
+        assert exported - declared == set(), f"{path} exports mpmvs_* names that include/mpmvs.h does not declare"
+        assert declared - exported == set(), f"{path} does not export every function of include/mpmvs.h"
+        for n in names:
+            assert not any(h in n for h in hidden), f"{path} exports the shared helper {n}"

@@ -38,7 +38,11 @@ def test_symbols_declared_exported_and_bound(eng):
     assert fns["cloud_knn"].restype is C.c_int and len(fns["cloud_knn"].argtypes) == 8
     assert fns["cloud_outliers"].restype is C.c_longlong and len(fns["cloud_outliers"].argtypes) == 12
     assert re.search(r"#define\s+MPMVS_KNN_MAX_K\s+32\b", header)
-    assert "pm_knn.hpp" in open(os.path.join(ROOT, "mp-mvs_amd", "csrc", "Makefile")).read()
+    # the library follows the header: the cloud unit includes it, and the objects depend on what they include (generated dependencies)
+    csrc = os.path.join(ROOT, "mp-mvs_amd", "csrc")
+    assert '#include "pm_knn.hpp"' in open(os.path.join(csrc, "mpmvs_cloud.hip")).read()
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert "mpmvs_cloud" in makefile and "-MMD" in makefile and "-include $(OBJS:.o=.d)" in makefile
 
 
 class Call:

@@ -32,7 +32,11 @@ def test_symbols_declared_exported_and_bound(eng):
         assert name[len("mpmvs_"):] in fns and name[len("mpmvs_"):] in fns_q8
     assert fns["cloud_normals"].restype is C.c_int and len(fns["cloud_normals"].argtypes) == 9
     assert fns["cloud_normals_ms"].restype is C.c_float and len(fns["cloud_normals_ms"].argtypes) == 2
-    assert "pm_normals.hpp" in open(os.path.join(ROOT, "mp-mvs_amd", "csrc", "Makefile")).read()
+    # the library follows the header: the cloud unit includes it, and the objects depend on what they include (generated dependencies)
+    csrc = os.path.join(ROOT, "mp-mvs_amd", "csrc")
+    assert '#include "pm_normals.hpp"' in open(os.path.join(csrc, "mpmvs_cloud.hip")).read()
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert "mpmvs_cloud" in makefile and "-MMD" in makefile and "-include $(OBJS:.o=.d)" in makefile
     cloud = importlib.import_module("mp-mvs_amd.cloud")
     assert callable(cloud.Cloud.normals) and callable(cloud.Cloud.normals_ms) and callable(cloud.estimate_normals)
 

@@ -37,7 +37,11 @@ def test_symbols_declared_exported_and_bound(eng):
         assert hasattr(lib, name) and hasattr(lib_q8, name)
         assert name[len("mpmvs_"):] in fns and name[len("mpmvs_"):] in fns_q8
     assert fns["cloud_voxel_downsample"].restype is C.c_longlong and len(fns["cloud_voxel_downsample"].argtypes) == 12
-    assert "pm_voxel.hpp" in open(os.path.join(ROOT, "mp-mvs_amd", "csrc", "Makefile")).read()
+    # the library follows the header: the cloud unit includes it, and the objects depend on what they include (generated dependencies)
+    csrc = os.path.join(ROOT, "mp-mvs_amd", "csrc")
+    assert '#include "pm_voxel.hpp"' in open(os.path.join(csrc, "mpmvs_cloud.hip")).read()
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert "mpmvs_cloud" in makefile and "-MMD" in makefile and "-include $(OBJS:.o=.d)" in makefile
 
 
 class Call:

@@ -1,7 +1,7 @@
 // align_check.cpp -- the ICP pass of csrc/pm_align.hpp replayed on the host, thread by thread in a scrambled order, through the
 // header's own __host__ __device__ code (the transform, the binning, the shared 27-cell search, the pair and its 18 terms per thread; the
 // scans, the wave sum -- the xor butterfly with every 64-bit value crossing as two dwords -- the four waves of a block and the
-// adds of the blocks are plain loops here), in the launch order of align_pass of mpmvs_api.hip and with buffers of exactly their
+// adds of the blocks are plain loops here), in the launch order of align_pass of mpmvs_cloud.hip and with buffers of exactly their
 // sizes, against the plain-loop statement of include/mpmvs.h; |a|, |b| <= 1 is asserted for every matched pair.  Then the solver
 // of csrc/pm_align_host.hpp on random, reflected, planar and under-determined inputs.
 // A host program, so that it runs under the sanitizers without a GPU:

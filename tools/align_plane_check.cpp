@@ -2,7 +2,7 @@
 // order, through the header's own __host__ __device__ code (the transform, the binning, the shared 27-cell search, the pair, its
 // normal and its 38 terms per thread; the scans, the wave sum -- the xor butterfly with every 64-bit value crossing as two dwords
 // -- the four waves of a block and the adds of the blocks are plain loops here), in the launch order of align_pass of
-// mpmvs_api.hip and with buffers of exactly their sizes, against the plain-loop statement of include/mpmvs.h written on its own;
+// mpmvs_cloud.hip and with buffers of exactly their sizes, against the plain-loop statement of include/mpmvs.h written on its own;
 // |nh| <= 1, |r| < 0.87 and |term| < 4 are asserted for every matched pair, and the sums of the negated normals must keep every
 // bit.  Then the solver of csrc/pm_align_host.hpp on random inputs, exact planes, the three-plane corner, too few pairs and a
 // step that asks for a scale <= 0.

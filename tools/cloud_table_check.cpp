@@ -1,6 +1,6 @@
 // cloud_table_check.cpp -- the passes of csrc/pm_cloud.hpp replayed on the host, thread by thread in a scrambled order, through
 // the header's own __host__ __device__ code (the key, packing, hashing and probing arithmetic and the per-thread body of every
-// kernel; the scans and the stats are plain loops here), in the launch order of cloud_build / cloud_query of mpmvs_api.hip and with
+// kernel; the scans and the stats are plain loops here), in the launch order of cloud_build / cloud_query of mpmvs_cloud.hip and with
 // buffers of exactly their sizes, against the brute-force statement: random clouds with non-finite and far-away points, 70 000
 // one-point cells, a full cell of duplicates, the cell-border lattice, and points on multiples of the radius with and without
 // a jitter of 1e-5 radius at 40 random radii and offsets; each with binned queries, with caller order and without out_idx.

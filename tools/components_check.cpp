@@ -1,6 +1,6 @@
 // components_check.cpp -- the connected components of csrc/pm_components.hpp replayed on the host through the header's own
 // __host__ __device__ code (the grid build and the binning of pm_cloud.hpp, then cc_init_one, cc_hook_one, cc_flatten_one,
-// cc_count_one and cc_gather_one per thread), with buffers of exactly the sizes mpmvs_cloud_components of mpmvs_api.hip gives them,
+// cc_count_one and cc_gather_one per thread), with buffers of exactly the sizes mpmvs_cloud_components of mpmvs_cloud.hip gives them,
 // against a plain union-find over brute-force adjacency written out below.  The hook pass is replayed twice:
 //   by threads  thread by thread in a scrambled order (the blocks ascending or descending, with and without the binning);
 //   by edges    all unions (i, j) of all threads are collected, shuffled and applied one by one through cc_union, the two ends in

@@ -1,5 +1,5 @@
 // fuse_lists_check.cpp -- the rules a depth-map fusion call's arguments must keep before anything touches the device
-// (csrc/pm_fusion_host.hpp, fuse_check_request; FuseRun::run of mpmvs_api.hip calls it first) against a table of requests and
+// (csrc/pm_fusion_host.hpp, fuse_check_request; FuseRun::run of mpmvs_fusion.hip calls it first) against a table of requests and
 // the codes they must end with: every rule broken alone, the accepted ends of each range, the track bound with and without
 // tracks, and requests with two faults that pin the precedence -1 before -2 before -3.  A host program, so that it runs under
 // the sanitizers without a GPU:

@@ -1,7 +1,7 @@
 // knn_check.cpp -- the k-nearest-neighbour search of csrc/pm_knn.hpp replayed on the host, thread by thread in a scrambled order,
 // through the header's own __host__ __device__ code (the grid build and the query binning of pm_cloud.hpp, then knn_list_one and
 // knn_reduce_one per thread for every list size K), with buffers of exactly the sizes mpmvs_cloud_knn and mpmvs_cloud_outliers of
-// mpmvs_api.hip give them, against a plain sort of all candidates written out below.
+// mpmvs_cloud.hip give them, against a plain sort of all candidates written out below.
 // A host program, so that it runs under the sanitizers without a GPU:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //         -Imp-mvs_amd/csrc -o build/knn_check tools/knn_check.cpp && build/knn_check

@@ -1,6 +1,6 @@
 // normals_check.cpp -- the normal estimation of csrc/pm_normals.hpp replayed on the host, thread by thread in a scrambled order,
 // through the header's own __host__ __device__ code (the grid build and the query binning of pm_cloud.hpp, then normal_one<K> per
-// thread for every list size K), with buffers of exactly the sizes mpmvs_cloud_normals of mpmvs_api.hip gives them, against the loop
+// thread for every list size K), with buffers of exactly the sizes mpmvs_cloud_normals of mpmvs_cloud.hip gives them, against the loop
 // of include/mpmvs.h written out below on its own: a plain sort of all candidates, the matrix and V as arrays.
 // A host program, so that it runs under the sanitizers without a GPU:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \

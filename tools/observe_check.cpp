@@ -1,6 +1,6 @@
 // observe_check.cpp -- the three passes of csrc/pm_observe.hpp replayed on the host, thread by thread in a scrambled order, through
 // the header's own __host__ __device__ code (the face and pixel rule and the per-thread body of every kernel), in the launch order of
-// observer_create_device / observer_classify_chunk of mpmvs_api.hip and with buffers of exactly their sizes (Zc for a chunk of
+// observer_create_device / observer_classify_chunk of mpmvs_cloud.hip and with buffers of exactly their sizes (Zc for a chunk of
 // kObserveChunk scanners, Zn for all of them), against a plain-loop statement of the contract written out on
 // its own: random scans and queries with non-finite, far-away and on-the-scanner points, the direction lattice with its ties and
 // the clamp at x == R, R = 1, a window larger than the face, an owner per point, more scanners than a chunk, and 70 001 points in

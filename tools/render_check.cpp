@@ -1,6 +1,6 @@
 // render_check.cpp -- the three passes of csrc/pm_render.hpp replayed on the host, thread by thread in a scrambled order, through
 // the header's own __host__ __device__ code (the projection, the in-view test and the per-thread body of every kernel), in the
-// launch order of cloud_render_chunk of mpmvs_api.hip and with buffers of exactly its sizes (the views of a chunk behind one
+// launch order of cloud_render_chunk of mpmvs_cloud.hip and with buffers of exactly its sizes (the views of a chunk behind one
 // another, chunks of kRenderChunk views), against a plain-loop statement of the contract: random clouds
 // with non-finite, far-away and behind-the-camera points in views of different sizes, more views than a chunk, a 1 x 1 view, the
 // image-border values, the visibility threshold, and a window larger than the image; each with all, some and no index maps.

@@ -1,5 +1,5 @@
 // track_sink_check.cpp -- the growing host arrays of the fusion's tracks (csrc/pm_tracks_host.hpp, TrackSink) driven the way
-// FuseRun::ship_tracks of mpmvs_api.hip drives them -- per image reserve(points, entries), a copy of exactly that many offsets and entries to
+// FuseRun::ship_tracks of mpmvs_fusion.hip drives them -- per image reserve(points, entries), a copy of exactly that many offsets and entries to
 // the tails, commit, and finish at the end -- against plain vectors: images with no points, with one point, with many, entry
 // counts that force every array to be moved several times, an empty result, a sink dropped without finish(), and a commit that
 // does not continue the arrays.  A host program, so that it runs under the sanitizers without a GPU:
