@@ -826,6 +826,85 @@ int mpmvs_align_plane_solve(const long long sums[38], const double frame[4], int
 int mpmvs_align_plane_icp(mpmvs_align* h, float radius, int with_scale, int max_iter, double eps, double M_inout[12], long long* iters,
                           long long* inliers, double* rmse_plane, double* rmse_point);
 
+/* ---- surface: TSDF volume and marching tetrahedra (mp-mvs_amd/mesh.py, tools/mesh_ply.py) --- */
+/* Depth maps to a triangle mesh: the maps are integrated into a dense truncated-signed-distance volume, and the zero level set is
+ * extracted by marching tetrahedra on the Kuhn split of every cell (mp-mvs_amd/csrc/pm_tsdf.hpp).  Both calls
+ * are DEFINED BY EQUIVALENCE with the plain loops below, bit for bit and independent of scheduling.
+ *
+ * THE VOLUME is a dense lattice of dims = (nx, ny, nz) sample points, x fastest: voxel (i, j, k) has the linear index
+ * (k*ny + j)*nx + i and the position P_a = (float)((double)origin[a] + (double)i_a * (double)voxel) along axis a.  Per voxel the
+ * handle keeps sum (fp32), weight (int32) and, with colour, four uint32: the B, G, R sums and their count.  A fresh handle is all
+ * zero.  mpmvs_tsdf_create touches no device: the handle opens `device` with the first get, set, integrate or mesh call that passes
+ * its argument checks (-100 from that call if it cannot).  Limits: every dim >= 1, n_vox <= 2^30 (-3), origin, voxel and trunc
+ * finite, voxel and trunc > 0, the far corner of the lattice finite in fp32, device >= 0.
+ *
+ * mpmvs_tsdf_integrate, fp32 throughout, no contraction, correctly rounded quotients.  For every voxel, the views in call order --
+ * successive calls continue the same sums, so two calls give the bits of one call with the concatenated view list -- and per view
+ * with camera c (K, R, t row-major, W = c.width, H = c.height; C, depth_min, depth_max unused):
+ *   1. xc = ((R[0]*Px + R[1]*Py) + R[2]*Pz) + t[0]; yc and z likewise from rows 1 and 2 of R and t[1], t[2].
+ *   2. Skip unless z > 0.
+ *   3. fu = ((K[0]*xc)/z + K[2]) + 0.5f and fv = ((K[4]*yc)/z + K[5]) + 0.5f.
+ *   4. Skip unless fu >= 0 && fu < (float)W && fv >= 0 && fv < (float)H (a comparison with a NaN is false).
+ *   5. ix = (int)floorf(fu), iy = (int)floorf(fv);  6. d = depth[iy*W + ix].
+ *   7. Skip unless d is finite and d > 0.   8. s = d - z.   9. Skip if s < -trunc.
+ *   10. sum += fminf(1.0f, s / trunc) and weight += 1.
+ *   11. With colour, and only if also s <= trunc: the pixel's three bytes are added to the B, G, R sums and 1 to the count; a grey
+ *       image (color_channels == 1) adds its byte to all three.
+ * depths[v] holds H*W floats, colors[v] H*W*color_channels bytes, tightly packed; views may differ in size.  colors is NULL iff the
+ * volume has no colour.  n_views == 0 returns 0 and touches nothing.  Blocks until done.
+ * Errors: -2 = a NULL handle, n_views < 0, colours given to a volume without colour or missing for one with colour, color_channels
+ * not 1 or 3 when colours are given, NULL cams or depths, a NULL depths[v] or colors[v], a non-positive width or height; -3 = a width
+ * or height above 2^24, a view of more than 2^31 - 1 pixels, more than 2^23 views integrated over the handle's life (so that the
+ * colour sums cannot overflow); -100 = HIP failure.  All but -100 are found before the device is touched.
+ *
+ * mpmvs_tsdf_get copies the volume out (color4 may be NULL), mpmvs_tsdf_set replaces it (tests, and volumes computed elsewhere); with
+ * colour a NULL color4 in set clears the colour sums.  Weights may be anything: a negative weight is never valid.  -2 = a NULL handle,
+ * sum or weight, or a color4 for a volume without colour.
+ *
+ * mpmvs_tsdf_mesh(min_weight):
+ *   CORNERS.  A corner (voxel) is VALID iff weight >= min_weight, min_weight >= 1; its value is f = sum / (float)weight; it is
+ *   INSIDE iff f < 0 (exact zero and NaN are outside).
+ *   TETRAHEDRA.  Cell (i, j, k), i < nx-1, j < ny-1, k < nz-1, is cut into six tetrahedra, one per permutation (a, b, c) of the axes,
+ *   in lexicographic order xyz, xzy, yxz, yzx, zxy, zyx, with the vertices v0 = corner 000, v1 = v0 + e_a, v2 = v1 + e_b,
+ *   v3 = corner 111.  A tetrahedron EMITS iff its four corners are valid and it has 1, 2 or 3 inside corners.
+ *   EDGES AND VERTICES.  Mesh vertices sit on lattice edges (A, B), B = A + off, off one of the 7 SLOTS 100, 010, 001, 110, 101, 011,
+ *   111 (as x y z); the edge is owned by voxel A.  A vertex exists iff at least one emitted triangle uses its edge.  Vertices are
+ *   numbered by owner linear index ascending, then slot ascending.  Position: t = fA / (fA - fB), p_a = PA_a + t * (PB_a - PA_a),
+ *   always from A to B, so every tetrahedron that uses the edge sees the same vertex.  Colour per channel from the corner means
+ *   m = (float)sum_c / (float)count where count > 0: both corners have a mean: mA + t*(mB - mA); one has: that mean; neither: 128.
+ *   The byte is (int)(val + 0.5f) (saturated to 0..255 and 0 for a NaN, which cannot arise while 0 <= t <= 1), written R, G, B.
+ *   TRIANGLES, ordered by cell linear index, then tetrahedron 0..5, then triangle 0 / 1.  With e(p, q) the vertex on the edge
+ *   between tetrahedron vertices p and q, and inside / outside corners listed in tetrahedron vertex order:
+ *     1 inside {a}, outside o1 < o2 < o3:   (e(a,o1), e(a,o2), e(a,o3))
+ *     3 inside a1 < a2 < a3, outside {o}:   (e(a1,o), e(a2,o), e(a3,o))
+ *     2 inside a < b, outside c < d:        (e(a,c), e(a,d), e(b,d)) and (e(a,c), e(b,d), e(b,c))
+ *   ORIENTATION.  Seen from outside (the positive side, where the cameras are) a triangle is counter-clockwise.  This is decided
+ *   combinatorially per (tetrahedron, case): the winding for which (p1-p0) x (p2-p0) points from the mean of the inside corners to
+ *   the mean of the outside corners WHEN EVERY VERTEX IS PUT AT THE MIDPOINT OF ITS EDGE; if the listed winding is the other one,
+ *   the triangle's last two vertices are swapped.  The surface is combinatorially manifold and consistently oriented by
+ *   construction; where invalid corners punch holes it has a boundary.
+ *   ANCHOR: the 10 x 9 x 8 lattice with unit spacing, every corner valid, f = (float)(sqrt((i-4.3)^2 + (j-3.9)^2 + (k-3.4)^2) - 2.7)
+ *   evaluated in fp64, gives 410 vertices, 1224 edges, 816 triangles.
+ * Returns the vertex count; *out_xyz (n x 3 floats), *out_rgb (n x 3 bytes; NULL iff the volume has no colour), *out_tri (*n_tri x 3
+ * int32) receive buffers to release with mpmvs_free.  An empty result returns 0 with *n_tri = 0 and all buffers NULL: a volume with a
+ * dimension of 1 has no cell and launches nothing; a volume with nothing valid or without a sign change is found empty after the mark
+ * and scan passes and launches no further pass.  On failure no buffer is allocated and the outputs are not written.
+ * Errors: -2 = a NULL handle, out_xyz, out_tri or n_tri, min_weight < 1, out_rgb NULL for a volume with colour or given for one
+ * without; -3 = more than 2^31 - 1 vertices or triangles (counted in 64 bits before anything is emitted; the handle stays usable);
+ * -100 = HIP failure. */
+typedef struct mpmvs_tsdf mpmvs_tsdf;
+int mpmvs_tsdf_create(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, mpmvs_tsdf** h);
+int mpmvs_tsdf_integrate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, const float* const* depths,
+                         const unsigned char* const* colors /* NULL iff the volume has no colour */, int color_channels /* 1 or 3 (B,G,R) */);
+int mpmvs_tsdf_get(mpmvs_tsdf* h, float* sum /* n_vox */, int32_t* weight /* n_vox */, uint32_t* color4 /* n_vox x 4: B G R sums, count; may be NULL */);
+int mpmvs_tsdf_set(mpmvs_tsdf* h, const float* sum, const int32_t* weight, const uint32_t* color4);
+long long mpmvs_tsdf_mesh(mpmvs_tsdf* h, int min_weight, float** out_xyz, unsigned char** out_rgb /* NULL iff no colour */, int32_t** out_tri,
+                          long long* n_tri);
+/* device ms (HIP events): ms[0] the kernels of the last integrate call, all chunks added up; ms[1..4] mark + count, scan, vertices,
+ * triangles of the last mesh call (0 for a pass that did not run) */
+int mpmvs_tsdf_pass_ms(const mpmvs_tsdf* h, float ms[5]);
+void mpmvs_tsdf_destroy(mpmvs_tsdf* h);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

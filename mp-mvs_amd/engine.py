@@ -107,6 +107,14 @@ _EXTRA = {
                                     C.POINTER(C.c_double)]),
     "align_plane_icp": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # TSDF volume and marching tetrahedra (mesh.py: Volume)
+    "tsdf_create": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int), C.c_float, C.c_int, C.POINTER(C.c_void_p)]),
+    "tsdf_integrate": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int]),
+    "tsdf_get": (C.c_int, [_P, _P, _P, _P]),
+    "tsdf_set": (C.c_int, [_P, _P, _P, _P]),
+    "tsdf_mesh": (C.c_longlong, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
+    "tsdf_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "tsdf_destroy": (None, [_P]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

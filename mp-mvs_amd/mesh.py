@@ -1,0 +1,201 @@
+"""Depth maps to a triangle mesh on the GPU: a dense TSDF volume and marching tetrahedra on the Kuhn split of its cells
+(mpmvs_tsdf_*, csrc/pm_tsdf.hpp, csrc/mpmvs_mesh.hip; contract: include/mpmvs.h), and the PLY files of a
+mesh.  Both device calls are bit for bit their plain-loop statements (tests/tsdf_common.py has them in numpy).  The work runs on
+the GPU; there is no CPU path."""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi, engine
+
+
+def _raise(f, what, rc):
+    msg = f["last_error"](None)
+    text = f"mpmvs_{what} failed ({rc}): " + (msg.decode() if msg else "")
+    raise (ValueError if rc in (-2, -3) else RuntimeError)(text)
+
+
+class Volume:
+    """mpmvs_tsdf: a lattice of dims = (nx, ny, nz) sample points, x fastest, voxel (i, j, k) at origin + (i, j, k) * voxel, with
+    the truncation distance `trunc`; per voxel the sum of the truncated signed distances (float32), the number of observations
+    (int32) and, with color=True, the B, G, R sums and their count (uint32 x 4).  Dense on purpose: every voxel of the box exists.
+    The device is opened by the first call that needs it."""
+
+    def __init__(self, origin, voxel, dims, trunc, color=False, device=0):
+        _, self._f = engine.load()
+        self._h = None
+        o = np.ascontiguousarray(origin, np.float32)
+        d = np.ascontiguousarray(dims, np.int32)
+        if o.shape != (3,) or d.shape != (3,):
+            raise ValueError(f"need an origin and dims of 3 numbers each, got {o.shape} and {d.shape}")
+        h = C.c_void_p()
+        rc = self._f["tsdf_create"](int(device), o.ctypes.data_as(C.POINTER(C.c_float)), float(voxel), d.ctypes.data_as(C.POINTER(C.c_int)), float(trunc),
+                                    1 if color else 0, C.byref(h))
+        if rc != 0:
+            _raise(self._f, "tsdf_create", rc)
+        self._h = h
+        self.origin, self.voxel, self.trunc, self.color, self.device = o, float(np.float32(voxel)), float(np.float32(trunc)), bool(color), int(device)
+        self.dims = tuple(int(v) for v in d)
+        self.n_vox = self.dims[0] * self.dims[1] * self.dims[2]
+
+    def close(self):
+        if self._h is not None:
+            self._f["tsdf_destroy"](self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def integrate(self, cams, depths, colors=None):
+        """mpmvs_tsdf_integrate: the views in order; cams: _abi.Camera (width and height give the maps' sizes), depths: float32
+        [H, W] each, colors (iff the volume has colour): uint8 [H, W] (grey) or [H, W, 3] (B, G, R), all of one kind.  Successive
+        calls continue the same sums."""
+        cams = list(cams)
+        n = len(cams)
+        if len(depths) != n or (colors is not None and len(colors) != n):
+            raise ValueError("need one depth map (and one colour image) per camera")
+        ds = [np.ascontiguousarray(d, np.float32) for d in depths]
+        for c, d in zip(cams, ds):
+            if d.shape != (int(c.height), int(c.width)):
+                raise ValueError(f"a depth map of shape {d.shape} for a camera of {int(c.height)} x {int(c.width)}")
+        cs, channels = None, 0
+        if colors is not None:
+            cs = [np.ascontiguousarray(c, np.uint8) for c in colors]
+            channels = 3 if n and cs[0].ndim == 3 else 1
+            for c, d in zip(cs, ds):
+                if c.shape != (d.shape + (3,) if channels == 3 else d.shape):
+                    raise ValueError(f"a colour image of shape {c.shape} for a depth map of shape {d.shape} ({channels} channel(s))")
+        arr = (_abi.Camera * max(n, 1))(*cams)
+        dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in ds])
+        cp = (C.c_void_p * max(n, 1))(*[c.ctypes.data for c in cs]) if cs is not None else None
+        rc = self._f["tsdf_integrate"](self._h, n, arr, dp, cp, channels)
+        if rc != 0:
+            _raise(self._f, "tsdf_integrate", rc)
+
+    def get(self):
+        """{"sum": float32 [nz, ny, nx], "weight": int32 [nz, ny, nx]} and, with colour, "color": uint32 [nz, ny, nx, 4]"""
+        nx, ny, nz = self.dims
+        out = {"sum": np.empty((nz, ny, nx), np.float32), "weight": np.empty((nz, ny, nx), np.int32)}
+        if self.color:
+            out["color"] = np.empty((nz, ny, nx, 4), np.uint32)
+        rc = self._f["tsdf_get"](self._h, out["sum"].ctypes.data, out["weight"].ctypes.data, out["color"].ctypes.data if self.color else None)
+        if rc != 0:
+            _raise(self._f, "tsdf_get", rc)
+        return out
+
+    def set(self, sum, weight, color=None):
+        """replaces the volume; with colour, color=None clears the colour sums"""
+        nx, ny, nz = self.dims
+        s, w = np.ascontiguousarray(sum, np.float32), np.ascontiguousarray(weight, np.int32)
+        c = np.ascontiguousarray(color, np.uint32) if color is not None else None
+        if s.size != self.n_vox or w.size != self.n_vox or (c is not None and c.size != 4 * self.n_vox):
+            raise ValueError(f"need {self.n_vox} sums and weights (and four colour entries per voxel)")
+        rc = self._f["tsdf_set"](self._h, s.ctypes.data, w.ctypes.data, c.ctypes.data if c is not None else None)
+        if rc != 0:
+            _raise(self._f, "tsdf_set", rc)
+
+    def mesh(self, min_weight=1):
+        """mpmvs_tsdf_mesh -> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3]}: the zero level set of
+        sum / weight over the voxels with weight >= min_weight, counter-clockwise seen from the positive side"""
+        lib, _ = engine.load()
+        lib.mpmvs_free.argtypes = [C.c_void_p]
+        lib.mpmvs_free.restype = None
+        px, pc, pt, nt = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_longlong(0)
+        nv = self._f["tsdf_mesh"](self._h, int(min_weight), C.byref(px), C.byref(pc) if self.color else None, C.byref(pt), C.byref(nt))
+        if nv < 0:
+            _raise(self._f, "tsdf_mesh", nv)
+        try:
+            xyz = np.ctypeslib.as_array(C.cast(px, C.POINTER(C.c_float)), (nv, 3)).copy() if nv else np.zeros((0, 3), np.float32)
+            tri = np.ctypeslib.as_array(C.cast(pt, C.POINTER(C.c_int32)), (nt.value, 3)).copy() if nt.value else np.zeros((0, 3), np.int32)
+            rgb = None
+            if self.color:
+                rgb = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_uint8)), (nv, 3)).copy() if nv else np.zeros((0, 3), np.uint8)
+        finally:
+            for p in (px, pc, pt):
+                if p.value:
+                    lib.mpmvs_free(p)
+        return {"xyz": xyz, "rgb": rgb, "tri": tri}
+
+    def pass_ms(self):
+        """device ms: {"integrate"} of the last integrate call, {"mark", "scan", "vertices", "triangles"} of the last mesh call"""
+        ms = (C.c_float * 5)()
+        rc = self._f["tsdf_pass_ms"](self._h, ms)
+        if rc != 0:
+            _raise(self._f, "tsdf_pass_ms", rc)
+        return dict(zip(("integrate", "mark", "scan", "vertices", "triangles"), (float(v) for v in ms)))
+
+
+def write_ply_mesh(path, xyz, tri, rgb=None):
+    """binary little-endian PLY: vertex x y z (float) and, with rgb, red green blue (uchar); face: list uchar int vertex_indices"""
+    xyz, tri = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3), np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}", "property float x", "property float y", "property float z"]
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        if len(rgb) != len(xyz):
+            raise ValueError(f"{len(rgb)} colours for {len(xyz)} vertices")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(xyz)):
+        raise ValueError("a triangle names a vertex that does not exist")
+    head += [f"element face {len(tri)}", "property list uchar int vertex_indices", "end_header"]
+    v = np.empty(len(xyz), np.dtype(fields))
+    for a, name in enumerate("xyz"):
+        v[name] = xyz[:, a]
+    if rgb is not None:
+        for a, name in enumerate(("red", "green", "blue")):
+            v[name] = rgb[:, a]
+    f = np.empty(len(tri), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    f["n"] = 3
+    f["v"] = tri
+    with open(path, "wb") as out:
+        out.write(("\n".join(head) + "\n").encode("ascii"))
+        out.write(v.tobytes())
+        out.write(f.tobytes())
+
+
+def read_ply_mesh(path):
+    """what write_ply_mesh writes -> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3]}.  Binary
+    little-endian files with float x y z (and uchar red green blue) per vertex and triangles only; anything else is a ValueError."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = [ln.split() for ln in data[:end].decode("ascii", "replace").splitlines()[1:] if ln.strip() and ln.split()[0] != "comment"]
+    if not lines or lines[0] != ["format", "binary_little_endian", "1.0"]:
+        raise ValueError(f"{path}: only binary_little_endian 1.0 mesh files are read")
+    elements = []
+    for w in lines[1:]:
+        if w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements:
+            elements[-1][2].append(tuple(w[1:]))
+        else:
+            raise ValueError(f"{path}: unknown header line {' '.join(w)!r}")
+    plain = [("float", "x"), ("float", "y"), ("float", "z")]
+    colour = [("uchar", "red"), ("uchar", "green"), ("uchar", "blue")]
+    if len(elements) != 2 or elements[0][0] != "vertex" or elements[1][0] != "face" or elements[0][2] not in (plain, plain + colour) \
+            or elements[1][2] != [("list", "uchar", "int", "vertex_indices")]:
+        raise ValueError(f"{path}: not the layout of write_ply_mesh")
+    nv, nf, has_rgb = elements[0][1], elements[1][1], elements[0][2] != plain
+    vdt = np.dtype([("xyz", "<f4", (3,))] + ([("rgb", "u1", (3,))] if has_rgb else []))
+    fdt = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+    at = nl + 1
+    if at + nv * vdt.itemsize + nf * fdt.itemsize > len(data):
+        raise ValueError(f"{path}: truncated body")
+    v = np.frombuffer(data, vdt, nv, at)
+    f = np.frombuffer(data, fdt, nf, at + nv * vdt.itemsize)
+    if nf and (f["n"] != 3).any():
+        raise ValueError(f"{path}: a face that is no triangle")
+    return {"xyz": v["xyz"].copy().reshape(-1, 3), "rgb": v["rgb"].copy().reshape(-1, 3) if has_rgb else None, "tri": f["v"].copy().reshape(-1, 3)}

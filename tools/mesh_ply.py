@@ -1,0 +1,142 @@
+#!/usr/bin/env python3
+"""A triangle mesh from the depth maps of a dense folder: the maps are integrated into a dense TSDF volume on the GPU and the zero
+level set is extracted by marching tetrahedra (mp-mvs_amd/mesh.py; csrc/pm_tsdf.hpp).
+
+    python tools/mesh_ply.py --dense_folder D --output mesh.ply --voxel V [--trunc 4V] [--min_weight 2]
+                             [--bbox x0 y0 z0 x1 y1 z1 | --bbox_from MPMVS_model.ply --bbox_percentile 1]
+
+Reads cams/<id>_cam.txt, images/<id>.* and <result_folder>/2333_<id>/depths.dmb (result_folder: D/MPMVS) with the readers of
+mp-mvs_amd/hostlib.py; a camera is rescaled to the size of its depth map as the fusion does, and the image is sampled at the map's
+pixels for the colours (--no_color: a volume without colour, 8 instead of 24 bytes per voxel).  The views go through
+mpmvs_tsdf_integrate in batches of --batch, so only one batch of maps is in host memory at a time.  The box is --bbox, or the
+--bbox_percentile .. 100 - --bbox_percentile range per axis of the points of --bbox_from (default: <result_folder>/MPMVS_model.ply),
+grown by the truncation distance.  The volume is dense: (box / voxel)^3 voxels, refused above --max_voxels.
+--trunc (4 voxels) and --min_weight (2) are untuned starting values, not tuned on any real scene.
+Prints one JSON line: n_vox, views, vertices, triangles, device ms per pass, wall seconds."""
+import argparse
+import glob
+import importlib
+import json
+import math
+import os
+import re
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def result_views(root):
+    out = []
+    for d in glob.glob(os.path.join(root, "2333_*")):
+        m = re.fullmatch(r"2333_(\d{8})", os.path.basename(d))
+        path = os.path.join(d, "depths.dmb")
+        if m and os.path.isfile(path):
+            out.append((int(m.group(1)), path))
+    return sorted(out)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--dense_folder", required=True)
+    ap.add_argument("--result_folder")
+    ap.add_argument("--output", required=True)
+    ap.add_argument("--voxel", type=float, required=True, help="lattice spacing in scene units")
+    ap.add_argument("--trunc", type=float, help="truncation distance; default 4 voxels, an untuned starting value")
+    ap.add_argument("--min_weight", type=int, default=2, help="observations a lattice point needs to take part; 2 is an untuned starting value")
+    ap.add_argument("--bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--bbox_from", help="a PLY whose points give the box (default: <result_folder>/MPMVS_model.ply)")
+    ap.add_argument("--bbox_percentile", type=float, default=1.0)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--no_color", action="store_true")
+    ap.add_argument("--max_voxels", type=int, default=1 << 30)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    if not (math.isfinite(args.voxel) and args.voxel > 0):
+        raise SystemExit("--voxel must be finite and positive")
+    trunc = 4.0 * args.voxel if args.trunc is None else args.trunc
+    if not (math.isfinite(trunc) and trunc > 0):
+        raise SystemExit("--trunc must be finite and positive")
+    if args.min_weight < 1 or args.batch < 1:
+        raise SystemExit("--min_weight and --batch must be at least 1")
+    if args.bbox and args.bbox_from:
+        raise SystemExit("give --bbox or --bbox_from, not both")
+    root = args.result_folder or os.path.join(args.dense_folder, "MPMVS")
+    views = result_views(root)
+    if not views:
+        raise SystemExit(f"no 2333_<id>/depths.dmb under {root}")
+
+    import torch  # noqa: F401  (the HIP runtime torch bundles, before our library: engine.load)
+    hostlib = importlib.import_module("mp-mvs_amd.hostlib")
+    depthmap = importlib.import_module("mp-mvs_amd.depthmap")
+    cloud = importlib.import_module("mp-mvs_amd.cloud")
+    mesh = importlib.import_module("mp-mvs_amd.mesh")
+
+    t0 = time.perf_counter()
+    if args.bbox:
+        lo, hi = np.array(args.bbox[:3], np.float64), np.array(args.bbox[3:], np.float64)
+    else:
+        path = args.bbox_from or os.path.join(root, "MPMVS_model.ply")
+        if not os.path.isfile(path):
+            raise SystemExit(f"no --bbox, and no point cloud at {path} to take the box from")
+        if not 0.0 <= args.bbox_percentile < 50.0:
+            raise SystemExit("--bbox_percentile must lie in [0, 50)")
+        pts = cloud.read_ply(path)["xyz"]
+        pts = pts[np.isfinite(pts).all(1)]
+        if not len(pts):
+            raise SystemExit(f"{path}: no finite point")
+        lo = np.percentile(pts, args.bbox_percentile, axis=0) - trunc
+        hi = np.percentile(pts, 100.0 - args.bbox_percentile, axis=0) + trunc
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+        raise SystemExit(f"the box {lo.tolist()} .. {hi.tolist()} is empty or not finite")
+    dims = [int(math.ceil((hi[a] - lo[a]) / args.voxel)) + 1 for a in range(3)]
+    n_vox = dims[0] * dims[1] * dims[2]
+    if n_vox > min(args.max_voxels, 1 << 30):
+        raise SystemExit(f"{dims[0]} x {dims[1]} x {dims[2]} = {n_vox} voxels exceed --max_voxels {min(args.max_voxels, 1 << 30)}: raise --voxel or shrink the box")
+
+    def load(vid, path):
+        d = hostlib.read_dmb(path)
+        if d.ndim != 2:
+            raise SystemExit(f"{path}: {d.shape[2]} channels, a depth map has one")
+        files = sorted(glob.glob(os.path.join(args.dense_folder, "images", f"{vid:08d}.*")))
+        if not files:
+            raise SystemExit(f"no image of view {vid:08d} under {args.dense_folder}/images")
+        img = hostlib.read_image(files[0], 3)
+        ih, iw = img.shape[:2]
+        H, W = d.shape
+        cam = depthmap.camera_at_size(hostlib.read_camera(os.path.join(args.dense_folder, "cams", f"{vid:08d}_cam.txt")), iw, ih, W, H)
+        if (ih, iw) != (H, W):   # the image at the map's pixel centres, nearest
+            ys = np.minimum(((np.arange(H) + 0.5) * ih / H).astype(np.int64), ih - 1)
+            xs = np.minimum(((np.arange(W) + 0.5) * iw / W).astype(np.int64), iw - 1)
+            img = img[ys][:, xs]
+        return cam, d, np.ascontiguousarray(img)
+
+    device_ms = {"integrate": 0.0}
+    try:
+        with mesh.Volume(lo.astype(np.float32), args.voxel, dims, trunc, color=not args.no_color, device=args.device) as vol:
+            for b in range(0, len(views), args.batch):
+                cams, depths, images = zip(*(load(vid, path) for vid, path in views[b:b + args.batch]))
+                vol.integrate(cams, depths, None if args.no_color else images)
+                device_ms["integrate"] += vol.pass_ms()["integrate"]
+            t1 = time.perf_counter()
+            m = vol.mesh(args.min_weight)
+            ms = vol.pass_ms()
+            device_ms.update({k: ms[k] for k in ("mark", "scan", "vertices", "triangles")})
+    except (ValueError, OSError, RuntimeError) as e:
+        raise SystemExit(str(e)) from None
+    t2 = time.perf_counter()
+    mesh.write_ply_mesh(args.output, m["xyz"], m["tri"], m["rgb"])
+    t3 = time.perf_counter()
+    res = {"n_vox": n_vox, "dims": dims, "origin": [float(v) for v in lo.astype(np.float32)], "voxel": args.voxel, "trunc": trunc, "min_weight": args.min_weight,
+           "views": len(views), "vertices": int(len(m["xyz"])), "triangles": int(len(m["tri"])),
+           "device_ms": {k: round(v, 4) for k, v in device_ms.items()},
+           "seconds": {"integrate": round(t1 - t0, 4), "mesh": round(t2 - t1, 4), "write": round(t3 - t2, 4), "wall": round(t3 - t0, 4)}, "output": args.output}
+    print(json.dumps(res))
+    return res
+
+
+if __name__ == "__main__":
+    main()
