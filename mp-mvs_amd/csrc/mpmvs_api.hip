@@ -112,7 +112,7 @@ struct mpmvs_ctx {
 };
 
 #ifdef PM_DBG_WAVETIME
-static size_t kWaveTimeBytes(int W, int H) { return (size_t)16 * ((size_t)(W / 16 + 2) * (H / 8 + 8)) * 4 * 8; }
+static size_t kWaveTimeBytes(int W, int H) { return (size_t)16 * ((size_t)(W / 16 + 2) * (H / 8 + 8)) * pm::kWaveRecWords * 8; }
 #endif
 
 #define HIPCHK(ctx, expr)                                                                           \
@@ -520,7 +520,7 @@ static int finish_views(mpmvs_ctx* c) {
         if (!rc && (pool_malloc(&c->d_band, band_bytes) != hipSuccess || hipMemsetAsync(c->d_band, 0, band_bytes, c->stream) != hipSuccess)) rc = -100;
     }
 #ifdef PM_DBG_WAVETIME
-    // room for 16 launches of one wave per 64 pixels of a colour, 4 x u64 each (generous: blocks overhang the image border)
+    // room for 16 launches of one wave per 64 pixels of a colour, kWaveRecWords x u64 each (generous: blocks overhang the image border)
     if (!rc && (hipMalloc(&c->S.wavetime, kWaveTimeBytes(c->W, c->H)) != hipSuccess || hipMemsetAsync(c->S.wavetime, 0, kWaveTimeBytes(c->W, c->H), c->stream) != hipSuccess)) rc = -100;
 #endif
     if (rc) return upload_failed(c, "allocation of the per-pixel state failed");
@@ -895,7 +895,7 @@ int mpmvs_set_prior(mpmvs_ctx* c, const void* prior4, const void* mask) {
 // launches
 // ---------------------------------------------------------------------------
 #ifdef PM_DBG_WAVETIME
-// measurement builds: the per-wave records of the last <= 16 update launches ([launch % 16][wave][4] u64; pm_kernels.hpp, WaveTimer)
+// measurement builds: the per-wave records of the last <= 16 update launches ([launch % 16][wave][kWaveRecWords] u64; pm_kernels.hpp, WaveTimer)
 extern "C" long mpmvs_dbg_wavetime(mpmvs_ctx* c, void* out, size_t cap_bytes) {
     if (!c || !c->S.wavetime) return -1;
     if (enter_device(c->device) != hipSuccess) return -1;

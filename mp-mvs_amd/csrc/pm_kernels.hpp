@@ -235,16 +235,57 @@ PM_DEV float prior_term(float depth_diff, float angle_cos, float two_ds2, float 
         return prior_term_body(depth_diff, angle_cos, two_ds2, two_as2);
 }
 
+// The points of update_body where a measurement build stamps the time (WaveTimer below; the callback is empty in every other build).
+enum Stamp {
+    kStampFirstEval,   // the prologue is over: the first NCC evaluation of phase A starts
+    kStampPhaseA,      // phase A is over: every candidate's cost against every view is known
+    kStampWeighted,    // view weights drawn, weighted candidate costs formed, min_idx known
+    kStampCurrent,     // the current plane is evaluated under the new weights
+    kStampDealBegin,   // acceptance of the best neighbour, draws and candidate planes done: in front of the first dealt round
+    kStampDealEnd,     // behind the last dealt round
+    kStampSections,
+    kStampRound = kStampSections,   // top of a dealt round
+    kStampPublished,                // behind the barrier that follows the publishing
+    kStampEvaluated,                // behind the barrier that follows the evaluation
+    kStampCollected                 // behind the barrier that follows the collecting
+};
 #ifdef PM_DBG_WAVETIME
 // Measurement builds only: every wave of the update kernel records when it entered the kernel, when its block's dependencies were met
 // (ready), when it started its first phase-A evaluation (first_eval: ready .. first_eval is the block's prologue -- reference tile,
-// candidate tile, search, weight records) and when it ended (s_memrealtime, 100 MHz) and where it ran (HW_ID: SIMD / CU / SH / SE, XCC_ID), 4 x u64 per wave at
+// candidate tile, search, weight records) and when it ended (s_memrealtime, 100 MHz) and where it ran (HW_ID: SIMD / CU / SH / SE, XCC_ID), the first 4 u64 of the wave's record at
 // [launch id % 16][raster block][wave]; tools/wave_timeline.py turns the records into the slot occupancy over time.
+//
+// The second half of the record (4 more u64) splits the wave's life after the prologue into the sections of update_body (the stamp
+// points above, `Stamp`): the ticks from each section mark to the next as 32-bit fields, and -- accumulated over the dealt rounds --
+// the ticks between the top of a round and the barrier behind the owners' publishing, and between the barrier behind the evaluation
+// and the one behind the collecting: what a round spends OUTSIDE ncc_cost.  A section stamp first waits for the wave's outstanding
+// loads, LDS operations and stores (they belong to the section that issued them) and for its own result.
+constexpr int kWaveRecWords = 8;   // u64 per wave record (mpmvs_api.hip sizes the buffer with it, tools/wave_timeline.py reads it)
 struct WaveTimer {
     unsigned long long t_enter, t_ready, t_eval;
-    PM_DEV WaveTimer() { t_enter = t_ready = t_eval = __builtin_amdgcn_s_memrealtime(); }
+    unsigned long long t_mark[kStampSections], t_round;
+    unsigned publish, collect, rounds;
+    PM_DEV static unsigned long long now_drained() {
+        unsigned long long t;
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory");
+        return t;
+    }
+    PM_DEV WaveTimer() {
+        t_enter = t_ready = t_eval = t_round = __builtin_amdgcn_s_memrealtime();
+        for (int i = 0; i < kStampSections; ++i) t_mark[i] = 0;
+        publish = collect = rounds = 0;
+    }
     PM_DEV void ready() { t_ready = t_eval = __builtin_amdgcn_s_memrealtime(); }   // the block's dependencies are met: the update itself starts
-    PM_DEV void first_eval() { t_eval = __builtin_amdgcn_s_memrealtime(); }        // the prologue is over: the first NCC evaluation of phase A starts
+    PM_DEV void first_eval() { t_eval = t_mark[kStampFirstEval] = __builtin_amdgcn_s_memrealtime(); }
+    PM_DEV void stamp(int point) {   // `point` is a constant at every call
+        if (point == kStampFirstEval) return first_eval();
+        const unsigned long long t = now_drained();
+        if (point < kStampSections) t_mark[point] = t;
+        if (point == kStampRound) t_round = t, rounds += 1;
+        if (point == kStampPublished) publish += (unsigned)(t - t_round);
+        if (point == kStampEvaluated) t_round = t;
+        if (point == kStampCollected) collect += (unsigned)(t - t_round);
+    }
     PM_DEV void finish(unsigned long long* base, uint32_t launch, int b, int n_blocks) const {
         const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
         uint32_t hw, xcc;
@@ -252,7 +293,7 @@ struct WaveTimer {
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         if ((threadIdx.x & 63) == 0 && b >= 0) {
             const unsigned waves = (unsigned)n_blocks * (blockDim.x >> 6);
-            unsigned long long* rec = base + ((size_t)(launch & 15u) * waves + (unsigned)b * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 4;
+            unsigned long long* rec = base + ((size_t)(launch & 15u) * waves + (unsigned)b * (blockDim.x >> 6) + (threadIdx.x >> 6)) * kWaveRecWords;
             rec[0] = t_enter;
             rec[1] = t_end;
             unsigned long long prologue = t_eval - t_ready;   // ticks of 10 ns between "ready" and the first evaluation (0 for a wave without a pixel)
@@ -261,6 +302,13 @@ struct WaveTimer {
             unsigned long long waited = t_ready - t_enter;   // ticks of 10 ns between kernel entry and the start of the update (ticket, wait for the neighbours, barriers)
             waited = waited > 0xffffffull ? 0xffffffull : waited;
             rec[3] = ((unsigned long long)(unsigned)b << 32) | (waited << 8) | (threadIdx.x >> 6);
+            // sections (all zero for a wave without a pixel: it never reached the first stamp)
+            const auto span = [&](int from, int to) -> unsigned long long { return (unsigned)(t_mark[to] - t_mark[from]); };
+            const bool ran = t_mark[kStampDealEnd] != 0;
+            rec[4] = !ran ? 0ull : span(kStampFirstEval, kStampPhaseA) | (span(kStampPhaseA, kStampWeighted) << 32);
+            rec[5] = !ran ? 0ull : span(kStampWeighted, kStampCurrent) | (span(kStampCurrent, kStampDealBegin) << 32);
+            rec[6] = !ran ? 0ull : span(kStampDealBegin, kStampDealEnd) | ((unsigned long long)(unsigned)(t_end - t_mark[kStampDealEnd]) << 32);
+            rec[7] = (unsigned long long)(publish & 0xffffffu) | ((unsigned long long)(collect & 0xffffffu) << 24) | ((unsigned long long)(rounds & 0xffffu) << 48);
         }
     }
 };
@@ -277,10 +325,10 @@ struct WaveTimer {
 // holds that plane's photometric cost per view at this window scale -- phase B reads them instead of evaluating the plane again.
 // (At window scales 1 and 2 the reference tile could be staged as a compact half tile of the pass's colour: built in round 6, bit-exact,
 // 0-0.7 % on the scale-2 passes -- the prologue's 37 reads per pixel are not what scale 2 pays for, profiles/EXPERIMENTS.md 52.)
-// `wait_for_neighbours` is called before the block's first load, `first_evaluation` when the prologue is over (the stamp of the measurement builds, empty otherwise).
+// `wait_for_neighbours` is called before the block's first load, `stamp` at the points of `Stamp` (the measurement builds' clock, empty otherwise).
 template <bool GEOM, bool PRIOR, int MAXV, bool U8, int SCALE, class WAIT, class STAMP>
 PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs& a, int b, int parity, uint32_t launch, float thr, bool use_own, WAIT wait_for_neighbours,
-                        STAMP first_evaluation) {
+                        STAMP stamp) {
     constexpr int NT = kUpdThreads<U8, SCALE>, BW = kChkBlockW, BH = kChkBlockH<NT>;
     // gathers of two window columns ahead (ncc_core): always with the 8-byte texels; with the 16-byte ones where the variant
     // still has the 24 registers of a third column (8 views; more views spill 4 .. 81 registers around the evaluations)
@@ -298,6 +346,18 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     // registers instead of 215 and <geometric, 24 views, fp32 texels> spills 33 instead of 13; issued early, <geometric, 8 views, fp32
     // texels> spills 21 instead of 15.  Everywhere else the two orders allocate alike and the planes are loaded where they are used.
     constexpr bool kPlanesEarly = (U8 && SCALE == 2) || (GEOM && !U8 && MAXV > 8);
+    // Which variants form the weighted candidate costs candidate by candidate, one private-memory load and one wait per (candidate,
+    // weighted view), as all did until round 23: the planar prior with 9 .. 16 views.  Their 16 weights live in registers and are picked
+    // by a chain of selects; view by view (below) the compiler forms the chain's 15 scalar conditions at once and spills 5 (fp32
+    // texels) and 6 (fp16) scalar registers more than before.  And, in the build with 8-bit interpolation fractions only, the
+    // photometric variant of 25 .. 32 views with fp16 texels at scale 0: 21 spilled scalar registers instead of 8.  Everywhere else
+    // view by view allocates no worse (profiles/r23_kernel_resources.txt beside r23_kernel_resources_parent.txt).
+#ifdef PM_TEX_Q8
+    constexpr bool kQ8 = true;
+#else
+    constexpr bool kQ8 = false;
+#endif
+    constexpr bool kCostsByCandidate = (PRIOR && MAXV == 16) || (kQ8 && !GEOM && !PRIOR && MAXV == 32 && U8 && SCALE == 0);
     typedef Win<SCALE, BW, BH, kLdsXchgFloats<NT>> Wn;
     typedef CandTile<BW, BH> CT;
     static_assert(CT::floats <= kLdsWeightFloatsOf<NT>, "the candidate tile lives in the weight records' area until they are written");
@@ -393,7 +453,8 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     const int idx = y * W + x;
     Rng g = rng_make(a.seed, (uint32_t)idx, launch);
 
-    float cost_arr[8 * MAXV];
+    // [view][candidate]: the eight costs of a view lie side by side, so that the weighted sums below fetch them as one batch
+    alignas(16) float cost_arr[MAXV * 8];
     int cnt[MAXV];       // good count | bad count << 8   (ref .cu:834-845)
     float tmpw[MAXV];
     float probs[MAXV];
@@ -449,7 +510,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         plane_to_m(P, cand_pl[slot], m0, m1, m2);
         cand_m[3 * slot] = m0, cand_m[3 * slot + 1] = m1, cand_m[3 * slot + 2] = m2;
     }
-    first_evaluation();
+    stamp(kStampFirstEval);
     for (int v = 0; v < V; ++v) {
         int cn = 0;       // good count | bad count << 8   (ref .cu:834-845)
         float tw = 0.0f;
@@ -463,7 +524,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 c = ncc_cost<U8, SCALE, kDeep, NT>(P.views[v], rw, x, y, m0, m1, m2);
             else
                 c = (slot == 0 && v == 0) ? 2.0f : 0.0f;  // `= {2.0f}` initialiser quirk, ref .cu:795
-            cost_arr[slot * MAXV + v] = c;
+            cost_arr[v * 8 + slot] = c;
             if (c < thr) {
                 tw += d_exp_inrange((c * c) / (-0.18f));  // c in [0, 2]: argument in [-22.3, 0]
                 cn += 1;
@@ -473,6 +534,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         cnt[v] = cn;
         tmpw[v] = tw;
     }
+    stamp(kStampPhaseA);
     {
     // ---- view weights (ref .cu:821-878)
     uint32_t s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -535,12 +597,19 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
             const float w = view_w[v];
             if (!(w > 0.0f)) continue;
             GeomCheck gc[8];
+            // the view's eight photometric costs leave private memory ahead of the depth gathers, as one batch (loaded_here: fetched
+            // where they are used, each pays its own round trip between two checks)
+            float c8[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c8[i] = cost_arr[v * 8 + i];
 #pragma unroll
             for (int i = 0; i < 8; ++i)
                 if ((flags >> i) & 1u) gc[i].issue(P.views[v], gz[i], x, y);
 #pragma unroll
+            for (int i = 0; i < 8; ++i) c8[i] = loaded_here(c8[i]);
+#pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const float c = cost_arr[i * MAXV + v];
+                const float c = c8[i];
                 if ((flags >> i) & 1u)
                     fcv[i] += w * (c + 0.2f * gc[i].finish(P.views[v], x, y));
                 else
@@ -552,14 +621,51 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
             fcv[i] = fcv[i] / weight_norm;
             final_costs[i] = fcv[i];
         }
-    } else {
+    } else if constexpr (kCostsByCandidate) {
         for (int i = 0; i < 8; ++i) {
             float fc = 0.0f;
             for (int v = 0; v < V; ++v)
-                if (view_w[v] > 0.0f) fc += view_w[v] * cost_arr[i * MAXV + v];
+                if (view_w[v] > 0.0f) fc += view_w[v] * cost_arr[v * 8 + i];
             const float fci = fc / weight_norm;
             final_costs[i] = fci;
             fcv[i] = fci;
+        }
+    } else {
+        // VIEW by view as well: the weight and the eight costs of a view are fetched from private memory together and waited for
+        // once (loaded_here: fetched under the test of the weight, every cost pays a round trip of its own, one after the other),
+        // then every candidate takes its term under the lane's test.  For a fixed candidate the views are still added in
+        // ascending order, each as w * c and then +; a view without weight adds nothing, not a zero product.
+#pragma unroll
+        for (int i = 0; i < 8; ++i) fcv[i] = 0.0f;
+        const auto add_view = [&](int v) {
+            const float w = view_w[v];
+            float c[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c[i] = cost_arr[v * 8 + i];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) c[i] = loaded_here(c[i]);
+            const bool weighted = w > 0.0f;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float sum = fcv[i] + w * c[i];
+                fcv[i] = weighted ? sum : fcv[i];
+            }
+        };
+        // (unrolled where the bucket has 8 views: the weights live in registers there and are named instead of picked through a
+        // chain of selects; a loop that leaves early is unrolled by its upper bound only up to 8 trips)
+        if constexpr (MAXV == 8) {
+#pragma unroll
+            for (int v = 0; v < 8; ++v) {
+                if (v >= V) break;
+                add_view(v);
+            }
+        } else {
+            for (int v = 0; v < V; ++v) add_view(v);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            fcv[i] = fcv[i] / weight_norm;
+            final_costs[i] = fcv[i];
         }
     }
     {
@@ -571,6 +677,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
             }
     }
     }
+    stamp(kStampWeighted);
 
     // ---- phase B: the current plane under the new weights (ref .cu:901-913), the acceptance of the best neighbour, then the
     // 5 refinement candidates (ref .cu:642-722).  From here on a view with weight 0 contributes exactly +0.0 to every sum (all
@@ -640,6 +747,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         cost_now = tc / weight_norm;
         if (GEOM) geom_now = tg / weight_norm;
     }
+    stamp(kStampCurrent);
     {
     // ---- acceptance of the best propagated neighbour (ref .cu:921-991)
     const float4 cur = plane_now;  // still the plane the pixel came in with
@@ -802,6 +910,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
         const int n_here = __builtin_popcountll(here);
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(here >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)here, 0u));
         float w_next = view_w[0];
+        stamp(kStampDealBegin);
         for (int v = 0; v < V; ++v) {
             const float w = w_next;
             w_next = view_w[v + 1 < MAXV ? v + 1 : v];
@@ -815,6 +924,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
             }
             for (int base = 0; base < total; base += n_here) {
                 // owners publish the items of this round
+                stamp(kStampRound);
 #pragma unroll
                 for (int ci = 0; ci < 5; ++ci)
                     if (((live >> ci) & 1u) && (unsigned)(pos[ci] - base) < (unsigned)n_here) {
@@ -825,6 +935,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                stamp(kStampPublished);
                 // the lane of rank r evaluates item base + r with its owner's pixel, weight records and window statistics
                 const bool have = base + rank < total;
                 const int owner = have ? (int)x_id[rank] : lane;
@@ -849,6 +960,7 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                stamp(kStampEvaluated);
                 // owners collect: for a fixed candidate the views are still added in ascending order
 #pragma unroll
                 for (int ci = 0; ci < 5; ++ci)
@@ -865,8 +977,10 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                stamp(kStampCollected);
             }
         }
+        stamp(kStampDealEnd);
     }
 #pragma unroll
     for (int ci = 0; ci < 5; ++ci) {
@@ -1020,15 +1134,15 @@ __global__ __launch_bounds__((kUpdThreads<U8, SCALE>), kWavesPerSimd) void k_upd
         wave_timer.ready();
 #endif
     };
-    const auto first_evaluation = [&]() {
+    const auto stamp = [&](int point) {
 #ifdef PM_DBG_WAVETIME
-        wave_timer.first_eval();
+        wave_timer.stamp(point);
 #endif
     };
     {
         const int k = a.parity + pass;
         const bool use_own = pass < 2 && ((ch.own_mask >> (k & 1)) & 1) != 0;
-        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0], use_own, wait_for_neighbours, first_evaluation);
+        update_body<GEOM, PRIOR, MAXV, U8, SCALE>(P, S, a, b, k & 1, a.launch + (uint32_t)pass, ch.thr[(k >> 1) < kChainMaxIters ? (k >> 1) : 0], use_own, wait_for_neighbours, stamp);
     }
     // completion: this wave's stores have left (write-through) before it counts itself done
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

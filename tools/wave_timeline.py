@@ -2,8 +2,9 @@
 """Slot occupancy of the update launches over time, from per-wave start / end stamps.
 
 Needs a measurement build of the HIP library with -DPM_DBG_WAVETIME (pm_kernels.hpp, WaveTimer: every wave of k_update records
-s_memrealtime at its start, when its block may go on, at its first NCC evaluation and at its end, HW_ID and XCC_ID):
-    make -C mp-mvs_amd/csrc EXTRA=-DPM_DBG_WAVETIME ... -o build/libmpmvs_hip_wt.so      (tools/build_variants.sh wt)
+s_memrealtime at its start, when its block may go on, at its first NCC evaluation, at the section marks of update_body and at its end,
+HW_ID and XCC_ID):
+    make -C mp-mvs_amd/csrc EXTRA=-DPM_DBG_WAVETIME ... -o build/libmpmvs_hip_wt.so      (tools/build_variant.sh wt -DPM_DBG_WAVETIME)
     MPMVS_HIP_LIB=$PWD/build/libmpmvs_hip_wt.so python tools/wave_timeline.py [--out profiles/r05_wave_timeline.txt]
 
 For every update launch of one cfg-1 Run() (1600x1200, 8 views, photometric, 3 iterations) it prints
@@ -16,6 +17,9 @@ For every update launch of one cfg-1 Run() (1600x1200, 8 views, photometric, 3 i
       gaps   = the rest: slots idle between the end of one block and the start of the next on the same CU,
   * the spread of wave durations, inside a block and over the launch,
   * an ASCII plot of resident waves over time (50 bins).
+--sections FILE adds, per pass, where a wave's lifetime goes inside update_body (the second half of the wave records: prologue, phase A,
+view weights and weighted costs, current plane, acceptance and draws, the dealt rounds and, of these, the owners' publishing and
+collecting, the final acceptance): mean, p50 and p95 in us and the share of the lifetime (profiles/r23_update_sections.txt).
 """
 import argparse
 import ctypes as C
@@ -28,10 +32,32 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 TICK_NS = 10.0   # s_memrealtime: 100 MHz
+REC = 8          # u64 per wave record (kWaveRecWords, pm_kernels.hpp)
+
+
+def sections(rec):
+    """The sections of update_body from the second half of the records of ONE launch: rows (name, mean us, p50, p95, share of the
+    waves' lifetime in %), over the waves that own a pixel; plus the mean number of dealt rounds."""
+    rec = rec[(rec[:, 0] != 0) & (rec[:, 6] != 0)]
+    life = (rec[:, 1].astype(np.int64) - rec[:, 0].astype(np.int64)).astype(np.float64)
+    lo, hi = (lambda w: (rec[:, w] & 0xffffffff).astype(np.float64)), (lambda w: (rec[:, w] >> 32).astype(np.float64))
+    cols = [("prologue", ((rec[:, 2] >> 36) & 0xffffff).astype(np.float64)),
+            ("phase A", lo(4)),
+            ("view weights, weighted costs, min_idx", hi(4)),
+            ("current plane", lo(5)),
+            ("acceptance, draws, candidate planes", hi(5)),
+            ("dealt rounds", lo(6)),
+            ("  of which publish", (rec[:, 7] & 0xffffff).astype(np.float64)),
+            ("  of which collect", ((rec[:, 7] >> 24) & 0xffffff).astype(np.float64)),
+            ("final acceptance, stores", hi(6)),
+            ("lifetime", life)]
+    us = TICK_NS / 1e3
+    rows = [(n, v.mean() * us, np.percentile(v, 50) * us, np.percentile(v, 95) * us, 100.0 * v.sum() / life.sum()) for n, v in cols]
+    return rows, float((rec[:, 7] >> 48).astype(np.float64).mean()), len(rec)
 
 
 def analyse(rec, waves_per_block, out):
-    """rec: [n_waves][4] u64 (start, end, hw | xcc << 32 | prologue << 36, wave | waited << 8 | block << 32) of ONE launch (rows of waves that never ran are zero)"""
+    """rec: [n_waves][REC] u64, of which the first four are (start, end, hw | xcc << 32 | prologue << 36, wave | waited << 8 | block << 32) of ONE launch (rows of waves that never ran are zero)"""
     ran = rec[:, 0] != 0
     rec = rec[ran]
     start, end = rec[:, 0].astype(np.int64), rec[:, 1].astype(np.int64)
@@ -136,6 +162,7 @@ def analyse(rec, waves_per_block, out):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sections", default=None, help="write the per-pass table of update_body's sections (the second half of the records) to this file")
     ap.add_argument("--size", default="1600x1200")
     ap.add_argument("--threads", type=int, default=64, help="threads per update block of the library in use (kUpdThreads, pm_kernels.hpp)")
     args = ap.parse_args()
@@ -169,7 +196,7 @@ def main():
            f"# HIP-event averages of this run: k_update {(ms[1] + ms[2]) / max(cnt[1] + cnt[2], 1):.4f} ms per launch (the stamps add two scalar memory operations per wave)"]
     occs, recs = [], []
     for launch in range(1, 7):
-        rec = buf[(launch & 15) * waves * 4:((launch & 15) + 1) * waves * 4].reshape(waves, 4)
+        rec = buf[(launch & 15) * waves * REC:((launch & 15) + 1) * waves * REC].reshape(waves, REC)
         recs.append(rec[rec[:, 0] != 0])
         out.append(f"launch {launch} ({'black' if launch % 2 else 'red'}, iteration {(launch - 1) // 2}):")
         occ, span = analyse(rec, wpb, out)
@@ -185,8 +212,19 @@ def main():
     overlap = [max(0, lasts[i] - firsts[i + 1]) * TICK_NS / 1e3 for i in range(5)]
     out.append(f"# all six passes together: first wave start -> last wave end {span * TICK_NS / 1e6:.3f} ms = {span * TICK_NS / 6e6:.3f} ms per pass, slot occupancy {100 * busy / (span * 2048):.2f} % of 2048 slots; "
                f"pass p + 1 starts before pass p ends by {', '.join(f'{o:.0f}' for o in overlap)} us")
+    sec = [f"# sections of update_body per pass of one cfg-1 Run() ({w}x{h}, 8 views, photometric, 3 iterations), from the per-wave stamps; library {os.environ.get('MPMVS_HIP_LIB', 'default')}",
+           f"# HIP-event average of this stamped build: k_update {(ms[1] + ms[2]) / max(cnt[1] + cnt[2], 1):.4f} ms per pass; mean (p50, p95) in us over the waves that own a pixel, share = sum / sum of lifetimes",
+           "# publish = top of a dealt round -> barrier behind the publishing, collect = barrier behind the evaluation -> barrier behind the collecting, summed over the wave's rounds"]
+    for launch, rec in enumerate(recs, 1):
+        rows, rounds, n = sections(rec)
+        sec.append(f"pass {launch}: {n} waves, {rounds:.1f} dealt rounds per wave")
+        for name, mean, p50, p95, share in rows:
+            sec.append(f"  {name:40s} {mean:8.2f} ({p50:7.2f}, {p95:7.2f})  {share:6.2f} %")
+    print("\n".join(out + sec))
     text = "\n".join(out)
-    print(text)
+    if args.sections:
+        with open(args.sections, "w") as f:
+            f.write("\n".join(sec) + "\n")
     if args.out:
         with open(args.out, "w") as f:
             f.write(text + "\n")
