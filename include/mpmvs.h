@@ -905,6 +905,70 @@ long long mpmvs_tsdf_mesh(mpmvs_tsdf* h, int min_weight, float** out_xyz, unsign
 int mpmvs_tsdf_pass_ms(const mpmvs_tsdf* h, float ms[5]);
 void mpmvs_tsdf_destroy(mpmvs_tsdf* h);
 
+/* ---- surface: the brick-sparse TSDF volume (mp-mvs_amd/mesh.py: SparseVolume, tools/mesh_ply.py --sparse) --- */
+/* The same handle type with the same origin, voxel, dims, trunc and with_color, but dims are VIRTUAL: only bricks near the surface
+ * exist (mp-mvs_amd/csrc/pm_tsdf_sparse.hpp).  There are two statements, A and B; everything else is the dense
+ * statement above under a mask.  Both are bit for bit and independent of scheduling.
+ *
+ * GEOMETRY.  A BRICK is 8 x 8 x 8 voxels: brick (I, J, K) covers the voxels 8I..8I+7 on each axis, cut off at dims.  The BRICK GRID has
+ * b_a = ceil(dims[a] / 8) bricks per axis; a brick's linear index is (K*by + J)*bx + I, a voxel's LOCAL INDEX within its brick
+ * (lk*8 + lj)*8 + li.  A voxel EXISTS iff its brick is allocated; a voxel that does not exist has weight 0 and is never valid.
+ * BRICK-MAJOR ORDER: bricks ascending by linear index, voxels within a brick ascending by local index.  This order replaces the
+ * dense linear index wherever the dense contract orders things: vertices by owner then slot, triangles by cell then tetrahedron
+ * then triangle.  Where bricks are stored is not observable; every output is in brick-major order.
+ *
+ * mpmvs_tsdf_create_sparse touches no device, like mpmvs_tsdf_create.  pad (in voxels) and max_bricks are fixed here.  Limits: every
+ * dim >= 1, origin, voxel, trunc finite, voxel and trunc > 0, the far corner finite in fp32, device >= 0, pad finite and
+ * 0 <= pad <= 8, max_bricks >= 1 (all -2); bx*by*bz <= 2^24, max_bricks <= 2^21 (2^30 voxels, the index width of the mesh scratch),
+ * n_s <= 2^16 (all -3).  On failure *h is not written.
+ *
+ * A. ALLOCATE.  mpmvs_tsdf_allocate(h, n_views, cams, depths) allocates a set of bricks that is a pure function of its arguments (the
+ * set is order-free).  fp32 with no contraction and correctly rounded quotients, except where a double is written out.
+ *   n_s = max(1, (int)ceil(4.0*(double)trunc/(double)voxel)).
+ *   A pixel (ix, iy) of a view (K, R, t, W, H as above) takes part iff d = depth[iy*W + ix] is finite and > 0.  For each such pixel
+ *   and m = 0..n_s:
+ *   1. z = (float)(((double)d - (double)trunc) + (double)m * ((2.0*(double)trunc)/(double)n_s)).  Skip unless z > 0.
+ *   2. xc = (((float)ix - K[2]) * z) / K[0] and yc = (((float)iy - K[5]) * z) / K[4].  (The pixel centre is ix, not ix + 0.5: step 3
+ *      of the integration adds 0.5 before floorf.)
+ *   3. a = xc - t[0], b = yc - t[1], c = z - t[2];  P_x = (R[0]*a + R[3]*b) + R[6]*c,  P_y = (R[1]*a + R[4]*b) + R[7]*c,
+ *      P_z = (R[2]*a + R[5]*b) + R[8]*c.
+ *   4. g_a = (P_a - origin[a]) / voxel per axis a.  Skip the sample unless all three are finite.
+ *   5. Per axis lo = floorf(g_a - pad), hi = floorf(g_a + pad).  Skip the sample if hi < 0 or lo > n_a - 1 on any axis (compared as
+ *      the integers they are); clamp both to [0, n_a - 1]; mark every brick of the box [lo>>3 .. hi>>3]^3 (at most 27).
+ *   Bricks already allocated stay, with their contents.  A new brick starts all zero.  If the call would raise the brick count above
+ *   max_bricks it returns -3 and changes nothing: all views are marked and counted before any brick is committed.
+ *   The argument checks and codes are those of mpmvs_tsdf_integrate (without the colours and the limit on the number of views);
+ *   -2 on a dense handle; n_views == 0 returns 0 and touches nothing.  pad = 1.0 is the default of mesh.py and the tools, an untuned
+ *   starting value.
+ *
+ * B. MASKED-DENSE EQUIVALENCE.
+ *   mpmvs_tsdf_integrate on a sparse handle never allocates: it applies the eleven steps above, unchanged, to every existing voxel
+ *   and to no other.  A brick holds exactly the dense sums of all views integrated since it was allocated.  With every allocate
+ *   before the first integrate, the state is the dense volume with the non-existing voxels zeroed, however the view list is split
+ *   over calls.
+ *   mpmvs_tsdf_mesh on a sparse handle equals the dense mesh statement on the virtual lattice with the weight of every non-existing
+ *   voxel set to 0, vertices and triangles renumbered into brick-major order.  Cells, tetrahedra, slots, t, colours, winding, the -3
+ *   rule and the empty-result rule (also: a handle without a brick launches nothing) are the dense ones.  CONSEQUENCE: the sparse
+ *   mesh is a sub-mesh of the dense mesh of the same views: the same vertex positions bit for bit and a subset of the triangles,
+ *   never a different triangle.
+ *
+ * mpmvs_tsdf_bricks returns the brick count; *coords (may be NULL: count only) receives n x 3 (I, J, K) in ascending linear index,
+ * to release with mpmvs_free, NULL when the count is 0.  mpmvs_tsdf_get_bricks copies n_bricks*512 entries per array in brick-major
+ * order (color4 may be NULL); voxels cut off by dims read 0.  mpmvs_tsdf_set_bricks replaces the whole volume with the given bricks
+ * (tests, and volumes computed elsewhere): coords strictly ascending by linear index and inside the grid (-2), n <= max_bricks (-3),
+ * found before anything is written; entries of cut-off voxels are ignored and stored as 0; with colour a NULL color4 clears the
+ * colour sums.  mpmvs_tsdf_sparse_stats: info = the brick count, max_bricks, the cells of the brick grid, the bytes of device memory
+ * the handle holds between calls; ms = the device ms of the last allocate: marking (all chunks), scan + commit.
+ * On a sparse handle mpmvs_tsdf_integrate, _mesh, _pass_ms and _destroy work as above; mpmvs_tsdf_get and _set return -2.  On a dense
+ * handle allocate, bricks, get_bricks, set_bricks and sparse_stats return -2.  A NULL handle is -2 everywhere. */
+int mpmvs_tsdf_create_sparse(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, float pad,
+                             long long max_bricks, mpmvs_tsdf** h);
+int mpmvs_tsdf_allocate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, const float* const* depths);
+long long mpmvs_tsdf_bricks(mpmvs_tsdf* h, int32_t** coords);
+int mpmvs_tsdf_get_bricks(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* color4);
+int mpmvs_tsdf_set_bricks(mpmvs_tsdf* h, long long n, const int32_t* coords, const float* sum, const int32_t* weight, const uint32_t* color4);
+int mpmvs_tsdf_sparse_stats(const mpmvs_tsdf* h, long long info[4], float ms[2]);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

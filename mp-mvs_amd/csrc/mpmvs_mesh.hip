@@ -1,7 +1,8 @@
-// mpmvs_mesh.hip -- the surface family of the C ABI declared in include/mpmvs.h: the dense TSDF volume handle (mpmvs_tsdf), the
-// integration of depth maps into it and the marching-tetrahedra mesh of its zero level set (kernels and per-thread bodies:
-// pm_tsdf.hpp).  Errors are reported like those of mpmvs_cloud_*: through mpmvs_last_error(NULL), per host
-// thread; everything but -100 is found before the device is touched.  A handle opens its device with the first call that needs it.
+// mpmvs_mesh.hip -- the surface family of the C ABI declared in include/mpmvs.h: the TSDF volume handle (mpmvs_tsdf), dense or
+// brick-sparse, the integration of depth maps into it and the marching-tetrahedra mesh of its zero level set (kernels and per-thread
+// bodies: pm_tsdf.hpp, pm_tsdf_sparse.hpp; DESIGN.md sections 22 and 23).  Errors are reported like those of mpmvs_cloud_*: through
+// mpmvs_last_error(NULL), per host thread; everything but -100 is found before the device is touched.  A handle opens its device
+// with the first call that needs it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "../../include/mpmvs.h"
 #include "pm_host.hpp"
 #include "pm_tsdf.hpp"
+#include "pm_tsdf_sparse.hpp"
 
 using namespace pm;
 
@@ -36,6 +38,16 @@ struct mpmvs_tsdf {
     int32_t* d_weight = nullptr;
     uint4* d_color = nullptr;
     float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // a brick-sparse handle (mpmvs_tsdf_create_sparse): d_sum, d_weight and d_color hold n_bricks * 512 entries in brick-major order
+    bool sparse = false;
+    TsdfAlloc alloc{};
+    int bx = 0, by = 0, bz = 0;
+    size_t n_grid = 0;
+    long long max_bricks = 0, n_bricks = 0;
+    int32_t* d_grid = nullptr;       // [n_grid]: rank or -1
+    int32_t* d_list = nullptr;       // [n_bricks]: linear index per rank
+    std::vector<int32_t> list;       // its host copy
+    float alloc_ms[2] = {0.0f, 0.0f};
 };
 
 // the first call that needs the device: the stream, the events and the volume, all zero
@@ -55,6 +67,21 @@ static int tsdf_ready(mpmvs_tsdf* h) {
     h->ready = true;
     return 0;
 }
+
+// a brick-sparse handle's first call that needs the device: the stream, the events and the brick grid, all -1
+static int tsdf_sparse_ready(mpmvs_tsdf* h) {
+    CALLCHK(enter_device(h->device));
+    if (h->ready) return 0;
+    if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->ev)
+        if (!e) CALLCHK(hipEventCreate(&e));
+    if (!h->d_grid) CALLCHK(pool_malloc(&h->d_grid, h->n_grid * 4));
+    CALLCHK(hipMemsetAsync(h->d_grid, 0xff, h->n_grid * 4, h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
+    h->ready = true;
+    return 0;
+}
+static TsdfBricks tsdf_bricks(const mpmvs_tsdf* h) { return TsdfBricks{h->bx, h->by, h->bz, h->d_grid, h->d_list}; }
 
 int mpmvs_tsdf_create(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, mpmvs_tsdf** out) {
     if (!out || !origin || !dims) return call_fail(-2, "tsdf create: bad argument");
@@ -83,10 +110,10 @@ int mpmvs_tsdf_create(int device, const float origin[3], float voxel, const int 
 
 void mpmvs_tsdf_destroy(mpmvs_tsdf* h) {
     if (!h) return;
-    if (h->stream || h->d_sum) {
+    if (h->stream || h->d_sum || h->d_grid) {
         (void)enter_device(h->device);
         if (h->stream) (void)hipStreamSynchronize(h->stream);
-        for (void* p : {(void*)h->d_sum, (void*)h->d_weight, (void*)h->d_color})
+        for (void* p : {(void*)h->d_sum, (void*)h->d_weight, (void*)h->d_color, (void*)h->d_grid, (void*)h->d_list})
             if (p) (void)pool_free(p);
         for (hipEvent_t e : h->ev)
             if (e) (void)hipEventDestroy(e);
@@ -133,7 +160,11 @@ static int tsdf_integrate_chunk(mpmvs_tsdf* h, int v0, int v1, const mpmvs_camer
     }
     const size_t tiles = (size_t)((h->V.nx + kTsdfTileX - 1) / kTsdfTileX) * (size_t)((h->V.ny + kTsdfTileY - 1) / kTsdfTileY) * (size_t)h->V.nz;
     CALLCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), 0, st, h->V, A, h->d_sum, h->d_weight, h->with_color ? h->d_color : (uint4*)nullptr);
+    if (h->sparse)
+        hipLaunchKernelGGL(k_tsdf_sparse_integrate, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), A, h->d_sum, h->d_weight,
+                           h->with_color ? h->d_color : (uint4*)nullptr);
+    else
+        hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), 0, st, h->V, A, h->d_sum, h->d_weight, h->with_color ? h->d_color : (uint4*)nullptr);
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[1], st));
     CALLCHK(hipStreamSynchronize(st));
@@ -161,7 +192,12 @@ int mpmvs_tsdf_integrate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, c
             return call_fail(-3, "tsdf integrate: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
     }
     if (h->views + (long long)n_views > kTsdfMaxViews) return call_fail(-3, "tsdf integrate: more than 2^23 views over the life of the volume");
-    const int rc = tsdf_ready(h);
+    if (h->sparse && h->n_bricks == 0) {   // no voxel exists: nothing to add to
+        h->ms[0] = 0.0f;
+        h->views += n_views;
+        return 0;
+    }
+    const int rc = h->sparse ? tsdf_sparse_ready(h) : tsdf_ready(h);
     if (rc) return rc;
     h->ms[0] = 0.0f;
     for (int v0 = 0; v0 < n_views;) {
@@ -182,6 +218,7 @@ int mpmvs_tsdf_integrate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, c
 int mpmvs_tsdf_get(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* color4) {
     if (!h || !sum || !weight) return call_fail(-2, "tsdf get: bad argument");
     if (color4 && !h->with_color) return call_fail(-2, "tsdf get: the volume has no colour");
+    if (h->sparse) return call_fail(-2, "tsdf get: a brick-sparse volume is read with mpmvs_tsdf_bricks and mpmvs_tsdf_get_bricks");
     const int rc = tsdf_ready(h);
     if (rc) return rc;
     CALLCHK(hipMemcpyAsync(sum, h->d_sum, h->n_vox * 4, hipMemcpyDeviceToHost, h->stream));
@@ -194,6 +231,7 @@ int mpmvs_tsdf_get(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* color4)
 int mpmvs_tsdf_set(mpmvs_tsdf* h, const float* sum, const int32_t* weight, const uint32_t* color4) {
     if (!h || !sum || !weight) return call_fail(-2, "tsdf set: bad argument");
     if (color4 && !h->with_color) return call_fail(-2, "tsdf set: the volume has no colour");
+    if (h->sparse) return call_fail(-2, "tsdf set: a brick-sparse volume is written with mpmvs_tsdf_set_bricks");
     const int rc = tsdf_ready(h);
     if (rc) return rc;
     CALLCHK(hipMemcpyAsync(h->d_sum, sum, h->n_vox * 4, hipMemcpyHostToDevice, h->stream));
@@ -207,7 +245,7 @@ int mpmvs_tsdf_set(mpmvs_tsdf* h, const float* sum, const int32_t* weight, const
 // the device half of mpmvs_tsdf_mesh; the host buffers are allocated once the counts are known and handed over on success only
 static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, unsigned char** rgb, int32_t** tri, long long* n_tri) {
     const hipStream_t st = h->stream;
-    const size_t n = h->n_vox;
+    const size_t n = h->sparse ? (size_t)h->n_bricks * kBrickVox : h->n_vox;   // sparse: the existing voxels in brick-major order
     const int n_tiles = (int)((n + kScanBlock - 1) / kScanBlock);
     const unsigned blocks = (unsigned)((n + 255) / 256);
     Scratch d_mask(st), d_vexcl(st), d_tcount(st), d_totals(st), d_grand(st);
@@ -221,7 +259,11 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     CALLCHK(hipMemsetAsync(d_grand.p, 0, 16, st));
     CALLCHK(hipEventRecord(h->ev[0], st));
     CALLCHK(hipMemsetAsync(d_mask.p, 0, n * 4, st));
-    hipLaunchKernelGGL(k_tsdf_mark, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>());
+    if (h->sparse)
+        hipLaunchKernelGGL(k_tsdf_sparse_mark, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight, min_weight,
+                           d_mask.as<uint32_t>(), d_tcount.as<int>());
+    else
+        hipLaunchKernelGGL(k_tsdf_mark, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>());
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[1], st));
     hipLaunchKernelGGL(k_tsdf_scan_tiles, dim3((unsigned)n_tiles), dim3(kScanBlock), 0, st, d_mask.as<uint32_t>(), n, d_vexcl.as<int>(), d_tcount.as<int>(), vtile, n_tiles);
@@ -248,12 +290,21 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     if (h->with_color) CALLCHK(d_rgb.alloc(nv * 3));
     CALLCHK(d_tri.alloc(nt * 12));
     CALLCHK(hipEventRecord(h->ev[5], st));
-    hipLaunchKernelGGL(k_tsdf_vertices, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, h->with_color ? h->d_color : (const uint4*)nullptr,
-                       d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(), h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
+    if (h->sparse)
+        hipLaunchKernelGGL(k_tsdf_sparse_vertices, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight,
+                           h->with_color ? h->d_color : (const uint4*)nullptr, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(),
+                           h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
+    else
+        hipLaunchKernelGGL(k_tsdf_vertices, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, h->with_color ? h->d_color : (const uint4*)nullptr,
+                           d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(), h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[3], st));
-    hipLaunchKernelGGL(k_tsdf_triangles, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile,
-                       d_tcount.as<int>(), ttile, d_tri.as<int32_t>());
+    if (h->sparse)
+        hipLaunchKernelGGL(k_tsdf_sparse_triangles, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight, min_weight,
+                           d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_tcount.as<int>(), ttile, d_tri.as<int32_t>());
+    else
+        hipLaunchKernelGGL(k_tsdf_triangles, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile,
+                           d_tcount.as<int>(), ttile, d_tri.as<int32_t>());
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[4], st));
     float* hx = (float*)std::malloc(nv * 12);
@@ -290,8 +341,8 @@ long long mpmvs_tsdf_mesh(mpmvs_tsdf* h, int min_weight, float** out_xyz, unsign
     int32_t* tri = nullptr;
     long long nt = 0, nv = 0;
     h->ms[1] = h->ms[2] = h->ms[3] = h->ms[4] = 0.0f;
-    if (h->V.nx > 1 && h->V.ny > 1 && h->V.nz > 1) {   // else there is no cell: nothing is launched
-        const int rc = tsdf_ready(h);
+    if (h->V.nx > 1 && h->V.ny > 1 && h->V.nz > 1 && !(h->sparse && h->n_bricks == 0)) {   // else there is no cell: nothing is launched
+        const int rc = h->sparse ? tsdf_sparse_ready(h) : tsdf_ready(h);
         if (rc) return rc;
         nv = tsdf_mesh_device(h, min_weight, &xyz, &rgb, &tri, &nt);
         if (nv < 0) return nv;
@@ -306,6 +357,284 @@ long long mpmvs_tsdf_mesh(mpmvs_tsdf* h, int min_weight, float** out_xyz, unsign
 int mpmvs_tsdf_pass_ms(const mpmvs_tsdf* h, float ms[5]) {
     if (!h || !ms) return call_fail(-2, "tsdf pass_ms: bad argument");
     std::memcpy(ms, h->ms, sizeof h->ms);
+    return 0;
+}
+
+// ---- the brick-sparse volume (statements A and B of include/mpmvs.h) -------------------------------------
+constexpr long long kTsdfMaxGrid = 1ll << 24, kTsdfMaxBricks = 1ll << 21, kTsdfMaxSamples = 1ll << 16;
+
+int mpmvs_tsdf_create_sparse(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, float pad, long long max_bricks,
+                             mpmvs_tsdf** out) {
+    if (!out || !origin || !dims) return call_fail(-2, "tsdf create_sparse: bad argument");
+    if (device < 0) return call_fail(-2, "tsdf create_sparse: negative device");
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(origin[a])) return call_fail(-2, "tsdf create_sparse: the origin must be finite");
+        if (dims[a] < 1) return call_fail(-2, "tsdf create_sparse: every dimension must be at least 1");
+    }
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return call_fail(-2, "tsdf create_sparse: voxel must be finite and positive");
+    if (!std::isfinite(trunc) || !(trunc > 0.0f)) return call_fail(-2, "tsdf create_sparse: trunc must be finite and positive");
+    if (!std::isfinite(pad) || !(pad >= 0.0f && pad <= 8.0f)) return call_fail(-2, "tsdf create_sparse: pad must be finite and in [0, 8] voxels");
+    if (max_bricks < 1) return call_fail(-2, "tsdf create_sparse: max_bricks must be at least 1");
+    if (max_bricks > kTsdfMaxBricks) return call_fail(-3, "tsdf create_sparse: max_bricks above 2^21");
+    long long b[3], cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        b[a] = ((long long)dims[a] + kBrick - 1) / kBrick;   // <= 2^28
+        cells = cells > kTsdfMaxGrid ? cells : cells * b[a];
+    }
+    if (cells > kTsdfMaxGrid) return call_fail(-3, "tsdf create_sparse: more than 2^24 cells in the brick grid");
+    const double ratio = std::ceil(4.0 * (double)trunc / (double)voxel);
+    if (!(ratio <= (double)kTsdfMaxSamples)) return call_fail(-3, "tsdf create_sparse: trunc / voxel asks for more than 2^16 samples per ray");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite((float)((double)origin[a] + (double)(dims[a] - 1) * (double)voxel)))
+            return call_fail(-2, "tsdf create_sparse: the far corner of the volume is not finite in fp32");
+    mpmvs_tsdf* h = new mpmvs_tsdf;
+    h->device = device;
+    h->V.nx = dims[0]; h->V.ny = dims[1]; h->V.nz = dims[2];
+    h->V.trunc = trunc;
+    for (int a = 0; a < 3; ++a) h->V.o[a] = (double)origin[a];
+    h->V.voxel = (double)voxel;
+    h->n_vox = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];   // virtual
+    h->with_color = with_color != 0;
+    h->sparse = true;
+    h->bx = (int)b[0]; h->by = (int)b[1]; h->bz = (int)b[2];
+    h->n_grid = (size_t)cells;
+    h->max_bricks = max_bricks;
+    h->alloc.n_s = std::max(1, (int)ratio);
+    h->alloc.step = (2.0 * (double)trunc) / (double)h->alloc.n_s;
+    for (int a = 0; a < 3; ++a) h->alloc.origin[a] = origin[a];
+    h->alloc.voxel = voxel;
+    h->alloc.pad = pad;
+    *out = h;
+    return 0;
+}
+
+// the pool of a new brick set: n bricks, all zero, and its list
+struct TsdfPool {
+    Scratch sum, weight, color, list;
+    explicit TsdfPool(hipStream_t st) : sum(st), weight(st), color(st), list(st) {}
+    int alloc(const mpmvs_tsdf* h, size_t n) {
+        CALLCHK(sum.alloc(n * kBrickVox * 4));
+        CALLCHK(weight.alloc(n * kBrickVox * 4));
+        if (h->with_color) CALLCHK(color.alloc(n * kBrickVox * 16));
+        CALLCHK(list.alloc(n * 4));
+        CALLCHK(hipMemsetAsync(sum.p, 0, n * kBrickVox * 4, h->stream));
+        CALLCHK(hipMemsetAsync(weight.p, 0, n * kBrickVox * 4, h->stream));
+        if (h->with_color) CALLCHK(hipMemsetAsync(color.p, 0, n * kBrickVox * 16, h->stream));
+        return 0;
+    }
+    // the handle takes the new pool, this object the old one (released when it goes out of scope); the stream must be idle
+    void swap_into(mpmvs_tsdf* h) {
+        std::swap(*(void**)&h->d_sum, sum.p);
+        std::swap(*(void**)&h->d_weight, weight.p);
+        std::swap(*(void**)&h->d_color, color.p);
+        std::swap(*(void**)&h->d_list, list.p);
+    }
+};
+
+// the scan, the refusal and the commit of mpmvs_tsdf_allocate, after the marking
+static int tsdf_commit(mpmvs_tsdf* h, const uint32_t* d_flags) {
+    const hipStream_t st = h->stream;
+    const int n_grid = (int)h->n_grid, n_tiles = (n_grid + kScanBlock - 1) / kScanBlock;
+    Scratch d_excl(st), d_totals(st), d_grand(st);
+    CALLCHK(d_excl.alloc((size_t)n_grid * 4));
+    CALLCHK(d_totals.alloc((size_t)n_tiles * 4));
+    CALLCHK(d_grand.alloc(4));
+    CALLCHK(hipEventRecord(h->ev[2], st));
+    hipLaunchKernelGGL(k_tsdf_brick_scan, dim3((unsigned)n_tiles), dim3(kScanBlock), 0, st, h->d_grid, d_flags, n_grid, d_excl.as<int>(), d_totals.as<int>());
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_totals.as<int>(), n_tiles, 0, d_grand.as<int>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[3], st));
+    int grand = 0;
+    CALLCHK(hipMemcpyAsync(&grand, d_grand.p, 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    CALLCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->alloc_ms[1] = ms;
+    const long long n_new = (long long)grand;   // at most 2^24 grid cells: the int cannot overflow, the comparison is in 64 bits
+    if (n_new > h->max_bricks)
+        return call_fail(-3, "tsdf allocate: " + std::to_string(n_new) + " bricks, max_bricks is " + std::to_string(h->max_bricks) + "; nothing was allocated");
+    if (n_new == h->n_bricks) return 0;   // the set only grows: no new brick
+    TsdfPool pool(st);
+    const int rc = pool.alloc(h, (size_t)n_new);
+    if (rc) return rc;
+    CALLCHK(hipEventRecord(h->ev[4], st));
+    if (h->n_bricks > 0) {
+        hipLaunchKernelGGL(k_tsdf_brick_move, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->d_list, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(),
+                           h->d_sum, h->d_weight, h->with_color ? h->d_color : (const uint4*)nullptr, pool.sum.as<float>(), pool.weight.as<int32_t>(),
+                           h->with_color ? pool.color.as<uint4>() : (uint4*)nullptr);
+        CALLCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_tsdf_brick_commit, dim3((unsigned)((n_grid + 255) / 256)), dim3(256), 0, st, n_grid, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(),
+                       pool.list.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[5], st));
+    std::vector<int32_t> list((size_t)n_new);
+    CALLCHK(hipMemcpyAsync(list.data(), pool.list.p, (size_t)n_new * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    CALLCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5]));
+    h->alloc_ms[1] += ms;
+    pool.swap_into(h);
+    h->list.swap(list);
+    h->n_bricks = n_new;
+    return 0;
+}
+
+// views [v0, v1) of an allocate call: the depth maps up, one marking launch, its time added to alloc_ms[0]
+static int tsdf_allocate_chunk(mpmvs_tsdf* h, int v0, int v1, const mpmvs_camera* cams, const float* const* depths, uint32_t* d_flags) {
+    const hipStream_t st = h->stream;
+    size_t pixels = 0, most = 0;
+    for (int v = v0; v < v1; ++v) {
+        pixels += (size_t)cams[v].width * (size_t)cams[v].height;
+        most = std::max(most, (size_t)cams[v].width * (size_t)cams[v].height);
+    }
+    Scratch d_depth(st);
+    CALLCHK(d_depth.alloc(pixels * 4));
+    TsdfChunkArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.n = v1 - v0;
+    size_t at = 0;
+    for (int v = v0; v < v1; ++v) {
+        const mpmvs_camera& c = cams[v];
+        TsdfView& W = A.v[v - v0];
+        std::memcpy(W.R, c.R, sizeof W.R);
+        std::memcpy(W.t, c.t, sizeof W.t);
+        W.K0 = c.K[0]; W.K2 = c.K[2]; W.K4 = c.K[4]; W.K5 = c.K[5];
+        W.w = c.width; W.h = c.height;
+        const size_t npix = (size_t)c.width * (size_t)c.height;
+        W.depth = d_depth.as<float>() + at;
+        CALLCHK(hipMemcpyAsync(d_depth.as<float>() + at, depths[v], npix * 4, hipMemcpyHostToDevice, st));
+        at += npix;
+    }
+    CALLCHK(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(k_tsdf_alloc_mark, dim3((unsigned)((most + 255) / 256), (unsigned)A.n), dim3(256), 0, st, h->V, tsdf_bricks(h), h->alloc, A, d_flags);
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[1], st));
+    CALLCHK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->alloc_ms[0] += ms;
+    return 0;
+}
+
+int mpmvs_tsdf_allocate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, const float* const* depths) {
+    if (!h || n_views < 0) return call_fail(-2, "tsdf allocate: bad argument");
+    if (!h->sparse) return call_fail(-2, "tsdf allocate: the volume is dense (mpmvs_tsdf_create_sparse makes a brick-sparse one)");
+    if (n_views == 0) return 0;
+    if (!cams || !depths) return call_fail(-2, "tsdf allocate: bad argument");
+    for (int v = 0; v < n_views; ++v) {
+        if (!depths[v]) return call_fail(-2, "tsdf allocate: view " + std::to_string(v) + " has no depth map");
+        if (cams[v].width <= 0 || cams[v].height <= 0) return call_fail(-2, "tsdf allocate: view " + std::to_string(v) + " has a non-positive width or height");
+    }
+    for (int v = 0; v < n_views; ++v) {
+        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return call_fail(-3, "tsdf allocate: view " + std::to_string(v) + " is wider or higher than 2^24");
+        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
+            return call_fail(-3, "tsdf allocate: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
+    }
+    const int rc = tsdf_sparse_ready(h);
+    if (rc) return rc;
+    h->alloc_ms[0] = h->alloc_ms[1] = 0.0f;
+    Scratch d_flags(h->stream);
+    CALLCHK(d_flags.alloc(h->n_grid * 4));
+    CALLCHK(hipMemsetAsync(d_flags.p, 0, h->n_grid * 4, h->stream));
+    for (int v0 = 0; v0 < n_views;) {
+        int v1 = v0 + 1;
+        size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
+        while (v1 < n_views && v1 - v0 < kTsdfChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kTsdfChunkPixels) {
+            pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
+            ++v1;
+        }
+        const int rc2 = tsdf_allocate_chunk(h, v0, v1, cams, depths, d_flags.as<uint32_t>());
+        if (rc2) return rc2;
+        v0 = v1;
+    }
+    return tsdf_commit(h, d_flags.as<uint32_t>());
+}
+
+long long mpmvs_tsdf_bricks(mpmvs_tsdf* h, int32_t** coords) {
+    if (!h) return call_fail(-2, "tsdf bricks: bad argument");
+    if (!h->sparse) return call_fail(-2, "tsdf bricks: the volume is dense");
+    if (!coords) return h->n_bricks;
+    int32_t* c = nullptr;
+    if (h->n_bricks > 0) {
+        c = (int32_t*)std::malloc((size_t)h->n_bricks * 12);
+        if (!c) return call_fail(-100, "tsdf bricks: out of host memory");
+        const TsdfBricks B = tsdf_bricks(h);
+        for (long long r = 0; r < h->n_bricks; ++r) {
+            int I, J, K;
+            tsdf_brick_coords(B, h->list[(size_t)r], I, J, K);
+            c[3 * r] = I; c[3 * r + 1] = J; c[3 * r + 2] = K;
+        }
+    }
+    *coords = c;
+    return h->n_bricks;
+}
+
+int mpmvs_tsdf_get_bricks(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* color4) {
+    if (!h || !sum || !weight) return call_fail(-2, "tsdf get_bricks: bad argument");
+    if (!h->sparse) return call_fail(-2, "tsdf get_bricks: the volume is dense (mpmvs_tsdf_get reads it)");
+    if (color4 && !h->with_color) return call_fail(-2, "tsdf get_bricks: the volume has no colour");
+    if (h->n_bricks == 0) return 0;
+    const int rc = tsdf_sparse_ready(h);
+    if (rc) return rc;
+    const size_t n = (size_t)h->n_bricks * kBrickVox;
+    CALLCHK(hipMemcpyAsync(sum, h->d_sum, n * 4, hipMemcpyDeviceToHost, h->stream));
+    CALLCHK(hipMemcpyAsync(weight, h->d_weight, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (color4) CALLCHK(hipMemcpyAsync(color4, h->d_color, n * 16, hipMemcpyDeviceToHost, h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+int mpmvs_tsdf_set_bricks(mpmvs_tsdf* h, long long n, const int32_t* coords, const float* sum, const int32_t* weight, const uint32_t* color4) {
+    if (!h || n < 0 || (n > 0 && (!coords || !sum || !weight))) return call_fail(-2, "tsdf set_bricks: bad argument");
+    if (!h->sparse) return call_fail(-2, "tsdf set_bricks: the volume is dense (mpmvs_tsdf_set writes it)");
+    if (color4 && !h->with_color) return call_fail(-2, "tsdf set_bricks: the volume has no colour");
+    if (n > h->max_bricks) return call_fail(-3, "tsdf set_bricks: " + std::to_string(n) + " bricks, max_bricks is " + std::to_string(h->max_bricks));
+    std::vector<int32_t> list((size_t)n);
+    for (long long r = 0; r < n; ++r) {
+        const int32_t I = coords[3 * r], J = coords[3 * r + 1], K = coords[3 * r + 2];
+        if (I < 0 || I >= h->bx || J < 0 || J >= h->by || K < 0 || K >= h->bz) return call_fail(-2, "tsdf set_bricks: brick " + std::to_string(r) + " is outside the brick grid");
+        list[(size_t)r] = (K * h->by + J) * h->bx + I;
+        if (r > 0 && list[(size_t)r] <= list[(size_t)r - 1])
+            return call_fail(-2, "tsdf set_bricks: the bricks must ascend strictly by linear index (brick " + std::to_string(r) + " does not)");
+    }
+    const int rc = tsdf_sparse_ready(h);
+    if (rc) return rc;
+    const hipStream_t st = h->stream;
+    std::vector<int32_t> grid(h->n_grid, -1);
+    for (long long r = 0; r < n; ++r) grid[(size_t)list[(size_t)r]] = (int32_t)r;
+    CALLCHK(hipMemcpyAsync(h->d_grid, grid.data(), h->n_grid * 4, hipMemcpyHostToDevice, st));
+    TsdfPool pool(st);
+    if (n > 0) {
+        const int rc2 = pool.alloc(h, (size_t)n);
+        if (rc2) return rc2;
+        const size_t e = (size_t)n * kBrickVox;
+        CALLCHK(hipMemcpyAsync(pool.list.p, list.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        CALLCHK(hipMemcpyAsync(pool.sum.p, sum, e * 4, hipMemcpyHostToDevice, st));
+        CALLCHK(hipMemcpyAsync(pool.weight.p, weight, e * 4, hipMemcpyHostToDevice, st));
+        if (color4) CALLCHK(hipMemcpyAsync(pool.color.p, color4, e * 16, hipMemcpyHostToDevice, st));
+        TsdfBricks B = tsdf_bricks(h);
+        B.list = pool.list.as<int32_t>();
+        hipLaunchKernelGGL(k_tsdf_brick_clip, dim3((unsigned)n), dim3(kBrickVox), 0, st, h->V, B, pool.sum.as<float>(), pool.weight.as<int32_t>(),
+                           h->with_color ? pool.color.as<uint4>() : (uint4*)nullptr);
+        CALLCHK(hipGetLastError());
+    }
+    CALLCHK(hipStreamSynchronize(st));
+    pool.swap_into(h);
+    h->list.swap(list);
+    h->n_bricks = n;
+    return 0;
+}
+
+int mpmvs_tsdf_sparse_stats(const mpmvs_tsdf* h, long long info[4], float ms[2]) {
+    if (!h || !info || !ms) return call_fail(-2, "tsdf sparse_stats: bad argument");
+    if (!h->sparse) return call_fail(-2, "tsdf sparse_stats: the volume is dense");
+    info[0] = h->n_bricks;
+    info[1] = h->max_bricks;
+    info[2] = (long long)h->n_grid;
+    info[3] = (h->d_grid ? (long long)h->n_grid * 4 : 0) + h->n_bricks * (4 + (long long)kBrickVox * (h->with_color ? 24 : 8));
+    ms[0] = h->alloc_ms[0];
+    ms[1] = h->alloc_ms[1];
     return 0;
 }
 

@@ -106,10 +106,10 @@ __host__ __device__ inline bool tsdf_view_live(const TsdfVol& V, const TsdfView&
     return !(tsdf_axis_dead(W.K0, W.K2, lo[0], hi[0], lo[2], hi[2], (float)W.w) || tsdf_axis_dead(W.K4, W.K5, lo[1], hi[1], lo[2], hi[2], (float)W.h));
 }
 
-// voxel (i, j, k) and the views of the chunk whose bit is set in `live`, in order
-__host__ __device__ inline void tsdf_integrate_one(const TsdfVol& V, const TsdfChunkArgs& A, unsigned live, int i, int j, int k, float* __restrict__ sum,
-                                                   int32_t* __restrict__ weight, uint4* __restrict__ color) {
-    const size_t vox = tsdf_index(V, i, j, k);
+// voxel (i, j, k), stored at entry `vox` of the arrays, and the views of the chunk whose bit is set in `live`, in order: the one
+// per-voxel body of the dense volume (vox = the linear index) and of the brick-sparse one (pm_tsdf_sparse.hpp: vox = the brick-major index)
+__host__ __device__ inline void tsdf_integrate_at(const TsdfVol& V, const TsdfChunkArgs& A, unsigned live, int i, int j, int k, size_t vox, float* __restrict__ sum,
+                                                  int32_t* __restrict__ weight, uint4* __restrict__ color) {
     const float px = tsdf_pos(V, 0, i), py = tsdf_pos(V, 1, j), pz = tsdf_pos(V, 2, k);
     float s_acc = sum[vox];
     int32_t w_acc = weight[vox];
@@ -144,6 +144,10 @@ __host__ __device__ inline void tsdf_integrate_one(const TsdfVol& V, const TsdfC
     }
     if (touched) { sum[vox] = s_acc; weight[vox] = w_acc; }
     if (painted) color[vox] = c_acc;
+}
+__host__ __device__ inline void tsdf_integrate_one(const TsdfVol& V, const TsdfChunkArgs& A, unsigned live, int i, int j, int k, float* __restrict__ sum,
+                                                   int32_t* __restrict__ weight, uint4* __restrict__ color) {
+    tsdf_integrate_at(V, A, live, i, j, k, tsdf_index(V, i, j, k), sum, weight, color);
 }
 
 __global__ __launch_bounds__(256) void k_tsdf_integrate(TsdfVol V, TsdfChunkArgs A, float* __restrict__ sum, int32_t* __restrict__ weight, uint4* __restrict__ color) {

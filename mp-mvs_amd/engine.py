@@ -115,6 +115,14 @@ _EXTRA = {
     "tsdf_mesh": (C.c_longlong, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
     "tsdf_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "tsdf_destroy": (None, [_P]),
+    # the brick-sparse volume (mesh.py: SparseVolume)
+    "tsdf_create_sparse": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int), C.c_float, C.c_int, C.c_float, C.c_longlong,
+                                     C.POINTER(C.c_void_p)]),
+    "tsdf_allocate": (C.c_int, [_P, C.c_int, _P, _P]),
+    "tsdf_bricks": (C.c_longlong, [_P, C.POINTER(C.c_void_p)]),
+    "tsdf_get_bricks": (C.c_int, [_P, _P, _P, _P]),
+    "tsdf_set_bricks": (C.c_int, [_P, C.c_longlong, _P, _P, _P, _P]),
+    "tsdf_sparse_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_float)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

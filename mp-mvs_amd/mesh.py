@@ -1,7 +1,8 @@
-"""Depth maps to a triangle mesh on the GPU: a dense TSDF volume and marching tetrahedra on the Kuhn split of its cells
-(mpmvs_tsdf_*, csrc/pm_tsdf.hpp, csrc/mpmvs_mesh.hip; contract: include/mpmvs.h), and the PLY files of a
-mesh.  Both device calls are bit for bit their plain-loop statements (tests/tsdf_common.py has them in numpy).  The work runs on
-the GPU; there is no CPU path."""
+"""Depth maps to a triangle mesh on the GPU: a TSDF volume, dense (Volume) or brick-sparse (SparseVolume), and marching tetrahedra
+on the Kuhn split of its cells (mpmvs_tsdf_*, csrc/pm_tsdf.hpp, csrc/pm_tsdf_sparse.hpp, csrc/mpmvs_mesh.hip; contract:
+include/mpmvs.h, DESIGN.md sections 22 and 23), and the PLY files of a mesh.  The device calls are bit for bit their plain-loop
+statements (tests/tsdf_common.py and tests/tsdf_sparse_common.py have them in numpy).  The work runs on the GPU; there is no CPU
+path."""
 import ctypes as C
 
 import numpy as np
@@ -132,6 +133,133 @@ class Volume:
         if rc != 0:
             _raise(self._f, "tsdf_pass_ms", rc)
         return dict(zip(("integrate", "mark", "scan", "vertices", "triangles"), (float(v) for v in ms)))
+
+
+class SparseVolume(Volume):
+    """mpmvs_tsdf_create_sparse: the lattice of Volume with virtual dims, of which only bricks of 8 x 8 x 8 voxels exist
+    (include/mpmvs.h, statements A and B).  allocate() marks the bricks within `pad` voxels of the samples
+    along every depth pixel's ray through the truncation band; integrate() and mesh() are the dense calls on the existing voxels.
+    Everything comes out in brick-major order: bricks ascending by (K*by + J)*bx + I, voxels within a brick by (lk*8 + lj)*8 + li.
+    pad = 1.0 is an untuned starting value.  max_bricks (default: the whole brick grid, at most 2^21) caps the pool; memory is
+    taken only for the bricks that exist."""
+
+    def __init__(self, origin, voxel, dims, trunc, color=False, pad=1.0, max_bricks=None, device=0):
+        _, self._f = engine.load()
+        self._h = None
+        o = np.ascontiguousarray(origin, np.float32)
+        d = np.ascontiguousarray(dims, np.int32)
+        if o.shape != (3,) or d.shape != (3,):
+            raise ValueError(f"need an origin and dims of 3 numbers each, got {o.shape} and {d.shape}")
+        grid = tuple((int(v) + 7) // 8 for v in d)
+        if max_bricks is None:
+            max_bricks = max(1, min(grid[0] * grid[1] * grid[2], 1 << 21))
+        h = C.c_void_p()
+        rc = self._f["tsdf_create_sparse"](int(device), o.ctypes.data_as(C.POINTER(C.c_float)), float(voxel), d.ctypes.data_as(C.POINTER(C.c_int)), float(trunc),
+                                           1 if color else 0, float(pad), int(max_bricks), C.byref(h))
+        if rc != 0:
+            _raise(self._f, "tsdf_create_sparse", rc)
+        self._h = h
+        self.origin, self.voxel, self.trunc, self.color, self.device = o, float(np.float32(voxel)), float(np.float32(trunc)), bool(color), int(device)
+        self.dims = tuple(int(v) for v in d)
+        self.n_vox = self.dims[0] * self.dims[1] * self.dims[2]   # virtual
+        self.grid, self.pad, self.max_bricks = grid, float(np.float32(pad)), int(max_bricks)
+
+    def allocate(self, cams, depths):
+        """mpmvs_tsdf_allocate: adds the bricks that the views' depth maps reach (statement A); existing bricks stay.  ValueError
+        (-3) if that needs more than max_bricks; nothing is allocated then."""
+        cams = list(cams)
+        n = len(cams)
+        if len(depths) != n:
+            raise ValueError("need one depth map per camera")
+        ds = [np.ascontiguousarray(d, np.float32) for d in depths]
+        for c, d in zip(cams, ds):
+            if d.shape != (int(c.height), int(c.width)):
+                raise ValueError(f"a depth map of shape {d.shape} for a camera of {int(c.height)} x {int(c.width)}")
+        arr = (_abi.Camera * max(n, 1))(*cams)
+        dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in ds])
+        rc = self._f["tsdf_allocate"](self._h, n, arr, dp)
+        if rc != 0:
+            _raise(self._f, "tsdf_allocate", rc)
+
+    def bricks(self):
+        """int32 [n, 3]: (I, J, K) of the allocated bricks in ascending linear index"""
+        lib, _ = engine.load()
+        lib.mpmvs_free.argtypes = [C.c_void_p]
+        lib.mpmvs_free.restype = None
+        p = C.c_void_p()
+        n = self._f["tsdf_bricks"](self._h, C.byref(p))
+        if n < 0:
+            _raise(self._f, "tsdf_bricks", n)
+        try:
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32)), (n, 3)).copy() if n else np.zeros((0, 3), np.int32)
+        finally:
+            if p.value:
+                lib.mpmvs_free(p)
+
+    def n_bricks(self):
+        n = self._f["tsdf_bricks"](self._h, None)
+        if n < 0:
+            _raise(self._f, "tsdf_bricks", n)
+        return int(n)
+
+    def get_bricks(self):
+        """{"coords": int32 [n, 3], "sum": float32 [n, 8, 8, 8] (indexed [brick, lk, lj, li]), "weight": int32 [n, 8, 8, 8]} and, with
+        colour, "color": uint32 [n, 8, 8, 8, 4]; voxels cut off by dims read 0"""
+        coords = self.bricks()
+        n = len(coords)
+        out = {"coords": coords, "sum": np.zeros((n, 8, 8, 8), np.float32), "weight": np.zeros((n, 8, 8, 8), np.int32)}
+        if self.color:
+            out["color"] = np.zeros((n, 8, 8, 8, 4), np.uint32)
+        if n:
+            rc = self._f["tsdf_get_bricks"](self._h, out["sum"].ctypes.data, out["weight"].ctypes.data, out["color"].ctypes.data if self.color else None)
+            if rc != 0:
+                _raise(self._f, "tsdf_get_bricks", rc)
+        return out
+
+    def set_bricks(self, coords, sum, weight, color=None):
+        """replaces the whole volume: coords int32 [n, 3] strictly ascending by linear index, 512 entries per brick and array"""
+        c = np.ascontiguousarray(coords, np.int32).reshape(-1, 3)
+        n = len(c)
+        s, w = np.ascontiguousarray(sum, np.float32), np.ascontiguousarray(weight, np.int32)
+        col = np.ascontiguousarray(color, np.uint32) if color is not None else None
+        if s.size != 512 * n or w.size != 512 * n or (col is not None and col.size != 2048 * n):
+            raise ValueError(f"need 512 sums and weights (and four colour entries per voxel) for each of the {n} bricks")
+        rc = self._f["tsdf_set_bricks"](self._h, n, c.ctypes.data if n else None, s.ctypes.data if n else None, w.ctypes.data if n else None,
+                                        col.ctypes.data if col is not None and n else None)
+        if rc != 0:
+            _raise(self._f, "tsdf_set_bricks", rc)
+
+    def get(self):
+        raise ValueError("a brick-sparse volume is read with get_bricks() or to_dense()")
+
+    def set(self, sum, weight, color=None):
+        raise ValueError("a brick-sparse volume is written with set_bricks()")
+
+    def to_dense(self):
+        """the volume scattered into dense arrays on the host, as Volume.get() returns them, non-existing voxels zero; for small
+        volumes (at most 2^27 voxels)"""
+        if self.n_vox > 1 << 27:
+            raise ValueError(f"to_dense: {self.n_vox} voxels, more than 2^27")
+        nx, ny, nz = self.dims
+        b = self.get_bricks()
+        out = {"sum": np.zeros((nz, ny, nx), np.float32), "weight": np.zeros((nz, ny, nx), np.int32)}
+        if self.color:
+            out["color"] = np.zeros((nz, ny, nx, 4), np.uint32)
+        for r, (I, J, K) in enumerate(b["coords"]):
+            sx, sy, sz = min(8, nx - 8 * I), min(8, ny - 8 * J), min(8, nz - 8 * K)
+            for key in out:
+                out[key][8 * K:8 * K + sz, 8 * J:8 * J + sy, 8 * I:8 * I + sx] = b[key][r, :sz, :sy, :sx]
+        return out
+
+    def stats(self):
+        """{"bricks", "max_bricks", "grid_cells", "device_bytes", "brick_share"} and the device ms of the last allocate:
+        {"allocate_mark", "allocate_commit"}"""
+        info, ms = (C.c_longlong * 4)(), (C.c_float * 2)()
+        rc = self._f["tsdf_sparse_stats"](self._h, info, ms)
+        if rc != 0:
+            _raise(self._f, "tsdf_sparse_stats", rc)
+        return {"bricks": int(info[0]), "max_bricks": int(info[1]), "grid_cells": int(info[2]), "device_bytes": int(info[3]),
+                "brick_share": float(info[0]) / float(info[2]), "allocate_mark": float(ms[0]), "allocate_commit": float(ms[1])}
 
 
 def write_ply_mesh(path, xyz, tri, rgb=None):

@@ -18,6 +18,15 @@ through the integration, the bytes each pass must at least move and their share 
 points per axis, once, with a check that both agree bit for bit.  Medians of --reps repetitions after --warmup; every repetition
 integrates into a fresh volume.  --trace: two repetitions and no statement, for
 `rocprofv3 --kernel-trace --stats -- python tools/bench_tsdf.py --trace` (never together with counters).
+
+--sparse: the brick-sparse volume (mesh.SparseVolume; csrc/pm_tsdf_sparse.hpp) beside the dense one on the same
+workload: per size of --sizes a dense and a sparse volume alternate, repetition by repetition, in this process, and the sizes of
+--sparse-sizes (default 1024) run sparse alone.  Per size: the device ms of allocate (marking; scan + commit), integrate and the four
+mesh passes, the bricks and their share of the brick grid, the device bytes both volumes hold between calls and the mesh scratch
+(12 bytes per dense voxel, per existing voxel), vertices and triangles beside the dense counts (the sparse mesh is a sub-mesh: the
+share of dense triangles it misses is 1 - sparse / dense), and the ratios dense / sparse.  --coverage-size N (default 256, 0: skip):
+once, the share of band voxels (a contribution with |s| <= trunc: exactly the voxels whose colour count a dense volume with colour
+raises) that lie outside the allocated bricks at --pad.  --pad (default 1.0) is an untuned starting value.
 Prints a table and one JSON line."""
 import argparse
 import importlib
@@ -72,6 +81,103 @@ def run(n, cams, depths, colors, reps, warmup, device):
     return m, {k: med(v) for k, v in ms.items()}, {k: med(v) for k, v in wall.items()}
 
 
+SPARSE_PASSES = ("allocate_mark", "allocate_commit") + PASSES
+
+
+def run_pair(n, cams, depths, reps, warmup, device, pad, with_dense):
+    """a dense and a sparse volume of n^3 alternating -> (dense mesh, dense ms, sparse mesh, sparse ms, sparse stats, wall seconds)"""
+    origin, voxel = box(n)
+    dms, sms = {k: [] for k in PASSES}, {k: [] for k in SPARSE_PASSES}
+    wall = {"dense": [], "sparse": []}
+    dm = sm = st = None
+    for r in range(warmup + reps):
+        if with_dense:
+            t0 = time.perf_counter()
+            with mesh.Volume(origin, voxel, (n, n, n), 4 * voxel, device=device) as v:
+                v.integrate(cams, depths)
+                dm = v.mesh(1)
+                p = v.pass_ms()
+            t1 = time.perf_counter()
+            if r >= warmup:
+                wall["dense"].append(t1 - t0)
+                for k in PASSES:
+                    dms[k].append(p[k])
+        t0 = time.perf_counter()
+        with mesh.SparseVolume(origin, voxel, (n, n, n), 4 * voxel, pad=pad, device=device) as v:
+            v.allocate(cams, depths)
+            v.integrate(cams, depths)
+            sm = v.mesh(1)
+            p = dict(v.pass_ms())
+            st = v.stats()
+        t1 = time.perf_counter()
+        p.update({"allocate_mark": st["allocate_mark"], "allocate_commit": st["allocate_commit"]})
+        if r >= warmup:
+            wall["sparse"].append(t1 - t0)
+            for k in SPARSE_PASSES:
+                sms[k].append(p[k])
+    return (dm, {k: med(v) for k, v in dms.items()} if with_dense else None, sm, {k: med(v) for k, v in sms.items()}, st,
+            {k: med(v) for k, v in wall.items() if v})
+
+
+def coverage(n, cams, depths, device, pad):
+    """the share of band voxels outside the allocated bricks: the band from a dense volume with (grey, all-zero) colour, whose colour
+    count rises exactly where a contribution has |s| <= trunc"""
+    origin, voxel = box(n)
+    grey = [np.zeros(d.shape, np.uint8) for d in depths]
+    with mesh.Volume(origin, voxel, (n, n, n), 4 * voxel, color=True, device=device) as v:
+        v.integrate(cams, depths, grey)
+        band = v.get()["color"][..., 3] > 0
+    with mesh.SparseVolume(origin, voxel, (n, n, n), 4 * voxel, pad=pad, device=device) as v:
+        v.allocate(cams, depths)
+        coords = v.bricks()
+    b = (n + 7) // 8
+    bricks = np.zeros((b, b, b), bool)
+    bricks[coords[:, 2], coords[:, 1], coords[:, 0]] = True
+    exists = np.repeat(np.repeat(np.repeat(bricks, 8, 0), 8, 1), 8, 2)[:n, :n, :n]
+    return int(band.sum()), int((band & ~exists).sum())
+
+
+def main_sparse(args, cams, depths, w, h, reps, warmup):
+    sizes = [(int(s), True) for s in args.sizes.split(",") if s.strip()] + [(int(s), False) for s in args.sparse_sizes.split(",") if s.strip()]
+    out = {"views": args.views, "size": [w, h], "sparse": True, "pad": args.pad, "reps": reps, "warmup": warmup, "sizes": {}}
+    print(f"{args.views} views of {w} x {h}, no colour, truncation 4 voxels, min_weight 1, pad {args.pad} (untuned); dense and sparse alternating")
+    print(f"{'n':>5} {'pass':>16} {'dense ms':>9} {'sparse ms':>9} {'ratio':>7}")
+    for n, with_dense in sizes:
+        dm, dms, sm, sms, st, wall = run_pair(n, cams, depths, reps, warmup, args.device, args.pad, with_dense)
+        rec = {"bricks": st["bricks"], "grid_cells": st["grid_cells"], "brick_share": round(st["brick_share"], 5),
+               "sparse_bytes_held": st["device_bytes"], "sparse_mesh_scratch": 12 * 512 * st["bricks"],
+               "sparse_ms": {k: round(v, 4) for k, v in sms.items()}, "sparse_vertices": len(sm["xyz"]), "sparse_triangles": len(sm["tri"]),
+               "wall_s": {k: round(v, 4) for k, v in wall.items()}}
+        s_int = sms["allocate_mark"] + sms["allocate_commit"] + sms["integrate"]
+        s_mesh = sum(sms[k] for k in PASSES[1:])
+        rec["sparse_sum_ms"] = {"allocate+integrate": round(s_int, 4), "mesh": round(s_mesh, 4)}
+        for k in SPARSE_PASSES:
+            d = dms[k] if with_dense and k in PASSES else None
+            ratio = f"{d / sms[k]:7.2f}" if d and sms[k] > 0 else f"{'':>7}"
+            print(f"{n:>5} {k:>16} {d if d is not None else float('nan'):9.3f} {sms[k]:9.3f} {ratio}")
+        if with_dense:
+            d_mesh = sum(dms[k] for k in PASSES[1:])
+            rec.update({"dense_ms": {k: round(v, 4) for k, v in dms.items()}, "dense_vertices": len(dm["xyz"]), "dense_triangles": len(dm["tri"]),
+                        "dense_bytes_held": 8 * n ** 3, "dense_mesh_scratch": 12 * n ** 3,
+                        "dense_sum_ms": {"integrate": round(dms["integrate"], 4), "mesh": round(d_mesh, 4)},
+                        "ratio_dense_over_sparse": {"integrate_vs_allocate+integrate": round(dms["integrate"] / s_int, 3), "mesh": round(d_mesh / s_mesh, 3),
+                                                    "bytes_held": round(8 * n ** 3 / st["device_bytes"], 3)},
+                        "dense_triangles_missing_share": round(1.0 - len(sm["tri"]) / max(len(dm["tri"]), 1), 6)})
+            print(f"{n:>5} sums: dense integrate {dms['integrate']:.3f} + mesh {d_mesh:.3f} ms; sparse allocate + integrate {s_int:.3f} + mesh {s_mesh:.3f} ms")
+            print(f"{n:>5} triangles dense {len(dm['tri'])}, sparse {len(sm['tri'])}; vertices dense {len(dm['xyz'])}, sparse {len(sm['xyz'])}")
+        else:
+            print(f"{n:>5} sums: sparse allocate + integrate {s_int:.3f} + mesh {s_mesh:.3f} ms; {len(sm['xyz'])} vertices, {len(sm['tri'])} triangles")
+        print(f"{n:>5} bricks {st['bricks']} of {st['grid_cells']} ({100 * st['brick_share']:.2f} %); held: sparse {st['device_bytes'] / 1e6:.1f} MB"
+              + (f", dense {8 * n ** 3 / 1e6:.1f} MB" if with_dense else "") + f"; mesh scratch: sparse {12 * 512 * st['bricks'] / 1e6:.1f} MB"
+              + (f", dense {12 * n ** 3 / 1e6:.1f} MB" if with_dense else ""))
+        out["sizes"][str(n)] = rec
+    if args.coverage_size > 0:
+        band, outside = coverage(args.coverage_size, cams, depths, args.device, args.pad)
+        out["coverage"] = {"n": args.coverage_size, "band_voxels": band, "outside_bricks": outside, "share_outside": round(outside / max(band, 1), 6)}
+        print(f"coverage at {args.coverage_size}^3, pad {args.pad}: {outside} of {band} band voxels lie outside the allocated bricks")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="256,512")
@@ -84,6 +190,10 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--no-statement", action="store_true")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--sparse", action="store_true", help="the brick-sparse volume beside the dense one")
+    ap.add_argument("--sparse-sizes", default="1024", help="--sparse: sizes that run sparse alone")
+    ap.add_argument("--pad", type=float, default=1.0, help="--sparse: voxels around a ray sample whose bricks are allocated; 1.0 is an untuned starting value")
+    ap.add_argument("--coverage-size", type=int, default=256, help="--sparse: the size at which the band voxels outside the bricks are counted (0: skip)")
     args = ap.parse_args()
     w, h = (int(v) for v in args.size.lower().split("x"))
     sizes = [int(s) for s in args.sizes.split(",") if s.strip()]
@@ -94,6 +204,10 @@ def main():
     views = sc.views[:args.views]
     cams, depths = [v.cam for v in views], [v.gt_depth for v in views]
     colors = [v.image.astype(np.uint8) for v in views] if args.color else None
+    if args.sparse:
+        if args.color:
+            raise SystemExit("--sparse measures without colour")
+        return main_sparse(args, cams, depths, w, h, reps, warmup)
     pixels = args.views * w * h
     out = {"views": args.views, "size": [w, h], "color": bool(args.color), "reps": reps, "warmup": warmup, "sizes": {}}
     per_vox = 48 if args.color else 16

@@ -4,6 +4,7 @@ level set is extracted by marching tetrahedra (mp-mvs_amd/mesh.py; csrc/pm_tsdf.
 
     python tools/mesh_ply.py --dense_folder D --output mesh.ply --voxel V [--trunc 4V] [--min_weight 2]
                              [--bbox x0 y0 z0 x1 y1 z1 | --bbox_from MPMVS_model.ply --bbox_percentile 1]
+                             [--sparse [--pad 1.0] [--max_bricks N]]
 
 Reads cams/<id>_cam.txt, images/<id>.* and <result_folder>/2333_<id>/depths.dmb (result_folder: D/MPMVS) with the readers of
 mp-mvs_amd/hostlib.py; a camera is rescaled to the size of its depth map as the fusion does, and the image is sampled at the map's
@@ -12,7 +13,12 @@ mpmvs_tsdf_integrate in batches of --batch, so only one batch of maps is in host
 --bbox_percentile .. 100 - --bbox_percentile range per axis of the points of --bbox_from (default: <result_folder>/MPMVS_model.ply),
 grown by the truncation distance.  The volume is dense: (box / voxel)^3 voxels, refused above --max_voxels.
 --trunc (4 voxels) and --min_weight (2) are untuned starting values, not tuned on any real scene.
-Prints one JSON line: n_vox, views, vertices, triangles, device ms per pass, wall seconds."""
+--sparse: a brick-sparse volume (mesh.SparseVolume): the views are read twice, first to allocate the bricks of
+8 x 8 x 8 voxels within --pad voxels (default 1.0, an untuned starting value) of the samples along every depth pixel's ray through the
+truncation band, at most --max_bricks of them (default: the whole brick grid, at most 2^21), then to integrate; the box is virtual
+and --max_voxels does not apply.  The mesh is a sub-mesh of the dense one: the same vertices, the triangles whose corners all exist.
+Prints one JSON line: n_vox, views, vertices, triangles, device ms per pass, wall seconds; with --sparse also bricks, brick_share and
+device_bytes."""
 import argparse
 import glob
 import importlib
@@ -53,8 +59,13 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--no_color", action="store_true")
     ap.add_argument("--max_voxels", type=int, default=1 << 30)
+    ap.add_argument("--sparse", action="store_true", help="a brick-sparse volume: allocate from all views, then integrate")
+    ap.add_argument("--pad", type=float, default=1.0, help="--sparse: voxels around a ray sample whose bricks are allocated; 1.0 is an untuned starting value")
+    ap.add_argument("--max_bricks", type=int, help="--sparse: the cap on allocated bricks (default: the whole brick grid, at most 2^21)")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if not args.sparse and (args.pad != 1.0 or args.max_bricks is not None):
+        raise SystemExit("--pad and --max_bricks go with --sparse")
     if not (math.isfinite(args.voxel) and args.voxel > 0):
         raise SystemExit("--voxel must be finite and positive")
     trunc = 4.0 * args.voxel if args.trunc is None else args.trunc
@@ -94,7 +105,7 @@ def main(argv=None):
         raise SystemExit(f"the box {lo.tolist()} .. {hi.tolist()} is empty or not finite")
     dims = [int(math.ceil((hi[a] - lo[a]) / args.voxel)) + 1 for a in range(3)]
     n_vox = dims[0] * dims[1] * dims[2]
-    if n_vox > min(args.max_voxels, 1 << 30):
+    if not args.sparse and n_vox > min(args.max_voxels, 1 << 30):
         raise SystemExit(f"{dims[0]} x {dims[1]} x {dims[2]} = {n_vox} voxels exceed --max_voxels {min(args.max_voxels, 1 << 30)}: raise --voxel or shrink the box")
 
     def load(vid, path):
@@ -115,8 +126,23 @@ def main(argv=None):
         return cam, d, np.ascontiguousarray(img)
 
     device_ms = {"integrate": 0.0}
+    sparse = None
     try:
-        with mesh.Volume(lo.astype(np.float32), args.voxel, dims, trunc, color=not args.no_color, device=args.device) as vol:
+        if args.sparse:
+            volume = mesh.SparseVolume(lo.astype(np.float32), args.voxel, dims, trunc, color=not args.no_color, pad=args.pad, max_bricks=args.max_bricks,
+                                       device=args.device)
+        else:
+            volume = mesh.Volume(lo.astype(np.float32), args.voxel, dims, trunc, color=not args.no_color, device=args.device)
+        with volume as vol:
+            if args.sparse:
+                device_ms.update({"allocate_mark": 0.0, "allocate_commit": 0.0})
+                for b in range(0, len(views), args.batch):
+                    cams, depths, _ = zip(*(load(vid, path) for vid, path in views[b:b + args.batch]))
+                    vol.allocate(cams, depths)
+                    st = vol.stats()
+                    device_ms["allocate_mark"] += st["allocate_mark"]
+                    device_ms["allocate_commit"] += st["allocate_commit"]
+                sparse = {k: vol.stats()[k] for k in ("bricks", "brick_share", "device_bytes")}
             for b in range(0, len(views), args.batch):
                 cams, depths, images = zip(*(load(vid, path) for vid, path in views[b:b + args.batch]))
                 vol.integrate(cams, depths, None if args.no_color else images)
@@ -134,6 +160,8 @@ def main(argv=None):
            "views": len(views), "vertices": int(len(m["xyz"])), "triangles": int(len(m["tri"])),
            "device_ms": {k: round(v, 4) for k, v in device_ms.items()},
            "seconds": {"integrate": round(t1 - t0, 4), "mesh": round(t2 - t1, 4), "write": round(t3 - t2, 4), "wall": round(t3 - t0, 4)}, "output": args.output}
+    if sparse is not None:
+        res.update(sparse)
     print(json.dumps(res))
     return res
 
