@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -50,62 +51,66 @@ struct mpmvs_tsdf {
     float alloc_ms[2] = {0.0f, 0.0f};
 };
 
-// the first call that needs the device: the stream, the events and the volume, all zero
+// the first call that needs the device: the stream and the events; then a dense handle's volume, all zero, or a brick-sparse
+// handle's brick grid, all -1
 static int tsdf_ready(mpmvs_tsdf* h) {
     CALLCHK(enter_device(h->device));
     if (h->ready) return 0;
     if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     for (hipEvent_t& e : h->ev)
         if (!e) CALLCHK(hipEventCreate(&e));
-    if (!h->d_sum) CALLCHK(pool_malloc(&h->d_sum, h->n_vox * 4));
-    if (!h->d_weight) CALLCHK(pool_malloc(&h->d_weight, h->n_vox * 4));
-    if (h->with_color && !h->d_color) CALLCHK(pool_malloc(&h->d_color, h->n_vox * 16));
-    CALLCHK(hipMemsetAsync(h->d_sum, 0, h->n_vox * 4, h->stream));
-    CALLCHK(hipMemsetAsync(h->d_weight, 0, h->n_vox * 4, h->stream));
-    if (h->with_color) CALLCHK(hipMemsetAsync(h->d_color, 0, h->n_vox * 16, h->stream));
-    CALLCHK(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return 0;
-}
-
-// a brick-sparse handle's first call that needs the device: the stream, the events and the brick grid, all -1
-static int tsdf_sparse_ready(mpmvs_tsdf* h) {
-    CALLCHK(enter_device(h->device));
-    if (h->ready) return 0;
-    if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev)
-        if (!e) CALLCHK(hipEventCreate(&e));
-    if (!h->d_grid) CALLCHK(pool_malloc(&h->d_grid, h->n_grid * 4));
-    CALLCHK(hipMemsetAsync(h->d_grid, 0xff, h->n_grid * 4, h->stream));
+    if (h->sparse) {
+        if (!h->d_grid) CALLCHK(pool_malloc(&h->d_grid, h->n_grid * 4));
+        CALLCHK(hipMemsetAsync(h->d_grid, 0xff, h->n_grid * 4, h->stream));
+    } else {
+        if (!h->d_sum) CALLCHK(pool_malloc(&h->d_sum, h->n_vox * 4));
+        if (!h->d_weight) CALLCHK(pool_malloc(&h->d_weight, h->n_vox * 4));
+        if (h->with_color && !h->d_color) CALLCHK(pool_malloc(&h->d_color, h->n_vox * 16));
+        CALLCHK(hipMemsetAsync(h->d_sum, 0, h->n_vox * 4, h->stream));
+        CALLCHK(hipMemsetAsync(h->d_weight, 0, h->n_vox * 4, h->stream));
+        if (h->with_color) CALLCHK(hipMemsetAsync(h->d_color, 0, h->n_vox * 16, h->stream));
+    }
     CALLCHK(hipStreamSynchronize(h->stream));
     h->ready = true;
     return 0;
 }
 static TsdfBricks tsdf_bricks(const mpmvs_tsdf* h) { return TsdfBricks{h->bx, h->by, h->bz, h->d_grid, h->d_list}; }
 
-int mpmvs_tsdf_create(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, mpmvs_tsdf** out) {
-    if (!out || !origin || !dims) return call_fail(-2, "tsdf create: bad argument");
-    if (device < 0) return call_fail(-2, "tsdf create: negative device");
+// the lattice arguments of both create calls (`name` is the call's, for the message): everything but the far corner, which each
+// call asks for with tsdf_new_handle after the size checks of its own
+static int tsdf_check_lattice(const std::string& name, int device, const float* origin, float voxel, const int* dims, float trunc, mpmvs_tsdf** out) {
+    if (!out || !origin || !dims) return call_fail(-2, name + ": bad argument");
+    if (device < 0) return call_fail(-2, name + ": negative device");
     for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(origin[a])) return call_fail(-2, "tsdf create: the origin must be finite");
-        if (dims[a] < 1) return call_fail(-2, "tsdf create: every dimension must be at least 1");
+        if (!std::isfinite(origin[a])) return call_fail(-2, name + ": the origin must be finite");
+        if (dims[a] < 1) return call_fail(-2, name + ": every dimension must be at least 1");
     }
-    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return call_fail(-2, "tsdf create: voxel must be finite and positive");
-    if (!std::isfinite(trunc) || !(trunc > 0.0f)) return call_fail(-2, "tsdf create: trunc must be finite and positive");
-    const long long n_vox = ((long long)dims[0] * (long long)dims[1] > kTsdfMaxVoxels) ? kTsdfMaxVoxels + 1 : (long long)dims[0] * (long long)dims[1] * (long long)dims[2];
-    if (n_vox > kTsdfMaxVoxels) return call_fail(-3, "tsdf create: more than 2^30 voxels");
+    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return call_fail(-2, name + ": voxel must be finite and positive");
+    if (!std::isfinite(trunc) || !(trunc > 0.0f)) return call_fail(-2, name + ": trunc must be finite and positive");
+    return 0;
+}
+// the last check of the lattice, then the handle with the fields that both kinds of volume have
+static int tsdf_new_handle(const std::string& name, int device, const float* origin, float voxel, const int* dims, float trunc, int with_color, mpmvs_tsdf** out) {
     for (int a = 0; a < 3; ++a)
-        if (!std::isfinite((float)((double)origin[a] + (double)(dims[a] - 1) * (double)voxel))) return call_fail(-2, "tsdf create: the far corner of the volume is not finite in fp32");
+        if (!std::isfinite((float)((double)origin[a] + (double)(dims[a] - 1) * (double)voxel))) return call_fail(-2, name + ": the far corner of the volume is not finite in fp32");
     mpmvs_tsdf* h = new mpmvs_tsdf;
     h->device = device;
     h->V.nx = dims[0]; h->V.ny = dims[1]; h->V.nz = dims[2];
     h->V.trunc = trunc;
     for (int a = 0; a < 3; ++a) h->V.o[a] = (double)origin[a];
     h->V.voxel = (double)voxel;
-    h->n_vox = (size_t)n_vox;
+    h->n_vox = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];   // of a brick-sparse volume: virtual
     h->with_color = with_color != 0;
     *out = h;
     return 0;
+}
+
+int mpmvs_tsdf_create(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, mpmvs_tsdf** out) {
+    const int rc = tsdf_check_lattice("tsdf create", device, origin, voxel, dims, trunc, out);
+    if (rc) return rc;
+    if ((long long)dims[0] * (long long)dims[1] > kTsdfMaxVoxels || (long long)dims[0] * (long long)dims[1] * (long long)dims[2] > kTsdfMaxVoxels)
+        return call_fail(-3, "tsdf create: more than 2^30 voxels");
+    return tsdf_new_handle("tsdf create", device, origin, voxel, dims, trunc, with_color, out);
 }
 
 void mpmvs_tsdf_destroy(mpmvs_tsdf* h) {
@@ -122,55 +127,90 @@ void mpmvs_tsdf_destroy(mpmvs_tsdf* h) {
     delete h;
 }
 
-// views [v0, v1) of an integrate call: the images up, one launch, its time added to ms[0]
-static int tsdf_integrate_chunk(mpmvs_tsdf* h, int v0, int v1, const mpmvs_camera* cams, const float* const* depths, const unsigned char* const* colors, int channels) {
-    const hipStream_t st = h->stream;
-    size_t pixels = 0;
-    for (int v = v0; v < v1; ++v) pixels += (size_t)cams[v].width * (size_t)cams[v].height;
-    Scratch d_depth(st), d_col(st);
-    CALLCHK(d_depth.alloc(pixels * 4));
-    if (colors) CALLCHK(d_col.alloc(pixels * (size_t)channels));
-    // the block test of pm_tsdf.hpp needs numbers throughout: every |P| of the volume and every camera entry it reads at most 2^40
-    float pmax = 0.0f;
-    const int last[3] = {h->V.nx - 1, h->V.ny - 1, h->V.nz - 1};
-    for (int a = 0; a < 3; ++a) pmax = std::max(pmax, std::max(std::fabs(tsdf_pos(h->V, a, 0)), std::fabs(tsdf_pos(h->V, a, last[a]))));
-    TsdfChunkArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.n = v1 - v0;
-    A.channels = colors ? channels : 0;
-    size_t at = 0;
-    for (int v = v0; v < v1; ++v) {
-        const mpmvs_camera& c = cams[v];
-        TsdfView& W = A.v[v - v0];
-        std::memcpy(W.R, c.R, sizeof W.R);
-        std::memcpy(W.t, c.t, sizeof W.t);
-        W.K0 = c.K[0]; W.K2 = c.K[2]; W.K4 = c.K[4]; W.K5 = c.K[5];
-        W.w = c.width; W.h = c.height;
-        W.cull = pmax <= kTsdfCullBound;
-        for (float x : c.R) W.cull = W.cull && std::fabs(x) <= kTsdfCullBound;   // false for a NaN
-        for (float x : {c.t[0], c.t[1], c.t[2], W.K0, W.K2, W.K4, W.K5}) W.cull = W.cull && std::fabs(x) <= kTsdfCullBound;
-        const size_t npix = (size_t)c.width * (size_t)c.height;
-        W.depth = d_depth.as<float>() + at;
-        CALLCHK(hipMemcpyAsync(d_depth.as<float>() + at, depths[v], npix * 4, hipMemcpyHostToDevice, st));
-        if (colors) {
-            W.color = d_col.as<unsigned char>() + at * (size_t)channels;
-            CALLCHK(hipMemcpyAsync(d_col.as<unsigned char>() + at * (size_t)channels, colors[v], npix * (size_t)channels, hipMemcpyHostToDevice, st));
-        }
-        at += npix;
+// the views of an integrate or allocate call (`name` is the call's, for the message): every -2 of every view before any -3
+static int tsdf_check_views(const std::string& name, int n_views, const mpmvs_camera* cams, const float* const* depths, const unsigned char* const* colors) {
+    if (!cams || !depths) return call_fail(-2, name + ": bad argument");
+    for (int v = 0; v < n_views; ++v) {
+        if (!depths[v]) return call_fail(-2, name + ": view " + std::to_string(v) + " has no depth map");
+        if (colors && !colors[v]) return call_fail(-2, name + ": view " + std::to_string(v) + " has no colour image");
+        if (cams[v].width <= 0 || cams[v].height <= 0) return call_fail(-2, name + ": view " + std::to_string(v) + " has a non-positive width or height");
     }
-    const size_t tiles = (size_t)((h->V.nx + kTsdfTileX - 1) / kTsdfTileX) * (size_t)((h->V.ny + kTsdfTileY - 1) / kTsdfTileY) * (size_t)h->V.nz;
-    CALLCHK(hipEventRecord(h->ev[0], st));
-    if (h->sparse)
-        hipLaunchKernelGGL(k_tsdf_sparse_integrate, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), A, h->d_sum, h->d_weight,
-                           h->with_color ? h->d_color : (uint4*)nullptr);
-    else
-        hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), 0, st, h->V, A, h->d_sum, h->d_weight, h->with_color ? h->d_color : (uint4*)nullptr);
+    for (int v = 0; v < n_views; ++v) {
+        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return call_fail(-3, name + ": view " + std::to_string(v) + " is wider or higher than 2^24");
+        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
+            return call_fail(-3, name + ": view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
+    }
+    return 0;
+}
+
+// the views in call order, cut into chunks [v0, v1) of at most kTsdfChunk views and (beyond the first view) kTsdfChunkPixels pixels
+static int tsdf_for_chunks(int n_views, const mpmvs_camera* cams, const std::function<int(int, int)>& chunk) {
+    for (int v0 = 0; v0 < n_views;) {
+        int v1 = v0 + 1;
+        size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
+        while (v1 < n_views && v1 - v0 < kTsdfChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kTsdfChunkPixels) {
+            pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
+            ++v1;
+        }
+        const int rc = chunk(v0, v1);
+        if (rc) return rc;
+        v0 = v1;
+    }
+    return 0;
+}
+
+// views [v0, v1) of a call as kernel arguments: their cameras in A, their depth maps and, if given, their colour images on the device
+struct TsdfChunk {
+    Scratch d_depth, d_col;
+    TsdfChunkArgs A;
+    explicit TsdfChunk(hipStream_t st) : d_depth(st), d_col(st) {}
+    int upload(const mpmvs_tsdf* h, int v0, int v1, const mpmvs_camera* cams, const float* const* depths, const unsigned char* const* colors, int channels) {
+        const hipStream_t st = h->stream;
+        size_t pixels = 0;
+        for (int v = v0; v < v1; ++v) pixels += (size_t)cams[v].width * (size_t)cams[v].height;
+        CALLCHK(d_depth.alloc(pixels * 4));
+        if (colors) CALLCHK(d_col.alloc(pixels * (size_t)channels));
+        // the block test of pm_tsdf.hpp needs numbers throughout: every |P| of the volume and every camera entry it reads at most 2^40
+        float pmax = 0.0f;
+        const int last[3] = {h->V.nx - 1, h->V.ny - 1, h->V.nz - 1};
+        for (int a = 0; a < 3; ++a) pmax = std::max(pmax, std::max(std::fabs(tsdf_pos(h->V, a, 0)), std::fabs(tsdf_pos(h->V, a, last[a]))));
+        std::memset(&A, 0, sizeof A);
+        A.n = v1 - v0;
+        A.channels = colors ? channels : 0;
+        size_t at = 0;
+        for (int v = v0; v < v1; ++v) {
+            const mpmvs_camera& c = cams[v];
+            TsdfView& W = A.v[v - v0];
+            std::memcpy(W.R, c.R, sizeof W.R);
+            std::memcpy(W.t, c.t, sizeof W.t);
+            W.K0 = c.K[0]; W.K2 = c.K[2]; W.K4 = c.K[4]; W.K5 = c.K[5];
+            W.w = c.width; W.h = c.height;
+            W.cull = pmax <= kTsdfCullBound;
+            for (float x : c.R) W.cull = W.cull && std::fabs(x) <= kTsdfCullBound;   // false for a NaN
+            for (float x : {c.t[0], c.t[1], c.t[2], W.K0, W.K2, W.K4, W.K5}) W.cull = W.cull && std::fabs(x) <= kTsdfCullBound;
+            const size_t npix = (size_t)c.width * (size_t)c.height;
+            W.depth = d_depth.as<float>() + at;
+            CALLCHK(hipMemcpyAsync(d_depth.as<float>() + at, depths[v], npix * 4, hipMemcpyHostToDevice, st));
+            if (colors) {
+                W.color = d_col.as<unsigned char>() + at * (size_t)channels;
+                CALLCHK(hipMemcpyAsync(d_col.as<unsigned char>() + at * (size_t)channels, colors[v], npix * (size_t)channels, hipMemcpyHostToDevice, st));
+            }
+            at += npix;
+        }
+        return 0;
+    }
+};
+
+// one launch between ev[a] and ev[b] of the handle, waited for; its time is added to *ms
+static int tsdf_timed(mpmvs_tsdf* h, int a, int b, float* ms, const std::function<void()>& launch) {
+    CALLCHK(hipEventRecord(h->ev[a], h->stream));
+    launch();
     CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    CALLCHK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms[0] += ms;
+    CALLCHK(hipEventRecord(h->ev[b], h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
+    float t = 0.0f;
+    CALLCHK(hipEventElapsedTime(&t, h->ev[a], h->ev[b]));
+    *ms += t;
     return 0;
 }
 
@@ -180,39 +220,32 @@ int mpmvs_tsdf_integrate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, c
     if (!colors && h->with_color && n_views > 0) return call_fail(-2, "tsdf integrate: a volume with colour needs colours");
     if (colors && color_channels != 1 && color_channels != 3) return call_fail(-2, "tsdf integrate: color_channels must be 1 or 3");
     if (n_views == 0) return 0;
-    if (!cams || !depths) return call_fail(-2, "tsdf integrate: bad argument");
-    for (int v = 0; v < n_views; ++v) {
-        if (!depths[v]) return call_fail(-2, "tsdf integrate: view " + std::to_string(v) + " has no depth map");
-        if (colors && !colors[v]) return call_fail(-2, "tsdf integrate: view " + std::to_string(v) + " has no colour image");
-        if (cams[v].width <= 0 || cams[v].height <= 0) return call_fail(-2, "tsdf integrate: view " + std::to_string(v) + " has a non-positive width or height");
-    }
-    for (int v = 0; v < n_views; ++v) {
-        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return call_fail(-3, "tsdf integrate: view " + std::to_string(v) + " is wider or higher than 2^24");
-        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
-            return call_fail(-3, "tsdf integrate: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
-    }
+    const int rc = tsdf_check_views("tsdf integrate", n_views, cams, depths, colors);
+    if (rc) return rc;
     if (h->views + (long long)n_views > kTsdfMaxViews) return call_fail(-3, "tsdf integrate: more than 2^23 views over the life of the volume");
     if (h->sparse && h->n_bricks == 0) {   // no voxel exists: nothing to add to
         h->ms[0] = 0.0f;
         h->views += n_views;
         return 0;
     }
-    const int rc = h->sparse ? tsdf_sparse_ready(h) : tsdf_ready(h);
-    if (rc) return rc;
+    const int rc2 = tsdf_ready(h);
+    if (rc2) return rc2;
     h->ms[0] = 0.0f;
-    for (int v0 = 0; v0 < n_views;) {
-        int v1 = v0 + 1;
-        size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
-        while (v1 < n_views && v1 - v0 < kTsdfChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kTsdfChunkPixels) {
-            pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
-            ++v1;
-        }
-        const int rc2 = tsdf_integrate_chunk(h, v0, v1, cams, depths, colors, color_channels);
-        if (rc2) return rc2;
-        h->views += v1 - v0;
-        v0 = v1;
-    }
-    return 0;
+    const hipStream_t st = h->stream;
+    const size_t tiles = (size_t)((h->V.nx + kTsdfTileX - 1) / kTsdfTileX) * (size_t)((h->V.ny + kTsdfTileY - 1) / kTsdfTileY) * (size_t)h->V.nz;
+    uint4* const d_color = h->with_color ? h->d_color : nullptr;
+    // per chunk: the images up, one launch, its time added to ms[0]
+    return tsdf_for_chunks(n_views, cams, [&](int v0, int v1) {
+        TsdfChunk c(st);
+        const int rc3 = c.upload(h, v0, v1, cams, depths, colors, color_channels);
+        if (rc3) return rc3;
+        const int rc4 = tsdf_timed(h, 0, 1, &h->ms[0], [&] {
+            if (h->sparse) hipLaunchKernelGGL(k_tsdf_sparse_integrate, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), c.A, h->d_sum, h->d_weight, d_color);
+            else hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), 0, st, h->V, c.A, h->d_sum, h->d_weight, d_color);
+        });
+        if (!rc4) h->views += v1 - v0;
+        return rc4;
+    });
 }
 
 int mpmvs_tsdf_get(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* color4) {
@@ -256,14 +289,17 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     CALLCHK(d_grand.alloc(16));
     int* vtile = d_totals.as<int>();
     int* ttile = vtile + n_tiles;
+    // passes 1, 3 and 4: a thread per voxel of the lattice, or a block per brick; the brick-sparse kernels take the brick table where
+    // the dense ones take the number of voxels, and the rest of the argument list is the same
+    auto launch = [&](auto dense, auto sparse, auto... args) {
+        if (h->sparse) hipLaunchKernelGGL(sparse, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), args...);
+        else hipLaunchKernelGGL(dense, dim3(blocks), dim3(256), 0, st, h->V, n, args...);
+    };
+    const uint4* const d_color = h->with_color ? h->d_color : nullptr;
     CALLCHK(hipMemsetAsync(d_grand.p, 0, 16, st));
     CALLCHK(hipEventRecord(h->ev[0], st));
     CALLCHK(hipMemsetAsync(d_mask.p, 0, n * 4, st));
-    if (h->sparse)
-        hipLaunchKernelGGL(k_tsdf_sparse_mark, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight, min_weight,
-                           d_mask.as<uint32_t>(), d_tcount.as<int>());
-    else
-        hipLaunchKernelGGL(k_tsdf_mark, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>());
+    launch(k_tsdf_mark, k_tsdf_sparse_mark, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>());
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[1], st));
     hipLaunchKernelGGL(k_tsdf_scan_tiles, dim3((unsigned)n_tiles), dim3(kScanBlock), 0, st, d_mask.as<uint32_t>(), n, d_vexcl.as<int>(), d_tcount.as<int>(), vtile, n_tiles);
@@ -290,21 +326,12 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     if (h->with_color) CALLCHK(d_rgb.alloc(nv * 3));
     CALLCHK(d_tri.alloc(nt * 12));
     CALLCHK(hipEventRecord(h->ev[5], st));
-    if (h->sparse)
-        hipLaunchKernelGGL(k_tsdf_sparse_vertices, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight,
-                           h->with_color ? h->d_color : (const uint4*)nullptr, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(),
-                           h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
-    else
-        hipLaunchKernelGGL(k_tsdf_vertices, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, h->with_color ? h->d_color : (const uint4*)nullptr,
-                           d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(), h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
+    launch(k_tsdf_vertices, k_tsdf_sparse_vertices, h->d_sum, h->d_weight, d_color, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(),
+           h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[3], st));
-    if (h->sparse)
-        hipLaunchKernelGGL(k_tsdf_sparse_triangles, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), h->d_sum, h->d_weight, min_weight,
-                           d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_tcount.as<int>(), ttile, d_tri.as<int32_t>());
-    else
-        hipLaunchKernelGGL(k_tsdf_triangles, dim3(blocks), dim3(256), 0, st, h->V, n, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile,
-                           d_tcount.as<int>(), ttile, d_tri.as<int32_t>());
+    launch(k_tsdf_triangles, k_tsdf_sparse_triangles, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_tcount.as<int>(), ttile,
+           d_tri.as<int32_t>());
     CALLCHK(hipGetLastError());
     CALLCHK(hipEventRecord(h->ev[4], st));
     float* hx = (float*)std::malloc(nv * 12);
@@ -342,7 +369,7 @@ long long mpmvs_tsdf_mesh(mpmvs_tsdf* h, int min_weight, float** out_xyz, unsign
     long long nt = 0, nv = 0;
     h->ms[1] = h->ms[2] = h->ms[3] = h->ms[4] = 0.0f;
     if (h->V.nx > 1 && h->V.ny > 1 && h->V.nz > 1 && !(h->sparse && h->n_bricks == 0)) {   // else there is no cell: nothing is launched
-        const int rc = h->sparse ? tsdf_sparse_ready(h) : tsdf_ready(h);
+        const int rc = tsdf_ready(h);
         if (rc) return rc;
         nv = tsdf_mesh_device(h, min_weight, &xyz, &rgb, &tri, &nt);
         if (nv < 0) return nv;
@@ -365,14 +392,8 @@ constexpr long long kTsdfMaxGrid = 1ll << 24, kTsdfMaxBricks = 1ll << 21, kTsdfM
 
 int mpmvs_tsdf_create_sparse(int device, const float origin[3], float voxel, const int dims[3], float trunc, int with_color, float pad, long long max_bricks,
                              mpmvs_tsdf** out) {
-    if (!out || !origin || !dims) return call_fail(-2, "tsdf create_sparse: bad argument");
-    if (device < 0) return call_fail(-2, "tsdf create_sparse: negative device");
-    for (int a = 0; a < 3; ++a) {
-        if (!std::isfinite(origin[a])) return call_fail(-2, "tsdf create_sparse: the origin must be finite");
-        if (dims[a] < 1) return call_fail(-2, "tsdf create_sparse: every dimension must be at least 1");
-    }
-    if (!std::isfinite(voxel) || !(voxel > 0.0f)) return call_fail(-2, "tsdf create_sparse: voxel must be finite and positive");
-    if (!std::isfinite(trunc) || !(trunc > 0.0f)) return call_fail(-2, "tsdf create_sparse: trunc must be finite and positive");
+    const int rc = tsdf_check_lattice("tsdf create_sparse", device, origin, voxel, dims, trunc, out);
+    if (rc) return rc;
     if (!std::isfinite(pad) || !(pad >= 0.0f && pad <= 8.0f)) return call_fail(-2, "tsdf create_sparse: pad must be finite and in [0, 8] voxels");
     if (max_bricks < 1) return call_fail(-2, "tsdf create_sparse: max_bricks must be at least 1");
     if (max_bricks > kTsdfMaxBricks) return call_fail(-3, "tsdf create_sparse: max_bricks above 2^21");
@@ -384,17 +405,9 @@ int mpmvs_tsdf_create_sparse(int device, const float origin[3], float voxel, con
     if (cells > kTsdfMaxGrid) return call_fail(-3, "tsdf create_sparse: more than 2^24 cells in the brick grid");
     const double ratio = std::ceil(4.0 * (double)trunc / (double)voxel);
     if (!(ratio <= (double)kTsdfMaxSamples)) return call_fail(-3, "tsdf create_sparse: trunc / voxel asks for more than 2^16 samples per ray");
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite((float)((double)origin[a] + (double)(dims[a] - 1) * (double)voxel)))
-            return call_fail(-2, "tsdf create_sparse: the far corner of the volume is not finite in fp32");
-    mpmvs_tsdf* h = new mpmvs_tsdf;
-    h->device = device;
-    h->V.nx = dims[0]; h->V.ny = dims[1]; h->V.nz = dims[2];
-    h->V.trunc = trunc;
-    for (int a = 0; a < 3; ++a) h->V.o[a] = (double)origin[a];
-    h->V.voxel = (double)voxel;
-    h->n_vox = (size_t)dims[0] * (size_t)dims[1] * (size_t)dims[2];   // virtual
-    h->with_color = with_color != 0;
+    const int rc2 = tsdf_new_handle("tsdf create_sparse", device, origin, voxel, dims, trunc, with_color, out);
+    if (rc2) return rc2;
+    mpmvs_tsdf* h = *out;
     h->sparse = true;
     h->bx = (int)b[0]; h->by = (int)b[1]; h->bz = (int)b[2];
     h->n_grid = (size_t)cells;
@@ -480,75 +493,31 @@ static int tsdf_commit(mpmvs_tsdf* h, const uint32_t* d_flags) {
     return 0;
 }
 
-// views [v0, v1) of an allocate call: the depth maps up, one marking launch, its time added to alloc_ms[0]
-static int tsdf_allocate_chunk(mpmvs_tsdf* h, int v0, int v1, const mpmvs_camera* cams, const float* const* depths, uint32_t* d_flags) {
-    const hipStream_t st = h->stream;
-    size_t pixels = 0, most = 0;
-    for (int v = v0; v < v1; ++v) {
-        pixels += (size_t)cams[v].width * (size_t)cams[v].height;
-        most = std::max(most, (size_t)cams[v].width * (size_t)cams[v].height);
-    }
-    Scratch d_depth(st);
-    CALLCHK(d_depth.alloc(pixels * 4));
-    TsdfChunkArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.n = v1 - v0;
-    size_t at = 0;
-    for (int v = v0; v < v1; ++v) {
-        const mpmvs_camera& c = cams[v];
-        TsdfView& W = A.v[v - v0];
-        std::memcpy(W.R, c.R, sizeof W.R);
-        std::memcpy(W.t, c.t, sizeof W.t);
-        W.K0 = c.K[0]; W.K2 = c.K[2]; W.K4 = c.K[4]; W.K5 = c.K[5];
-        W.w = c.width; W.h = c.height;
-        const size_t npix = (size_t)c.width * (size_t)c.height;
-        W.depth = d_depth.as<float>() + at;
-        CALLCHK(hipMemcpyAsync(d_depth.as<float>() + at, depths[v], npix * 4, hipMemcpyHostToDevice, st));
-        at += npix;
-    }
-    CALLCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(k_tsdf_alloc_mark, dim3((unsigned)((most + 255) / 256), (unsigned)A.n), dim3(256), 0, st, h->V, tsdf_bricks(h), h->alloc, A, d_flags);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    CALLCHK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->alloc_ms[0] += ms;
-    return 0;
-}
-
 int mpmvs_tsdf_allocate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, const float* const* depths) {
     if (!h || n_views < 0) return call_fail(-2, "tsdf allocate: bad argument");
     if (!h->sparse) return call_fail(-2, "tsdf allocate: the volume is dense (mpmvs_tsdf_create_sparse makes a brick-sparse one)");
     if (n_views == 0) return 0;
-    if (!cams || !depths) return call_fail(-2, "tsdf allocate: bad argument");
-    for (int v = 0; v < n_views; ++v) {
-        if (!depths[v]) return call_fail(-2, "tsdf allocate: view " + std::to_string(v) + " has no depth map");
-        if (cams[v].width <= 0 || cams[v].height <= 0) return call_fail(-2, "tsdf allocate: view " + std::to_string(v) + " has a non-positive width or height");
-    }
-    for (int v = 0; v < n_views; ++v) {
-        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return call_fail(-3, "tsdf allocate: view " + std::to_string(v) + " is wider or higher than 2^24");
-        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
-            return call_fail(-3, "tsdf allocate: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
-    }
-    const int rc = tsdf_sparse_ready(h);
+    const int rc = tsdf_check_views("tsdf allocate", n_views, cams, depths, nullptr);
     if (rc) return rc;
+    const int rc2 = tsdf_ready(h);
+    if (rc2) return rc2;
     h->alloc_ms[0] = h->alloc_ms[1] = 0.0f;
-    Scratch d_flags(h->stream);
+    const hipStream_t st = h->stream;
+    Scratch d_flags(st);
     CALLCHK(d_flags.alloc(h->n_grid * 4));
-    CALLCHK(hipMemsetAsync(d_flags.p, 0, h->n_grid * 4, h->stream));
-    for (int v0 = 0; v0 < n_views;) {
-        int v1 = v0 + 1;
-        size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
-        while (v1 < n_views && v1 - v0 < kTsdfChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kTsdfChunkPixels) {
-            pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
-            ++v1;
-        }
-        const int rc2 = tsdf_allocate_chunk(h, v0, v1, cams, depths, d_flags.as<uint32_t>());
-        if (rc2) return rc2;
-        v0 = v1;
-    }
-    return tsdf_commit(h, d_flags.as<uint32_t>());
+    CALLCHK(hipMemsetAsync(d_flags.p, 0, h->n_grid * 4, st));
+    // per chunk: the depth maps up, one marking launch (blockIdx.y: the view), its time added to alloc_ms[0]
+    const int rc3 = tsdf_for_chunks(n_views, cams, [&](int v0, int v1) {
+        TsdfChunk c(st);
+        const int rc4 = c.upload(h, v0, v1, cams, depths, nullptr, 0);
+        if (rc4) return rc4;
+        size_t most = 0;
+        for (int v = 0; v < c.A.n; ++v) most = std::max(most, (size_t)c.A.v[v].w * (size_t)c.A.v[v].h);
+        return tsdf_timed(h, 0, 1, &h->alloc_ms[0], [&] {
+            hipLaunchKernelGGL(k_tsdf_alloc_mark, dim3((unsigned)((most + 255) / 256), (unsigned)c.A.n), dim3(256), 0, st, h->V, tsdf_bricks(h), h->alloc, c.A, d_flags.as<uint32_t>());
+        });
+    });
+    return rc3 ? rc3 : tsdf_commit(h, d_flags.as<uint32_t>());
 }
 
 long long mpmvs_tsdf_bricks(mpmvs_tsdf* h, int32_t** coords) {
@@ -575,7 +544,7 @@ int mpmvs_tsdf_get_bricks(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* 
     if (!h->sparse) return call_fail(-2, "tsdf get_bricks: the volume is dense (mpmvs_tsdf_get reads it)");
     if (color4 && !h->with_color) return call_fail(-2, "tsdf get_bricks: the volume has no colour");
     if (h->n_bricks == 0) return 0;
-    const int rc = tsdf_sparse_ready(h);
+    const int rc = tsdf_ready(h);
     if (rc) return rc;
     const size_t n = (size_t)h->n_bricks * kBrickVox;
     CALLCHK(hipMemcpyAsync(sum, h->d_sum, n * 4, hipMemcpyDeviceToHost, h->stream));
@@ -598,7 +567,7 @@ int mpmvs_tsdf_set_bricks(mpmvs_tsdf* h, long long n, const int32_t* coords, con
         if (r > 0 && list[(size_t)r] <= list[(size_t)r - 1])
             return call_fail(-2, "tsdf set_bricks: the bricks must ascend strictly by linear index (brick " + std::to_string(r) + " does not)");
     }
-    const int rc = tsdf_sparse_ready(h);
+    const int rc = tsdf_ready(h);
     if (rc) return rc;
     const hipStream_t st = h->stream;
     std::vector<int32_t> grid(h->n_grid, -1);

@@ -6,9 +6,9 @@
 // Integrate (k_tsdf_integrate): a block is a tile of 64 x 4 voxels of one z layer, one thread per voxel, so a wave covers 64
 //   consecutive i and the traffic of sum / weight / colour is coalesced.  The views of a chunk are kernel arguments, indexed
 //   uniformly (scalar loads); the depth and colour images are plain arrays.  Per view the block first asks whether every voxel of
-//   its tile lies behind the camera or outside the image (tsdf_view_live: exact ranges from the four corners of the tile, by the
-//   monotonicity of rounded arithmetic, see there) and skips the view if so.  Every voxel is projected from its own position;
-//   nothing is stepped incrementally.
+//   its tile lies behind the camera or outside the image (tsdf_view_live = tsdf_box_live on one layer: exact ranges from the four
+//   corners of the tile, by the monotonicity of rounded arithmetic, see there) and skips the view if so.  Every voxel is projected
+//   from its own position; nothing is stepped incrementally.
 // Mesh: four passes, one thread per voxel (a voxel stands for the cell whose corner 000 it is, and owns the 7 edges that leave it in
 //   positive directions):
 //   1. k_tsdf_mark      per cell: the six tetrahedra, the used edges ORed into the owners' masks, the cell's triangle count (<= 12)
@@ -20,6 +20,8 @@
 // The case analysis and the winding are not typed in: tsdf_case_code builds the triangles of a case from the rule of the contract,
 // tsdf_flip_code decides the winding of every (tetrahedron, case) with the vertices at the midpoints of their edges in integer
 // arithmetic, both at compile time.
+// The bodies of passes 1, 3 and 4 (tsdf_mark_cell, tsdf_vertex_cell, tsdf_triangle_cell) are written once, over an object that says
+// where a cell's corners are stored; the brick-sparse volume of pm_tsdf_sparse.hpp runs the same bodies with its own addressing.
 // The per-thread bodies are host and device code, so that tools/mesh_check.cpp replays the passes thread by thread under the
 // sanitizers.
 #pragma once
@@ -33,7 +35,7 @@ namespace pm {
 
 constexpr int kTsdfChunk = 8;        // views per launch of the integration
 constexpr int kTsdfTileX = 64, kTsdfTileY = 4;
-constexpr float kTsdfCullBound = 0x1p40f;   // see tsdf_view_live
+constexpr float kTsdfCullBound = 0x1p40f;   // see tsdf_box_live
 
 struct TsdfVol {
     int nx, ny, nz;
@@ -45,7 +47,7 @@ struct TsdfView {
     float R[9], t[3];
     float K0, K2, K4, K5;
     int w, h;
-    int cull;                     // the block test may be used: the camera and the volume are small enough (tsdf_view_live)
+    int cull;                     // the block test may be used: the camera and the volume are small enough (tsdf_box_live)
     const float* depth;           // [h * w]
     const unsigned char* color;   // [h * w * channels] or null
 };
@@ -60,8 +62,8 @@ __host__ __device__ inline bool tsdf_finite(float x) { return fabsf(x) <= 3.4028
 
 __host__ __device__ inline float tsdf_cam_row(const float* R, float t, float px, float py, float pz) { return ((R[0] * px + R[1] * py) + R[2] * pz) + t; }
 
-// Is the view alive for the tile of voxels [i0, i0 + 64) x [j0, j0 + 4) of layer k, or does every voxel of it fail step 2 or step 4 of
-// the statement?  Exact, by the monotonicity of rounded arithmetic:
+// Is the view alive for the box of voxels [i0, i1] x [j0, j1] x [k0, k1] (inside the lattice), or does every voxel of it fail step 2
+// or step 4 of the statement?  Exact, by the monotonicity of rounded arithmetic.  First for one layer, k0 == k1:
 //   With j, k fixed, P_x is a non-decreasing function of i (a rounded sum of a constant and a non-decreasing product), R * P_x is
 //   monotone in P_x, and every further rounded sum with a fixed second operand keeps the order: xc, yc and z are monotone in i, in a
 //   direction that only the sign of a camera entry decides, and likewise in j.  A function on a rectangle that is monotone in each
@@ -75,6 +77,12 @@ __host__ __device__ inline float tsdf_cam_row(const float* R, float t, float px,
 // R, t, K0, K2, K4, K5 and every |P| is at most 2^40 in magnitude, so that nothing before the quotient exceeds 2^122, and z0 > 0
 // keeps the quotient from 0 / 0.  A comparison with a NaN is false and leaves the view alive.  A view that is not culled is simply
 // evaluated: the result has the same bits either way.
+//   One variable more, k0 < k1: with i, j fixed, P_z is a non-decreasing function of k, R[.][2] * P_z is monotone in P_z, and the
+//   rounded sum ((R0*Px + R1*Py) + R2*Pz) + t has the rounded (R0*Px + R1*Py) as a fixed first operand, so xc, yc and z are monotone
+//   in k too, in a direction that only the sign of a camera entry decides.  (In i and j the monotone term enters the inner sum, whose
+//   rounded result then meets fixed operands: each rounded operation keeps the order.)  A function on a box that is monotone in each
+//   variable takes its extrema at the corners: the 8 corners give the exact ranges of xc, yc and z over the box, and from there on
+//   the argument is the one above word for word.
 __host__ __device__ inline void tsdf_range(float v, float& lo, float& hi) {
     lo = v < lo ? v : lo;
     hi = v > hi ? v : hi;
@@ -88,13 +96,16 @@ __host__ __device__ inline bool tsdf_axis_dead(float k0, float k2, float c0, flo
     const float f0 = (q0 + k2) + 0.5f, f1 = (q1 + k2) + 0.5f;
     return f1 < 0.0f || f0 >= size;
 }
-__host__ __device__ inline bool tsdf_view_live(const TsdfVol& V, const TsdfView& W, int i0, int j0, int k) {
+// kCorners = 4: one layer, k0 == k1, known where the call is written (the dense tile); 8: any box.  A box that happens to have one
+// layer may be asked with 8: over duplicated corners the range is the same range.  The count is a template argument because a test
+// of k0 == k1 at run time splits the 8 corners into two dependent halves: k_tsdf_sparse_integrate measured 1 to 5 % slower with it.
+template <int kCorners>
+__host__ __device__ inline bool tsdf_box_live(const TsdfVol& V, const TsdfView& W, int i0, int i1, int j0, int j1, int k0, int k1) {
+    static_assert(kCorners == 4 || kCorners == 8, "a layer or a box");
     if (!W.cull) return true;
-    const int i1 = i0 + kTsdfTileX - 1 < V.nx - 1 ? i0 + kTsdfTileX - 1 : V.nx - 1, j1 = j0 + kTsdfTileY - 1 < V.ny - 1 ? j0 + kTsdfTileY - 1 : V.ny - 1;
-    const float pz = tsdf_pos(V, 2, k);
     float lo[3], hi[3];
-    for (int corner = 0; corner < 4; ++corner) {
-        const float px = tsdf_pos(V, 0, (corner & 1) ? i1 : i0), py = tsdf_pos(V, 1, (corner & 2) ? j1 : j0);
+    for (int corner = 0; corner < kCorners; ++corner) {
+        const float px = tsdf_pos(V, 0, (corner & 1) ? i1 : i0), py = tsdf_pos(V, 1, (corner & 2) ? j1 : j0), pz = tsdf_pos(V, 2, (corner & 4) ? k1 : k0);
         for (int r = 0; r < 3; ++r) {
             const float c = tsdf_cam_row(W.R + 3 * r, W.t[r], px, py, pz);
             if (corner == 0) lo[r] = hi[r] = c;
@@ -104,6 +115,10 @@ __host__ __device__ inline bool tsdf_view_live(const TsdfVol& V, const TsdfView&
     if (hi[2] <= 0.0f) return false;
     if (!(lo[2] > 0.0f)) return true;
     return !(tsdf_axis_dead(W.K0, W.K2, lo[0], hi[0], lo[2], hi[2], (float)W.w) || tsdf_axis_dead(W.K4, W.K5, lo[1], hi[1], lo[2], hi[2], (float)W.h));
+}
+// the tile of voxels [i0, i0 + 64) x [j0, j0 + 4) of layer k
+__host__ __device__ inline bool tsdf_view_live(const TsdfVol& V, const TsdfView& W, int i0, int j0, int k) {
+    return tsdf_box_live<4>(V, W, i0, i0 + kTsdfTileX - 1 < V.nx - 1 ? i0 + kTsdfTileX - 1 : V.nx - 1, j0, j0 + kTsdfTileY - 1 < V.ny - 1 ? j0 + kTsdfTileY - 1 : V.ny - 1, k, k);
 }
 
 // voxel (i, j, k), stored at entry `vox` of the arrays, and the views of the chunk whose bit is set in `live`, in order: the one
@@ -317,6 +332,38 @@ __host__ __device__ inline bool tsdf_is_cell(const TsdfVol& V, size_t vox, int& 
     return i < V.nx - 1 && j < V.ny - 1 && k < V.nz - 1;
 }
 
+// ---- the per-cell bodies of passes 1, 3 and 4, once for both volumes --------------------------------------------------------------
+// All that a volume adds is where a cell's corners are stored: `at(c)` is the entry of corner code c (bit 0: x, 1: y, 2: z) of the
+// cell in sum / weight / colour and in the masks and scans, at(0) = `vox`, the cell's own entry.  The dense volume steps through the
+// linear index; the brick-sparse one (pm_tsdf_sparse.hpp) goes through its block's neighbour table.  `valid` and `inside` are the
+// cell's bits as the caller read them (tsdf_cell, or the sparse volume's staged tile).
+struct TsdfDenseAt {
+    const TsdfVol& V;
+    size_t vox;
+    __host__ __device__ size_t operator()(uint32_t c) const { return vox + tsdf_step(V, c); }
+};
+
+// pass 1 for a cell: the used edges into their owners' masks (zero before); returns the cell's triangle count
+template <class At>
+__host__ __device__ inline int tsdf_mark_cell(const At& at, uint32_t valid, uint32_t inside, uint32_t* mask) {
+    int nt = 0;
+    if ((inside & valid) == 0u || (inside & valid) == 255u) return nt;
+    for (int t = 0; t < 6; ++t) {
+        uint32_t flips;
+        const uint32_t corners = tsdf_tet_word(t, flips);
+        const unsigned m = tsdf_tet_case(corners, valid, inside);
+        if (!m) continue;
+        nt += (int)(tsdf_case_word(m) & 3u);
+        for (int p = 0; p < 3; ++p)
+            for (int q = p + 1; q < 4; ++q) {
+                if (!(((m >> p) ^ (m >> q)) & 1u)) continue;
+                const uint32_t cp = (corners >> (4 * p)) & 7u, cq = (corners >> (4 * q)) & 7u;
+                tsdf_or(&mask[at(cp)], 1u << tsdf_slot_of(cq ^ cp));   // a corner of an emitting tetrahedron is valid: it exists
+            }
+    }
+    return nt;
+}
+
 // pass 1: mask must be zero before
 __host__ __device__ inline void tsdf_mark_one(const TsdfVol& V, size_t vox, const float* __restrict__ sum, const int32_t* __restrict__ weight, int min_weight,
                                               uint32_t* mask, int* __restrict__ tcount) {
@@ -324,21 +371,7 @@ __host__ __device__ inline void tsdf_mark_one(const TsdfVol& V, size_t vox, cons
     if (tsdf_is_cell(V, vox, i, j, k)) {
         uint32_t valid, inside;
         tsdf_cell(V, vox, sum, weight, min_weight, valid, inside);
-        if ((inside & valid) != 0u && (inside & valid) != 255u) {
-            for (int t = 0; t < 6; ++t) {
-                uint32_t flips;
-                const uint32_t corners = tsdf_tet_word(t, flips);
-                const unsigned m = tsdf_tet_case(corners, valid, inside);
-                if (!m) continue;
-                nt += (int)(tsdf_case_word(m) & 3u);
-                for (int p = 0; p < 3; ++p)
-                    for (int q = p + 1; q < 4; ++q) {
-                        if (!(((m >> p) ^ (m >> q)) & 1u)) continue;
-                        const uint32_t cp = (corners >> (4 * p)) & 7u, cq = (corners >> (4 * q)) & 7u;
-                        tsdf_or(&mask[vox + tsdf_step(V, cp)], 1u << tsdf_slot_of(cq ^ cp));
-                    }
-            }
-        }
+        nt = tsdf_mark_cell(TsdfDenseAt{V, vox}, valid, inside, mask);
     }
     tcount[vox] = nt;
 }
@@ -377,27 +410,25 @@ __host__ __device__ inline unsigned char tsdf_byte(float val) {
     return v >= 255.0f ? (unsigned char)255 : v >= 0.0f ? (unsigned char)(int)v : (unsigned char)0;
 }
 
-// pass 3: the vertices of the edges that voxel `vox` owns.  vexcl / vtile: the scans of pass 2 (base = vexcl[vox] + vtile[tile])
-__host__ __device__ inline void tsdf_vertex_one(const TsdfVol& V, size_t vox, const float* __restrict__ sum, const int32_t* __restrict__ weight,
-                                                const uint4* __restrict__ color, const uint32_t* __restrict__ mask, const int* __restrict__ vexcl,
-                                                const int* __restrict__ vtile, float* __restrict__ xyz, unsigned char* __restrict__ rgb) {
-    const uint32_t m = mask[vox];
-    if (!m) return;
-    int i, j, k;
-    (void)tsdf_is_cell(V, vox, i, j, k);
-    const int at[3] = {i, j, k};
+// pass 3 for the voxel (i, j, k) at entry `vox`, whose mask m is not 0: one vertex per edge that it owns, in slot order.  vexcl /
+// vtile: the scans of pass 2 (base = vexcl[vox] + vtile[tile])
+template <class At>
+__host__ __device__ inline void tsdf_vertex_cell(const TsdfVol& V, const At& at, int i, int j, int k, size_t vox, uint32_t m, const float* __restrict__ sum,
+                                                 const int32_t* __restrict__ weight, const uint4* __restrict__ color, const int* __restrict__ vexcl,
+                                                 const int* __restrict__ vtile, float* __restrict__ xyz, unsigned char* __restrict__ rgb) {
+    const int ijk[3] = {i, j, k};
     size_t out = (size_t)vexcl[vox] + (size_t)vtile[vox / kScanBlock];
     const float fa = sum[vox] / (float)weight[vox];
     float pa[3];
-    for (int a = 0; a < 3; ++a) pa[a] = tsdf_pos(V, a, at[a]);
+    for (int a = 0; a < 3; ++a) pa[a] = tsdf_pos(V, a, ijk[a]);
     for (int s = 0; s < 7; ++s) {
         if (!((m >> s) & 1u)) continue;
         const uint32_t off = tsdf_off_of(s);
-        const size_t b = vox + tsdf_step(V, off);
+        const size_t b = at(off);   // a set bit: the far corner is valid, so it exists
         const float fb = sum[b] / (float)weight[b];
         const float t = fa / (fa - fb);
         for (int a = 0; a < 3; ++a) {
-            const float pb = tsdf_pos(V, a, at[a] + (int)((off >> a) & 1u));
+            const float pb = tsdf_pos(V, a, ijk[a] + (int)((off >> a) & 1u));
             xyz[3 * out + a] = pa[a] + t * (pb - pa[a]);
         }
         if (rgb) {
@@ -420,6 +451,17 @@ __host__ __device__ inline void tsdf_vertex_one(const TsdfVol& V, size_t vox, co
     }
 }
 
+// pass 3: the vertices of the edges that voxel `vox` owns
+__host__ __device__ inline void tsdf_vertex_one(const TsdfVol& V, size_t vox, const float* __restrict__ sum, const int32_t* __restrict__ weight,
+                                                const uint4* __restrict__ color, const uint32_t* __restrict__ mask, const int* __restrict__ vexcl,
+                                                const int* __restrict__ vtile, float* __restrict__ xyz, unsigned char* __restrict__ rgb) {
+    const uint32_t m = mask[vox];
+    if (!m) return;
+    int i, j, k;
+    (void)tsdf_is_cell(V, vox, i, j, k);
+    tsdf_vertex_cell(V, TsdfDenseAt{V, vox}, i, j, k, vox, m, sum, weight, color, vexcl, vtile, xyz, rgb);
+}
+
 __global__ __launch_bounds__(256) void k_tsdf_vertices(TsdfVol V, size_t n_vox, const float* __restrict__ sum, const int32_t* __restrict__ weight,
                                                        const uint4* __restrict__ color, const uint32_t* __restrict__ mask, const int* __restrict__ vexcl,
                                                        const int* __restrict__ vtile, float* __restrict__ xyz, unsigned char* __restrict__ rgb) {
@@ -427,14 +469,12 @@ __global__ __launch_bounds__(256) void k_tsdf_vertices(TsdfVol V, size_t n_vox, 
     if (vox < n_vox) tsdf_vertex_one(V, vox, sum, weight, color, mask, vexcl, vtile, xyz, rgb);
 }
 
-// pass 4: the triangles of cell `vox`.  texcl / ttile: the scans of the triangle counts
-__host__ __device__ inline void tsdf_triangle_one(const TsdfVol& V, size_t vox, const float* __restrict__ sum, const int32_t* __restrict__ weight, int min_weight,
-                                                  const uint32_t* __restrict__ mask, const int* __restrict__ vexcl, const int* __restrict__ vtile,
-                                                  const int* __restrict__ texcl, const int* __restrict__ ttile, int32_t* __restrict__ tri) {
-    int i, j, k;
-    if (!tsdf_is_cell(V, vox, i, j, k)) return;
-    uint32_t valid, inside;
-    tsdf_cell(V, vox, sum, weight, min_weight, valid, inside);
+// pass 4 for the cell at entry `vox`: its triangles again, a vertex number = the owner's base + the rank of the slot within the
+// owner's mask.  texcl / ttile: the scans of the triangle counts
+template <class At>
+__host__ __device__ inline void tsdf_triangle_cell(const At& at, uint32_t valid, uint32_t inside, size_t vox, const uint32_t* __restrict__ mask,
+                                                   const int* __restrict__ vexcl, const int* __restrict__ vtile, const int* __restrict__ texcl,
+                                                   const int* __restrict__ ttile, int32_t* __restrict__ tri) {
     if ((inside & valid) == 0u || (inside & valid) == 255u) return;
     size_t out = (size_t)texcl[vox] + (size_t)ttile[vox / kScanBlock];
     for (int t = 0; t < 6; ++t) {
@@ -449,7 +489,7 @@ __host__ __device__ inline void tsdf_triangle_one(const TsdfVol& V, size_t vox, 
             for (int v = 0; v < 3; ++v) {
                 const uint32_t e = (code >> (2 + 4 * (3 * r + v))) & 15u;
                 const uint32_t cp = (corners >> (4 * (e & 3u))) & 7u, cq = (corners >> (4 * (e >> 2))) & 7u;
-                const size_t owner = vox + tsdf_step(V, cp);
+                const size_t owner = at(cp);
                 const int slot = tsdf_slot_of(cq ^ cp);
                 id[v] = vexcl[owner] + vtile[owner / kScanBlock] + tsdf_popc(mask[owner] & ((1u << slot) - 1u));
             }
@@ -460,6 +500,17 @@ __host__ __device__ inline void tsdf_triangle_one(const TsdfVol& V, size_t vox, 
             ++out;
         }
     }
+}
+
+// pass 4: the triangles of cell `vox`
+__host__ __device__ inline void tsdf_triangle_one(const TsdfVol& V, size_t vox, const float* __restrict__ sum, const int32_t* __restrict__ weight, int min_weight,
+                                                  const uint32_t* __restrict__ mask, const int* __restrict__ vexcl, const int* __restrict__ vtile,
+                                                  const int* __restrict__ texcl, const int* __restrict__ ttile, int32_t* __restrict__ tri) {
+    int i, j, k;
+    if (!tsdf_is_cell(V, vox, i, j, k)) return;
+    uint32_t valid, inside;
+    tsdf_cell(V, vox, sum, weight, min_weight, valid, inside);
+    tsdf_triangle_cell(TsdfDenseAt{V, vox}, valid, inside, vox, mask, vexcl, vtile, texcl, ttile, tri);
 }
 
 __global__ __launch_bounds__(256) void k_tsdf_triangles(TsdfVol V, size_t n_vox, const float* __restrict__ sum, const int32_t* __restrict__ weight, int min_weight,

@@ -11,12 +11,14 @@
 //                               by k_scan_totals<Sum>; the host refuses on the new count before anything is written
 //           k_tsdf_brick_move   an old brick's 512 entries to its new rank (only when bricks existed before)
 //           k_tsdf_brick_commit grid[g] = rank, list[rank] = g
-// Integrate (k_tsdf_sparse_integrate): one block per brick, one thread per voxel; per view the block asks tsdf_box_live, the corner
-//   argument of tsdf_view_live extended to the 8 corners of the brick's box; the per-voxel body is tsdf_integrate_at of pm_tsdf.hpp.
+// Integrate (k_tsdf_sparse_integrate): one block per brick, one thread per voxel; per view the block asks tsdf_box_live of
+//   pm_tsdf.hpp with the 8 corners of the brick's box; the per-voxel body is tsdf_integrate_at of pm_tsdf.hpp.
 // Mesh: the four passes of pm_tsdf.hpp with one block per brick.  A cell's corners lie in up to 8 bricks (the brick itself and its
 //   neighbours towards +x, +y, +z); their ranks are resolved once per block from the grid (tsdf_brick_resolve) and every corner is
 //   addressed through that table (tsdf_brick_at).  A corner in a brick that does not exist has weight 0: it is never valid.  Mark and
 //   triangles read the corners' validity and values from a 9 x 9 x 9 tile that the block stages in LDS (tsdf_tile_load_one).
+// Shared with the dense volume: tsdf_box_live, tsdf_integrate_at and the mesh bodies tsdf_mark_cell / tsdf_vertex_cell /
+//   tsdf_triangle_cell; the sparse side supplies the corner addressing (TsdfBrickAt) and the cell's bits from the tile (tsdf_tile_cell).
 // The per-thread bodies are host and device code: tools/mesh_sparse_check.cpp replays them thread by thread under the sanitizers.
 #pragma once
 
@@ -156,32 +158,10 @@ __global__ __launch_bounds__(kBrickVox) void k_tsdf_brick_clip(TsdfVol V, TsdfBr
 }
 
 // ---- B. integrate --------------------------------------------------------------------------------------------------------------
-// tsdf_view_live for a box of voxels [i0, i1] x [j0, j1] x [k0, k1] (inside the lattice): does every voxel of it fail step 2 or
-// step 4?  The argument of tsdf_view_live, one variable more: with i, j fixed, P_z is a non-decreasing function of k, R[.][2] * P_z
-// is monotone in P_z, and the rounded sum ((R0*Px + R1*Py) + R2*Pz) + t has the rounded (R0*Px + R1*Py) as a fixed first operand,
-// so xc, yc and z are monotone in k too, in a direction that only the sign of a camera entry decides.  (In i and j the monotone
-// term enters the inner sum, whose rounded result then meets fixed operands: each rounded operation keeps the order.)  A function on
-// a box that is monotone in each variable takes its extrema at the corners: the 8 corners give the exact ranges of xc, yc and z
-// over the box, and from there on the argument is the one of tsdf_view_live word for word (tsdf_axis_dead is its code).  W.cull has
-// the meaning it has there.
-__host__ __device__ inline bool tsdf_box_live(const TsdfVol& V, const TsdfView& W, int i0, int i1, int j0, int j1, int k0, int k1) {
-    if (!W.cull) return true;
-    float lo[3], hi[3];
-    for (int corner = 0; corner < 8; ++corner) {
-        const float px = tsdf_pos(V, 0, (corner & 1) ? i1 : i0), py = tsdf_pos(V, 1, (corner & 2) ? j1 : j0), pz = tsdf_pos(V, 2, (corner & 4) ? k1 : k0);
-        for (int r = 0; r < 3; ++r) {
-            const float c = tsdf_cam_row(W.R + 3 * r, W.t[r], px, py, pz);
-            if (corner == 0) lo[r] = hi[r] = c;
-            else tsdf_range(c, lo[r], hi[r]);
-        }
-    }
-    if (hi[2] <= 0.0f) return false;
-    if (!(lo[2] > 0.0f)) return true;
-    return !(tsdf_axis_dead(W.K0, W.K2, lo[0], hi[0], lo[2], hi[2], (float)W.w) || tsdf_axis_dead(W.K4, W.K5, lo[1], hi[1], lo[2], hi[2], (float)W.h));
-}
+// tsdf_box_live of pm_tsdf.hpp for the brick at (I, J, K), cut to the lattice
 __host__ __device__ inline bool tsdf_brick_live(const TsdfVol& V, const TsdfView& W, int I, int J, int K) {
     const int i0 = kBrick * I, j0 = kBrick * J, k0 = kBrick * K;
-    return tsdf_box_live(V, W, i0, i0 + 7 < V.nx - 1 ? i0 + 7 : V.nx - 1, j0, j0 + 7 < V.ny - 1 ? j0 + 7 : V.ny - 1, k0, k0 + 7 < V.nz - 1 ? k0 + 7 : V.nz - 1);
+    return tsdf_box_live<8>(V, W, i0, i0 + 7 < V.nx - 1 ? i0 + 7 : V.nx - 1, j0, j0 + 7 < V.ny - 1 ? j0 + 7 : V.ny - 1, k0, k0 + 7 < V.nz - 1 ? k0 + 7 : V.nz - 1);
 }
 
 // entry `local` of the brick of rank `rank` at (I, J, K); a voxel that dims cut off does not exist and stays 0
@@ -216,6 +196,12 @@ __host__ __device__ inline long long tsdf_brick_at(const int* nb, int local, uin
     const int r = nb[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
     return r < 0 ? -1ll : (long long)r * kBrickVox + (long long)((((z & 7) << 3 | (y & 7)) << 3) | (x & 7));
 }
+// the corner addressing that the mesh bodies of pm_tsdf.hpp ask for; they only follow corners that are valid, so the entry exists
+struct TsdfBrickAt {
+    const int* nb;
+    int local;
+    __host__ __device__ long long operator()(uint32_t c) const { return tsdf_brick_at(nb, local, c); }
+};
 
 struct TsdfBrickCell {
     int i, j, k;      // the voxel on the virtual lattice
@@ -266,21 +252,7 @@ __host__ __device__ inline void tsdf_sparse_mark_one(const TsdfVol& V, const int
     if (tsdf_brick_cell(V, I, J, K, local).cell) {
         uint32_t valid, inside;
         tsdf_tile_cell(tile_f, tile_v, local, valid, inside);
-        if ((inside & valid) != 0u && (inside & valid) != 255u) {
-            for (int t = 0; t < 6; ++t) {
-                uint32_t flips;
-                const uint32_t corners = tsdf_tet_word(t, flips);
-                const unsigned m = tsdf_tet_case(corners, valid, inside);
-                if (!m) continue;
-                nt += (int)(tsdf_case_word(m) & 3u);
-                for (int p = 0; p < 3; ++p)
-                    for (int q = p + 1; q < 4; ++q) {
-                        if (!(((m >> p) ^ (m >> q)) & 1u)) continue;
-                        const uint32_t cp = (corners >> (4 * p)) & 7u, cq = (corners >> (4 * q)) & 7u;
-                        tsdf_or(&mask[tsdf_brick_at(nb, local, cp)], 1u << tsdf_slot_of(cq ^ cp));   // a corner of an emitting tetrahedron is valid: it exists
-                    }
-            }
-        }
+        nt = tsdf_mark_cell(TsdfBrickAt{nb, local}, valid, inside, mask);
     }
     tcount[(size_t)nb[0] * kBrickVox + (size_t)local] = nt;
 }
@@ -293,39 +265,7 @@ __host__ __device__ inline void tsdf_sparse_vertex_one(const TsdfVol& V, const i
     const uint32_t m = mask[vox];
     if (!m) return;
     const TsdfBrickCell at = tsdf_brick_cell(V, I, J, K, local);
-    const int ijk[3] = {at.i, at.j, at.k};
-    size_t out = (size_t)vexcl[vox] + (size_t)vtile[vox / kScanBlock];
-    const float fa = sum[vox] / (float)weight[vox];
-    float pa[3];
-    for (int a = 0; a < 3; ++a) pa[a] = tsdf_pos(V, a, ijk[a]);
-    for (int s = 0; s < 7; ++s) {
-        if (!((m >> s) & 1u)) continue;
-        const uint32_t off = tsdf_off_of(s);
-        const size_t b = (size_t)tsdf_brick_at(nb, local, off);   // a set bit: the far corner is valid, so it exists
-        const float fb = sum[b] / (float)weight[b];
-        const float t = fa / (fa - fb);
-        for (int a = 0; a < 3; ++a) {
-            const float pb = tsdf_pos(V, a, ijk[a] + (int)((off >> a) & 1u));
-            xyz[3 * out + a] = pa[a] + t * (pb - pa[a]);
-        }
-        if (rgb) {
-            const uint4 ca = color[vox], cb = color[b];
-            const unsigned sa[3] = {ca.x, ca.y, ca.z}, sb[3] = {cb.x, cb.y, cb.z};
-            for (int c = 0; c < 3; ++c) {   // sums are B, G, R; the bytes go out R, G, B
-                float val = 128.0f;
-                if (ca.w > 0u && cb.w > 0u) {
-                    const float ma = (float)sa[c] / (float)ca.w, mb = (float)sb[c] / (float)cb.w;
-                    val = ma + t * (mb - ma);
-                } else if (ca.w > 0u) {
-                    val = (float)sa[c] / (float)ca.w;
-                } else if (cb.w > 0u) {
-                    val = (float)sb[c] / (float)cb.w;
-                }
-                rgb[3 * out + (size_t)(2 - c)] = tsdf_byte(val);
-            }
-        }
-        ++out;
-    }
+    tsdf_vertex_cell(V, TsdfBrickAt{nb, local}, at.i, at.j, at.k, vox, m, sum, weight, color, vexcl, vtile, xyz, rgb);
 }
 
 // pass 4 (tsdf_triangle_one); the tile must be loaded
@@ -335,32 +275,7 @@ __host__ __device__ inline void tsdf_sparse_triangle_one(const TsdfVol& V, const
     if (!tsdf_brick_cell(V, I, J, K, local).cell) return;
     uint32_t valid, inside;
     tsdf_tile_cell(tile_f, tile_v, local, valid, inside);
-    if ((inside & valid) == 0u || (inside & valid) == 255u) return;
-    const size_t vox = (size_t)nb[0] * kBrickVox + (size_t)local;
-    size_t out = (size_t)texcl[vox] + (size_t)ttile[vox / kScanBlock];
-    for (int t = 0; t < 6; ++t) {
-        uint32_t flips;
-        const uint32_t corners = tsdf_tet_word(t, flips);
-        const unsigned m = tsdf_tet_case(corners, valid, inside);
-        if (!m) continue;
-        const uint32_t code = tsdf_case_word(m);
-        const int nt = (int)(code & 3u);
-        for (int r = 0; r < nt; ++r) {
-            int32_t id[3];
-            for (int v = 0; v < 3; ++v) {
-                const uint32_t e = (code >> (2 + 4 * (3 * r + v))) & 15u;
-                const uint32_t cp = (corners >> (4 * (e & 3u))) & 7u, cq = (corners >> (4 * (e >> 2))) & 7u;
-                const size_t owner = (size_t)tsdf_brick_at(nb, local, cp);
-                const int slot = tsdf_slot_of(cq ^ cp);
-                id[v] = vexcl[owner] + vtile[owner / kScanBlock] + tsdf_popc(mask[owner] & ((1u << slot) - 1u));
-            }
-            const bool flip = (flips >> (2 * m + r)) & 1u;
-            tri[3 * out] = id[0];
-            tri[3 * out + 1] = flip ? id[2] : id[1];
-            tri[3 * out + 2] = flip ? id[1] : id[2];
-            ++out;
-        }
-    }
+    tsdf_triangle_cell(TsdfBrickAt{nb, local}, valid, inside, (size_t)nb[0] * kBrickVox + (size_t)local, mask, vexcl, vtile, texcl, ttile, tri);
 }
 
 // one block per brick, one thread per voxel; the first 8 threads resolve the neighbour table; mark and triangles then stage the
