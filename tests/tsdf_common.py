@@ -119,15 +119,17 @@ def integrate_statement(origin, voxel, dims, trunc, cams, depths, colors=None, s
     return total, weight, color4
 
 
-def mesh_statement(total, weight, color4, dims, origin, voxel, min_weight=1):
-    """-> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3]}"""
+def mesh_statement(total, weight, color4, dims, origin, voxel, min_weight=1, details=False):
+    """-> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3]}; with `details` also what a census asks for:
+    "keys" (owner linear index * 7 + slot per vertex), "val" (float32 [n, 3], the colour values in B, G, R order before the byte, or
+    None), "tri_cell" and "tri_case" (per triangle the cell's linear index and tetrahedron * 16 + inside mask)"""
     nx, ny, nz = dims
     total, weight = np.asarray(total, F).reshape(nz, ny, nx), np.asarray(weight, np.int32).reshape(nz, ny, nx)
     valid = weight >= min_weight
     with np.errstate(all="ignore"):
         f = np.where(valid, total / np.where(valid, weight, 1).astype(F), F(0)).astype(F)
     inside = valid & (f < 0)
-    tris = []   # three (owner linear index * 7 + slot) keys each
+    tris, tri_cell, tri_case = [], [], []   # three (owner linear index * 7 + slot) keys each
     if nx > 1 and ny > 1 and nz > 1:
         some_in = np.zeros((nz - 1, ny - 1, nx - 1), bool)
         some_out = np.zeros_like(some_in)
@@ -152,6 +154,8 @@ def mesh_statement(total, weight, color4, dims, origin, voxel, min_weight=1):
                     if FLIP[t][m][r]:
                         keys = [keys[0], keys[2], keys[1]]
                     tris.append(keys)
+                    tri_cell.append((k * ny + j) * nx + i)
+                    tri_case.append(t * 16 + m)
     tri_keys = np.array(tris, np.int64).reshape(-1, 3)
     vert_keys = np.unique(tri_keys)   # owner ascending, then slot ascending
     tri = np.searchsorted(vert_keys, tri_keys).astype(np.int32)
@@ -167,18 +171,41 @@ def mesh_statement(total, weight, color4, dims, origin, voxel, min_weight=1):
         for a in range(3):
             pa, pb = pos[a][ia[:, a]], pos[a][ib[:, a]]
             xyz[:, a] = pa + t * (pb - pa)
-        rgb = None
+        rgb = vals = None
         if color4 is not None:
             color4 = np.asarray(color4, np.uint32).reshape(nz, ny, nx, 4)
             ca, cb = color4[ia[:, 2], ia[:, 1], ia[:, 0]], color4[ib[:, 2], ib[:, 1], ib[:, 0]]
             has_a, has_b = ca[:, 3] > 0, cb[:, 3] > 0
-            rgb = np.empty((len(owner), 3), np.uint8)
+            rgb, vals = np.empty((len(owner), 3), np.uint8), np.empty((len(owner), 3), F)
             for c in range(3):   # sums are B, G, R; the bytes go out R, G, B
                 ma = ca[:, c].astype(F) / np.where(has_a, ca[:, 3], 1).astype(F)
                 mb = cb[:, c].astype(F) / np.where(has_b, cb[:, 3], 1).astype(F)
                 val = np.where(has_a & has_b, ma + t * (mb - ma), np.where(has_a, ma, np.where(has_b, mb, F(128)))).astype(F)
-                rgb[:, 2 - c] = (val + F(0.5)).astype(np.int32).astype(np.uint8)
-    return {"xyz": xyz, "rgb": rgb, "tri": tri}
+                rgb[:, 2 - c], vals[:, c] = color_byte(val), val
+    out = {"xyz": xyz, "rgb": rgb, "tri": tri}
+    if details:
+        out.update(keys=vert_keys, val=vals, tri_cell=np.array(tri_cell, np.int64), tri_case=np.array(tri_case, np.int64))
+    return out
+
+
+def color_byte(val):
+    """the colour byte of the contract: with v = val + 0.5f, 255 where v >= 255, (int)v where v >= 0, else 0 (a NaN included)"""
+    with np.errstate(all="ignore"):
+        v = (np.asarray(val, F) + F(0.5)).astype(F)
+        mid = v >= 0
+        return np.where(v >= F(255), 255, np.where(mid, np.where(mid, v, F(0)).astype(np.int32), 0)).astype(np.uint8)
+
+
+def same_bits(got, want):
+    """the comparison rule of the TSDF sweeps (that of fusion_fuzz_common.same_bits): equal bits wherever `want` is not NaN, NaN
+    wherever it is; the payload of a NaN is not part of the contract"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if got.shape != want.shape or got.dtype != want.dtype:
+        return False
+    if got.dtype != np.float32:
+        return bool(np.array_equal(got, want))
+    nan = np.isnan(want)
+    return bool(np.isnan(got[nan]).all() and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan]))
 
 
 def sphere_volume(dims, centre, radius):
