@@ -969,6 +969,72 @@ int mpmvs_tsdf_get_bricks(mpmvs_tsdf* h, float* sum, int32_t* weight, uint32_t* 
 int mpmvs_tsdf_set_bricks(mpmvs_tsdf* h, long long n, const int32_t* coords, const float* sum, const int32_t* weight, const uint32_t* color4);
 int mpmvs_tsdf_sparse_stats(const mpmvs_tsdf* h, long long info[4], float ms[2]);
 
+/* ---- surface: cleaning and shading an indexed triangle mesh (mp-mvs_amd/mesh.py: Mesh, tools/clean_mesh.py) --- */
+/* A handle for an indexed triangle mesh resident on the device: n vertices (xyz fp32, optional rgb bytes) and m triangles of three
+ * int32 indices, wherever it came from (mpmvs_tsdf_mesh, a PLY file).  Kernels and per-thread bodies: mp-mvs_amd/csrc/pm_mesh.hpp and
+ * pm_unionfind.hpp; DESIGN.md section 24.  The three statements below are bit for bit and independent of scheduling.
+ *
+ * mpmvs_mesh_create touches no device and copies its inputs; the handle opens `device` with the first operation that passes its
+ * argument checks and has something to do.  -2, with *h not written: a NULL h, n < 0 or m < 0, a NULL xyz with n > 0, a NULL tri with
+ * m > 0, device < 0, a triangle with an index outside [0, n) (the text names the first such triangle and the index).  -3: n or m
+ * above 2^30.  n == 0 and m == 0 are legal.  The mesh has colour iff rgb is not NULL.
+ * Every refusal of an operation writes nothing and is found before the device is touched, except -100 (HIP failure).  An operation
+ * with nothing to do (n == 0, or m == 0 where only triangles matter) answers on the host and launches nothing.  A NULL handle is -2
+ * everywhere.
+ *
+ * 1. COMPONENTS.  mpmvs_mesh_components.  Two vertices are JOINED iff some triangle names both; a repeated index inside a triangle
+ *    is legal and joins what it names.  The components are the classes of the transitive closure over all n vertices.
+ *    Connectivity is BY INDEX, NOT BY POSITION: coincident vertices with different indices are not welded.
+ *      out_label[v] = the smallest vertex index of v's component; a vertex that no triangle names has out_label[v] = v.
+ *      out_verts[v] = the number of vertices of that component.
+ *      out_tris[v]  = its number of triangles; a triangle belongs to the component of its first index.
+ *      counts = {components with at least one triangle, vertices no triangle names, triangles of the largest component, its label}:
+ *               largest by triangle count, among equals the smallest label; with m == 0 {0, n, 0, -1}.
+ *    -2: a NULL handle, a NULL out_label with n > 0.  out_verts, out_tris and counts may be NULL.
+ *
+ * 2. AREA-WEIGHTED VERTEX NORMALS.  mpmvs_mesh_normals.  All in fp64, no contraction, only + - * / sqrt, comparisons and one llrint,
+ *    each correctly rounded.
+ *    1. A vertex is FINITE iff its three coordinates are.  ext = the largest per-axis (double)max - (double)min over the finite
+ *       vertices.  With no finite vertex, ext == 0 or m == 0 every normal is (0, 0, 0) and n_defined = 0.
+ *    2. B = 2.0 * (ext * ext); e = the integer with 2^(e-1) <= B < 2^e (frexp); b = the least integer with max(m, 1) <= 2^b;
+ *       scale = ldexp(1.0, 61 - b - e).  Every cross-product component is at most B in magnitude (an edge component is at most ext
+ *       because rounding is monotone; a product of two at most fl(ext*ext); their difference at most twice that, which is B), so
+ *       every term is below 2^(61-b) in magnitude; a triangle with a repeated index has C = 0 exactly, so a vertex receives at most
+ *       m non-zero terms and every sum stays below 2^61 < 2^62 in magnitude.
+ *    3. For every triangle (a, b, c) whose three vertices are finite: u = P_b - P_a, w = P_c - P_a per component from the floats
+ *       converted to double; C = (u_y*w_z - u_z*w_y, u_z*w_x - u_x*w_z, u_x*w_y - u_y*w_x); F_k = llrint(C_k * scale), to nearest
+ *       even; S[a] += F, S[b] += F, S[c] += F in int64 (a triangle that names a vertex twice adds twice; its C is 0 anyway).
+ *    4. Per vertex x, y, z = (double)S_k, len = sqrt((x*x + y*y) + z*z); len == 0 gives (0, 0, 0), otherwise
+ *       out = ((float)(x/len), (float)(y/len), (float)(z/len)).  n_defined counts the vertices with len > 0.
+ *    Integer addition commutes: the order of the triangles never shows.  e follows ext, so scaling every coordinate by a power of
+ *    two leaves every bit of the output unchanged (short of overflow and underflow of the floats).  The triangles of mpmvs_tsdf_mesh
+ *    are counter-clockwise seen from outside, so its normals point to the positive side, where the cameras are.
+ *    -2: a NULL handle, a NULL out_normals with n > 0.  n_defined may be NULL.
+ *
+ * 3. SELECT.  mpmvs_mesh_select compacts the mesh on the device; the handle itself is not changed.  A triangle is kept iff all three
+ *    of its vertices have keep[v] != 0.  A vertex is kept iff keep[v] != 0 and, with drop_unreferenced != 0, some kept triangle names
+ *    it.  Kept vertices keep their order and are renumbered 0..n'-1; kept triangles keep their order and carry the new numbers;
+ *    out_src[new] = old.  Returns n'; *out_xyz (n' x 3 floats), *out_rgb (n' x 3 bytes), *out_tri (*m_out x 3 int32; NULL when
+ *    *m_out == 0) and *out_src (n' int32) receive buffers to release with mpmvs_free.  An empty result returns 0 with *m_out = 0 and
+ *    all buffers NULL.  On failure no buffer is allocated and the outputs are not written.
+ *    -2: a NULL handle, a NULL keep with n > 0, a NULL out_xyz, out_tri or m_out, out_rgb NULL for a mesh with colour or given for
+ *    one without.  out_src may be NULL.
+ *
+ * mpmvs_mesh_pass_ms: device ms (HIP events): ms[0..2] the hook (with init), flatten and size passes of the last components call,
+ * ms[3..4] accumulate and finish of the last normals call, ms[5..7] flag, scan and emit of the last select call; 0 for a pass that
+ * did not run in the last call of its kind. */
+typedef struct mpmvs_mesh mpmvs_mesh;
+int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned char* rgb /* n x 3, may be NULL */, long long m,
+                      const int32_t* tri /* m x 3 */, mpmvs_mesh** h);
+int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label /* n */, int32_t* out_verts /* n, may be NULL */, int32_t* out_tris /* n, may be NULL */,
+                          long long counts[4] /* may be NULL */);
+int mpmvs_mesh_normals(mpmvs_mesh* h, float* out_normals /* n x 3 */, long long* n_defined /* may be NULL */);
+long long mpmvs_mesh_select(mpmvs_mesh* h, const unsigned char* keep /* n */, int drop_unreferenced, float** out_xyz,
+                            unsigned char** out_rgb /* NULL iff the mesh has no colour */, int32_t** out_tri,
+                            int32_t** out_src /* new vertex -> old index; may be NULL */, long long* m_out);
+int mpmvs_mesh_pass_ms(const mpmvs_mesh* h, float ms[8]);
+void mpmvs_mesh_destroy(mpmvs_mesh* h);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

@@ -1,6 +1,7 @@
 // mpmvs_mesh.hip -- the surface family of the C ABI declared in include/mpmvs.h: the TSDF volume handle (mpmvs_tsdf), dense or
 // brick-sparse, the integration of depth maps into it and the marching-tetrahedra mesh of its zero level set (kernels and per-thread
-// bodies: pm_tsdf.hpp, pm_tsdf_sparse.hpp; DESIGN.md sections 22 and 23).  Errors are reported like those of mpmvs_cloud_*: through
+// bodies: pm_tsdf.hpp, pm_tsdf_sparse.hpp; DESIGN.md sections 22 and 23); and the indexed triangle mesh handle (mpmvs_mesh): its
+// connected components, vertex normals and compaction (pm_mesh.hpp, pm_unionfind.hpp).  Errors are reported like those of mpmvs_cloud_*: through
 // mpmvs_last_error(NULL), per host thread; everything but -100 is found before the device is touched.  A handle opens its device
 // with the first call that needs it.
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 
 #include "../../include/mpmvs.h"
 #include "pm_host.hpp"
+#include "pm_mesh.hpp"
 #include "pm_tsdf.hpp"
 #include "pm_tsdf_sparse.hpp"
 
@@ -604,6 +606,314 @@ int mpmvs_tsdf_sparse_stats(const mpmvs_tsdf* h, long long info[4], float ms[2])
     info[3] = (h->d_grid ? (long long)h->n_grid * 4 : 0) + h->n_bricks * (4 + (long long)kBrickVox * (h->with_color ? 24 : 8));
     ms[0] = h->alloc_ms[0];
     ms[1] = h->alloc_ms[1];
+    return 0;
+}
+
+// ---- an indexed triangle mesh: components, vertex normals, select (statements 1 to 3 of include/mpmvs.h) ----
+constexpr long long kMeshMax = 1ll << 30;
+
+struct mpmvs_mesh {
+    int device = 0;
+    long long n = 0, m = 0;
+    bool with_color = false, ready = false;
+    double scale = 0.0;                  // of the normals (mesh_scale); 0: every normal is (0, 0, 0)
+    std::vector<float> xyz;              // the copies of create, until the first operation on the device has uploaded them
+    std::vector<unsigned char> rgb;
+    std::vector<int32_t> tri;
+    float* d_xyz = nullptr;
+    unsigned char* d_rgb = nullptr;
+    int32_t* d_tri = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+};
+
+int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned char* rgb, long long m, const int32_t* tri, mpmvs_mesh** out) {
+    if (!out) return call_fail(-2, "mesh create: bad argument");
+    if (n < 0 || m < 0) return call_fail(-2, "mesh create: a negative count");
+    if ((n > 0 && !xyz) || (m > 0 && !tri)) return call_fail(-2, "mesh create: vertices or triangles missing");
+    if (device < 0) return call_fail(-2, "mesh create: negative device");
+    if (n > kMeshMax || m > kMeshMax) return call_fail(-3, "mesh create: more than 2^30 vertices or triangles");
+    for (long long k = 0; k < 3 * m; ++k)
+        if (tri[k] < 0 || (long long)tri[k] >= n)
+            return call_fail(-2, "mesh create: triangle " + std::to_string(k / 3) + " names vertex " + std::to_string(tri[k]) + ", outside [0, " + std::to_string(n) + ")");
+    mpmvs_mesh* h = new mpmvs_mesh;
+    h->device = device;
+    h->n = n;
+    h->m = m;
+    h->with_color = rgb != nullptr;
+    if (n > 0) h->xyz.assign(xyz, xyz + 3 * n);
+    if (n > 0 && rgb) h->rgb.assign(rgb, rgb + 3 * n);
+    if (m > 0) h->tri.assign(tri, tri + 3 * m);
+    h->scale = mesh_scale(h->xyz.data(), n, m);
+    *out = h;
+    return 0;
+}
+
+void mpmvs_mesh_destroy(mpmvs_mesh* h) {
+    if (!h) return;
+    if (h->stream || h->d_xyz) {
+        (void)enter_device(h->device);
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        for (void* p : {(void*)h->d_xyz, (void*)h->d_rgb, (void*)h->d_tri})
+            if (p) (void)pool_free(p);
+        for (hipEvent_t e : h->ev)
+            if (e) (void)hipEventDestroy(e);
+        if (h->stream) (void)hipStreamDestroy(h->stream);
+    }
+    delete h;
+}
+
+// the first operation that needs the device: the stream, the events and the mesh itself
+static int mesh_ready(mpmvs_mesh* h) {
+    CALLCHK(enter_device(h->device));
+    if (h->ready) return 0;
+    if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->ev)
+        if (!e) CALLCHK(hipEventCreate(&e));
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
+    if (!h->d_xyz) CALLCHK(pool_malloc(&h->d_xyz, n * 12));
+    if (h->with_color && !h->d_rgb) CALLCHK(pool_malloc(&h->d_rgb, n * 3));
+    if (m > 0 && !h->d_tri) CALLCHK(pool_malloc(&h->d_tri, m * 12));
+    CALLCHK(hipMemcpyAsync(h->d_xyz, h->xyz.data(), n * 12, hipMemcpyHostToDevice, h->stream));
+    if (h->with_color) CALLCHK(hipMemcpyAsync(h->d_rgb, h->rgb.data(), n * 3, hipMemcpyHostToDevice, h->stream));
+    if (m > 0) CALLCHK(hipMemcpyAsync(h->d_tri, h->tri.data(), m * 12, hipMemcpyHostToDevice, h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
+    std::vector<float>().swap(h->xyz);
+    std::vector<unsigned char>().swap(h->rgb);
+    std::vector<int32_t>().swap(h->tri);
+    h->ready = true;
+    return 0;
+}
+static unsigned mesh_blocks(size_t count) { return (unsigned)((count + 255) / 256); }
+// ms[k] = the time between ev[a] and ev[a + 1]; the stream is idle
+static int mesh_elapsed(mpmvs_mesh* h, int a, int k) {
+    float t = 0.0f;
+    CALLCHK(hipEventElapsedTime(&t, h->ev[a], h->ev[a + 1]));
+    h->ms[k] = t;
+    return 0;
+}
+
+int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label, int32_t* out_verts, int32_t* out_tris, long long counts[4]) {
+    if (!h || (h->n > 0 && !out_label)) return call_fail(-2, "mesh components: bad argument");
+    h->ms[0] = h->ms[1] = h->ms[2] = 0.0f;
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
+    if (m == 0) {   // nothing is joined: answered here
+        for (size_t v = 0; v < n; ++v) {
+            out_label[v] = (int32_t)v;
+            if (out_verts) out_verts[v] = 1;
+            if (out_tris) out_tris[v] = 0;
+        }
+        if (counts) counts[0] = 0, counts[1] = h->n, counts[2] = 0, counts[3] = -1;
+        return 0;
+    }
+    const int rc = mesh_ready(h);
+    if (rc) return rc;
+    const hipStream_t st = h->stream;
+    const int ni = (int)h->n, mi = (int)h->m;
+    Scratch d_parent(st), d_label(st), d_cnt(st), d_verts(st), d_tris(st);
+    CALLCHK(d_parent.alloc(n * 4));
+    CALLCHK(d_label.alloc(n * 4));
+    CALLCHK(d_cnt.alloc(n * 8));    // the vertex counts, then the triangle counts
+    CALLCHK(d_verts.alloc(n * 4));
+    CALLCHK(d_tris.alloc(n * 4));
+    int* const vcnt = d_cnt.as<int>();
+    int* const tcnt = vcnt + n;
+    CALLCHK(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(k_mesh_cc_init, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_parent.as<int>());
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_cc_hook, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_parent.as<int>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[1], st));
+    hipLaunchKernelGGL(k_cc_flatten, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_parent.as<int>(), d_label.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[2], st));
+    CALLCHK(hipMemsetAsync(d_cnt.p, 0, n * 8, st));
+    hipLaunchKernelGGL(k_cc_count, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), vcnt);
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_mesh_tri_count, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_label.as<int32_t>(), tcnt);
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cc_gather, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), vcnt, d_verts.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_cc_gather, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), tcnt, d_tris.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[3], st));
+    std::vector<int32_t> tris_host;   // the counts need the triangle counts whether the caller wants them or not
+    if (counts && !out_tris) tris_host.resize(n);
+    int32_t* const tris = out_tris ? out_tris : tris_host.data();
+    CALLCHK(hipMemcpyAsync(out_label, d_label.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_verts) CALLCHK(hipMemcpyAsync(out_verts, d_verts.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_tris || counts) CALLCHK(hipMemcpyAsync(tris, d_tris.p, n * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; ++k) {
+        const int rc2 = mesh_elapsed(h, k, k);
+        if (rc2) return rc2;
+    }
+    if (counts) {
+        // a vertex that a triangle names lies in a component with that triangle; one that none names is alone with 0 triangles
+        long long comps = 0, unnamed = 0, best = 0, best_label = -1;
+        for (size_t v = 0; v < n; ++v) {
+            if (tris[v] == 0) ++unnamed;
+            if (out_label[v] != (int32_t)v || tris[v] == 0) continue;
+            ++comps;
+            if (tris[v] > best) best = tris[v], best_label = (long long)v;   // ascending labels: among equals the smallest stays
+        }
+        counts[0] = comps, counts[1] = unnamed, counts[2] = best, counts[3] = best_label;
+    }
+    return 0;
+}
+
+int mpmvs_mesh_normals(mpmvs_mesh* h, float* out_normals, long long* n_defined) {
+    if (!h || (h->n > 0 && !out_normals)) return call_fail(-2, "mesh normals: bad argument");
+    h->ms[3] = h->ms[4] = 0.0f;
+    const size_t n = (size_t)h->n;
+    if (n == 0 || h->scale == 0.0) {   // no triangle, no finite vertex or no extent: every normal is zero
+        if (n > 0) std::memset(out_normals, 0, n * 12);
+        if (n_defined) *n_defined = 0;
+        return 0;
+    }
+    const int rc = mesh_ready(h);
+    if (rc) return rc;
+    const hipStream_t st = h->stream;
+    Scratch d_sum(st), d_out(st), d_def(st);
+    CALLCHK(d_sum.alloc(n * 24));
+    CALLCHK(d_out.alloc(n * 12));
+    CALLCHK(d_def.alloc(4));
+    CALLCHK(hipMemsetAsync(d_def.p, 0, 4, st));
+    CALLCHK(hipEventRecord(h->ev[0], st));
+    CALLCHK(hipMemsetAsync(d_sum.p, 0, n * 24, st));
+    hipLaunchKernelGGL(k_mesh_nrm_accum, dim3(mesh_blocks((size_t)h->m)), dim3(256), 0, st, (int)h->m, h->d_xyz, h->d_tri, h->scale, d_sum.as<long long>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[1], st));
+    hipLaunchKernelGGL(k_mesh_nrm_finish, dim3(mesh_blocks(n)), dim3(256), 0, st, (int)h->n, d_sum.as<long long>(), d_out.as<float>(), d_def.as<int>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(h->ev[2], st));
+    int defined = 0;
+    CALLCHK(hipMemcpyAsync(out_normals, d_out.p, n * 12, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(&defined, d_def.p, 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; ++k) {
+        const int rc2 = mesh_elapsed(h, k, 3 + k);
+        if (rc2) return rc2;
+    }
+    if (n_defined) *n_defined = defined;
+    return 0;
+}
+
+// the device half of mpmvs_mesh_select; the host buffers are allocated once the counts are known and handed over on success only
+static long long mesh_select_device(mpmvs_mesh* h, const unsigned char* keep, int drop, float** xyz, unsigned char** rgb, int32_t** tri, int32_t** src, long long* m_out) {
+    const hipStream_t st = h->stream;
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
+    const int ni = (int)h->n, mi = (int)h->m;
+    const int v_tiles = (int)((n + kScanBlock - 1) / kScanBlock), t_tiles = (int)((m + kScanBlock - 1) / kScanBlock);
+    Scratch d_keep(st), d_vflag(st), d_tflag(st), d_vexcl(st), d_texcl(st), d_tiles(st), d_grand(st);
+    CALLCHK(d_keep.alloc(n));
+    CALLCHK(d_vflag.alloc(n * 4));
+    CALLCHK(d_tflag.alloc(m * 4));
+    CALLCHK(d_vexcl.alloc(n * 4));
+    CALLCHK(d_texcl.alloc(m * 4));
+    CALLCHK(d_tiles.alloc((size_t)(v_tiles + t_tiles) * 4));
+    CALLCHK(d_grand.alloc(8));
+    int* const vtile = d_tiles.as<int>();
+    int* const ttile = vtile + v_tiles;
+    int* const grand = d_grand.as<int>();
+    CALLCHK(hipMemcpyAsync(d_keep.p, keep, n, hipMemcpyHostToDevice, st));
+    CALLCHK(hipMemsetAsync(d_grand.p, 0, 8, st));
+    CALLCHK(hipEventRecord(h->ev[0], st));
+    hipLaunchKernelGGL(k_mesh_sel_verts, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_keep.as<unsigned char>(), drop, d_vflag.as<int>());
+    CALLCHK(hipGetLastError());
+    if (m > 0) {
+        hipLaunchKernelGGL(k_mesh_sel_tris, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_keep.as<unsigned char>(), drop, d_tflag.as<int>(), d_vflag.as<int>());
+        CALLCHK(hipGetLastError());
+    }
+    CALLCHK(hipEventRecord(h->ev[1], st));
+    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)v_tiles), dim3(kScanBlock), 0, st, d_vflag.as<int>(), ni, d_vexcl.as<int>(), vtile);
+    CALLCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, vtile, v_tiles, 0, grand);
+    CALLCHK(hipGetLastError());
+    if (m > 0) {
+        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)t_tiles), dim3(kScanBlock), 0, st, d_tflag.as<int>(), mi, d_texcl.as<int>(), ttile);
+        CALLCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, ttile, t_tiles, 0, grand + 1);
+        CALLCHK(hipGetLastError());
+    }
+    CALLCHK(hipEventRecord(h->ev[2], st));
+    int g[2] = {0, 0};
+    CALLCHK(hipMemcpyAsync(g, d_grand.p, 8, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; ++k) {
+        const int rc = mesh_elapsed(h, k, 5 + k);
+        if (rc) return rc;
+    }
+    const size_t nv = (size_t)g[0], nt = (size_t)g[1];
+    if (nv == 0) return 0;   // then nt == 0 too: a kept triangle keeps its vertices
+    Scratch d_xyz(st), d_rgb(st), d_tri(st), d_src(st);
+    CALLCHK(d_xyz.alloc(nv * 12));
+    if (h->with_color) CALLCHK(d_rgb.alloc(nv * 3));
+    CALLCHK(d_tri.alloc(nt * 12));
+    CALLCHK(d_src.alloc(nv * 4));
+    CALLCHK(hipEventRecord(h->ev[3], st));
+    hipLaunchKernelGGL(k_mesh_emit_verts, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, h->d_xyz, h->with_color ? h->d_rgb : (const unsigned char*)nullptr, d_vflag.as<int>(),
+                       d_vexcl.as<int>(), vtile, d_xyz.as<float>(), d_rgb.as<unsigned char>(), d_src.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    if (nt > 0) {
+        hipLaunchKernelGGL(k_mesh_emit_tris, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_tflag.as<int>(), d_texcl.as<int>(), ttile, d_vexcl.as<int>(), vtile,
+                           d_tri.as<int32_t>());
+        CALLCHK(hipGetLastError());
+    }
+    CALLCHK(hipEventRecord(h->ev[4], st));
+    float* hx = (float*)std::malloc(nv * 12);
+    int32_t* ht = nt ? (int32_t*)std::malloc(nt * 12) : nullptr;
+    unsigned char* hc = h->with_color ? (unsigned char*)std::malloc(nv * 3) : nullptr;
+    int32_t* hs = src ? (int32_t*)std::malloc(nv * 4) : nullptr;
+    struct Guard {
+        void *a, *b, *c, *d;
+        ~Guard() { std::free(a); std::free(b); std::free(c); std::free(d); }
+    } guard{hx, ht, hc, hs};
+    if (!hx || (nt && !ht) || (h->with_color && !hc) || (src && !hs)) return call_fail(-100, "mesh select: out of host memory");
+    CALLCHK(hipMemcpyAsync(hx, d_xyz.p, nv * 12, hipMemcpyDeviceToHost, st));
+    if (ht) CALLCHK(hipMemcpyAsync(ht, d_tri.p, nt * 12, hipMemcpyDeviceToHost, st));
+    if (hc) CALLCHK(hipMemcpyAsync(hc, d_rgb.p, nv * 3, hipMemcpyDeviceToHost, st));
+    if (hs) CALLCHK(hipMemcpyAsync(hs, d_src.p, nv * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    const int rc = mesh_elapsed(h, 3, 7);
+    if (rc) return rc;
+    guard.a = guard.b = guard.c = guard.d = nullptr;
+    *xyz = hx;
+    *tri = ht;
+    *rgb = hc;
+    if (src) *src = hs;
+    *m_out = (long long)nt;
+    return (long long)nv;
+}
+
+long long mpmvs_mesh_select(mpmvs_mesh* h, const unsigned char* keep, int drop_unreferenced, float** out_xyz, unsigned char** out_rgb, int32_t** out_tri,
+                            int32_t** out_src, long long* m_out) {
+    if (!h || !out_xyz || !out_tri || !m_out || (h->n > 0 && !keep)) return call_fail(-2, "mesh select: bad argument");
+    if (h->with_color && !out_rgb) return call_fail(-2, "mesh select: a mesh with colour needs out_rgb");
+    if (!h->with_color && out_rgb) return call_fail(-2, "mesh select: the mesh has no colour");
+    float* xyz = nullptr;
+    unsigned char* rgb = nullptr;
+    int32_t *tri = nullptr, *src = nullptr;
+    long long nt = 0, nv = 0;
+    h->ms[5] = h->ms[6] = h->ms[7] = 0.0f;
+    if (h->n > 0 && !(drop_unreferenced && h->m == 0)) {   // else nothing can be kept: nothing is launched
+        const int rc = mesh_ready(h);
+        if (rc) return rc;
+        nv = mesh_select_device(h, keep, drop_unreferenced != 0, &xyz, &rgb, &tri, out_src ? &src : nullptr, &nt);
+        if (nv < 0) return nv;
+    }
+    *out_xyz = xyz;
+    *out_tri = tri;
+    if (out_rgb) *out_rgb = rgb;
+    if (out_src) *out_src = src;
+    *m_out = nt;
+    return nv;
+}
+
+int mpmvs_mesh_pass_ms(const mpmvs_mesh* h, float ms[8]) {
+    if (!h || !ms) return call_fail(-2, "mesh pass_ms: bad argument");
+    std::memcpy(ms, h->ms, sizeof h->ms);
     return 0;
 }
 

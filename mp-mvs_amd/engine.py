@@ -123,6 +123,14 @@ _EXTRA = {
     "tsdf_get_bricks": (C.c_int, [_P, _P, _P, _P]),
     "tsdf_set_bricks": (C.c_int, [_P, C.c_longlong, _P, _P, _P, _P]),
     "tsdf_sparse_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_float)]),
+    # an indexed triangle mesh: components, vertex normals, select (mesh.py: Mesh)
+    "mesh_create": (C.c_int, [C.c_int, C.c_longlong, _P, _P, C.c_longlong, _P, C.POINTER(C.c_void_p)]),
+    "mesh_components": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_longlong)]),
+    "mesh_normals": (C.c_int, [_P, _P, C.POINTER(C.c_longlong)]),
+    "mesh_select": (C.c_longlong, [_P, _P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_longlong)]),
+    "mesh_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "mesh_destroy": (None, [_P]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

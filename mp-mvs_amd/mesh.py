@@ -1,6 +1,8 @@
 """Depth maps to a triangle mesh on the GPU: a TSDF volume, dense (Volume) or brick-sparse (SparseVolume), and marching tetrahedra
 on the Kuhn split of its cells (mpmvs_tsdf_*, csrc/pm_tsdf.hpp, csrc/pm_tsdf_sparse.hpp, csrc/mpmvs_mesh.hip; contract:
-include/mpmvs.h, DESIGN.md sections 22 and 23), and the PLY files of a mesh.  The device calls are bit for bit their plain-loop
+include/mpmvs.h, DESIGN.md sections 22 and 23); an indexed triangle mesh on the device (Mesh: mpmvs_mesh_*, csrc/pm_mesh.hpp;
+DESIGN.md section 24) with its connected components, area-weighted vertex normals and compaction, remove_small_components and
+vertex_normals on top of it; and the PLY files of a mesh.  The device calls are bit for bit their plain-loop
 statements (tests/tsdf_common.py and tests/tsdf_sparse_common.py have them in numpy).  The work runs on the GPU; there is no CPU
 path."""
 import ctypes as C
@@ -262,11 +264,172 @@ class SparseVolume(Volume):
                 "brick_share": float(info[0]) / float(info[2]), "allocate_mark": float(ms[0]), "allocate_commit": float(ms[1])}
 
 
-def write_ply_mesh(path, xyz, tri, rgb=None):
-    """binary little-endian PLY: vertex x y z (float) and, with rgb, red green blue (uchar); face: list uchar int vertex_indices"""
+class Mesh:
+    """mpmvs_mesh: an indexed triangle mesh resident on the device: xyz float32 [n, 3], tri int32 [m, 3] with indices in [0, n),
+    rgb uint8 [n, 3] or None (include/mpmvs.h, statements 1 to 3).  Wherever the mesh came from: Volume.mesh()
+    or read_ply_mesh().  The arrays are copied; the device is opened by the first call that needs it."""
+
+    def __init__(self, xyz, tri, rgb=None, device=0):
+        _, self._f = engine.load()
+        self._h = None
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3) if rgb is not None else None
+        if c is not None and len(c) != len(x):
+            raise ValueError(f"{len(c)} colours for {len(x)} vertices")
+        if c is not None and len(x) == 0:
+            c = np.zeros((1, 3), np.uint8)   # a pointer that is not NULL: the mesh has colour
+        h = C.c_void_p()
+        rc = self._f["mesh_create"](int(device), len(x), x.ctypes.data if len(x) else None, c.ctypes.data if c is not None else None, len(t),
+                                    t.ctypes.data if len(t) else None, C.byref(h))
+        if rc != 0:
+            _raise(self._f, "mesh_create", rc)
+        self._h = h
+        self.n, self.m, self.color, self.device = len(x), len(t), rgb is not None, int(device)
+
+    def close(self):
+        if self._h is not None:
+            self._f["mesh_destroy"](self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def components(self, want_verts=True, want_tris=True):
+        """mpmvs_mesh_components -> (label int32 [n], verts int32 [n] or None, tris int32 [n] or None, counts): the smallest vertex
+        index of each vertex's component, its vertex and triangle counts, and counts = {"components", "unnamed",
+        "largest_triangles", "largest_label"}.  Connectivity is by index: coincident vertices are not welded."""
+        label = np.empty(self.n, np.int32)
+        verts = np.empty(self.n, np.int32) if want_verts else None
+        tris = np.empty(self.n, np.int32) if want_tris else None
+        counts = (C.c_longlong * 4)()
+        rc = self._f["mesh_components"](self._h, label.ctypes.data, verts.ctypes.data if want_verts else None, tris.ctypes.data if want_tris else None, counts)
+        if rc != 0:
+            _raise(self._f, "mesh_components", rc)
+        return label, verts, tris, dict(zip(("components", "unnamed", "largest_triangles", "largest_label"), (int(v) for v in counts)))
+
+    def normals(self):
+        """mpmvs_mesh_normals -> (float32 [n, 3], n_defined): the area-weighted vertex normals, (0, 0, 0) where undefined"""
+        out = np.empty((self.n, 3), np.float32)
+        nd = C.c_longlong(0)
+        rc = self._f["mesh_normals"](self._h, out.ctypes.data, C.byref(nd))
+        if rc != 0:
+            _raise(self._f, "mesh_normals", rc)
+        return out, int(nd.value)
+
+    def select(self, keep, drop_unreferenced=True):
+        """mpmvs_mesh_select -> {"xyz", "rgb", "tri", "src"}: the vertices with keep[v] != 0 (and, with drop_unreferenced, a kept
+        triangle), the triangles whose three vertices are kept, renumbered in order; src[new] = old.  The handle is unchanged."""
+        k = np.ascontiguousarray(keep).reshape(-1)
+        if len(k) != self.n:
+            raise ValueError(f"a mask of {len(k)} entries for {self.n} vertices")
+        k = np.ascontiguousarray(k != 0, np.uint8)
+        lib, _ = engine.load()
+        lib.mpmvs_free.argtypes = [C.c_void_p]
+        lib.mpmvs_free.restype = None
+        px, pc, pt, ps, mo = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_longlong(0)
+        nv = self._f["mesh_select"](self._h, k.ctypes.data if self.n else None, 1 if drop_unreferenced else 0, C.byref(px), C.byref(pc) if self.color else None,
+                                    C.byref(pt), C.byref(ps), C.byref(mo))
+        if nv < 0:
+            _raise(self._f, "mesh_select", nv)
+        try:
+            def take(p, ctype, rows, cols, dtype):
+                if not rows:
+                    return np.zeros((0, cols) if cols > 1 else (0,), dtype)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), (rows, cols) if cols > 1 else (rows,)).copy()
+            out = {"xyz": take(px, C.c_float, nv, 3, np.float32), "rgb": take(pc, C.c_uint8, nv, 3, np.uint8) if self.color else None,
+                   "tri": take(pt, C.c_int32, mo.value, 3, np.int32), "src": take(ps, C.c_int32, nv, 1, np.int32)}
+        finally:
+            for p in (px, pc, pt, ps):
+                if p.value:
+                    lib.mpmvs_free(p)
+        return out
+
+    def pass_ms(self):
+        """device ms of the last components, normals and select calls"""
+        ms = (C.c_float * 8)()
+        rc = self._f["mesh_pass_ms"](self._h, ms)
+        if rc != 0:
+            _raise(self._f, "mesh_pass_ms", rc)
+        return dict(zip(("cc_hook", "cc_flatten", "cc_sizes", "normals_accumulate", "normals_finish", "select_flag", "select_scan", "select_emit"),
+                        (float(v) for v in ms)))
+
+
+def rank_components(label, tris, min_triangles=1, largest=None):
+    """the keep mask of remove_small_components from the labels and per-vertex triangle counts of Mesh.components(): the vertices of
+    the components with at least min_triangles triangles (never fewer than 1: a vertex no triangle names goes) and, with
+    largest=K, of only the K largest of them by triangle count, ties to the smaller label.  Host work."""
+    label, tris = np.asarray(label, np.int64), np.asarray(tris, np.int64)
+    roots = np.flatnonzero((label == np.arange(len(label))) & (tris >= max(int(min_triangles), 1)))
+    if largest is not None:
+        if largest < 0:
+            raise ValueError("largest must not be negative")
+        roots = roots[np.argsort(-tris[roots], kind="stable")[:largest]]   # roots ascend: a stable sort sends ties to the smaller label
+    good = np.zeros(len(label), bool)
+    good[roots] = True
+    return good[label] if len(label) else good
+
+
+def remove_small_components(m, min_triangles=1, largest=None, device=0):
+    """m: a mesh dict {"xyz", "tri", "rgb"}.  Keeps the components with at least min_triangles triangles; with largest=K only the K
+    largest by triangle count, ties to the smaller label (the rule of cloud.remove_small_clusters).  Vertices no triangle names are
+    dropped.  Returns the selected mesh dict {"xyz", "rgb", "tri", "src"} plus "keep" (bool [n]), "label", "tris", "counts".  The
+    union-find and the compaction run on the device; the ranking is host work on the downloaded labels."""
+    with Mesh(m["xyz"], m["tri"], m.get("rgb"), device=device) as h:
+        label, _, tris, counts = h.components(want_verts=False)
+        keep = rank_components(label, tris, min_triangles, largest)
+        out = h.select(keep, drop_unreferenced=True)
+        out["device_ms"] = h.pass_ms()
+    out.update({"keep": keep, "label": label, "tris": tris, "counts": counts})
+    return out
+
+
+def vertex_normals(m, device=0):
+    """m: a mesh dict -> (float32 [n, 3], n_defined): Mesh.normals() of it"""
+    with Mesh(m["xyz"], m["tri"], None, device=device) as h:
+        return h.normals()
+
+
+def clean_and_shade(m, min_component=0, largest=None, normals=False, device=0):
+    """what tools/mesh_ply.py and tools/clean_mesh.py do to a mesh dict after their flags: cleaned first (if min_component > 0 or
+    largest is given), then shaded (if normals) -> ({"mesh": the mesh dict, "device_ms": {...}, and only for what was asked:
+    "components", "largest_component", "removed_triangles", "normals_defined"}, normals or None)"""
+    info, ms, nrm = {}, {}, None
+    if min_component > 0 or largest is not None:
+        before = len(m["tri"])
+        c = remove_small_components(m, max(int(min_component), 1), largest, device=device)
+        ms.update({k: v for k, v in c["device_ms"].items() if k.startswith(("cc_", "select_"))})
+        info.update(components=c["counts"]["components"], largest_component=c["counts"]["largest_triangles"], removed_triangles=before - len(c["tri"]))
+        m = {"xyz": c["xyz"], "rgb": c["rgb"], "tri": c["tri"]}
+    if normals:
+        with Mesh(m["xyz"], m["tri"], None, device=device) as h:
+            nrm, info["normals_defined"] = h.normals()
+            ms.update({k: v for k, v in h.pass_ms().items() if k.startswith("normals_")})
+    info.update(mesh=m, device_ms=ms)
+    return info, nrm
+
+
+def write_ply_mesh(path, xyz, tri, rgb=None, normals=None):
+    """binary little-endian PLY: vertex x y z (float), with normals nx ny nz (float) and, with rgb, red green blue (uchar); face: list
+    uchar int vertex_indices"""
     xyz, tri = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3), np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(xyz)}", "property float x", "property float y", "property float z"]
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if len(normals) != len(xyz):
+            raise ValueError(f"{len(normals)} normals for {len(xyz)} vertices")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        head += ["property float nx", "property float ny", "property float nz"]
     if rgb is not None:
         rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
         if len(rgb) != len(xyz):
@@ -279,6 +442,9 @@ def write_ply_mesh(path, xyz, tri, rgb=None):
     v = np.empty(len(xyz), np.dtype(fields))
     for a, name in enumerate("xyz"):
         v[name] = xyz[:, a]
+    if normals is not None:
+        for a, name in enumerate(("nx", "ny", "nz")):
+            v[name] = normals[:, a]
     if rgb is not None:
         for a, name in enumerate(("red", "green", "blue")):
             v[name] = rgb[:, a]
@@ -292,8 +458,9 @@ def write_ply_mesh(path, xyz, tri, rgb=None):
 
 
 def read_ply_mesh(path):
-    """what write_ply_mesh writes -> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3]}.  Binary
-    little-endian files with float x y z (and uchar red green blue) per vertex and triangles only; anything else is a ValueError."""
+    """what write_ply_mesh writes -> {"xyz": float32 [n, 3], "rgb": uint8 [n, 3] or None, "tri": int32 [m, 3], "normals": float32
+    [n, 3] or None}.  Binary little-endian files with float x y z (then float nx ny nz, then uchar red green blue) per vertex and
+    triangles only; anything else is a ValueError."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header")
@@ -312,12 +479,15 @@ def read_ply_mesh(path):
         else:
             raise ValueError(f"{path}: unknown header line {' '.join(w)!r}")
     plain = [("float", "x"), ("float", "y"), ("float", "z")]
+    shaded = [("float", "nx"), ("float", "ny"), ("float", "nz")]
     colour = [("uchar", "red"), ("uchar", "green"), ("uchar", "blue")]
-    if len(elements) != 2 or elements[0][0] != "vertex" or elements[1][0] != "face" or elements[0][2] not in (plain, plain + colour) \
+    layouts = (plain, plain + colour, plain + shaded, plain + shaded + colour)
+    if len(elements) != 2 or elements[0][0] != "vertex" or elements[1][0] != "face" or elements[0][2] not in layouts \
             or elements[1][2] != [("list", "uchar", "int", "vertex_indices")]:
         raise ValueError(f"{path}: not the layout of write_ply_mesh")
-    nv, nf, has_rgb = elements[0][1], elements[1][1], elements[0][2] != plain
-    vdt = np.dtype([("xyz", "<f4", (3,))] + ([("rgb", "u1", (3,))] if has_rgb else []))
+    nv, nf = elements[0][1], elements[1][1]
+    has_nrm, has_rgb = shaded[0] in elements[0][2], colour[0] in elements[0][2]
+    vdt = np.dtype([("xyz", "<f4", (3,))] + ([("nrm", "<f4", (3,))] if has_nrm else []) + ([("rgb", "u1", (3,))] if has_rgb else []))
     fdt = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
     at = nl + 1
     if at + nv * vdt.itemsize + nf * fdt.itemsize > len(data):
@@ -326,4 +496,5 @@ def read_ply_mesh(path):
     f = np.frombuffer(data, fdt, nf, at + nv * vdt.itemsize)
     if nf and (f["n"] != 3).any():
         raise ValueError(f"{path}: a face that is no triangle")
-    return {"xyz": v["xyz"].copy().reshape(-1, 3), "rgb": v["rgb"].copy().reshape(-1, 3) if has_rgb else None, "tri": f["v"].copy().reshape(-1, 3)}
+    return {"xyz": v["xyz"].copy().reshape(-1, 3), "rgb": v["rgb"].copy().reshape(-1, 3) if has_rgb else None, "tri": f["v"].copy().reshape(-1, 3),
+            "normals": v["nrm"].copy().reshape(-1, 3) if has_nrm else None}

@@ -5,6 +5,7 @@ level set is extracted by marching tetrahedra (mp-mvs_amd/mesh.py; csrc/pm_tsdf.
     python tools/mesh_ply.py --dense_folder D --output mesh.ply --voxel V [--trunc 4V] [--min_weight 2]
                              [--bbox x0 y0 z0 x1 y1 z1 | --bbox_from MPMVS_model.ply --bbox_percentile 1]
                              [--sparse [--pad 1.0] [--max_bricks N]]
+                             [--min_component N] [--largest K] [--normals]
 
 Reads cams/<id>_cam.txt, images/<id>.* and <result_folder>/2333_<id>/depths.dmb (result_folder: D/MPMVS) with the readers of
 mp-mvs_amd/hostlib.py; a camera is rescaled to the size of its depth map as the fusion does, and the image is sampled at the map's
@@ -17,8 +18,13 @@ grown by the truncation distance.  The volume is dense: (box / voxel)^3 voxels, 
 8 x 8 x 8 voxels within --pad voxels (default 1.0, an untuned starting value) of the samples along every depth pixel's ray through the
 truncation band, at most --max_bricks of them (default: the whole brick grid, at most 2^21), then to integrate; the box is virtual
 and --max_voxels does not apply.  The mesh is a sub-mesh of the dense one: the same vertices, the triangles whose corners all exist.
+--min_component N (triangles; 0 = off, the default) and --largest K drop the small detached pieces of the mesh on the GPU
+(mesh.remove_small_components): the connected components with fewer than N triangles go, and all but the K
+largest; vertices no triangle names go with them.  --normals writes area-weighted vertex normals (nx ny nz after z).  The mesh is
+cleaned first, then shaded.  N has not been tuned on any real scene.
 Prints one JSON line: n_vox, views, vertices, triangles, device ms per pass, wall seconds; with --sparse also bricks, brick_share and
-device_bytes."""
+device_bytes; with the cleaning flags also components, largest_component and removed_triangles, with --normals normals_defined, and
+the device ms of their passes."""
 import argparse
 import glob
 import importlib
@@ -62,8 +68,13 @@ def main(argv=None):
     ap.add_argument("--sparse", action="store_true", help="a brick-sparse volume: allocate from all views, then integrate")
     ap.add_argument("--pad", type=float, default=1.0, help="--sparse: voxels around a ray sample whose bricks are allocated; 1.0 is an untuned starting value")
     ap.add_argument("--max_bricks", type=int, help="--sparse: the cap on allocated bricks (default: the whole brick grid, at most 2^21)")
+    ap.add_argument("--min_component", type=int, default=0, help="drop connected components with fewer triangles; 0 = off; untuned on real scenes")
+    ap.add_argument("--largest", type=int, help="keep only the K largest components by triangle count")
+    ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    if args.min_component < 0 or (args.largest is not None and args.largest < 1):
+        raise SystemExit("--min_component must not be negative and --largest must be at least 1")
     if not args.sparse and (args.pad != 1.0 or args.max_bricks is not None):
         raise SystemExit("--pad and --max_bricks go with --sparse")
     if not (math.isfinite(args.voxel) and args.voxel > 0):
@@ -151,17 +162,27 @@ def main(argv=None):
             m = vol.mesh(args.min_weight)
             ms = vol.pass_ms()
             device_ms.update({k: ms[k] for k in ("mark", "scan", "vertices", "triangles")})
+        t2 = time.perf_counter()
+        extra, normals = mesh.clean_and_shade(m, args.min_component, args.largest, args.normals, device=args.device)
+        m = extra.pop("mesh")
+        device_ms.update(extra.pop("device_ms"))
     except (ValueError, OSError, RuntimeError) as e:
         raise SystemExit(str(e)) from None
-    t2 = time.perf_counter()
-    mesh.write_ply_mesh(args.output, m["xyz"], m["tri"], m["rgb"])
+    t2b = time.perf_counter()
+    if normals is None:
+        mesh.write_ply_mesh(args.output, m["xyz"], m["tri"], m["rgb"])
+    else:
+        mesh.write_ply_mesh(args.output, m["xyz"], m["tri"], m["rgb"], normals=normals)
     t3 = time.perf_counter()
     res = {"n_vox": n_vox, "dims": dims, "origin": [float(v) for v in lo.astype(np.float32)], "voxel": args.voxel, "trunc": trunc, "min_weight": args.min_weight,
            "views": len(views), "vertices": int(len(m["xyz"])), "triangles": int(len(m["tri"])),
            "device_ms": {k: round(v, 4) for k, v in device_ms.items()},
-           "seconds": {"integrate": round(t1 - t0, 4), "mesh": round(t2 - t1, 4), "write": round(t3 - t2, 4), "wall": round(t3 - t0, 4)}, "output": args.output}
+           "seconds": {"integrate": round(t1 - t0, 4), "mesh": round(t2 - t1, 4), "write": round(t3 - t2b, 4), "wall": round(t3 - t0, 4)}, "output": args.output}
     if sparse is not None:
         res.update(sparse)
+    if extra:
+        res["seconds"]["clean"] = round(t2b - t2, 4)
+        res.update(extra)
     print(json.dumps(res))
     return res
 
