@@ -358,6 +358,20 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     constexpr bool kQ8 = false;
 #endif
     constexpr bool kCostsByCandidate = (PRIOR && MAXV == 16) || (kQ8 && !GEOM && !PRIOR && MAXV == 32 && U8 && SCALE == 0);
+    // Which variants keep the five refinement candidates' planes in registers instead of private memory (cpl, below).  In memory every
+    // dealt round publishes with one scratch_load_dwordx4 and one s_waitcnt vmcnt(0) per candidate that has an item in it, on the same
+    // in-order queue as the gathers, and the final acceptance reloads the survivors the same way.  In registers only what is distinct
+    // stays alive (three normals, five offsets, most of them live anyway as plane_now and the draws): 3 .. 12 registers and 16 B of
+    // scratch.  Two sieves, per variant (profiles/EXPERIMENTS.md 69).  Allocation: registers may cost, in both libraries, no spilled
+    // register (vector or scalar) more than memory, at most 256 registers and at most 16 B of scratch
+    // (profiles/r24_kernel_resources.txt, every variant in registers, beside r24_kernel_resources_parent.txt).  That leaves
+    //   fp16 texels: photometric and geometric up to 24 views; photometric with 25 .. 32 views at scales 0 and 2 (scale 1 spills one
+    //     scalar register more, the geometric variant too); the planar prior with 8 views (above 8: 48 B of scratch, 14 scalar spills);
+    //   fp32 texels: the bucket of 9 .. 16 views without the prior.  The others sit at 248 .. 256 registers and spill 1 .. 53 more.
+    // Time (profiles/r24_scales_modes.txt): of these, photometric with 9 .. 24 views and fp16 texels is 2.4 - 3.3 % SLOWER in registers
+    // (218 -> 229 and 234 -> 245 registers) and stays in memory; the others gain 0.5 - 1.8 %, 25 .. 32 views 13 %.
+    constexpr bool kPlanesInRegs = U8 ? (PRIOR ? MAXV == 8 : GEOM ? MAXV <= 24 : (MAXV == 8 || (MAXV == 32 && SCALE != 1)))
+                                      : (!PRIOR && MAXV == 16);
     typedef Win<SCALE, BW, BH, kLdsXchgFloats<NT>> Wn;
     typedef CandTile<BW, BH> CT;
     static_assert(CT::floats <= kLdsWeightFloatsOf<NT>, "the candidate tile lives in the weight records' area until they are written");
@@ -852,9 +866,9 @@ PM_DEV void update_body(const ProblemDev& P, const StateDev& S, const LaunchArgs
     //     term is therefore accepted in turn, each overwriting the one before: only the LAST of them leaves a trace, the
     //     evaluations of all the others are dead.
     float cpl[5 * 4], tcs[5], tgs[5], pr5[5];
-    // the candidate planes are parked in every variant: in registers they push other state out instead (scratch 352 -> 528 B,
-    // spills in the fp32 variants; profiles/EXPERIMENTS.md 24)
-    keep_in_memory(cpl);
+    // the candidate planes: in registers where the variant has them (kPlanesInRegs, above; every index below is a compile-time
+    // constant of an unrolled loop), parked in private memory where registers would push other state out (profiles/EXPERIMENTS.md 69)
+    if constexpr (!kPlanesInRegs) keep_in_memory(cpl);
     uint32_t dead = 0;
 #pragma unroll
     for (int ci = 0; ci < 5; ++ci) {
