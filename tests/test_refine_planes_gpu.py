@@ -23,12 +23,13 @@ Three states at which the register form can go wrong, each at view counts of var
      (the same plane gives the same restricted cost, and the test is strict), restricted_cost stays 0, every in-range candidate with
      a valid prior term would be accepted in turn and only the last of them is evaluated: the final acceptance takes exactly that one;
   3. source views 2-7 (and their repetitions) blank: few views carry weight and a round publishes for few candidates.
-The build with 8-bit interpolation fractions runs the flagship variant only (photometric, 8 views, fp16 texels, scale 0).
+The build with 8-bit interpolation fractions runs the flagship variant only here (photometric, 8 views, fp16 texels, scale 0); its
+other variants and these states run in tests/test_q8_variants_gpu.py, on the helpers of tests/update_variants_common.py.
 """
-import os
-
 import numpy as np
 import pytest
+
+from update_variants_common import assert_state, cpu_handle, gpu_handle, one_plane, params, prior_planes, problem, start, state, wanted
 
 pytestmark = pytest.mark.gpu
 
@@ -44,85 +45,12 @@ def cases(views, per_pass):
     return [(W, H, V, q, False) for (W, H) in SIZES for (V, q) in views] + [(33, 17) + per_pass + (True,)]
 
 
-def same(a, b):
-    return np.array_equal(np.asarray(a).view(np.uint32), np.asarray(b).view(np.uint32))
-
-
-def state(h, geom=False):
-    """planes, costs, (geometric costs,) selected views"""
-    return tuple(np.array(a) for a in h.get(geom=geom)) + (np.array(h.get_selected_views()),)
-
-
-def assert_state(what, got, want):
-    names = ("planes", "costs", "geom costs", "selected views") if len(want) == 4 else ("planes", "costs", "selected views")
-    for n, g, w in zip(names, got, want):
-        assert same(g, w), f"{what}: {n} differ on {int((np.asarray(g).view(np.uint32) != np.asarray(w).view(np.uint32)).sum())} values"
-
-
-_scenes = {}
-
-
-def problem(pm, W, H, V, quantize):
-    key = (W, H, V, quantize)
-    if key not in _scenes:
-        sc = pm.synth.make_problem_scene(W, H, n_src=8, spacing=0.5, quantize=quantize)
-        cams, imgs = sc.problem(0, [1 + (i % 8) for i in range(V)])
-        dmin, dmax = pm.synth.kernel_depth_range(cams[0])
-        _scenes[key] = (sc, cams, imgs, float(dmin), float(dmax))
-    return _scenes[key]
-
-
-def params(pm, W, H, V, quantize, **kw):
-    sc, cams, imgs, dmin, dmax = problem(pm, W, H, V, quantize)
-    return pm.PatchMatchParams(num_images=V + 1, depth_min=dmin, depth_max=dmax, **kw)
-
-
-def cpu_handle(pm, oracle, W, H, V, quantize, imgs=None, q8=False):
-    sc, cams, own, dmin, dmax = problem(pm, W, H, V, quantize)
-    cpu = oracle.create()
-    if q8:
-        oracle.set_texture_q8(cpu, True)
-    cpu.set_views(cams, own if imgs is None else imgs)
-    return cpu
-
-
-def gpu_handle(pm, engine, W, H, V, quantize, per_pass=False, imgs=None, q8=False):
-    sc, cams, own, dmin, dmax = problem(pm, W, H, V, quantize)
-    if per_pass:
-        os.environ["MPMVS_CHAIN"] = "0"
-    try:
-        gpu = engine.create_q8(0) if q8 else engine.create(0)
-    finally:
-        os.environ.pop("MPMVS_CHAIN", None)
-    gpu.set_views(cams, own if imgs is None else imgs)
-    assert gpu.texture_format() == ("u8" if quantize else "f32")
-    assert gpu.chain_status() == (0 if per_pass else 1)
-    return gpu
-
-
-_wanted = {}
-
-
-def wanted(key, compute):
-    """the oracle's result of a case: computed once, shared by the tests and launch modes that need it, never written to"""
-    if key not in _wanted:
-        _wanted[key] = compute()
-        for a in _wanted[key]:
-            a.setflags(write=False)
-    return _wanted[key]
-
-
 def photometric(pm, oracle, W, H, V, quantize):
     def compute():
         cpu = cpu_handle(pm, oracle, W, H, V, quantize)
         cpu.run(params(pm, W, H, V, quantize, max_scale=2), SEED)
         return state(cpu)
     return wanted(("photo", W, H, V, quantize), compute)
-
-
-def start(h, st):
-    h.set_state(st[0], st[1])
-    h.set_selected_views(st[2])
 
 
 @pytest.mark.parametrize("W,H,V,quantize,per_pass", cases(PHOTO_VIEWS, (25, True)))
@@ -152,20 +80,6 @@ def test_geometric_run(pm, oracle, engine, W, H, V, quantize, per_pass):
     assert_state(f"geometric {W}x{H}, {V} views", run(gpu_handle(pm, engine, W, H, V, quantize, per_pass)), want)
 
 
-def prior_planes(sc, W, H, rng):
-    """planes close to the ground truth, and a mask that covers 60 % of the pixels"""
-    cam, gt = sc.views[0].cam, sc.views[0].gt_depth.astype(np.float64)
-    u, v = np.meshgrid(np.arange(W), np.arange(H))
-    X = np.stack([gt * (u - cam.K[2]) / cam.K[0], gt * (v - cam.K[5]) / cam.K[4], gt], -1)
-    n = np.zeros((H, W, 3))
-    n[..., 2] = -1.0
-    n[..., 0] = 0.05 * rng.standard_normal((H, W))
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    prior = np.concatenate([n, -(n * X).sum(-1)[..., None]], -1).astype(np.float32)
-    mask = (rng.uniform(size=(H, W)) < 0.6).astype(np.uint32) * np.arange(1, H * W + 1, dtype=np.uint32).reshape(H, W)
-    return prior, mask
-
-
 @pytest.mark.parametrize("W,H,V,quantize,per_pass", cases(PRIOR_VIEWS, (8, True)))
 def test_planar_prior_run(pm, oracle, engine, W, H, V, quantize, per_pass):
     st = photometric(pm, oracle, W, H, V, quantize)
@@ -182,12 +96,6 @@ def test_planar_prior_run(pm, oracle, engine, W, H, V, quantize, per_pass):
 
     want = wanted(("prior", W, H, V, quantize), lambda: run(cpu_handle(pm, oracle, W, H, V, quantize)))
     assert_state(f"prior {W}x{H}, {V} views", run(gpu_handle(pm, engine, W, H, V, quantize, per_pass)), want)
-
-
-def one_plane(W, H, d):
-    planes = np.zeros((H, W, 4), np.float32)
-    planes[..., 2], planes[..., 3] = -1.0, d
-    return planes
 
 
 @pytest.mark.parametrize("V,quantize", [(8, True), (32, True), (16, False)])
