@@ -110,22 +110,6 @@ static int cloud_create_device(mpmvs_cloud* c, const float* xyz) {
     return 0;
 }
 
-// the host's pass over a cloud, shared by every entry point that builds a grid: the number of points with three finite
-// coordinates and their bounding box (mn, mx untouched when there is none)
-static long long cloud_bbox(long long n, const float* xyz, float mn[3], float mx[3]) {
-    long long n_fin = 0;
-    for (long long i = 0; i < n; ++i) {
-        const float* p = xyz + 3 * i;
-        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = n_fin ? std::min(mn[a], p[a]) : p[a];
-            mx[a] = n_fin ? std::max(mx[a], p[a]) : p[a];
-        }
-        ++n_fin;
-    }
-    return n_fin;
-}
-
 // a handle on the host side only: the count, the bounding box and the table size of n points (n <= 2^31 - 1); nullptr, with the
 // -3 text under the name `who`, beyond 2^29 finite points
 static mpmvs_cloud* cloud_new(int device, long long n, const float* xyz, const char* who) {
@@ -453,16 +437,16 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
     if (slots_log2 > kCloudMaxSlotsLog2) return call_fail(-3, "voxel: more than 2^29 finite points (the table would exceed 2^30 slots)");
     VoxelGrid g;
     voxel_origin(mn, voxel, g);
-    if (n_fin > 0)
-        for (int a = 0; a < 3; ++a) {
-            const double top = std::floor(((double)mx[a] - g.o[a]) / g.e);   // the cell of the highest point: the cells are monotonic in x
-            if (!(top < (double)kCloudAxisCells)) {
-                char msg[200];
-                std::snprintf(msg, sizeof msg, "voxel: the points span %.6g cells of edge %.6g along %c, more than 2^21 (extent / voxel = %.6g)", top + 1.0, g.e,
-                              "xyz"[a], ((double)mx[a] - (double)mn[a]) / g.e);
-                return call_fail(-3, msg);
-            }
+    if (n_fin > 0) {
+        double top = 0.0;
+        const int a = voxel_span_axis(mx, g, &top);
+        if (a >= 0) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "voxel: the points span %.6g cells of edge %.6g along %c, more than 2^21 (extent / voxel = %.6g)", top + 1.0, g.e,
+                          "xyz"[a], ((double)mx[a] - (double)mn[a]) / g.e);
+            return call_fail(-3, msg);
         }
+    }
     if (n_fin == 0) {   // nothing occupies a voxel: answered on the host
         if (out_voxel_of)
             for (long long i = 0; i < n; ++i) out_voxel_of[i] = -1;

@@ -1,14 +1,16 @@
 // mpmvs_mesh.hip -- the surface family of the C ABI declared in include/mpmvs.h: the TSDF volume handle (mpmvs_tsdf), dense or
 // brick-sparse, the integration of depth maps into it and the marching-tetrahedra mesh of its zero level set (kernels and per-thread
 // bodies: pm_tsdf.hpp, pm_tsdf_sparse.hpp; DESIGN.md sections 22 and 23); and the indexed triangle mesh handle (mpmvs_mesh): its
-// connected components, vertex normals and compaction (pm_mesh.hpp, pm_unionfind.hpp).  Errors are reported like those of mpmvs_cloud_*: through
-// mpmvs_last_error(NULL), per host thread; everything but -100 is found before the device is touched.  A handle opens its device
-// with the first call that needs it.
+// connected components, vertex normals and compaction (pm_mesh.hpp, pm_unionfind.hpp), and its simplification by
+// vertex clustering (pm_simplify.hpp on the clustering passes of pm_cloud.hpp and pm_voxel.hpp).  Errors are
+// reported like those of mpmvs_cloud_*: through mpmvs_last_error(NULL), per host thread; everything but -100 is found before the
+// device is touched.  A handle opens its device with the first call that needs it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -18,6 +20,7 @@
 #include "../../include/mpmvs.h"
 #include "pm_host.hpp"
 #include "pm_mesh.hpp"
+#include "pm_simplify.hpp"
 #include "pm_tsdf.hpp"
 #include "pm_tsdf_sparse.hpp"
 
@@ -626,6 +629,10 @@ struct mpmvs_mesh {
     hipStream_t stream = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // for mpmvs_simplify_mesh: the finite vertices and their bounding box, taken at create while the host copy exists
+    long long n_fin = 0;
+    float mn[3] = {0.0f, 0.0f, 0.0f}, mx[3] = {0.0f, 0.0f, 0.0f};
+    float simp_ms[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 };
 
 int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned char* rgb, long long m, const int32_t* tri, mpmvs_mesh** out) {
@@ -646,6 +653,7 @@ int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned 
     if (n > 0 && rgb) h->rgb.assign(rgb, rgb + 3 * n);
     if (m > 0) h->tri.assign(tri, tri + 3 * m);
     h->scale = mesh_scale(h->xyz.data(), n, m);
+    h->n_fin = cloud_bbox(n, h->xyz.data(), h->mn, h->mx);
     *out = h;
     return 0;
 }
@@ -914,6 +922,246 @@ long long mpmvs_mesh_select(mpmvs_mesh* h, const unsigned char* keep, int drop_u
 int mpmvs_mesh_pass_ms(const mpmvs_mesh* h, float ms[8]) {
     if (!h || !ms) return call_fail(-2, "mesh pass_ms: bad argument");
     std::memcpy(ms, h->ms, sizeof h->ms);
+    return 0;
+}
+
+// ---- simplification by vertex clustering (statement 4 of include/mpmvs.h) -------------------------------------
+namespace {
+// the borders of the passes; destroyed after the stream has been waited for
+struct SimpEvents {
+    hipEvent_t e[13] = {};
+    ~SimpEvents() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+// the host buffers of the result: released unless the call succeeds
+struct SimpOut {
+    float* xyz = nullptr;
+    unsigned char *rgb = nullptr, *placed = nullptr;
+    int32_t *tri = nullptr, *count = nullptr, *src = nullptr;
+    bool keep = false;
+    ~SimpOut() {
+        if (!keep)
+            for (void* x : {(void*)xyz, (void*)rgb, (void*)placed, (void*)tri, (void*)count, (void*)src}) std::free(x);
+    }
+};
+}  // namespace
+
+// the device half of mpmvs_simplify_mesh: n_fin > 0.  class_counts = {alive, non-finite, collapsed}
+static long long mesh_simplify_device(mpmvs_mesh* h, const VoxelGrid& g, int slots_log2, int placement, SimpOut& out, int32_t* out_cluster_of, bool want_count,
+                                      bool want_placed, bool want_src, long long* m_out, long long class_counts[3]) {
+    const hipStream_t st = h->stream;
+    const size_t n = (size_t)h->n, m = (size_t)h->m, slots = (size_t)1 << slots_log2;
+    const int ni = (int)h->n, mi = (int)h->m, ntiles = (ni + kScanBlock - 1) / kScanBlock;
+    const unsigned char* const d_rgb = h->with_color ? h->d_rgb : nullptr;
+    SimpEvents ev;
+    for (hipEvent_t& e : ev.e) CALLCHK(hipEventCreate(&e));
+    float* const ms = h->simp_ms;
+    auto elapsed = [&](int a, int b, float* t) { return hipEventElapsedTime(t, ev.e[a], ev.e[b]); };
+
+    // ---- clusters: the voxel passes as mpmvs_cloud_voxel_downsample runs them, on the resident vertices
+    Scratch d_slot_of(st), d_flag(st), d_num(st), d_tsum(st), d_nc(st), d_keys(st), d_cnt(st), d_first(st), d_vox_of_slot(st);
+    CALLCHK(d_slot_of.alloc(n * 4));
+    CALLCHK(d_flag.alloc(n * 4));
+    CALLCHK(d_num.alloc(n * 4));
+    CALLCHK(d_tsum.alloc((size_t)ntiles * 4));
+    CALLCHK(d_nc.alloc(4));
+    CALLCHK(d_keys.alloc(slots * 8));
+    CALLCHK(d_cnt.alloc(slots * 4));
+    CALLCHK(d_first.alloc(slots * 4));
+    CALLCHK(d_vox_of_slot.alloc(slots * 4));
+    CALLCHK(hipMemsetAsync(d_keys.p, 0xff, slots * 8, st));
+    CALLCHK(hipMemsetAsync(d_cnt.p, 0, slots * 4, st));
+    CALLCHK(hipMemsetAsync(d_first.p, 0xff, slots * 4, st));
+    const dim3 gp((unsigned)ntiles), blk(256);
+    CALLCHK(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(k_cloud_insert, gp, blk, 0, st, h->d_xyz, ni, g.o[0], g.o[1], g.o[2], g.e, (unsigned)(slots - 1), d_keys.as<unsigned long long>(), d_cnt.as<int>(),
+                       d_slot_of.as<int>());
+    hipLaunchKernelGGL(k_voxel_first, gp, blk, 0, st, ni, d_slot_of.as<int>(), d_first.as<unsigned>());
+    hipLaunchKernelGGL(k_voxel_flag, gp, blk, 0, st, ni, d_slot_of.as<int>(), d_first.as<unsigned>(), d_flag.as<int>());
+    hipLaunchKernelGGL(k_scan_tiles, gp, dim3(kScanBlock), 0, st, d_flag.as<int>(), ni, d_num.as<int>(), d_tsum.as<int>());
+    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_tsum.as<int>(), ntiles, 0, d_nc.as<int>());
+    hipLaunchKernelGGL(k_vs_scan_add, gp, dim3(kScanBlock), 0, st, d_num.as<int>(), ni, d_tsum.as<int>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(ev.e[1], st));
+    int nci = 0;
+    CALLCHK(hipMemcpyAsync(&nci, d_nc.p, 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    if (nci <= 0 || (long long)nci > h->n_fin)
+        return call_fail(-100, "mesh simplify: the device counted " + std::to_string(nci) + " clusters for " + std::to_string(h->n_fin) + " finite vertices");
+    const size_t nc = (size_t)nci;
+
+    // ---- numbering, the position (and colour) sums, the quadrics, the representatives
+    Scratch d_out_first(st), d_out_count(st), d_cluster_of(st), d_acc(st), d_qrt(st), d_out_xyz(st), d_out_rgb(st), d_placed(st);
+    CALLCHK(d_out_first.alloc(nc * 4));
+    CALLCHK(d_out_count.alloc(nc * 4));
+    CALLCHK(d_cluster_of.alloc(n * 4));
+    CALLCHK(d_acc.alloc((h->with_color ? 2 : 1) * nc * 24));   // S, then C
+    if (placement == 1) CALLCHK(d_qrt.alloc(nc * kSimpSums * 8));
+    CALLCHK(d_out_xyz.alloc(nc * 12));
+    if (h->with_color) CALLCHK(d_out_rgb.alloc(nc * 3));
+    CALLCHK(d_placed.alloc(nc));
+    unsigned long long* const d_S = d_acc.as<unsigned long long>();
+    unsigned long long* const d_C = h->with_color ? d_S + 3 * nc : nullptr;
+    CALLCHK(hipMemsetAsync(d_acc.p, 0, (h->with_color ? 2 : 1) * nc * 24, st));
+    CALLCHK(hipMemsetAsync(d_placed.p, 0, nc, st));
+    CALLCHK(hipEventRecord(ev.e[2], st));
+    hipLaunchKernelGGL(k_voxel_number, gp, blk, 0, st, ni, d_flag.as<int>(), d_num.as<int>(), d_slot_of.as<int>(), d_cnt.as<int>(), d_vox_of_slot.as<int>(),
+                       d_out_first.as<int32_t>(), d_out_count.as<int32_t>());
+    CALLCHK(hipEventRecord(ev.e[3], st));
+    hipLaunchKernelGGL(k_voxel_accumulate, gp, blk, 0, st, ni, h->d_xyz, (const float*)nullptr, d_rgb, g, d_slot_of.as<int>(), d_vox_of_slot.as<int>(), d_S,
+                       (unsigned long long*)nullptr, d_C, d_cluster_of.as<int32_t>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(ev.e[4], st));
+    if (placement == 1 && m > 0) {
+        CALLCHK(hipMemsetAsync(d_qrt.p, 0, nc * kSimpSums * 8, st));
+        hipLaunchKernelGGL(k_simp_quadric, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_xyz, h->d_tri, g, d_cluster_of.as<int32_t>(), d_qrt.as<unsigned long long>());
+        CALLCHK(hipGetLastError());
+    }
+    CALLCHK(hipEventRecord(ev.e[5], st));
+    hipLaunchKernelGGL(k_voxel_finish, dim3(mesh_blocks(nc)), blk, 0, st, nci, h->d_xyz, d_out_first.as<int32_t>(), d_out_count.as<int32_t>(), g, d_S,
+                       (const unsigned long long*)nullptr, d_C, d_out_xyz.as<float>(), (float*)nullptr, h->with_color ? d_out_rgb.as<unsigned char>() : (unsigned char*)nullptr);
+    if (placement == 1 && m > 0)   // without a triangle no cluster has a plane: placed stays 0 everywhere
+        hipLaunchKernelGGL(k_simp_place, dim3(mesh_blocks(nc)), blk, 0, st, nci, h->d_xyz, d_out_first.as<int32_t>(), d_out_count.as<int32_t>(), g, d_S,
+                           d_qrt.as<unsigned long long>(), d_out_xyz.as<float>(), d_placed.as<unsigned char>());
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipEventRecord(ev.e[6], st));
+
+    // ---- triangles: classes and keys, the duplicate filter, the scan of the kept flags, the emit
+    Scratch d_cls(st), d_key(st), d_class(st), d_table(st), d_kept(st), d_excl(st), d_ttile(st), d_grand(st), d_tri(st), d_src(st);
+    const int t_tiles = (int)((m + kScanBlock - 1) / kScanBlock);
+    int cc[3] = {0, 0, 0};
+    size_t nt = 0;
+    if (m > 0) {
+        CALLCHK(d_cls.alloc(m));
+        CALLCHK(d_key.alloc(m * 12));
+        CALLCHK(d_class.alloc(12));
+        CALLCHK(hipMemsetAsync(d_class.p, 0, 12, st));
+        hipLaunchKernelGGL(k_simp_classify, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_tri, d_cluster_of.as<int32_t>(), d_cls.as<unsigned char>(), d_key.as<int32_t>(),
+                           d_class.as<int>());
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipEventRecord(ev.e[7], st));
+        CALLCHK(hipMemcpyAsync(cc, d_class.p, 12, hipMemcpyDeviceToHost, st));
+        CALLCHK(hipStreamSynchronize(st));
+        if (cc[0] < 0 || cc[1] < 0 || cc[2] < 0 || (long long)cc[0] + cc[1] + cc[2] != h->m) return call_fail(-100, "mesh simplify: the classes do not add up to the triangles");
+    }
+    if (cc[0] > 0) {
+        const int tl2 = simp_slots_log2(cc[0]);
+        const size_t tslots = (size_t)1 << tl2;
+        CALLCHK(d_table.alloc(tslots * 4));
+        CALLCHK(d_kept.alloc(m * 4));
+        CALLCHK(d_excl.alloc(m * 4));
+        CALLCHK(d_ttile.alloc((size_t)t_tiles * 4));
+        CALLCHK(d_grand.alloc(4));
+        CALLCHK(hipEventRecord(ev.e[8], st));
+        CALLCHK(hipMemsetAsync(d_table.p, 0xff, tslots * 4, st));
+        hipLaunchKernelGGL(k_simp_insert, dim3(mesh_blocks(m)), blk, 0, st, mi, d_cls.as<unsigned char>(), d_key.as<int32_t>(), (uint32_t)(tslots - 1), d_table.as<uint32_t>());
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipEventRecord(ev.e[9], st));
+        CALLCHK(hipMemsetAsync(d_kept.p, 0, m * 4, st));
+        hipLaunchKernelGGL(k_simp_owner, dim3(mesh_blocks(tslots)), blk, 0, st, (uint32_t)tslots, d_table.as<uint32_t>(), d_kept.as<int>());
+        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)t_tiles), dim3(kScanBlock), 0, st, d_kept.as<int>(), mi, d_excl.as<int>(), d_ttile.as<int>());
+        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_ttile.as<int>(), t_tiles, 0, d_grand.as<int>());
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipEventRecord(ev.e[10], st));
+        int kept = 0;
+        CALLCHK(hipMemcpyAsync(&kept, d_grand.p, 4, hipMemcpyDeviceToHost, st));
+        CALLCHK(hipStreamSynchronize(st));
+        if (kept <= 0 || kept > cc[0]) return call_fail(-100, "mesh simplify: the device kept " + std::to_string(kept) + " of " + std::to_string(cc[0]) + " alive triangles");
+        nt = (size_t)kept;
+        CALLCHK(d_tri.alloc(nt * 12));
+        CALLCHK(d_src.alloc(nt * 4));
+        CALLCHK(hipEventRecord(ev.e[11], st));
+        hipLaunchKernelGGL(k_simp_emit, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_tri, d_cluster_of.as<int32_t>(), d_kept.as<int>(), d_excl.as<int>(), d_ttile.as<int>(),
+                           d_tri.as<int32_t>(), d_src.as<int32_t>());
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipEventRecord(ev.e[12], st));
+    }
+
+    out.xyz = (float*)std::malloc(nc * 12);
+    if (h->with_color) out.rgb = (unsigned char*)std::malloc(nc * 3);
+    if (want_count) out.count = (int32_t*)std::malloc(nc * 4);
+    if (want_placed) out.placed = (unsigned char*)std::malloc(nc);
+    if (nt) out.tri = (int32_t*)std::malloc(nt * 12);
+    if (nt && want_src) out.src = (int32_t*)std::malloc(nt * 4);
+    if (!out.xyz || (h->with_color && !out.rgb) || (want_count && !out.count) || (want_placed && !out.placed) || (nt && !out.tri) || (nt && want_src && !out.src))
+        return call_fail(-100, "mesh simplify: out of host memory");
+    CALLCHK(hipMemcpyAsync(out.xyz, d_out_xyz.p, nc * 12, hipMemcpyDeviceToHost, st));
+    if (out.rgb) CALLCHK(hipMemcpyAsync(out.rgb, d_out_rgb.p, nc * 3, hipMemcpyDeviceToHost, st));
+    if (out.count) CALLCHK(hipMemcpyAsync(out.count, d_out_count.p, nc * 4, hipMemcpyDeviceToHost, st));
+    if (out.placed) CALLCHK(hipMemcpyAsync(out.placed, d_placed.p, nc, hipMemcpyDeviceToHost, st));
+    if (out.tri) CALLCHK(hipMemcpyAsync(out.tri, d_tri.p, nt * 12, hipMemcpyDeviceToHost, st));
+    if (out.src) CALLCHK(hipMemcpyAsync(out.src, d_src.p, nt * 4, hipMemcpyDeviceToHost, st));
+    if (out_cluster_of) CALLCHK(hipMemcpyAsync(out_cluster_of, d_cluster_of.p, n * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    float a = 0.0f, b = 0.0f;
+    CALLCHK(elapsed(0, 1, &a));
+    CALLCHK(elapsed(2, 3, &b));
+    ms[0] = a + b;
+    CALLCHK(elapsed(3, 4, &ms[1]));
+    if (placement == 1 && m > 0) CALLCHK(elapsed(4, 5, &ms[2]));
+    CALLCHK(elapsed(5, 6, &ms[3]));
+    if (m > 0) CALLCHK(elapsed(6, 7, &ms[4]));
+    if (cc[0] > 0) {
+        CALLCHK(elapsed(8, 9, &a));
+        ms[4] += a;
+        CALLCHK(elapsed(9, 10, &ms[5]));
+        CALLCHK(elapsed(11, 12, &ms[6]));
+    }
+    *m_out = (long long)nt;
+    class_counts[0] = cc[0], class_counts[1] = cc[1], class_counts[2] = cc[2];
+    return (long long)nc;
+}
+
+long long mpmvs_simplify_mesh(mpmvs_mesh* h, float cell, int placement, float** out_xyz, unsigned char** out_rgb, int32_t** out_tri, long long* m_out,
+                              int32_t* out_cluster_of, int32_t** out_count, unsigned char** out_placed, int32_t** out_tri_src, long long counts[3]) {
+    if (!h || !out_xyz || !out_tri || !m_out) return call_fail(-2, "mesh simplify: bad argument");
+    if (!std::isfinite(cell) || !(cell > 0.0f)) return call_fail(-2, "mesh simplify: the cell size must be finite and positive");
+    if (placement != 0 && placement != 1) return call_fail(-2, "mesh simplify: placement must be 0 (mean) or 1 (quadric)");
+    if (h->with_color && !out_rgb) return call_fail(-2, "mesh simplify: a mesh with colour needs out_rgb");
+    if (!h->with_color && out_rgb) return call_fail(-2, "mesh simplify: the mesh has no colour");
+    // the refusals of mpmvs_cloud_voxel_downsample on these vertices
+    const int slots_log2 = cloud_slots_log2(h->n_fin);
+    if (slots_log2 > kCloudMaxSlotsLog2) return call_fail(-3, "mesh simplify: more than 2^29 finite vertices (the table would exceed 2^30 slots)");
+    VoxelGrid g;
+    voxel_origin(h->mn, cell, g);
+    if (h->n_fin > 0) {
+        double top = 0.0;
+        const int a = voxel_span_axis(h->mx, g, &top);
+        if (a >= 0) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "mesh simplify: the vertices span %.6g cells of edge %.6g along %c, more than 2^21 (extent / cell = %.6g)", top + 1.0, g.e,
+                          "xyz"[a], ((double)h->mx[a] - (double)h->mn[a]) / g.e);
+            return call_fail(-3, msg);
+        }
+    }
+    SimpOut out;
+    long long nc = 0, nt = 0, cc[3] = {0, h->m, 0};   // without a finite vertex every triangle names a non-finite one
+    std::memset(h->simp_ms, 0, sizeof h->simp_ms);
+    if (h->n_fin > 0) {
+        const int rc = mesh_ready(h);
+        if (rc) return rc;
+        nc = mesh_simplify_device(h, g, slots_log2, placement, out, out_cluster_of, out_count != nullptr, out_placed != nullptr, out_tri_src != nullptr, &nt, cc);
+        if (nc < 0) return nc;
+    } else if (out_cluster_of) {
+        for (long long v = 0; v < h->n; ++v) out_cluster_of[v] = -1;
+    }
+    *out_xyz = out.xyz;
+    *out_tri = out.tri;
+    if (out_rgb) *out_rgb = out.rgb;
+    if (out_count) *out_count = out.count;
+    if (out_placed) *out_placed = out.placed;
+    if (out_tri_src) *out_tri_src = out.src;
+    *m_out = nt;
+    if (counts) counts[0] = cc[1], counts[1] = cc[2], counts[2] = cc[0] - nt;
+    out.keep = true;
+    return nc;
+}
+
+int mpmvs_simplify_mesh_ms(const mpmvs_mesh* h, float ms[7]) {
+    if (!h || !ms) return call_fail(-2, "mesh simplify_ms: bad argument");
+    std::memcpy(ms, h->simp_ms, sizeof h->simp_ms);
     return 0;
 }
 

@@ -97,6 +97,27 @@ __host__ __device__ inline int cloud_slots_log2(long long n_finite) {
     return b;
 }
 
+// The kernels below are `inline`: two translation units of the library include this header (the clouds and, for its clustering, the
+// mesh simplification), as pm_scan.hpp says of its own.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
+
+// host only -- the pass over the coordinates that every entry point which builds a grid makes: the number of points with three finite
+// coordinates and their bounding box (mn, mx untouched when there is none)
+inline long long cloud_bbox(long long n, const float* xyz, float mn[3], float mx[3]) {
+    long long n_fin = 0;
+    for (long long i = 0; i < n; ++i) {
+        const float* p = xyz + 3 * i;
+        if (!(cloud_finite(p[0]) && cloud_finite(p[1]) && cloud_finite(p[2]))) continue;
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = n_fin ? (p[a] < mn[a] ? p[a] : mn[a]) : p[a];
+            mx[a] = n_fin ? (p[a] > mx[a] ? p[a] : mx[a]) : p[a];
+        }
+        ++n_fin;
+    }
+    return n_fin;
+}
+
 struct CloudGrid {
     double mn[3];
     double edge;
@@ -137,14 +158,14 @@ __host__ __device__ inline void cloud_insert_one(size_t i, const float* __restri
     slot_of[i] = s;
 }
 
-__global__ __launch_bounds__(256) void k_cloud_insert(const float* __restrict__ xyz, int n, double mnx, double mny, double mnz, double edge, unsigned mask,
+inline __global__ __launch_bounds__(256) void k_cloud_insert(const float* __restrict__ xyz, int n, double mnx, double mny, double mnz, double edge, unsigned mask,
                                                       unsigned long long* __restrict__ keys, int* __restrict__ cnt, int* __restrict__ slot_of) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)n) cloud_insert_one(i, xyz, mnx, mny, mnz, edge, mask, keys, cnt, slot_of);
 }
 
 // st[0] += occupied slots, st[1] = max(count)
-__global__ __launch_bounds__(256) void k_cloud_stats(const int* __restrict__ cnt, unsigned slots, int* __restrict__ st) {
+inline __global__ __launch_bounds__(256) void k_cloud_stats(const int* __restrict__ cnt, unsigned slots, int* __restrict__ st) {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int c = k < slots ? cnt[k] : 0;
     int occ = c > 0 ? 1 : 0, mx = c;
@@ -170,7 +191,7 @@ __host__ __device__ inline void cloud_scatter_one(size_t i, const float* __restr
     pts[pos] = rec;
 }
 
-__global__ __launch_bounds__(256) void k_cloud_scatter(const float* __restrict__ xyz, int n, const int* __restrict__ slot_of, const int* __restrict__ off,
+inline __global__ __launch_bounds__(256) void k_cloud_scatter(const float* __restrict__ xyz, int n, const int* __restrict__ slot_of, const int* __restrict__ off,
                                                        int* __restrict__ cnt, uint4* __restrict__ pts) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)n) cloud_scatter_one(i, xyz, slot_of, off, cnt, pts);
@@ -202,7 +223,7 @@ __host__ __device__ inline void cloud_qbin_one(size_t i, const float* __restrict
     cloud_fetch_add(&qcnt[b], 1);
 }
 
-__global__ __launch_bounds__(256) void k_cloud_qbin(const float* __restrict__ q, int nq, CloudGrid g, unsigned bin_mask, int* __restrict__ qcnt,
+inline __global__ __launch_bounds__(256) void k_cloud_qbin(const float* __restrict__ q, int nq, CloudGrid g, unsigned bin_mask, int* __restrict__ qcnt,
                                                     int* __restrict__ qbin) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)nq) cloud_qbin_one(i, q, g, bin_mask, qcnt, qbin);
@@ -214,7 +235,7 @@ __host__ __device__ inline void cloud_qorder_one(size_t i, const int* __restrict
     order[qoff[b] + cloud_fetch_add(&qcnt[b], -1) - 1] = (int)i;
 }
 
-__global__ __launch_bounds__(256) void k_cloud_qorder(int nq, const int* __restrict__ qbin, const int* __restrict__ qoff, int* __restrict__ qcnt,
+inline __global__ __launch_bounds__(256) void k_cloud_qorder(int nq, const int* __restrict__ qbin, const int* __restrict__ qoff, int* __restrict__ qcnt,
                                                       int* __restrict__ order) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)nq) cloud_qorder_one(i, qbin, qoff, qcnt, order);
@@ -304,10 +325,11 @@ __host__ __device__ inline void cloud_query_one(size_t j, const float* __restric
 }
 
 // one thread per query
-__global__ __launch_bounds__(256) void k_cloud_query(const float* __restrict__ q, int nq, const int* __restrict__ order, CloudGrid g, float* __restrict__ out_d2,
+inline __global__ __launch_bounds__(256) void k_cloud_query(const float* __restrict__ q, int nq, const int* __restrict__ order, CloudGrid g, float* __restrict__ out_d2,
                                                      int32_t* __restrict__ out_idx) {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (j < (size_t)nq) cloud_query_one(j, q, order, g, out_d2, out_idx);
 }
+#pragma clang diagnostic pop
 
 }  // namespace pm

@@ -64,13 +64,26 @@ __host__ __device__ inline long long voxel_fix(double x) {
 #endif
 }
 
+// host only -- the cell-span limit of the grid over the finite bounding box: the first axis whose highest point lies in cell 2^21 or
+// beyond (the cells are monotonic in x), with that cell in *top; -1 if every axis fits
+inline int voxel_span_axis(const float mx[3], const VoxelGrid& g, double* top) {
+    for (int a = 0; a < 3; ++a) {
+        *top = floor(((double)mx[a] - g.o[a]) / g.e);
+        if (!(*top < (double)kCloudAxisCells)) return a;
+    }
+    return -1;
+}
+
+// the kernels are `inline`: the clouds and the mesh simplification include this header from two translation units
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
 // ---- pass 2 ------------------------------------------------------------------------------------------------------------
 // first[] starts as all ones: above every index
 __host__ __device__ inline void voxel_first_one(size_t i, const int* __restrict__ slot_of, unsigned* __restrict__ first) {
     const int s = slot_of[i];
     if (s >= 0) voxel_min(&first[s], (unsigned)i);
 }
-__global__ __launch_bounds__(256) void k_voxel_first(int n, const int* __restrict__ slot_of, unsigned* __restrict__ first) {
+inline __global__ __launch_bounds__(256) void k_voxel_first(int n, const int* __restrict__ slot_of, unsigned* __restrict__ first) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)n) voxel_first_one(i, slot_of, first);
 }
@@ -80,7 +93,7 @@ __host__ __device__ inline void voxel_flag_one(size_t i, const int* __restrict__
     const int s = slot_of[i];
     flag[i] = (s >= 0 && first[s] == (unsigned)i) ? 1 : 0;
 }
-__global__ __launch_bounds__(256) void k_voxel_flag(int n, const int* __restrict__ slot_of, const unsigned* __restrict__ first, int* __restrict__ flag) {
+inline __global__ __launch_bounds__(256) void k_voxel_flag(int n, const int* __restrict__ slot_of, const unsigned* __restrict__ first, int* __restrict__ flag) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (size_t)n) voxel_flag_one(i, slot_of, first, flag);
 }
@@ -96,7 +109,7 @@ __host__ __device__ inline void voxel_number_one(size_t i, const int* __restrict
     out_first[v] = (int32_t)i;
     out_count[v] = cnt[s];
 }
-__global__ __launch_bounds__(256) void k_voxel_number(int n, const int* __restrict__ flag, const int* __restrict__ num, const int* __restrict__ slot_of,
+inline __global__ __launch_bounds__(256) void k_voxel_number(int n, const int* __restrict__ flag, const int* __restrict__ num, const int* __restrict__ slot_of,
                                                       const int* __restrict__ cnt, int* __restrict__ vox_of_slot, int32_t* __restrict__ out_first,
                                                       int32_t* __restrict__ out_count) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -145,7 +158,7 @@ __host__ __device__ inline void voxel_accumulate_one(size_t i, const float* __re
             if (b) voxel_add(&C[3 * v + k], (long long)b);
         }
 }
-__global__ __launch_bounds__(256) void k_voxel_accumulate(int n, const float* __restrict__ xyz, const float* __restrict__ normals,
+inline __global__ __launch_bounds__(256) void k_voxel_accumulate(int n, const float* __restrict__ xyz, const float* __restrict__ normals,
                                                           const unsigned char* __restrict__ rgb, VoxelGrid g, const int* __restrict__ slot_of,
                                                           const int* __restrict__ vox_of_slot, unsigned long long* __restrict__ S,
                                                           unsigned long long* __restrict__ N, unsigned long long* __restrict__ C,
@@ -177,12 +190,13 @@ __host__ __device__ inline void voxel_finish_one(size_t v, const float* __restri
     if (out_rgb)
         for (int k = 0; k < 3; ++k) out_rgb[3 * v + k] = (unsigned char)((2 * (long long)C[3 * v + k] + cn) / (2 * cn));   // round half up
 }
-__global__ __launch_bounds__(256) void k_voxel_finish(int m, const float* __restrict__ xyz, const int32_t* __restrict__ first, const int32_t* __restrict__ count,
+inline __global__ __launch_bounds__(256) void k_voxel_finish(int m, const float* __restrict__ xyz, const int32_t* __restrict__ first, const int32_t* __restrict__ count,
                                                       VoxelGrid g, const unsigned long long* __restrict__ S, const unsigned long long* __restrict__ N,
                                                       const unsigned long long* __restrict__ C, float* __restrict__ out_xyz, float* __restrict__ out_normals,
                                                       unsigned char* __restrict__ out_rgb) {
     const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (v < (size_t)m) voxel_finish_one(v, xyz, first, count, g, S, N, C, out_xyz, out_normals, out_rgb);
 }
+#pragma clang diagnostic pop
 
 }  // namespace pm

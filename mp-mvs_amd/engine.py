@@ -131,6 +131,10 @@ _EXTRA = {
                                    C.POINTER(C.c_longlong)]),
     "mesh_pass_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "mesh_destroy": (None, [_P]),
+    # simplification by vertex clustering with quadrics (mesh.py: Mesh.simplify)
+    "simplify_mesh": (C.c_longlong, [_P, C.c_float, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong), _P,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_longlong)]),
+    "simplify_mesh_ms": (C.c_int, [_P, C.POINTER(C.c_float)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

@@ -264,6 +264,10 @@ class SparseVolume(Volume):
                 "brick_share": float(info[0]) / float(info[2]), "allocate_mark": float(ms[0]), "allocate_commit": float(ms[1])}
 
 
+PLACEMENTS = {"mean": 0, "quadric": 1}
+SIMPLIFY_PASSES = ("cluster", "position_accumulate", "quadric_accumulate", "place", "classify_insert", "flag_scan", "emit")
+
+
 class Mesh:
     """mpmvs_mesh: an indexed triangle mesh resident on the device: xyz float32 [n, 3], tri int32 [m, 3] with indices in [0, n),
     rgb uint8 [n, 3] or None (include/mpmvs.h, statements 1 to 3).  Wherever the mesh came from: Volume.mesh()
@@ -354,6 +358,47 @@ class Mesh:
                     lib.mpmvs_free(p)
         return out
 
+    def simplify(self, cell, placement="quadric"):
+        """mpmvs_simplify_mesh -> {"xyz", "rgb", "tri", "cluster_of", "count", "placed", "tri_src", "counts"}: vertex clustering on a
+        grid of edge `cell`; one vertex per occupied cell, at the mean of its members (placement="mean") or where its plane quadric
+        is smallest inside the cell ("quadric"; placed[k] = 1 where that was used, 2 where it fell back to the mean, 0 where the
+        cluster has no plane).  Collapsed and duplicate triangles go; tri_src[new] = old; counts = {"non_finite", "collapsed",
+        "duplicates"}.  Clusters no kept triangle names stay in the result.  The handle is unchanged."""
+        if placement not in PLACEMENTS:
+            raise ValueError(f"placement must be one of {sorted(PLACEMENTS)}, not {placement!r}")
+        lib, _ = engine.load()
+        lib.mpmvs_free.argtypes = [C.c_void_p]
+        lib.mpmvs_free.restype = None
+        px, pc, pt, pn, pp, ps = (C.c_void_p() for _ in range(6))
+        mo, counts = C.c_longlong(0), (C.c_longlong * 3)()
+        cluster_of = np.empty(self.n, np.int32)
+        nc = self._f["simplify_mesh"](self._h, float(cell), PLACEMENTS[placement], C.byref(px), C.byref(pc) if self.color else None, C.byref(pt), C.byref(mo),
+                                      cluster_of.ctypes.data if self.n else None, C.byref(pn), C.byref(pp), C.byref(ps), counts)
+        if nc < 0:
+            _raise(self._f, "simplify_mesh", nc)
+        try:
+            def take(p, ctype, rows, cols, dtype):
+                if not rows:
+                    return np.zeros((0, cols) if cols > 1 else (0,), dtype)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), (rows, cols) if cols > 1 else (rows,)).copy()
+            out = {"xyz": take(px, C.c_float, nc, 3, np.float32), "rgb": take(pc, C.c_uint8, nc, 3, np.uint8) if self.color else None,
+                   "tri": take(pt, C.c_int32, mo.value, 3, np.int32), "cluster_of": cluster_of, "count": take(pn, C.c_int32, nc, 1, np.int32),
+                   "placed": take(pp, C.c_uint8, nc, 1, np.uint8), "tri_src": take(ps, C.c_int32, mo.value, 1, np.int32),
+                   "counts": dict(zip(("non_finite", "collapsed", "duplicates"), (int(v) for v in counts)))}
+        finally:
+            for p in (px, pc, pt, pn, pp, ps):
+                if p.value:
+                    lib.mpmvs_free(p)
+        return out
+
+    def simplify_ms(self):
+        """device ms of the last simplify call, pass by pass"""
+        ms = (C.c_float * 7)()
+        rc = self._f["simplify_mesh_ms"](self._h, ms)
+        if rc != 0:
+            _raise(self._f, "simplify_mesh_ms", rc)
+        return dict(zip(SIMPLIFY_PASSES, (float(v) for v in ms)))
+
     def pass_ms(self):
         """device ms of the last components, normals and select calls"""
         ms = (C.c_float * 8)()
@@ -416,6 +461,29 @@ def clean_and_shade(m, min_component=0, largest=None, normals=False, device=0):
             ms.update({k: v for k, v in h.pass_ms().items() if k.startswith("normals_")})
     info.update(mesh=m, device_ms=ms)
     return info, nrm
+
+
+def simplify(m, cell, placement="quadric", drop_unreferenced=True, normals=False, device=0):
+    """m: a mesh dict {"xyz", "tri", "rgb"}.  Mesh.simplify on it; with drop_unreferenced the clusters that no kept triangle names are
+    removed (Mesh.select on the new mesh; "src"[new] = the cluster number); with normals the vertex normals of the new mesh.
+    Returns the new mesh dict {"xyz", "rgb", "tri"} plus "cluster_of", "count", "placed" (all three by cluster number), "tri_src",
+    "counts", "src" (or None), "normals" and "normals_defined" (or None) and "device_ms"."""
+    with Mesh(m["xyz"], m["tri"], m.get("rgb"), device=device) as h:
+        out = h.simplify(cell, placement)
+        ms = h.simplify_ms()
+    out.update(src=None, normals=None, normals_defined=None)
+    if drop_unreferenced or normals:
+        with Mesh(out["xyz"], out["tri"], out["rgb"], device=device) as h:
+            if drop_unreferenced:
+                sel = h.select(np.ones(h.n, np.uint8), drop_unreferenced=True)
+                out.update(xyz=sel["xyz"], rgb=sel["rgb"], tri=sel["tri"], src=sel["src"])
+                ms.update({k: v for k, v in h.pass_ms().items() if k.startswith("select_")})
+        if normals:
+            with Mesh(out["xyz"], out["tri"], None, device=device) as h:
+                out["normals"], out["normals_defined"] = h.normals()
+                ms.update({k: v for k, v in h.pass_ms().items() if k.startswith("normals_")})
+    out["device_ms"] = ms
+    return out
 
 
 def write_ply_mesh(path, xyz, tri, rgb=None, normals=None):

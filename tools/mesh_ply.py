@@ -5,7 +5,7 @@ level set is extracted by marching tetrahedra (mp-mvs_amd/mesh.py; csrc/pm_tsdf.
     python tools/mesh_ply.py --dense_folder D --output mesh.ply --voxel V [--trunc 4V] [--min_weight 2]
                              [--bbox x0 y0 z0 x1 y1 z1 | --bbox_from MPMVS_model.ply --bbox_percentile 1]
                              [--sparse [--pad 1.0] [--max_bricks N]]
-                             [--min_component N] [--largest K] [--normals]
+                             [--min_component N] [--largest K] [--simplify C [--simplify_placement mean|quadric]] [--normals]
 
 Reads cams/<id>_cam.txt, images/<id>.* and <result_folder>/2333_<id>/depths.dmb (result_folder: D/MPMVS) with the readers of
 mp-mvs_amd/hostlib.py; a camera is rescaled to the size of its depth map as the fusion does, and the image is sampled at the map's
@@ -22,6 +22,10 @@ and --max_voxels does not apply.  The mesh is a sub-mesh of the dense one: the s
 (mesh.remove_small_components): the connected components with fewer than N triangles go, and all but the K
 largest; vertices no triangle names go with them.  --normals writes area-weighted vertex normals (nx ny nz after z).  The mesh is
 cleaned first, then shaded.  N has not been tuned on any real scene.
+--simplify C (scene units; off by default) clusters the vertices on a grid of edge C after the cleaning and before --normals
+(mesh.simplify): one vertex per occupied cell, placed by plane quadrics (--simplify_placement quadric, the
+default) or at the mean; collapsed and duplicate triangles and the vertices no triangle names any more go.  The result line then
+holds simplified = {vertices_in, triangles_in, clusters, non_finite, collapsed, duplicates, placed}.
 Prints one JSON line: n_vox, views, vertices, triangles, device ms per pass, wall seconds; with --sparse also bricks, brick_share and
 device_bytes; with the cleaning flags also components, largest_component and removed_triangles, with --normals normals_defined, and
 the device ms of their passes."""
@@ -70,11 +74,15 @@ def main(argv=None):
     ap.add_argument("--max_bricks", type=int, help="--sparse: the cap on allocated bricks (default: the whole brick grid, at most 2^21)")
     ap.add_argument("--min_component", type=int, default=0, help="drop connected components with fewer triangles; 0 = off; untuned on real scenes")
     ap.add_argument("--largest", type=int, help="keep only the K largest components by triangle count")
+    ap.add_argument("--simplify", type=float, help="cluster the vertices on a grid of this edge (scene units) after the cleaning; off by default")
+    ap.add_argument("--simplify_placement", choices=("mean", "quadric"), default="quadric")
     ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     if args.min_component < 0 or (args.largest is not None and args.largest < 1):
         raise SystemExit("--min_component must not be negative and --largest must be at least 1")
+    if args.simplify is not None and not (0.0 < args.simplify < float("inf")):
+        raise SystemExit("--simplify must be finite and positive")
     if not args.sparse and (args.pad != 1.0 or args.max_bricks is not None):
         raise SystemExit("--pad and --max_bricks go with --sparse")
     if not (math.isfinite(args.voxel) and args.voxel > 0):
@@ -163,9 +171,21 @@ def main(argv=None):
             ms = vol.pass_ms()
             device_ms.update({k: ms[k] for k in ("mark", "scan", "vertices", "triangles")})
         t2 = time.perf_counter()
-        extra, normals = mesh.clean_and_shade(m, args.min_component, args.largest, args.normals, device=args.device)
-        m = extra.pop("mesh")
-        device_ms.update(extra.pop("device_ms"))
+        if args.simplify is None:
+            extra, normals = mesh.clean_and_shade(m, args.min_component, args.largest, args.normals, device=args.device)
+            m = extra.pop("mesh")
+            device_ms.update(extra.pop("device_ms"))
+        else:   # cleaned, simplified, then shaded
+            extra, _ = mesh.clean_and_shade(m, args.min_component, args.largest, False, device=args.device)
+            m = extra.pop("mesh")
+            device_ms.update(extra.pop("device_ms"))
+            s = mesh.simplify(m, args.simplify, args.simplify_placement, drop_unreferenced=True, normals=args.normals, device=args.device)
+            extra["simplified"] = dict(vertices_in=int(len(m["xyz"])), triangles_in=int(len(m["tri"])), clusters=int(len(s["count"])),
+                                       placed=[int((s["placed"] == p).sum()) for p in range(3)], **s["counts"])
+            device_ms.update({(k if k.startswith("normals_") else "simplify_" + k): v for k, v in s["device_ms"].items()})   # its select is not the cleaning's
+            m, normals = {"xyz": s["xyz"], "rgb": s["rgb"], "tri": s["tri"]}, s["normals"]
+            if args.normals:
+                extra["normals_defined"] = s["normals_defined"]
     except (ValueError, OSError, RuntimeError) as e:
         raise SystemExit(str(e)) from None
     t2b = time.perf_counter()
