@@ -175,8 +175,14 @@ int mpmvs_prior_vertices(mpmvs_ctx* ctx, int geom_rule, int* out_xy, int cap, in
  * (:723-755) with the depths of the last mpmvs_run, the depth-range test (:583-595, params->depth_min/max) and
  * CudaPlanarPriorInitialization (:978-996), all on the device.  tri_xy = n x {x1 y1 x2 y2 x3 y3}, every vertex inside
  * the image (the caller drops the others as :555 does); triangle k is label k + 1.  Installs the prior like
- * mpmvs_set_prior. */
+ * mpmvs_set_prior.  -2: a vertex outside the image (refused before anything is counted or launched); -3: an image side above
+ * 65 535, the limit of the vertex list's (y << 16) | x packing. */
 int mpmvs_prior_from_triangles(mpmvs_ctx* ctx, const mpmvs_params* params, const int* tri_xy, int n);
+/* the p-rows mpmvs_prior_from_triangles dispatches for a triangle whose longest edge has the integer square edge_sq[i]
+ * (pm::prior_rows, csrc/pm_prior.hpp): never fewer than the reference's `for (float p = 0; p < 1.0; p += step)` runs, never
+ * 64 or more above.  -1 for an edge_sq outside [0, 2 * 65535^2], the largest an image of 65 535 x 65 535 holds.  Host arithmetic
+ * only, no device is touched; for tests and tools. */
+int mpmvs_prior_rows(const long long* edge_sq, int n, int* rows);
 /* the installed prior planes (float4) and mask (u32) back on the host, for tests; either may be NULL */
 int mpmvs_get_prior(mpmvs_ctx* ctx, void* prior_planes4, void* mask_u32);
 

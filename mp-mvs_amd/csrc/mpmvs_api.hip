@@ -1653,18 +1653,15 @@ int mpmvs_prior_from_triangles(mpmvs_ctx* c, const mpmvs_params* p, const int* t
     ENTER(c);
     if (!c->S.planes) return fail(c, -1, "set_views first");
     const int W = c->W, H = c->H;
-    // vertex check and task table in one parallel sweep: 64 consecutive p-rows of one triangle per wave (pm_prior.hpp); a
-    // triangle of longest edge L has at most floor(L) + 2 rows (the accumulated p passes 1 after L + 1 steps; the kernel's own
-    // p < 1 test is what decides).  Chunks of triangles are counted, their task ranges follow by a prefix sum, then filled:
-    // the table is the one the sequential loop would build.
+    // the vertex picker packs (y << 16) | x and the row bound of the raster is stated up to that size (pm_prior.hpp)
+    if (W > kPriorMaxSide || H > kPriorMaxSide) return fail(c, -3, "image side above 65535: no planar prior at this size");
+    // vertex check and task table in one parallel sweep: 64 consecutive p-rows of one triangle per wave (pm_prior.hpp).  The
+    // rows of a triangle are prior_rows() of its longest edge: at least as many as the reference's fp32 accumulation of p runs
+    // (which is not floor(L) + 2: from L ~ 12 000 on the rounding of the accumulation adds whole rows), and less than one task
+    // more; the kernel's own p < 1 test is what decides.  Chunks of triangles are counted, their task ranges follow by a
+    // prefix sum, then filled: the table is the one the sequential loop would build.
     const size_t wh = (size_t)W * H;
-    auto rows_of = [&](int t) {
-        const int* v = tri_xy + 6 * (size_t)t;
-        const long long e01 = (long long)(v[0] - v[2]) * (v[0] - v[2]) + (long long)(v[1] - v[3]) * (v[1] - v[3]);
-        const long long e02 = (long long)(v[0] - v[4]) * (v[0] - v[4]) + (long long)(v[1] - v[5]) * (v[1] - v[5]);
-        const long long e12 = (long long)(v[2] - v[4]) * (v[2] - v[4]) + (long long)(v[3] - v[5]) * (v[3] - v[5]);
-        return (int)std::sqrt((double)std::max(e01, std::max(e02, e12))) + 3;
-    };
+    auto rows_of = [&](int t) { return prior_rows(prior_longest_edge_sq(tri_xy + 6 * (size_t)t)); };
     const unsigned hw = std::thread::hardware_concurrency();
     const int nchunks = n >= 65536 ? (int)std::max(1u, std::min(8u, hw ? hw : 1u)) : 1;
     std::vector<size_t> chunk_tasks((size_t)nchunks + 1, 0);
@@ -1687,7 +1684,8 @@ int mpmvs_prior_from_triangles(mpmvs_ctx* c, const mpmvs_params* p, const int* t
         for (int t = t0; t < t1; ++t) {
             const int* v = tri_xy + 6 * (size_t)t;
             for (int i = 0; i < 6; i += 2) ok &= v[i] >= 0 && v[i] < W && v[i + 1] >= 0 && v[i + 1] < H;
-            k += (size_t)(rows_of(t) + 63) / 64;
+            if (!ok) break;  // the call is refused: no rows are counted for coordinates that were not checked
+            k += (size_t)(rows_of(t) + kPriorTaskRows - 1) / kPriorTaskRows;
         }
         chunk_tasks[(size_t)ch + 1] = k;
         if (!ok) inside = false;
@@ -1704,7 +1702,7 @@ int mpmvs_prior_from_triangles(mpmvs_ctx* c, const mpmvs_params* p, const int* t
         size_t k = chunk_tasks[(size_t)ch];
         for (int t = t0; t < t1; ++t) {
             const int rows = rows_of(t);
-            for (int r0 = 0; r0 < rows; r0 += 64) {
+            for (int r0 = 0; r0 < rows; r0 += kPriorTaskRows) {
                 task_tri[k] = t;
                 task_row0[k++] = r0;
             }
@@ -1746,6 +1744,23 @@ int mpmvs_get_prior(mpmvs_ctx* c, void* prior4, void* mask) {
     if (prior4) HIPCHK(c, hipMemcpyAsync(prior4, c->d_prior, wh * 16, hipMemcpyDeviceToHost, c->stream));
     if (mask) HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, wh * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int mpmvs_prior_rows(const long long* edge_sq, int n, int* rows) {
+    if (n < 0 || (n > 0 && (!edge_sq || !rows))) return -1;
+    for (int i = 0; i < n; ++i)
+        if (edge_sq[i] < 0 || edge_sq[i] > kPriorMaxEdgeSq) return -1;
+    // long edges cost O(L) each: interleaved over a few host threads
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int nthreads = n >= 1024 ? (int)std::max(1u, std::min(16u, hw ? hw : 1u)) : 1;
+    auto part = [&](int k) {
+        for (int i = k; i < n; i += nthreads) rows[i] = prior_rows(edge_sq[i]);
+    };
+    std::vector<std::thread> pool;
+    for (int k = 1; k < nthreads; ++k) pool.emplace_back(part, k);
+    part(0);
+    for (std::thread& t : pool) t.join();
     return 0;
 }
 

@@ -12,14 +12,62 @@
 // Arithmetic: the same fp32 / fp64 IEEE operations in the same order as the host implementation (planar_prior.cpp), so the
 // two produce identical bits (tests/test_prior_gpu.py) and both are pinned by the independent fixtures of
 // tests/golden/prior_golden_v1.npz.
+//
+// The row bound of the raster's task table (prior_rows) is plain host code: this header is includable without HIP, and then
+// holds nothing else (tools/prior_rows_check.cpp).
 #pragma once
 
-#include "pm_device.hpp"
-#include "pm_scan.hpp"
+#include <cmath>
 
 namespace pm {
 
 constexpr int kPriorCell = 5;
+constexpr int kPriorTaskRows = 64;                  // p-rows of one raster task: one per lane of a wave
+constexpr long long kPriorExactFrom = 1ll << 24;    // squared longest edge (L = 4096) from which prior_rows counts the loop itself
+constexpr int kPriorMaxSide = 65535;                // the longest image side the prior is built for: the (y << 16) | x packing of the vertices
+constexpr long long kPriorMaxEdgeSq = 2ll * kPriorMaxSide * kPriorMaxSide;   // no edge inside such an image has a larger square
+
+// How many p-rows the reference's `for (float p = 0; p < 1.0; p += step)` (ref :564) can run for a triangle whose longest edge
+// has the integer square e, step = (float)(1.0 / (float)sqrt(e)): the rows the task table has to cover.  Never below the
+// loop's own count and never kPriorTaskRows or more above it, for every edge an image can hold (the (y << 16) | x packing of
+// the vertices keeps both image sides at or below 65 535, so e < 2 * 65 535^2); the kernel's own p < 1 test decides which of
+// the dispatched rows run.
+//   The count is not floor(L) + 2: p is accumulated in fp32, every addition inside one binade of p rounds the same way, and the
+// error left after the ~L / 2 additions between 0.5 and 1 grows like L^2 * 2^-26 rows.  For integer L <= 65 535 the loop runs
+// between floor(L) - 63 and floor(L) + 64 rows; among integer L it first outruns floor(L) + 3 at L = 14 457 and that bound
+// rounded up to whole tasks at L = 14 973, among other e somewhat earlier (L = 12 695.9 in the sample of
+// tools/prior_rows_check.cpp; DESIGN.md, the planar-prior section).  Below L = 4096 the loop runs floor(L) .. floor(L) + 2
+// rows and floor(L) + 3 holds (tools/prior_rows_check.cpp: every e below 2^20 and both ends of every run of equal floor(L)
+// up to 4096; the count never falls as e grows); from there on the count is taken from the accumulation itself, O(L) host
+// additions for the few slivers that are so long.  No closed form of L alone can stay within a task of a count that strays
+// 63 rows to either side.
+//   Total: -1 for e outside [0, kPriorMaxEdgeSq].  Beyond it the count is no use (at L ~ 3.4e7 the step falls below half an ulp of
+// 0.5, p stops moving and the reference's loop never ends), and the callers refuse such edges; inside it the loop below ends after
+// fewer than 93 000 additions.
+inline int prior_rows(long long e) {
+    if (e < 0 || e > kPriorMaxEdgeSq) return -1;
+    if (e < kPriorExactFrom) return (int)std::sqrt((double)e) + 3;
+    const float step = (float)(1.0 / (double)(float)std::sqrt((double)e));
+    int rows = 0;
+    for (float p = 0.0f; p < 1.0; p += step) ++rows;
+    return rows;
+}
+
+// the squared longest edge of a triangle {x1 y1 x2 y2 x3 y3} whose vertices lie inside an image (coordinates in [0, 2^24))
+inline long long prior_longest_edge_sq(const int* v) {
+    const long long e01 = (long long)(v[0] - v[2]) * (v[0] - v[2]) + (long long)(v[1] - v[3]) * (v[1] - v[3]);
+    const long long e02 = (long long)(v[0] - v[4]) * (v[0] - v[4]) + (long long)(v[1] - v[5]) * (v[1] - v[5]);
+    const long long e12 = (long long)(v[2] - v[4]) * (v[2] - v[4]) + (long long)(v[3] - v[5]) * (v[3] - v[5]);
+    return e01 > e02 ? (e01 > e12 ? e01 : e12) : (e02 > e12 ? e02 : e12);
+}
+
+}  // namespace pm
+
+#if defined(__HIPCC__)
+#include "pm_device.hpp"
+#include "pm_scan.hpp"
+
+namespace pm {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // vertices
@@ -123,9 +171,10 @@ __global__ __launch_bounds__(256) void k_prior_raster(const int* __restrict__ tr
     const int W = P.W, H = P.H;
     const int t = task_tri[task], row0 = task_row0[task];
     const int x1 = tri[6 * t], y1 = tri[6 * t + 1], x2 = tri[6 * t + 2], y2 = tri[6 * t + 3], x3 = tri[6 * t + 4], y3 = tri[6 * t + 5];
-    const float L01 = (float)__builtin_sqrt((double)((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2)));
-    const float L02 = (float)__builtin_sqrt((double)((x1 - x3) * (x1 - x3) + (y1 - y3) * (y1 - y3)));
-    const float L12 = (float)__builtin_sqrt((double)((x2 - x3) * (x2 - x3) + (y2 - y3) * (y2 - y3)));
+    // the squares in double as the reference's pow(.., 2) forms them (ref :557-559): exact, where an int product wraps from 46 341 px on
+    const float L01 = (float)__builtin_sqrt((double)(x1 - x2) * (double)(x1 - x2) + (double)(y1 - y2) * (double)(y1 - y2));
+    const float L02 = (float)__builtin_sqrt((double)(x1 - x3) * (double)(x1 - x3) + (double)(y1 - y3) * (double)(y1 - y3));
+    const float L12 = (float)__builtin_sqrt((double)(x2 - x3) * (double)(x2 - x3) + (double)(y2 - y3) * (double)(y2 - y3));
     const float max_edge = fmaxf(L01, fmaxf(L02, L12));
     const float step = (float)(1.0 / (double)max_edge);
     const uint32_t lab = (uint32_t)t + 1u;
@@ -195,3 +244,4 @@ __global__ __launch_bounds__(256) void k_prior_finish(const ProblemDev* __restri
 }
 
 }  // namespace pm
+#endif  // __HIPCC__

@@ -35,6 +35,7 @@ _EXTRA = {
     "prior_vertices": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_int)]),
     "prior_from_triangles": (C.c_int, [_P, C.POINTER(_abi.PatchMatchParams), _P, C.c_int]),
     "get_prior": (C.c_int, [_P, _P, _P]),
+    "prior_rows": (C.c_int, [_P, C.c_int, _P]),
     "alloc_pinned": (C.c_void_p, [C.c_size_t]),
     "free_pinned": (None, [C.c_void_p]),
     "peer_info": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -313,6 +314,17 @@ class HipPatchMatch(_abi.PatchMatchHandle):
 
     def export_depth_device(self, ptr):
         self._chk(self._f["export_depth_device"](self._ctx, int(ptr)), "export_depth_device")
+
+
+def prior_rows(edge_sq):
+    """the p-rows prior_from_triangles dispatches per squared longest edge (mpmvs_prior_rows; host arithmetic, no device): int32 array"""
+    import numpy as np
+    _, fns = load()
+    e = np.ascontiguousarray(edge_sq, np.int64).reshape(-1)
+    rows = np.empty(len(e), np.int32)
+    if fns["prior_rows"](e.ctypes.data, len(e), rows.ctypes.data) != 0:
+        raise RuntimeError("mpmvs_prior_rows refused its arguments")
+    return rows
 
 
 def peer_info(device, peer):

@@ -785,9 +785,12 @@ void BuildPrior(const Camera& cam, int width, int height, const std::vector<Tria
     for (long k = 0; k < (long)keep.size(); ++k) {
         const Triangle& t = triangles[keep[k]];
         const uint32_t lab = (uint32_t)k + 1u;
-        const float L01 = (float)std::sqrt((double)((t.pt1.x - t.pt2.x) * (t.pt1.x - t.pt2.x) + (t.pt1.y - t.pt2.y) * (t.pt1.y - t.pt2.y)));
-        const float L02 = (float)std::sqrt((double)((t.pt1.x - t.pt3.x) * (t.pt1.x - t.pt3.x) + (t.pt1.y - t.pt3.y) * (t.pt1.y - t.pt3.y)));
-        const float L12 = (float)std::sqrt((double)((t.pt2.x - t.pt3.x) * (t.pt2.x - t.pt3.x) + (t.pt2.y - t.pt3.y) * (t.pt2.y - t.pt3.y)));
+        // the squares in double as the reference's pow(.., 2) forms them (src/PatchMatch.cpp:557-559): an int product wraps from 46 341 px on
+        auto edge = [](Point a, Point b) {
+            const double dx = (double)a.x - (double)b.x, dy = (double)a.y - (double)b.y;
+            return (float)std::sqrt(dx * dx + dy * dy);
+        };
+        const float L01 = edge(t.pt1, t.pt2), L02 = edge(t.pt1, t.pt3), L12 = edge(t.pt2, t.pt3);
         const float max_edge = std::max(L01, std::max(L02, L12));
         const float step = (float)(1.0 / max_edge);
         // barycentric stepping of the reference (src/PatchMatch.cpp:564-570)
