@@ -739,9 +739,8 @@ int mpmvs_resize_u8(int device, const unsigned char* src, int src_w, int src_h, 
     float* d_out = call.alloc<float>(out_bytes);
     if (!d_src || !d_out) return -100;
     if (hipMemcpy2DAsync(d_src, (size_t)src_w, src, pitch_bytes, (size_t)src_w, (size_t)src_h, hipMemcpyHostToDevice, call.stream()) != hipSuccess) return -100;
-    hipLaunchKernelGGL(k_ingest_pad, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0, call.stream(), ingest_src(d_src, src_w, src_h, dst_w, dst_h), dst_w, dst_h,
-                       d_out, 0);
-    if (hipGetLastError() != hipSuccess) return -100;
+    if (launch(k_ingest_pad, dim3((dst_w + 255) / 256, dst_h), dim3(256), call.stream(), ingest_src(d_src, src_w, src_h, dst_w, dst_h), dst_w, dst_h, d_out, 0) != hipSuccess)
+        return -100;
     if (hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, call.stream()) != hipSuccess || hipStreamSynchronize(call.stream()) != hipSuccess) return -100;
     return 0;
 }
@@ -1523,8 +1522,7 @@ int mpmvs_export_depth_device(mpmvs_ctx* c, float* d_out) {
     ENTER(c);
     if (!c->S.planes) return fail(c, -1, "set_views first");
     const int n = c->W * c->H;
-    hipLaunchKernelGGL(k_export_depth, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S.planes, d_out, n);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch(k_export_depth, dim3((n + 255) / 256), dim3(256), c->stream, c->S.planes, d_out, n));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -1593,8 +1591,7 @@ int mpmvs_eval_geom(mpmvs_ctx* c, const mpmvs_params* p, const void* planes_cam4
     HIPCHK(c, d_out.alloc(wh * 4 * V));
     HIPCHK(c, hipMemcpyAsync(d_pl.p, planes_cam4, wh * 16, hipMemcpyHostToDevice, c->stream));
     const dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
-    hipLaunchKernelGGL(k_eval_geom, grid, dim3(256), 0, c->stream, c->dP, d_pl.as<float4>(), d_out.as<float>());
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch(k_eval_geom, grid, dim3(256), c->stream, c->dP, d_pl.as<float4>(), d_out.as<float>()));
     HIPCHK(c, hipMemcpyAsync(out, d_out.p, wh * 4 * V, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -1607,8 +1604,7 @@ int mpmvs_homography(mpmvs_ctx* c, const void* plane4, int v, void* H9) {
     Scratch d_h(c->stream);
     HIPCHK(c, d_h.alloc(9 * 4));
     const float* pf = (const float*)plane4;
-    hipLaunchKernelGGL(k_homography, dim3(1), dim3(64), 0, c->stream, c->dP, make_float4(pf[0], pf[1], pf[2], pf[3]), v, d_h.as<float>());
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, launch(k_homography, dim3(1), dim3(64), c->stream, c->dP, make_float4(pf[0], pf[1], pf[2], pf[3]), v, d_h.as<float>()));
     HIPCHK(c, hipMemcpyAsync(H9, d_h.p, 9 * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
@@ -1770,8 +1766,7 @@ int mpmvs_math(int fn, const void* in, void* out, int n) {
     float *d_in = call.alloc<float>((size_t)n * 4), *d_out = call.alloc<float>((size_t)n * 4);
     if (!d_in || !d_out) return -100;
     if (hipMemcpy(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return -100;
-    hipLaunchKernelGGL(k_math, dim3((n + 255) / 256), dim3(256), 0, call.stream(), fn, d_in, d_out, n);
-    if (hipGetLastError() != hipSuccess) return -100;
+    if (launch(k_math, dim3((n + 255) / 256), dim3(256), call.stream(), fn, d_in, d_out, n) != hipSuccess) return -100;
     return hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
 
@@ -1781,8 +1776,7 @@ int mpmvs_verify_rcp(unsigned long long counts[4]) {
     unsigned long long* d = call.alloc<unsigned long long>(32);
     if (!d || hipMemset(d, 0, 32) != hipSuccess) return -100;
     for (uint64_t base = 0; base < (1ULL << 32); base += (1ULL << 24)) {
-        hipLaunchKernelGGL(k_verify_rcp, dim3(1 << 16), dim3(256), 0, call.stream(), (uint32_t)base, d);
-        if (hipGetLastError() != hipSuccess) return -100;
+        if (launch(k_verify_rcp, dim3(1 << 16), dim3(256), call.stream(), (uint32_t)base, d) != hipSuccess) return -100;
     }
     return hipMemcpy(counts, d, 32, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
@@ -1792,8 +1786,7 @@ int mpmvs_rng(uint64_t seed, uint32_t pix, uint32_t launch_id, int n, void* out)
     DeviceCall call;
     float* d_out = call.alloc<float>((size_t)n * 4);
     if (!d_out) return -100;
-    hipLaunchKernelGGL(k_rng, dim3(1), dim3(64), 0, call.stream(), seed, pix, launch_id, n, d_out);
-    if (hipGetLastError() != hipSuccess) return -100;
+    if (launch(k_rng, dim3(1), dim3(64), call.stream(), seed, pix, launch_id, n, d_out) != hipSuccess) return -100;
     return hipMemcpy(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -100;
 }
 

@@ -17,8 +17,10 @@
 
 #include "../../include/mpmvs.h"
 #include "pm_host.hpp"
+#include "pm_scan_host.hpp"
 #include "pm_cloud.hpp"
 #include "pm_voxel.hpp"
+#include "pm_cluster_host.hpp"
 #include "pm_knn.hpp"
 #include "pm_normals.hpp"
 #include "pm_components.hpp"
@@ -59,7 +61,7 @@ static float cloud_op_ms(const CloudOpMs& t, float* build_ms) {
 struct mpmvs_cloud {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // build begin / end, query begin / end; a render: the borders of its three passes
+    PassClock<4> clock;   // build begin / end, query begin / end; a render: the borders of its three passes
     long long n = 0, n_fin = 0;
     float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // finite bounding box
     int slots_log2 = 0;
@@ -88,16 +90,13 @@ static void cloud_release(mpmvs_cloud* c) {
     for (CloudGridBuf& g : c->grids) cloud_free_grid(g);
     for (void* p : {(void*)c->d_xyz, (void*)c->d_cnt, (void*)c->d_tsum, (void*)c->d_slot_of, (void*)c->d_st, (void*)c->d_cc})
         if (p) (void)pool_free(p);
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the clock goes here: the stream has been waited for
 }
 
 static int cloud_create_device(mpmvs_cloud* c, const float* xyz) {
     CALLCHK(enter_device(c->device));
     CALLCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : c->ev) CALLCHK(hipEventCreate(&e));
     if (c->n_fin == 0) return 0;   // nothing to search: every call answers on the host
     const size_t n = (size_t)c->n, slots = (size_t)1 << c->slots_log2;
     CALLCHK(pool_malloc(&c->d_xyz, n * 12));
@@ -148,14 +147,6 @@ void mpmvs_cloud_destroy(mpmvs_cloud* c) {
     cloud_release(c);
 }
 
-// slot counts -> offsets (off[n] = the total): the library's scan plus the add pass
-static void cloud_scan(hipStream_t st, const int* cnt, int n, int* off, int* tsum) {
-    const int ntiles = (n + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kScanBlock), 0, st, cnt, n, off, tsum);
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, tsum, ntiles, 0, off + n);
-    hipLaunchKernelGGL(k_vs_scan_add, dim3(ntiles), dim3(kScanBlock), 0, st, off, n, tsum);
-}
-
 // builds the grid of `radius` into g, whose buffers exist
 static int cloud_build(mpmvs_cloud* c, CloudGridBuf& g, float radius) {
     const hipStream_t st = c->stream;
@@ -165,19 +156,18 @@ static int cloud_build(mpmvs_cloud* c, CloudGridBuf& g, float radius) {
     CALLCHK(hipMemsetAsync(g.d_keys, 0xff, slots * 8, st));
     CALLCHK(hipMemsetAsync(c->d_cnt, 0, slots * 4, st));
     CALLCHK(hipMemsetAsync(c->d_st, 0, 8, st));
-    CALLCHK(hipEventRecord(c->ev[0], st));
+    CALLCHK(c->clock.mark(0, st));
     const dim3 gp((n + 255) / 256), gs((unsigned)(slots / 256));
-    hipLaunchKernelGGL(k_cloud_insert, gp, dim3(256), 0, st, c->d_xyz, n, (double)c->mn[0], (double)c->mn[1], (double)c->mn[2], edge, (unsigned)(slots - 1),
-                       g.d_keys, c->d_cnt, c->d_slot_of);
-    hipLaunchKernelGGL(k_cloud_stats, gs, dim3(256), 0, st, c->d_cnt, (unsigned)slots, c->d_st);
-    cloud_scan(st, c->d_cnt, (int)slots, g.d_off, c->d_tsum);
-    hipLaunchKernelGGL(k_cloud_scatter, gp, dim3(256), 0, st, c->d_xyz, n, c->d_slot_of, g.d_off, c->d_cnt, g.d_pts);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[1], st));
+    CALLCHK(launch(k_cloud_insert, gp, dim3(256), st, c->d_xyz, n, (double)c->mn[0], (double)c->mn[1], (double)c->mn[2], edge, (unsigned)(slots - 1), g.d_keys,
+                   c->d_cnt, c->d_slot_of));
+    CALLCHK(launch(k_cloud_stats, gs, dim3(256), st, c->d_cnt, (unsigned)slots, c->d_st));
+    CALLCHK(scan_offsets(st, c->d_cnt, (int)slots, g.d_off, c->d_tsum, g.d_off + slots, true));   // slot counts -> offsets, off[slots] = the total
+    CALLCHK(launch(k_cloud_scatter, gp, dim3(256), st, c->d_xyz, n, c->d_slot_of, g.d_off, c->d_cnt, g.d_pts));
+    CALLCHK(c->clock.mark(1, st));
     int h_st[2] = {0, 0};
     CALLCHK(hipMemcpyAsync(h_st, c->d_st, 8, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&c->query.build_ms, c->ev[0], c->ev[1]));
+    CALLCHK(c->clock.ms(0, 1, &c->query.build_ms));
     g.occupied = h_st[0], g.fullest = h_st[1];
     g.radius = radius;
     return 0;
@@ -265,35 +255,36 @@ struct CloudBins {
 };
 
 extern "C++" {
-// The one binning path: the serving order of nq <= cap queries into b.order.  The counts are cleared, `begin` (may be null) is
-// recorded -- the callers whose timed interval opens after the memset pass their begin event -- and then count / scan / order run.
-// count(grid, bin_mask, qcnt, qbin) launches the counting kernel, the only part that differs: k_cloud_qbin on raw queries,
-// k_align_qbin on transformed sources.
-template <typename Count>
-static int cloud_bin(hipStream_t st, CloudBins& b, int nq, hipEvent_t begin, Count&& count) {
+// The one binning path: the serving order of nq <= cap queries into b.order.  The counts are cleared, begin() marks the caller's
+// clock -- the callers whose timed interval opens after the memset pass their mark, the others no_mark -- and then count / scan /
+// order run.  count(grid, bin_mask, qcnt, qbin) launches the counting kernel, the only part that differs: k_cloud_qbin on raw
+// queries, k_align_qbin on transformed sources.
+template <typename Begin, typename Count>
+static int cloud_bin(hipStream_t st, CloudBins& b, int nq, Begin&& begin, Count&& count) {
     const size_t bins = (size_t)1 << cloud_bins_log2(nq);   // <= what alloc sized
     const dim3 gq(((unsigned)nq + 255u) / 256u);            // unsigned: nq may be 2^31 - 1
     CALLCHK(hipMemsetAsync(b.qcnt.p, 0, bins * 4, st));
-    if (begin) CALLCHK(hipEventRecord(begin, st));
-    count(gq, (unsigned)(bins - 1), b.qcnt.as<int>(), b.qbin.as<int>());
-    cloud_scan(st, b.qcnt.as<int>(), (int)bins, b.qoff.as<int>(), b.qtsum.as<int>());
-    hipLaunchKernelGGL(k_cloud_qorder, gq, dim3(256), 0, st, nq, b.qbin.as<int>(), b.qoff.as<int>(), b.qcnt.as<int>(), b.order.as<int>());
+    CALLCHK(begin());
+    CALLCHK(count(gq, (unsigned)(bins - 1), b.qcnt.as<int>(), b.qbin.as<int>()));
+    CALLCHK(scan_offsets(st, b.qcnt.as<int>(), (int)bins, b.qoff.as<int>(), b.qtsum.as<int>(), b.qoff.as<int>() + bins, true));
+    CALLCHK(launch(k_cloud_qorder, gq, dim3(256), st, nq, b.qbin.as<int>(), b.qoff.as<int>(), b.qcnt.as<int>(), b.order.as<int>()));
     return 0;
 }
+static hipError_t no_mark() { return hipSuccess; }
 // the counting launch of raw queries
 static auto cloud_count_queries(hipStream_t st, const float* d_q, int nq, const CloudGrid& g) {
-    return [=](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) { hipLaunchKernelGGL(k_cloud_qbin, gq, dim3(256), 0, st, d_q, nq, g, bin_mask, qcnt, qbin); };
+    return [=](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) { return launch(k_cloud_qbin, gq, dim3(256), st, d_q, nq, g, bin_mask, qcnt, qbin); };
 }
 
-// The one dispatch over the list sizes of the kNN family (pm_knn.hpp: knn_list_size): launch(std::integral_constant<int, K>) with
-// the K of 4, 8, 16 or 32 that serves k
+// The one dispatch over the list sizes of the kNN family (pm_knn.hpp: knn_list_size): run(std::integral_constant<int, K>) with
+// the K of 4, 8, 16 or 32 that serves k; what run returns
 template <typename F>
-static void knn_dispatch(int k, F&& launch) {
+static int knn_dispatch(int k, F&& run) {
     switch (knn_list_size(k)) {
-        case 4: launch(std::integral_constant<int, 4>{}); break;
-        case 8: launch(std::integral_constant<int, 8>{}); break;
-        case 16: launch(std::integral_constant<int, 16>{}); break;
-        default: launch(std::integral_constant<int, 32>{}); break;
+        case 4: return run(std::integral_constant<int, 4>{});
+        case 8: return run(std::integral_constant<int, 8>{});
+        case 16: return run(std::integral_constant<int, 16>{});
+        default: return run(std::integral_constant<int, 32>{});
     }
 }
 }  // extern "C++"
@@ -367,19 +358,18 @@ int mpmvs_cloud_nearest(mpmvs_cloud* c, float radius, long long n_q, const float
     if (bin) CALLCHK(bins.alloc(q));
     CALLCHK(hipMemcpyAsync(d_q.p, q_xyz, q * 12, hipMemcpyHostToDevice, st));
     if (bin) {
-        const int brc = cloud_bin(st, bins, nq, c->ev[2], cloud_count_queries(st, d_q.as<float>(), nq, g));
+        const int brc = cloud_bin(st, bins, nq, [&] { return c->clock.mark(2, st); }, cloud_count_queries(st, d_q.as<float>(), nq, g));
         if (brc) return brc;
     } else {
-        CALLCHK(hipEventRecord(c->ev[2], st));
+        CALLCHK(c->clock.mark(2, st));
     }
-    hipLaunchKernelGGL(k_cloud_query, dim3(((unsigned)nq + 255u) / 256u), dim3(256), 0, st, d_q.as<float>(), nq, bin ? bins.order.as<int>() : (const int*)nullptr, g,
-                       d_d2.as<float>(), out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[3], st));
+    CALLCHK(launch(k_cloud_query, dim3(((unsigned)nq + 255u) / 256u), dim3(256), st, d_q.as<float>(), nq, bins.order.as<int>(), g, d_d2.as<float>(),
+                   d_idx.as<int32_t>()));
+    CALLCHK(c->clock.mark(3, st));
     CALLCHK(hipMemcpyAsync(out_d2, d_d2.p, q * 4, hipMemcpyDeviceToHost, st));
     if (out_idx) CALLCHK(hipMemcpyAsync(out_idx, d_idx.p, q * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&c->query.ms, c->ev[2], c->ev[3]));
+    CALLCHK(c->clock.ms(2, 3, &c->query.ms));
     return 0;
 }
 
@@ -402,26 +392,6 @@ void mpmvs_cloud_voxel_pass_ms(float ms[6]) {
     if (ms) std::memcpy(ms, g_voxel_pass_ms, sizeof g_voxel_pass_ms);
 }
 
-namespace {
-// the borders of the six passes; destroyed after the DeviceCall declared below them has synchronised its stream
-struct VoxelEvents {
-    hipEvent_t e[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~VoxelEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-// the host buffers of the result: released unless the call succeeds
-struct VoxelOut {
-    void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool keep = false;
-    ~VoxelOut() {
-        if (!keep)
-            for (void* x : p) std::free(x);
-    }
-};
-}  // namespace
-
 long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz, const float* normals, const unsigned char* rgb, float voxel, float** out_xyz,
                                        float** out_normals, unsigned char** out_rgb, int32_t** out_count, int32_t** out_first, int32_t* out_voxel_of) {
     if (n < 0 || (n > 0 && !xyz) || !out_xyz || !out_count || !out_first || (normals && !out_normals) || (rgb && !out_rgb))
@@ -433,20 +403,10 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
     if (n > INT32_MAX) return call_fail(-3, "voxel: more than 2^31 - 1 points");
     float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
     const long long n_fin = cloud_bbox(n, xyz, mn, mx);
-    const int slots_log2 = cloud_slots_log2(n_fin);
-    if (slots_log2 > kCloudMaxSlotsLog2) return call_fail(-3, "voxel: more than 2^29 finite points (the table would exceed 2^30 slots)");
+    const ClusterNames names = {"voxel", "points", "voxel", "voxels"};
+    int slots_log2 = 0;
     VoxelGrid g;
-    voxel_origin(mn, voxel, g);
-    if (n_fin > 0) {
-        double top = 0.0;
-        const int a = voxel_span_axis(mx, g, &top);
-        if (a >= 0) {
-            char msg[200];
-            std::snprintf(msg, sizeof msg, "voxel: the points span %.6g cells of edge %.6g along %c, more than 2^21 (extent / voxel = %.6g)", top + 1.0, g.e,
-                          "xyz"[a], ((double)mx[a] - (double)mn[a]) / g.e);
-            return call_fail(-3, msg);
-        }
-    }
+    if (cluster_refusal(names, n_fin, mn, mx, voxel, &slots_log2, &g)) return -3;
     if (n_fin == 0) {   // nothing occupies a voxel: answered on the host
         if (out_voxel_of)
             for (long long i = 0; i < n; ++i) out_voxel_of[i] = -1;
@@ -455,101 +415,44 @@ long long mpmvs_cloud_voxel_downsample(int device, long long n, const float* xyz
         return 0;
     }
 
-    VoxelEvents ev;
-    VoxelOut out;
+    HostOut out;
     DeviceCall call(device);
     if (!call.ok()) return call_fail(-100, "voxel: the device could not be selected or gave no stream");
     const hipStream_t st = call.stream();
-    for (hipEvent_t& e : ev.e) CALLCHK(hipEventCreate(&e));
-    const size_t np = (size_t)n, slots = (size_t)1 << slots_log2;
-    const int ni = (int)n, ntiles = (ni + kScanBlock - 1) / kScanBlock;
+    Clusters cl(st, names, true);   // after the call: its buffers and its clock go while the stream exists
+    const size_t np = (size_t)n;
     float* d_xyz = call.alloc<float>(np * 12);
-    int* d_slot_of = call.alloc<int>(np * 4);
-    int* d_flag = call.alloc<int>(np * 4);
-    int* d_num = call.alloc<int>(np * 4);
-    int* d_tsum = call.alloc<int>((size_t)ntiles * 4);
-    int* d_m = call.alloc<int>(4);
-    unsigned long long* d_keys = call.alloc<unsigned long long>(slots * 8);
-    int* d_cnt = call.alloc<int>(slots * 4);
-    unsigned* d_first = call.alloc<unsigned>(slots * 4);
-    int* d_vox_of_slot = call.alloc<int>(slots * 4);
     float* d_nrm = normals ? call.alloc<float>(np * 12) : nullptr;
     unsigned char* d_rgb = rgb ? call.alloc<unsigned char>(np * 3) : nullptr;
-    int32_t* d_voxel_of = out_voxel_of ? call.alloc<int32_t>(np * 4) : nullptr;
-    if (!d_xyz || !d_slot_of || !d_flag || !d_num || !d_tsum || !d_m || !d_keys || !d_cnt || !d_first || !d_vox_of_slot || (normals && !d_nrm) ||
-        (rgb && !d_rgb) || (out_voxel_of && !d_voxel_of))
-        return call_fail(-100, "voxel: no device memory");
+    if (!d_xyz || (normals && !d_nrm) || (rgb && !d_rgb)) return call_fail(-100, "voxel: no device memory");
     CALLCHK(hipMemcpyAsync(d_xyz, xyz, np * 12, hipMemcpyHostToDevice, st));
     if (normals) CALLCHK(hipMemcpyAsync(d_nrm, normals, np * 12, hipMemcpyHostToDevice, st));
     if (rgb) CALLCHK(hipMemcpyAsync(d_rgb, rgb, np * 3, hipMemcpyHostToDevice, st));
-    CALLCHK(hipMemsetAsync(d_keys, 0xff, slots * 8, st));
-    CALLCHK(hipMemsetAsync(d_cnt, 0, slots * 4, st));
-    CALLCHK(hipMemsetAsync(d_first, 0xff, slots * 4, st));
-    const dim3 gp((unsigned)ntiles), blk(256);
-    CALLCHK(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(k_cloud_insert, gp, blk, 0, st, d_xyz, ni, g.o[0], g.o[1], g.o[2], g.e, (unsigned)(slots - 1), d_keys, d_cnt, d_slot_of);
-    CALLCHK(hipEventRecord(ev.e[1], st));
-    hipLaunchKernelGGL(k_voxel_first, gp, blk, 0, st, ni, d_slot_of, d_first);
-    CALLCHK(hipEventRecord(ev.e[2], st));
-    hipLaunchKernelGGL(k_voxel_flag, gp, blk, 0, st, ni, d_slot_of, d_first, d_flag);
-    hipLaunchKernelGGL(k_scan_tiles, gp, dim3(kScanBlock), 0, st, d_flag, ni, d_num, d_tsum);
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_tsum, ntiles, 0, d_m);
-    hipLaunchKernelGGL(k_vs_scan_add, gp, dim3(kScanBlock), 0, st, d_num, ni, d_tsum);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(ev.e[3], st));
-    int m = 0;
-    CALLCHK(hipMemcpyAsync(&m, d_m, 4, hipMemcpyDeviceToHost, st));
-    CALLCHK(hipStreamSynchronize(st));
-    if (m <= 0 || (long long)m > n_fin) return call_fail(-100, "voxel: the device counted " + std::to_string(m) + " voxels for " + std::to_string(n_fin) + " finite points");
-
-    const size_t mv = (size_t)m;
-    int32_t* d_out_first = call.alloc<int32_t>(mv * 4);
-    int32_t* d_out_count = call.alloc<int32_t>(mv * 4);
-    float* d_out_xyz = call.alloc<float>(mv * 12);
-    float* d_out_nrm = normals ? call.alloc<float>(mv * 12) : nullptr;
-    unsigned char* d_out_rgb = rgb ? call.alloc<unsigned char>(mv * 3) : nullptr;
-    // S, then N, then C: 3 x 64 bits per voxel each
-    const size_t acc_parts = 1 + (normals ? 1 : 0) + (rgb ? 1 : 0);
-    unsigned long long* d_acc = call.alloc<unsigned long long>(acc_parts * mv * 24);
-    if (!d_out_first || !d_out_count || !d_out_xyz || (normals && !d_out_nrm) || (rgb && !d_out_rgb) || !d_acc) return call_fail(-100, "voxel: no device memory");
-    unsigned long long* d_S = d_acc;
-    unsigned long long* d_N = normals ? d_acc + 3 * mv : nullptr;
-    unsigned long long* d_C = rgb ? d_acc + 3 * mv * (normals ? 2 : 1) : nullptr;
-    out.p[0] = std::malloc(mv * 12), out.p[1] = std::malloc(mv * 4), out.p[2] = std::malloc(mv * 4);
-    if (normals) out.p[3] = std::malloc(mv * 12);
-    if (rgb) out.p[4] = std::malloc(mv * 3);
-    if (!out.p[0] || !out.p[1] || !out.p[2] || (normals && !out.p[3]) || (rgb && !out.p[4])) return call_fail(-100, "voxel: no host memory for the result");
-    CALLCHK(hipMemsetAsync(d_acc, 0, acc_parts * mv * 24, st));
-    CALLCHK(hipEventRecord(ev.e[4], st));   // pass 4 begins here: the wait for m is not device time
-    hipLaunchKernelGGL(k_voxel_number, gp, blk, 0, st, ni, d_flag, d_num, d_slot_of, d_cnt, d_vox_of_slot, d_out_first, d_out_count);
-    CALLCHK(hipEventRecord(ev.e[5], st));
-    hipLaunchKernelGGL(k_voxel_accumulate, gp, blk, 0, st, ni, d_xyz, d_nrm, d_rgb, g, d_slot_of, d_vox_of_slot, d_S, d_N, d_C, d_voxel_of);
-    CALLCHK(hipEventRecord(ev.e[6], st));
-    hipLaunchKernelGGL(k_voxel_finish, dim3((unsigned)((mv + 255) / 256)), blk, 0, st, m, d_xyz, d_out_first, d_out_count, g, d_S, d_N, d_C, d_out_xyz, d_out_nrm,
-                       d_out_rgb);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(ev.e[7], st));
-    CALLCHK(hipMemcpyAsync(out.p[0], d_out_xyz, mv * 12, hipMemcpyDeviceToHost, st));
-    CALLCHK(hipMemcpyAsync(out.p[1], d_out_count, mv * 4, hipMemcpyDeviceToHost, st));
-    CALLCHK(hipMemcpyAsync(out.p[2], d_out_first, mv * 4, hipMemcpyDeviceToHost, st));
-    if (normals) CALLCHK(hipMemcpyAsync(out.p[3], d_out_nrm, mv * 12, hipMemcpyDeviceToHost, st));
-    if (rgb) CALLCHK(hipMemcpyAsync(out.p[4], d_out_rgb, mv * 3, hipMemcpyDeviceToHost, st));
-    if (out_voxel_of) CALLCHK(hipMemcpyAsync(out_voxel_of, d_voxel_of, np * 4, hipMemcpyDeviceToHost, st));
+    if (cl.mark(d_xyz, (int)n, n_fin, slots_log2, g)) return -100;
+    const size_t mv = (size_t)cl.count;
+    float* h_xyz = out.take<float>(mv * 3);
+    int32_t* h_count = out.take<int32_t>(mv);
+    int32_t* h_first = out.take<int32_t>(mv);
+    float* h_nrm = normals ? out.take<float>(mv * 3) : nullptr;
+    unsigned char* h_rgb = rgb ? out.take<unsigned char>(mv * 3) : nullptr;
+    if (!h_xyz || !h_count || !h_first || (normals && !h_nrm) || (rgb && !h_rgb)) return call_fail(-100, "voxel: no host memory for the result");
+    if (cl.number_and_accumulate(d_nrm, d_rgb, out_voxel_of != nullptr) || cl.finish()) return -100;
+    CALLCHK(hipMemcpyAsync(h_xyz, cl.out_xyz.p, mv * 12, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(h_count, cl.out_count.p, mv * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(h_first, cl.out_first.p, mv * 4, hipMemcpyDeviceToHost, st));
+    if (normals) CALLCHK(hipMemcpyAsync(h_nrm, cl.out_normals.p, mv * 12, hipMemcpyDeviceToHost, st));
+    if (rgb) CALLCHK(hipMemcpyAsync(h_rgb, cl.out_rgb.p, mv * 3, hipMemcpyDeviceToHost, st));
+    if (out_voxel_of) CALLCHK(hipMemcpyAsync(out_voxel_of, cl.cluster_of.p, np * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
     float ms[6] = {0, 0, 0, 0, 0, 0};
-    CALLCHK(hipEventElapsedTime(&ms[0], ev.e[0], ev.e[1]));
-    CALLCHK(hipEventElapsedTime(&ms[1], ev.e[1], ev.e[2]));
-    CALLCHK(hipEventElapsedTime(&ms[2], ev.e[2], ev.e[3]));
-    CALLCHK(hipEventElapsedTime(&ms[3], ev.e[4], ev.e[5]));
-    CALLCHK(hipEventElapsedTime(&ms[4], ev.e[5], ev.e[6]));
-    CALLCHK(hipEventElapsedTime(&ms[5], ev.e[6], ev.e[7]));
+    if (cl.pass_ms(ms)) return -100;
     std::memcpy(g_voxel_pass_ms, ms, sizeof ms);
     g_voxel_ms = ((ms[0] + ms[1]) + (ms[2] + ms[3])) + (ms[4] + ms[5]);
-    *out_xyz = (float*)out.p[0], *out_count = (int32_t*)out.p[1], *out_first = (int32_t*)out.p[2];
-    if (normals) *out_normals = (float*)out.p[3];
-    if (rgb) *out_rgb = (unsigned char*)out.p[4];
-    out.keep = true;
-    return m;
+    *out_xyz = h_xyz, *out_count = h_count, *out_first = h_first;
+    if (normals) *out_normals = h_nrm;
+    if (rgb) *out_rgb = h_rgb;
+    out.keep();
+    return cl.count;
 }
 
 // ---------------------------------------------------------------------------
@@ -595,26 +498,25 @@ int mpmvs_cloud_knn(mpmvs_cloud* c, float radius, int k, long long n_q, const fl
     for (size_t i0 = 0; i0 < nq; i0 += chunk) {
         const int cn = (int)std::min(chunk, nq - i0);
         const float* d_qc = d_all + 3 * i0;
-        CALLCHK(hipEventRecord(c->ev[2], st));
+        CALLCHK(c->clock.mark(2, st));
         if (bin) {
-            const int brc = cloud_bin(st, bins, cn, nullptr, cloud_count_queries(st, d_qc, cn, g));
+            const int brc = cloud_bin(st, bins, cn, no_mark, cloud_count_queries(st, d_qc, cn, g));
             if (brc) return brc;
         }
-        const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
         const long long self_base = q_xyz ? -1ll : (long long)i0;
-        int32_t* di = out_idx ? d_idx.as<int32_t>() : (int32_t*)nullptr;
-        int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
-        knn_dispatch(k, [&](auto K) {
-            hipLaunchKernelGGL(k_knn_list<K>, dim3((cn + 255) / 256), dim3(256), 0, st, d_qc, cn, order, g, self_base, k, d_d2.as<float>(), di, dw);
+        const int krc = knn_dispatch(k, [&](auto K) {   // order, idx and within: null where not allocated
+            CALLCHK(launch(k_knn_list<K>, dim3((cn + 255) / 256), dim3(256), st, d_qc, cn, bins.order.as<int>(), g, self_base, k, d_d2.as<float>(),
+                           d_idx.as<int32_t>(), d_within.as<int32_t>()));
+            return 0;
         });
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(c->ev[3], st));
+        if (krc) return krc;
+        CALLCHK(c->clock.mark(3, st));
         CALLCHK(hipMemcpyAsync(out_d2 + i0 * kk, d_d2.p, (size_t)cn * kk * 4, hipMemcpyDeviceToHost, st));
         if (out_idx) CALLCHK(hipMemcpyAsync(out_idx + i0 * kk, d_idx.p, (size_t)cn * kk * 4, hipMemcpyDeviceToHost, st));
         if (out_within) CALLCHK(hipMemcpyAsync(out_within + i0, d_within.p, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
         CALLCHK(hipStreamSynchronize(st));
         float ms = 0.0f;
-        CALLCHK(hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+        CALLCHK(c->clock.ms(2, 3, &ms));
         c->knn.ms += ms;
     }
     return 0;
@@ -640,19 +542,20 @@ static int outliers_device(mpmvs_cloud* c, const float* xyz, float radius, int k
     CALLCHK(d_mean.alloc(n * 4));
     CALLCHK(d_within.alloc(n * 4));
     if (bin) CALLCHK(bins.alloc(n));
-    CALLCHK(hipEventRecord(c->ev[2], st));
-    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
-    const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
-    knn_dispatch(k, [&](auto K) {
-        hipLaunchKernelGGL(k_knn_reduce<K>, dim3((ni + 255) / 256), dim3(256), 0, st, c->d_xyz, ni, order, g, 0ll, k, d_mean.as<float>(), d_within.as<int32_t>());
+    CALLCHK(c->clock.mark(2, st));
+    if (bin && (rc = cloud_bin(st, bins, ni, no_mark, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
+    rc = knn_dispatch(k, [&](auto K) {   // order: null without binning
+        CALLCHK(launch(k_knn_reduce<K>, dim3((ni + 255) / 256), dim3(256), st, c->d_xyz, ni, bins.order.as<int>(), g, 0ll, k, d_mean.as<float>(),
+                       d_within.as<int32_t>()));
+        return 0;
     });
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[3], st));
+    if (rc) return rc;
+    CALLCHK(c->clock.mark(3, st));
     CALLCHK(hipMemcpyAsync(mean, d_mean.p, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipMemcpyAsync(within, d_within.p, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
     float q_ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&q_ms, c->ev[2], c->ev[3]));
+    CALLCHK(c->clock.ms(2, 3, &q_ms));
     *ms = c->query.build_ms + q_ms;
     return 0;
 }
@@ -767,22 +670,20 @@ int mpmvs_cloud_normals(mpmvs_cloud* c, float radius, int k, int orient, const d
         CALLCHK(hipMemcpyAsync(d_ref.p, ref_normals, n * 12, hipMemcpyHostToDevice, st));
     }
     if (bin) CALLCHK(bins.alloc(n));
-    CALLCHK(hipEventRecord(c->ev[2], st));
-    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
-    const int* order = bin ? bins.order.as<int>() : (const int*)nullptr;
-    const float* dr = orient == 2 ? d_ref.as<float>() : (const float*)nullptr;
-    float* dc = out_curvature ? d_curv.as<float>() : (float*)nullptr;
-    int32_t* dw = out_within ? d_within.as<int32_t>() : (int32_t*)nullptr;
-    knn_dispatch(k, [&](auto K) {
-        hipLaunchKernelGGL(k_knn_normal<K>, dim3((ni + 255) / 256), dim3(256), 0, st, c->d_xyz, ni, order, g, k, orient, v[0], v[1], v[2], dr, d_n.as<float>(), dc, dw);
+    CALLCHK(c->clock.mark(2, st));
+    if (bin && (rc = cloud_bin(st, bins, ni, no_mark, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
+    rc = knn_dispatch(k, [&](auto K) {   // order, reference normals, curvature and within: null where not allocated
+        CALLCHK(launch(k_knn_normal<K>, dim3((ni + 255) / 256), dim3(256), st, c->d_xyz, ni, bins.order.as<int>(), g, k, orient, v[0], v[1], v[2], d_ref.as<float>(),
+                       d_n.as<float>(), d_curv.as<float>(), d_within.as<int32_t>()));
+        return 0;
     });
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[3], st));
+    if (rc) return rc;
+    CALLCHK(c->clock.mark(3, st));
     CALLCHK(hipMemcpyAsync(out_normals, d_n.p, n * 12, hipMemcpyDeviceToHost, st));
     if (out_curvature) CALLCHK(hipMemcpyAsync(out_curvature, d_curv.p, n * 4, hipMemcpyDeviceToHost, st));
     if (out_within) CALLCHK(hipMemcpyAsync(out_within, d_within.p, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&c->normals.ms, c->ev[2], c->ev[3]));
+    CALLCHK(c->clock.ms(2, 3, &c->normals.ms));
     return 0;
 }
 
@@ -825,24 +726,23 @@ int mpmvs_cloud_components(mpmvs_cloud* c, float radius, int32_t* out_label, int
     if (want_size && !out_size) size_own.resize(n);
     int32_t* size = out_size ? out_size : size_own.data();
     // the grid is built: its two events are free again, and the four borders of the three passes fit the handle's four
-    CALLCHK(hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_cc_init, gp, dim3(256), 0, st, c->d_xyz, ni, c->d_cc);
-    if (bin && (rc = cloud_bin(st, bins, ni, nullptr, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
-    hipLaunchKernelGGL(k_cc_hook, gp, dim3(256), 0, st, c->d_xyz, ni, bin ? bins.order.as<int>() : (const int*)nullptr, g, c->d_cc);
-    CALLCHK(hipEventRecord(c->ev[1], st));
-    hipLaunchKernelGGL(k_cc_flatten, gp, dim3(256), 0, st, ni, c->d_cc, d_label.as<int32_t>());
-    CALLCHK(hipEventRecord(c->ev[2], st));
+    CALLCHK(c->clock.mark(0, st));
+    CALLCHK(launch(k_cc_init, gp, dim3(256), st, c->d_xyz, ni, c->d_cc));
+    if (bin && (rc = cloud_bin(st, bins, ni, no_mark, cloud_count_queries(st, c->d_xyz, ni, g))) != 0) return rc;
+    CALLCHK(launch(k_cc_hook, gp, dim3(256), st, c->d_xyz, ni, bins.order.as<int>(), g, c->d_cc));   // order: null without binning
+    CALLCHK(c->clock.mark(1, st));
+    CALLCHK(launch(k_cc_flatten, gp, dim3(256), st, ni, c->d_cc, d_label.as<int32_t>()));
+    CALLCHK(c->clock.mark(2, st));
     if (want_size) {   // the parents have served: the same ints count the members of every label
         CALLCHK(hipMemsetAsync(c->d_cc, 0, n * 4, st));
-        hipLaunchKernelGGL(k_cc_count, gp, dim3(256), 0, st, ni, d_label.as<int32_t>(), c->d_cc);
-        hipLaunchKernelGGL(k_cc_gather, gp, dim3(256), 0, st, ni, d_label.as<int32_t>(), c->d_cc, d_size.as<int32_t>());
+        CALLCHK(launch(k_cc_count, gp, dim3(256), st, ni, d_label.as<int32_t>(), c->d_cc));
+        CALLCHK(launch(k_cc_gather, gp, dim3(256), st, ni, d_label.as<int32_t>(), c->d_cc, d_size.as<int32_t>()));
     }
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[3], st));
+    CALLCHK(c->clock.mark(3, st));
     CALLCHK(hipMemcpyAsync(out_label, d_label.p, n * 4, hipMemcpyDeviceToHost, st));
     if (want_size) CALLCHK(hipMemcpyAsync(size, d_size.p, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    for (int p = 0; p < 3; ++p) CALLCHK(hipEventElapsedTime(&c->cc_pass_ms[p], c->ev[p], c->ev[p + 1]));
+    for (int p = 0; p < 3; ++p) CALLCHK(c->clock.ms(p, p + 1, &c->cc_pass_ms[p]));
     if (!want_size) c->cc_pass_ms[2] = 0.0f;   // two events with nothing between them
     c->cc.ms = (c->cc_pass_ms[0] + c->cc_pass_ms[1]) + c->cc_pass_ms[2];
     if (counts) {   // a component is counted at its label; the largest, ties to the smallest label
@@ -873,7 +773,7 @@ int mpmvs_cloud_components_pass_ms(const mpmvs_cloud* c, float ms[3]) {
 struct mpmvs_align {
     mpmvs_cloud* target;   // borrowed: its stream, grids and points serve every pass
     long long n = 0;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    PassClock<2> clock;   // the borders of a pass
     float* d_src = nullptr;
     float* d_nrm = nullptr;   // a normal per target, caller order (mpmvs_align_set_normals); owned by this handle
     bool has_nrm = false;     // also true for normals of a target without points
@@ -887,15 +787,12 @@ static void align_release(mpmvs_align* h) {
     if (h->target->stream) (void)hipStreamSynchronize(h->target->stream);
     for (void* p : {(void*)h->d_src, (void*)h->d_nrm, (void*)h->d_sums})
         if (p) (void)pool_free(p);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete h;   // the bins go back to the pool here
+    delete h;   // the bins go back to the pool here, and the clock goes
 }
 
 static int align_create_device(mpmvs_align* h, const float* s_xyz) {
     const hipStream_t st = h->target->stream;
     CALLCHK(enter_device(h->target->device));
-    for (hipEvent_t& e : h->ev) CALLCHK(hipEventCreate(&e));
     if (h->n == 0) return 0;
     const size_t n = (size_t)h->n;
     CALLCHK(pool_malloc(&h->d_src, n * 12));
@@ -943,24 +840,23 @@ static int align_pass(mpmvs_align* h, float radius, const AlignXf& f, bool plane
     const size_t sums_bytes = (size_t)(plane ? kAlignPlaneTerms : kAlignTerms) * 8;
     CALLCHK(hipMemsetAsync(h->d_sums, 0, sums_bytes, st));
     if (bin) {   // by the cell of the transformed source
-        const int brc = cloud_bin(st, h->bins, n, h->ev[0], [&](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) {
-            hipLaunchKernelGGL(k_align_qbin, gq, dim3(256), 0, st, h->d_src, n, f, g, bin_mask, qcnt, qbin);
+        const int brc = cloud_bin(st, h->bins, n, [&] { return h->clock.mark(0, st); }, [&](dim3 gq, unsigned bin_mask, int* qcnt, int* qbin) {
+            return launch(k_align_qbin, gq, dim3(256), st, h->d_src, n, f, g, bin_mask, qcnt, qbin);
         });
         if (brc) return brc;
     } else {
-        CALLCHK(hipEventRecord(h->ev[0], st));
+        CALLCHK(h->clock.mark(0, st));
     }
     const dim3 gq(((unsigned)n + 255u) / 256u);   // unsigned: n may be 2^31 - 1
-    const int* order = bin ? h->bins.order.as<int>() : (const int*)nullptr;
+    const int* order = bin ? h->bins.order.as<int>() : nullptr;   // the bins exist either way
     if (plane)
-        hipLaunchKernelGGL(k_align_plane_pass, gq, dim3(256), 0, st, h->d_src, n, order, f, g, c->d_xyz, h->d_nrm, h->d_sums);
+        CALLCHK(launch(k_align_plane_pass, gq, dim3(256), st, h->d_src, n, order, f, g, c->d_xyz, h->d_nrm, h->d_sums));
     else
-        hipLaunchKernelGGL(k_align_pass, gq, dim3(256), 0, st, h->d_src, n, order, f, g, c->d_xyz, h->d_sums);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
+        CALLCHK(launch(k_align_pass, gq, dim3(256), st, h->d_src, n, order, f, g, c->d_xyz, h->d_sums));
+    CALLCHK(h->clock.mark(1, st));
     CALLCHK(hipMemcpyAsync(sums, h->d_sums, sums_bytes, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&h->pass_ms, h->ev[0], h->ev[1]));
+    CALLCHK(h->clock.ms(0, 1, &h->pass_ms));
     return 0;
 }
 
@@ -1117,20 +1013,19 @@ static int cloud_render_chunk(mpmvs_cloud* c, int v0, int v1, const mpmvs_camera
     if (any_idx) CALLCHK(hipMemsetAsync(d_idx.p, 0xff, total * 4, st));
     const int n = (int)c->n;
     const dim3 gp((n + 255) / 256);
-    CALLCHK(hipEventRecord(c->ev[0], st));
-    hipLaunchKernelGGL(k_render_zmin, gp, dim3(256), 0, st, c->d_xyz, n, A);
-    CALLCHK(hipEventRecord(c->ev[1], st));
-    if (any_idx) hipLaunchKernelGGL(k_render_index, gp, dim3(256), 0, st, c->d_xyz, n, A);
-    CALLCHK(hipEventRecord(c->ev[2], st));
+    CALLCHK(c->clock.mark(0, st));
+    CALLCHK(launch(k_render_zmin, gp, dim3(256), st, c->d_xyz, n, A));
+    CALLCHK(c->clock.mark(1, st));
+    if (any_idx) CALLCHK(launch(k_render_index, gp, dim3(256), st, c->d_xyz, n, A));
+    CALLCHK(c->clock.mark(2, st));
     at = 0;
     for (int k = 0; k < A.n; ++k) {
         const RenderView& V = A.v[k];
         const size_t npix = (size_t)V.w * (size_t)V.h;
-        hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, V.zc, V.w, V.h, splat, m, d_depth.as<float>() + at, V.idx);
+        CALLCHK(launch(k_render_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), st, V.zc, V.w, V.h, splat, m, d_depth.as<float>() + at, V.idx));
         at += npix;
     }
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(c->ev[3], st));
+    CALLCHK(c->clock.mark(3, st));
     at = 0;
     for (int k = 0; k < A.n; ++k) {
         const RenderView& V = A.v[k];
@@ -1143,7 +1038,7 @@ static int cloud_render_chunk(mpmvs_cloud* c, int v0, int v1, const mpmvs_camera
     for (int p = 0; p < 3; ++p) {
         if (p == 1 && !any_idx) continue;   // no index pass: the gap between two event records is not its time
         float ms = 0.0f;
-        CALLCHK(hipEventElapsedTime(&ms, c->ev[p], c->ev[p + 1]));
+        CALLCHK(c->clock.ms(p, p + 1, &ms));
         c->render_pass_ms[p] += ms;
     }
     return 0;
@@ -1208,7 +1103,7 @@ constexpr long long kObserveChunkQueries = 1ll << 24;       // queries per launc
 struct mpmvs_observer {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // the borders of the two passes of a chunk; ev[0], ev[1]: of a classify launch
+    PassClock<3> clock;                               // the borders of the two passes of a chunk; marks 0 and 1: of a classify launch
     ObserveScanners sc;                               // all scanners, j0 = 0
     int R = 0, w = 0;
     float* d_zn = nullptr;                            // [n_scanners][6][R][R]
@@ -1219,17 +1114,14 @@ struct mpmvs_observer {
 static void observer_release(mpmvs_observer* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->d_zn) (void)pool_free(h->d_zn);
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // the clock goes here: the stream has been waited for
 }
 
 // the device half of mpmvs_observer_create: Zc and Zn of one chunk of scanners after the other; the scan's points are read in place
 static int observer_create_device(mpmvs_observer* h, const mpmvs_cloud* scan, const int* owner) {
     CALLCHK(enter_device(scan->device));
     CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev) CALLCHK(hipEventCreate(&e));
     const hipStream_t st = h->stream;
     const size_t map = (size_t)6 * (size_t)h->R * (size_t)h->R, total = map * (size_t)h->sc.n;
     CALLCHK(pool_malloc(&h->d_zn, total * 4));
@@ -1253,18 +1145,16 @@ static int observer_create_device(mpmvs_observer* h, const mpmvs_cloud* scan, co
         A.j0 = j0, A.n = std::min(per, h->sc.n - j0);
         const size_t n_pix = map * (size_t)A.n;
         CALLCHK(hipMemsetD32Async((hipDeviceptr_t)d_zc.p, (int)kRenderInfBits, n_pix, st));
-        CALLCHK(hipEventRecord(h->ev[0], st));
-        hipLaunchKernelGGL(k_observe_zmin, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, scan->d_xyz, n, owner ? d_owner.as<int>() : (const int*)nullptr, A,
-                           h->R, d_zc.as<uint32_t>());
-        CALLCHK(hipEventRecord(h->ev[1], st));
-        hipLaunchKernelGGL(k_observe_near, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, st, d_zc.as<uint32_t>(), n_pix, h->R, h->w,
-                           h->d_zn + map * (size_t)j0, d_cnt.as<unsigned long long>());
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(h->ev[2], st));
+        CALLCHK(h->clock.mark(0, st));
+        CALLCHK(launch(k_observe_zmin, dim3(((unsigned)n + 255u) / 256u), dim3(256), st, scan->d_xyz, n, d_owner.as<int>(), A, h->R, d_zc.as<uint32_t>()));   // owner: null if not given
+        CALLCHK(h->clock.mark(1, st));
+        CALLCHK(launch(k_observe_near, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), st, d_zc.as<uint32_t>(), n_pix, h->R, h->w, h->d_zn + map * (size_t)j0,
+                       d_cnt.as<unsigned long long>()));
+        CALLCHK(h->clock.mark(2, st));
         CALLCHK(hipStreamSynchronize(st));
         for (int p = 0; p < 2; ++p) {
             float ms = 0.0f;
-            CALLCHK(hipEventElapsedTime(&ms, h->ev[p], h->ev[p + 1]));
+            CALLCHK(h->clock.ms(p, p + 1, &ms));
             h->build_pass_ms[p] += ms;
         }
     }
@@ -1320,16 +1210,15 @@ static int observer_classify_chunk(mpmvs_observer* h, int n, const float* q_xyz,
     CALLCHK(d_free.alloc((size_t)n * 4));
     if (out_covered) CALLCHK(d_cov.alloc((size_t)n * 4));
     CALLCHK(hipMemcpyAsync(d_q.p, q_xyz, (size_t)n * 12, hipMemcpyHostToDevice, st));
-    CALLCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(k_observe_classify, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, st, d_q.as<float>(), n, h->sc, h->R, h->d_zn, m1, abs_margin,
-                       d_free.as<int>(), out_covered ? d_cov.as<int>() : (int*)nullptr);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
+    CALLCHK(h->clock.mark(0, st));
+    CALLCHK(launch(k_observe_classify, dim3(((unsigned)n + 255u) / 256u), dim3(256), st, d_q.as<float>(), n, h->sc, h->R, h->d_zn, m1, abs_margin, d_free.as<int>(),
+                   d_cov.as<int>()));   // covered: null if not wanted
+    CALLCHK(h->clock.mark(1, st));
     CALLCHK(hipMemcpyAsync(out_free, d_free.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     if (out_covered) CALLCHK(hipMemcpyAsync(out_covered, d_cov.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
     float ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    CALLCHK(h->clock.ms(0, 1, &ms));
     h->classify_ms += ms;
     return 0;
 }

@@ -35,8 +35,7 @@ int mpmvs_sky_bilateral(int device, const unsigned char* bgr, const float* mask,
         return -100;
     (void)call.begin();
     const dim3 grid((width + kSkyTW - 1) / kSkyTW, (height + kSkyTH - 1) / kSkyTH);
-    hipLaunchKernelGGL(k_sky_bilateral, grid, dim3(256), 0, st, d_img, d_mask, d_out, height, width);
-    if (hipGetLastError() != hipSuccess) return -100;
+    if (launch(k_sky_bilateral, grid, dim3(256), st, d_img, d_mask, d_out, height, width) != hipSuccess) return -100;
     (void)call.end();
     if (hipStreamSynchronize(st) != hipSuccess) return -100;
     (void)call.elapsed(&g_sky_kernel_ms);

@@ -19,6 +19,8 @@
 
 #include "../../include/mpmvs.h"
 #include "pm_host.hpp"
+#include "pm_scan_host.hpp"
+#include "pm_cluster_host.hpp"
 #include "pm_mesh.hpp"
 #include "pm_simplify.hpp"
 #include "pm_tsdf.hpp"
@@ -39,7 +41,7 @@ struct mpmvs_tsdf {
     bool with_color = false, ready = false;
     long long views = 0;   // integrated over the handle's life
     hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // mesh: mark, scan, [the host reads the counts] vertices, triangles; ev[0], ev[1]: an integration launch
+    PassClock<6> clock;   // mesh: mark, scan, [the host reads the counts] vertices, triangles; marks 0 and 1: an integration launch
     float* d_sum = nullptr;
     int32_t* d_weight = nullptr;
     uint4* d_color = nullptr;
@@ -56,14 +58,12 @@ struct mpmvs_tsdf {
     float alloc_ms[2] = {0.0f, 0.0f};
 };
 
-// the first call that needs the device: the stream and the events; then a dense handle's volume, all zero, or a brick-sparse
+// the first call that needs the device: the stream; then a dense handle's volume, all zero, or a brick-sparse
 // handle's brick grid, all -1
 static int tsdf_ready(mpmvs_tsdf* h) {
     CALLCHK(enter_device(h->device));
     if (h->ready) return 0;
     if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev)
-        if (!e) CALLCHK(hipEventCreate(&e));
     if (h->sparse) {
         if (!h->d_grid) CALLCHK(pool_malloc(&h->d_grid, h->n_grid * 4));
         CALLCHK(hipMemsetAsync(h->d_grid, 0xff, h->n_grid * 4, h->stream));
@@ -125,11 +125,9 @@ void mpmvs_tsdf_destroy(mpmvs_tsdf* h) {
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         for (void* p : {(void*)h->d_sum, (void*)h->d_weight, (void*)h->d_color, (void*)h->d_grid, (void*)h->d_list})
             if (p) (void)pool_free(p);
-        for (hipEvent_t e : h->ev)
-            if (e) (void)hipEventDestroy(e);
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
-    delete h;
+    delete h;   // the clock goes here: the stream has been waited for
 }
 
 // the views of an integrate or allocate call (`name` is the call's, for the message): every -2 of every view before any -3
@@ -206,15 +204,15 @@ struct TsdfChunk {
     }
 };
 
-// one launch between ev[a] and ev[b] of the handle, waited for; its time is added to *ms
-static int tsdf_timed(mpmvs_tsdf* h, int a, int b, float* ms, const std::function<void()>& launch) {
-    CALLCHK(hipEventRecord(h->ev[a], h->stream));
-    launch();
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[b], h->stream));
+// one launch (run: 0 or its -100) between the marks 0 and 1 of the handle's clock, waited for; its time is added to *ms
+static int tsdf_timed(mpmvs_tsdf* h, float* ms, const std::function<int()>& run) {
+    CALLCHK(h->clock.mark(0, h->stream));
+    const int rc = run();
+    if (rc) return rc;
+    CALLCHK(h->clock.mark(1, h->stream));
     CALLCHK(hipStreamSynchronize(h->stream));
     float t = 0.0f;
-    CALLCHK(hipEventElapsedTime(&t, h->ev[a], h->ev[b]));
+    CALLCHK(h->clock.ms(0, 1, &t));
     *ms += t;
     return 0;
 }
@@ -244,9 +242,10 @@ int mpmvs_tsdf_integrate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, c
         TsdfChunk c(st);
         const int rc3 = c.upload(h, v0, v1, cams, depths, colors, color_channels);
         if (rc3) return rc3;
-        const int rc4 = tsdf_timed(h, 0, 1, &h->ms[0], [&] {
-            if (h->sparse) hipLaunchKernelGGL(k_tsdf_sparse_integrate, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), c.A, h->d_sum, h->d_weight, d_color);
-            else hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), 0, st, h->V, c.A, h->d_sum, h->d_weight, d_color);
+        const int rc4 = tsdf_timed(h, &h->ms[0], [&] {
+            if (h->sparse) CALLCHK(launch(k_tsdf_sparse_integrate, dim3((unsigned)h->n_bricks), dim3(kBrickVox), st, h->V, tsdf_bricks(h), c.A, h->d_sum, h->d_weight, d_color));
+            else CALLCHK(launch(k_tsdf_integrate, dim3((unsigned)tiles), dim3(256), st, h->V, c.A, h->d_sum, h->d_weight, d_color));
+            return 0;
         });
         if (!rc4) h->views += v1 - v0;
         return rc4;
@@ -296,32 +295,26 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     int* ttile = vtile + n_tiles;
     // passes 1, 3 and 4: a thread per voxel of the lattice, or a block per brick; the brick-sparse kernels take the brick table where
     // the dense ones take the number of voxels, and the rest of the argument list is the same
-    auto launch = [&](auto dense, auto sparse, auto... args) {
-        if (h->sparse) hipLaunchKernelGGL(sparse, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->V, tsdf_bricks(h), args...);
-        else hipLaunchKernelGGL(dense, dim3(blocks), dim3(256), 0, st, h->V, n, args...);
+    auto per_voxel = [&](auto dense, auto sparse, auto... args) {
+        return h->sparse ? launch(sparse, dim3((unsigned)h->n_bricks), dim3(kBrickVox), st, h->V, tsdf_bricks(h), args...)
+                         : launch(dense, dim3(blocks), dim3(256), st, h->V, n, args...);
     };
     const uint4* const d_color = h->with_color ? h->d_color : nullptr;
     CALLCHK(hipMemsetAsync(d_grand.p, 0, 16, st));
-    CALLCHK(hipEventRecord(h->ev[0], st));
+    CALLCHK(h->clock.mark(0, st));
     CALLCHK(hipMemsetAsync(d_mask.p, 0, n * 4, st));
-    launch(k_tsdf_mark, k_tsdf_sparse_mark, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    hipLaunchKernelGGL(k_tsdf_scan_tiles, dim3((unsigned)n_tiles), dim3(kScanBlock), 0, st, d_mask.as<uint32_t>(), n, d_vexcl.as<int>(), d_tcount.as<int>(), vtile, n_tiles);
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_tsdf_sum_totals, dim3((unsigned)((n_tiles + kScanBlock - 1) / kScanBlock), 2), dim3(kScanBlock), 0, st, vtile, n_tiles, d_grand.as<unsigned long long>());
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(2), dim3(kScanBlock), 0, st, vtile, n_tiles, 0, (int*)nullptr);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[2], st));
+    CALLCHK(per_voxel(k_tsdf_mark, k_tsdf_sparse_mark, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_tcount.as<int>()));
+    CALLCHK(h->clock.mark(1, st));
+    // not scan_offsets: the tiles come from the masks' popcounts and the triangle counts at once, and the totals are 64-bit sums
+    CALLCHK(launch(k_tsdf_scan_tiles, dim3((unsigned)n_tiles), dim3(kScanBlock), st, d_mask.as<uint32_t>(), n, d_vexcl.as<int>(), d_tcount.as<int>(), vtile, n_tiles));
+    CALLCHK(launch(k_tsdf_sum_totals, dim3((unsigned)((n_tiles + kScanBlock - 1) / kScanBlock), 2), dim3(kScanBlock), st, vtile, n_tiles, d_grand.as<unsigned long long>()));
+    CALLCHK(launch(k_scan_totals<Sum>, dim3(2), dim3(kScanBlock), st, vtile, n_tiles, 0, nullptr));
+    CALLCHK(h->clock.mark(2, st));
     unsigned long long grand[2] = {0, 0};
     CALLCHK(hipMemcpyAsync(grand, d_grand.p, 16, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->ms[1] = ms;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
-    h->ms[2] = ms;
+    CALLCHK(h->clock.ms(0, 1, &h->ms[1]));
+    CALLCHK(h->clock.ms(1, 2, &h->ms[2]));
     if (grand[0] > (unsigned long long)INT32_MAX || grand[1] > (unsigned long long)INT32_MAX)
         return call_fail(-3, "tsdf mesh: " + std::to_string(grand[0]) + " vertices and " + std::to_string(grand[1]) + " triangles: more than 2^31 - 1");
     const size_t nv = (size_t)grand[0], nt = (size_t)grand[1];
@@ -330,32 +323,25 @@ static long long tsdf_mesh_device(mpmvs_tsdf* h, int min_weight, float** xyz, un
     CALLCHK(d_xyz.alloc(nv * 12));
     if (h->with_color) CALLCHK(d_rgb.alloc(nv * 3));
     CALLCHK(d_tri.alloc(nt * 12));
-    CALLCHK(hipEventRecord(h->ev[5], st));
-    launch(k_tsdf_vertices, k_tsdf_sparse_vertices, h->d_sum, h->d_weight, d_color, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(),
-           h->with_color ? d_rgb.as<unsigned char>() : (unsigned char*)nullptr);
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[3], st));
-    launch(k_tsdf_triangles, k_tsdf_sparse_triangles, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_tcount.as<int>(), ttile,
-           d_tri.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[4], st));
-    float* hx = (float*)std::malloc(nv * 12);
-    int32_t* ht = (int32_t*)std::malloc(nt * 12);
-    unsigned char* hc = h->with_color ? (unsigned char*)std::malloc(nv * 3) : nullptr;
-    struct Guard {
-        void *a, *b, *c;
-        ~Guard() { std::free(a); std::free(b); std::free(c); }
-    } g{hx, ht, hc};
+    CALLCHK(h->clock.mark(5, st));
+    CALLCHK(per_voxel(k_tsdf_vertices, k_tsdf_sparse_vertices, h->d_sum, h->d_weight, d_color, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_xyz.as<float>(),
+                      d_rgb.as<unsigned char>()));   // rgb: null without colour
+    CALLCHK(h->clock.mark(3, st));
+    CALLCHK(per_voxel(k_tsdf_triangles, k_tsdf_sparse_triangles, h->d_sum, h->d_weight, min_weight, d_mask.as<uint32_t>(), d_vexcl.as<int>(), vtile, d_tcount.as<int>(),
+                      ttile, d_tri.as<int32_t>()));
+    CALLCHK(h->clock.mark(4, st));
+    HostOut out;
+    float* hx = out.take<float>(nv * 3);
+    int32_t* ht = out.take<int32_t>(nt * 3);
+    unsigned char* hc = h->with_color ? out.take<unsigned char>(nv * 3) : nullptr;
     if (!hx || !ht || (h->with_color && !hc)) return call_fail(-100, "tsdf mesh: out of host memory");
     CALLCHK(hipMemcpyAsync(hx, d_xyz.p, nv * 12, hipMemcpyDeviceToHost, st));
     CALLCHK(hipMemcpyAsync(ht, d_tri.p, nt * 12, hipMemcpyDeviceToHost, st));
     if (hc) CALLCHK(hipMemcpyAsync(hc, d_rgb.p, nv * 3, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[5], h->ev[3]));
-    h->ms[3] = ms;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[3], h->ev[4]));
-    h->ms[4] = ms;
-    g.a = g.b = g.c = nullptr;
+    CALLCHK(h->clock.ms(5, 3, &h->ms[3]));
+    CALLCHK(h->clock.ms(3, 4, &h->ms[4]));
+    out.keep();
     *xyz = hx;
     *tri = ht;
     *rgb = hc;
@@ -457,17 +443,16 @@ static int tsdf_commit(mpmvs_tsdf* h, const uint32_t* d_flags) {
     CALLCHK(d_excl.alloc((size_t)n_grid * 4));
     CALLCHK(d_totals.alloc((size_t)n_tiles * 4));
     CALLCHK(d_grand.alloc(4));
-    CALLCHK(hipEventRecord(h->ev[2], st));
-    hipLaunchKernelGGL(k_tsdf_brick_scan, dim3((unsigned)n_tiles), dim3(kScanBlock), 0, st, h->d_grid, d_flags, n_grid, d_excl.as<int>(), d_totals.as<int>());
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_totals.as<int>(), n_tiles, 0, d_grand.as<int>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[3], st));
+    CALLCHK(h->clock.mark(2, st));
+    // not scan_offsets: the tiles are scanned by a kernel that forms the flags from the grid and the marks as it reads them
+    CALLCHK(launch(k_tsdf_brick_scan, dim3((unsigned)n_tiles), dim3(kScanBlock), st, h->d_grid, d_flags, n_grid, d_excl.as<int>(), d_totals.as<int>()));
+    CALLCHK(launch(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), st, d_totals.as<int>(), n_tiles, 0, d_grand.as<int>()));
+    CALLCHK(h->clock.mark(3, st));
     int grand = 0;
     CALLCHK(hipMemcpyAsync(&grand, d_grand.p, 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
     float ms = 0.0f;
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    CALLCHK(h->clock.ms(2, 3, &ms));
     h->alloc_ms[1] = ms;
     const long long n_new = (long long)grand;   // at most 2^24 grid cells: the int cannot overflow, the comparison is in 64 bits
     if (n_new > h->max_bricks)
@@ -476,21 +461,17 @@ static int tsdf_commit(mpmvs_tsdf* h, const uint32_t* d_flags) {
     TsdfPool pool(st);
     const int rc = pool.alloc(h, (size_t)n_new);
     if (rc) return rc;
-    CALLCHK(hipEventRecord(h->ev[4], st));
-    if (h->n_bricks > 0) {
-        hipLaunchKernelGGL(k_tsdf_brick_move, dim3((unsigned)h->n_bricks), dim3(kBrickVox), 0, st, h->d_list, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(),
-                           h->d_sum, h->d_weight, h->with_color ? h->d_color : (const uint4*)nullptr, pool.sum.as<float>(), pool.weight.as<int32_t>(),
-                           h->with_color ? pool.color.as<uint4>() : (uint4*)nullptr);
-        CALLCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_tsdf_brick_commit, dim3((unsigned)((n_grid + 255) / 256)), dim3(256), 0, st, n_grid, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(),
-                       pool.list.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[5], st));
+    CALLCHK(h->clock.mark(4, st));
+    if (h->n_bricks > 0)   // the colours, old and new: null without colour
+        CALLCHK(launch(k_tsdf_brick_move, dim3((unsigned)h->n_bricks), dim3(kBrickVox), st, h->d_list, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(), h->d_sum,
+                       h->d_weight, h->with_color ? h->d_color : nullptr, pool.sum.as<float>(), pool.weight.as<int32_t>(), pool.color.as<uint4>()));
+    CALLCHK(launch(k_tsdf_brick_commit, dim3((unsigned)((n_grid + 255) / 256)), dim3(256), st, n_grid, h->d_grid, d_flags, d_excl.as<int>(), d_totals.as<int>(),
+                   pool.list.as<int32_t>()));
+    CALLCHK(h->clock.mark(5, st));
     std::vector<int32_t> list((size_t)n_new);
     CALLCHK(hipMemcpyAsync(list.data(), pool.list.p, (size_t)n_new * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    CALLCHK(hipEventElapsedTime(&ms, h->ev[4], h->ev[5]));
+    CALLCHK(h->clock.ms(4, 5, &ms));
     h->alloc_ms[1] += ms;
     pool.swap_into(h);
     h->list.swap(list);
@@ -518,8 +499,9 @@ int mpmvs_tsdf_allocate(mpmvs_tsdf* h, int n_views, const mpmvs_camera* cams, co
         if (rc4) return rc4;
         size_t most = 0;
         for (int v = 0; v < c.A.n; ++v) most = std::max(most, (size_t)c.A.v[v].w * (size_t)c.A.v[v].h);
-        return tsdf_timed(h, 0, 1, &h->alloc_ms[0], [&] {
-            hipLaunchKernelGGL(k_tsdf_alloc_mark, dim3((unsigned)((most + 255) / 256), (unsigned)c.A.n), dim3(256), 0, st, h->V, tsdf_bricks(h), h->alloc, c.A, d_flags.as<uint32_t>());
+        return tsdf_timed(h, &h->alloc_ms[0], [&] {
+            CALLCHK(launch(k_tsdf_alloc_mark, dim3((unsigned)((most + 255) / 256), (unsigned)c.A.n), dim3(256), st, h->V, tsdf_bricks(h), h->alloc, c.A, d_flags.as<uint32_t>()));
+            return 0;
         });
     });
     return rc3 ? rc3 : tsdf_commit(h, d_flags.as<uint32_t>());
@@ -589,9 +571,8 @@ int mpmvs_tsdf_set_bricks(mpmvs_tsdf* h, long long n, const int32_t* coords, con
         if (color4) CALLCHK(hipMemcpyAsync(pool.color.p, color4, e * 16, hipMemcpyHostToDevice, st));
         TsdfBricks B = tsdf_bricks(h);
         B.list = pool.list.as<int32_t>();
-        hipLaunchKernelGGL(k_tsdf_brick_clip, dim3((unsigned)n), dim3(kBrickVox), 0, st, h->V, B, pool.sum.as<float>(), pool.weight.as<int32_t>(),
-                           h->with_color ? pool.color.as<uint4>() : (uint4*)nullptr);
-        CALLCHK(hipGetLastError());
+        CALLCHK(launch(k_tsdf_brick_clip, dim3((unsigned)n), dim3(kBrickVox), st, h->V, B, pool.sum.as<float>(), pool.weight.as<int32_t>(),
+                       pool.color.as<uint4>()));   // null without colour
     }
     CALLCHK(hipStreamSynchronize(st));
     pool.swap_into(h);
@@ -627,7 +608,7 @@ struct mpmvs_mesh {
     unsigned char* d_rgb = nullptr;
     int32_t* d_tri = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    PassClock<5> clock;
     float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     // for mpmvs_simplify_mesh: the finite vertices and their bounding box, taken at create while the host copy exists
     long long n_fin = 0;
@@ -665,20 +646,16 @@ void mpmvs_mesh_destroy(mpmvs_mesh* h) {
         if (h->stream) (void)hipStreamSynchronize(h->stream);
         for (void* p : {(void*)h->d_xyz, (void*)h->d_rgb, (void*)h->d_tri})
             if (p) (void)pool_free(p);
-        for (hipEvent_t e : h->ev)
-            if (e) (void)hipEventDestroy(e);
         if (h->stream) (void)hipStreamDestroy(h->stream);
     }
-    delete h;
+    delete h;   // the clock goes here: the stream has been waited for
 }
 
-// the first operation that needs the device: the stream, the events and the mesh itself
+// the first operation that needs the device: the stream and the mesh itself
 static int mesh_ready(mpmvs_mesh* h) {
     CALLCHK(enter_device(h->device));
     if (h->ready) return 0;
     if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& e : h->ev)
-        if (!e) CALLCHK(hipEventCreate(&e));
     const size_t n = (size_t)h->n, m = (size_t)h->m;
     if (!h->d_xyz) CALLCHK(pool_malloc(&h->d_xyz, n * 12));
     if (h->with_color && !h->d_rgb) CALLCHK(pool_malloc(&h->d_rgb, n * 3));
@@ -693,14 +670,7 @@ static int mesh_ready(mpmvs_mesh* h) {
     h->ready = true;
     return 0;
 }
-static unsigned mesh_blocks(size_t count) { return (unsigned)((count + 255) / 256); }
-// ms[k] = the time between ev[a] and ev[a + 1]; the stream is idle
-static int mesh_elapsed(mpmvs_mesh* h, int a, int k) {
-    float t = 0.0f;
-    CALLCHK(hipEventElapsedTime(&t, h->ev[a], h->ev[a + 1]));
-    h->ms[k] = t;
-    return 0;
-}
+static dim3 mesh_blocks(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
 
 int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label, int32_t* out_verts, int32_t* out_tris, long long counts[4]) {
     if (!h || (h->n > 0 && !out_label)) return call_fail(-2, "mesh components: bad argument");
@@ -727,25 +697,19 @@ int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label, int32_t* out_verts,
     CALLCHK(d_tris.alloc(n * 4));
     int* const vcnt = d_cnt.as<int>();
     int* const tcnt = vcnt + n;
-    CALLCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(k_mesh_cc_init, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_parent.as<int>());
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_mesh_cc_hook, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_parent.as<int>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    hipLaunchKernelGGL(k_cc_flatten, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_parent.as<int>(), d_label.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[2], st));
+    const dim3 blk(256);
+    CALLCHK(h->clock.mark(0, st));
+    CALLCHK(launch(k_mesh_cc_init, mesh_blocks(n), blk, st, ni, d_parent.as<int>()));
+    CALLCHK(launch(k_mesh_cc_hook, mesh_blocks(m), blk, st, mi, h->d_tri, d_parent.as<int>()));
+    CALLCHK(h->clock.mark(1, st));
+    CALLCHK(launch(k_cc_flatten, mesh_blocks(n), blk, st, ni, d_parent.as<int>(), d_label.as<int32_t>()));
+    CALLCHK(h->clock.mark(2, st));
     CALLCHK(hipMemsetAsync(d_cnt.p, 0, n * 8, st));
-    hipLaunchKernelGGL(k_cc_count, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), vcnt);
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_mesh_tri_count, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_label.as<int32_t>(), tcnt);
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cc_gather, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), vcnt, d_verts.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_cc_gather, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_label.as<int32_t>(), tcnt, d_tris.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[3], st));
+    CALLCHK(launch(k_cc_count, mesh_blocks(n), blk, st, ni, d_label.as<int32_t>(), vcnt));
+    CALLCHK(launch(k_mesh_tri_count, mesh_blocks(m), blk, st, mi, h->d_tri, d_label.as<int32_t>(), tcnt));
+    CALLCHK(launch(k_cc_gather, mesh_blocks(n), blk, st, ni, d_label.as<int32_t>(), vcnt, d_verts.as<int32_t>()));
+    CALLCHK(launch(k_cc_gather, mesh_blocks(n), blk, st, ni, d_label.as<int32_t>(), tcnt, d_tris.as<int32_t>()));
+    CALLCHK(h->clock.mark(3, st));
     std::vector<int32_t> tris_host;   // the counts need the triangle counts whether the caller wants them or not
     if (counts && !out_tris) tris_host.resize(n);
     int32_t* const tris = out_tris ? out_tris : tris_host.data();
@@ -753,10 +717,7 @@ int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label, int32_t* out_verts,
     if (out_verts) CALLCHK(hipMemcpyAsync(out_verts, d_verts.p, n * 4, hipMemcpyDeviceToHost, st));
     if (out_tris || counts) CALLCHK(hipMemcpyAsync(tris, d_tris.p, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < 3; ++k) {
-        const int rc2 = mesh_elapsed(h, k, k);
-        if (rc2) return rc2;
-    }
+    for (int k = 0; k < 3; ++k) CALLCHK(h->clock.ms(k, k + 1, &h->ms[k]));
     if (counts) {
         // a vertex that a triangle names lies in a component with that triangle; one that none names is alone with 0 triangles
         long long comps = 0, unnamed = 0, best = 0, best_label = -1;
@@ -788,22 +749,17 @@ int mpmvs_mesh_normals(mpmvs_mesh* h, float* out_normals, long long* n_defined) 
     CALLCHK(d_out.alloc(n * 12));
     CALLCHK(d_def.alloc(4));
     CALLCHK(hipMemsetAsync(d_def.p, 0, 4, st));
-    CALLCHK(hipEventRecord(h->ev[0], st));
+    CALLCHK(h->clock.mark(0, st));
     CALLCHK(hipMemsetAsync(d_sum.p, 0, n * 24, st));
-    hipLaunchKernelGGL(k_mesh_nrm_accum, dim3(mesh_blocks((size_t)h->m)), dim3(256), 0, st, (int)h->m, h->d_xyz, h->d_tri, h->scale, d_sum.as<long long>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    hipLaunchKernelGGL(k_mesh_nrm_finish, dim3(mesh_blocks(n)), dim3(256), 0, st, (int)h->n, d_sum.as<long long>(), d_out.as<float>(), d_def.as<int>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(h->ev[2], st));
+    CALLCHK(launch(k_mesh_nrm_accum, mesh_blocks((size_t)h->m), dim3(256), st, (int)h->m, h->d_xyz, h->d_tri, h->scale, d_sum.as<long long>()));
+    CALLCHK(h->clock.mark(1, st));
+    CALLCHK(launch(k_mesh_nrm_finish, mesh_blocks(n), dim3(256), st, (int)h->n, d_sum.as<long long>(), d_out.as<float>(), d_def.as<int>()));
+    CALLCHK(h->clock.mark(2, st));
     int defined = 0;
     CALLCHK(hipMemcpyAsync(out_normals, d_out.p, n * 12, hipMemcpyDeviceToHost, st));
     CALLCHK(hipMemcpyAsync(&defined, d_def.p, 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < 2; ++k) {
-        const int rc2 = mesh_elapsed(h, k, 3 + k);
-        if (rc2) return rc2;
-    }
+    for (int k = 0; k < 2; ++k) CALLCHK(h->clock.ms(k, k + 1, &h->ms[3 + k]));
     if (n_defined) *n_defined = defined;
     return 0;
 }
@@ -813,46 +769,33 @@ static long long mesh_select_device(mpmvs_mesh* h, const unsigned char* keep, in
     const hipStream_t st = h->stream;
     const size_t n = (size_t)h->n, m = (size_t)h->m;
     const int ni = (int)h->n, mi = (int)h->m;
-    const int v_tiles = (int)((n + kScanBlock - 1) / kScanBlock), t_tiles = (int)((m + kScanBlock - 1) / kScanBlock);
+    const size_t v_tiles = (n + kScanBlock - 1) / kScanBlock, t_tiles = (m + kScanBlock - 1) / kScanBlock;
     Scratch d_keep(st), d_vflag(st), d_tflag(st), d_vexcl(st), d_texcl(st), d_tiles(st), d_grand(st);
     CALLCHK(d_keep.alloc(n));
     CALLCHK(d_vflag.alloc(n * 4));
     CALLCHK(d_tflag.alloc(m * 4));
     CALLCHK(d_vexcl.alloc(n * 4));
     CALLCHK(d_texcl.alloc(m * 4));
-    CALLCHK(d_tiles.alloc((size_t)(v_tiles + t_tiles) * 4));
+    CALLCHK(d_tiles.alloc((v_tiles + t_tiles) * 4));
     CALLCHK(d_grand.alloc(8));
     int* const vtile = d_tiles.as<int>();
     int* const ttile = vtile + v_tiles;
     int* const grand = d_grand.as<int>();
     CALLCHK(hipMemcpyAsync(d_keep.p, keep, n, hipMemcpyHostToDevice, st));
     CALLCHK(hipMemsetAsync(d_grand.p, 0, 8, st));
-    CALLCHK(hipEventRecord(h->ev[0], st));
-    hipLaunchKernelGGL(k_mesh_sel_verts, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, d_keep.as<unsigned char>(), drop, d_vflag.as<int>());
-    CALLCHK(hipGetLastError());
-    if (m > 0) {
-        hipLaunchKernelGGL(k_mesh_sel_tris, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_keep.as<unsigned char>(), drop, d_tflag.as<int>(), d_vflag.as<int>());
-        CALLCHK(hipGetLastError());
-    }
-    CALLCHK(hipEventRecord(h->ev[1], st));
-    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)v_tiles), dim3(kScanBlock), 0, st, d_vflag.as<int>(), ni, d_vexcl.as<int>(), vtile);
-    CALLCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, vtile, v_tiles, 0, grand);
-    CALLCHK(hipGetLastError());
-    if (m > 0) {
-        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)t_tiles), dim3(kScanBlock), 0, st, d_tflag.as<int>(), mi, d_texcl.as<int>(), ttile);
-        CALLCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, ttile, t_tiles, 0, grand + 1);
-        CALLCHK(hipGetLastError());
-    }
-    CALLCHK(hipEventRecord(h->ev[2], st));
+    const dim3 blk(256);
+    CALLCHK(h->clock.mark(0, st));
+    CALLCHK(launch(k_mesh_sel_verts, mesh_blocks(n), blk, st, ni, d_keep.as<unsigned char>(), drop, d_vflag.as<int>()));
+    if (m > 0) CALLCHK(launch(k_mesh_sel_tris, mesh_blocks(m), blk, st, mi, h->d_tri, d_keep.as<unsigned char>(), drop, d_tflag.as<int>(), d_vflag.as<int>()));
+    CALLCHK(h->clock.mark(1, st));
+    // the emit kernels add the tile offsets themselves
+    CALLCHK(scan_offsets(st, d_vflag.as<int>(), ni, d_vexcl.as<int>(), vtile, grand, false));
+    if (m > 0) CALLCHK(scan_offsets(st, d_tflag.as<int>(), mi, d_texcl.as<int>(), ttile, grand + 1, false));
+    CALLCHK(h->clock.mark(2, st));
     int g[2] = {0, 0};
     CALLCHK(hipMemcpyAsync(g, d_grand.p, 8, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < 2; ++k) {
-        const int rc = mesh_elapsed(h, k, 5 + k);
-        if (rc) return rc;
-    }
+    for (int k = 0; k < 2; ++k) CALLCHK(h->clock.ms(k, k + 1, &h->ms[5 + k]));
     const size_t nv = (size_t)g[0], nt = (size_t)g[1];
     if (nv == 0) return 0;   // then nt == 0 too: a kept triangle keeps its vertices
     Scratch d_xyz(st), d_rgb(st), d_tri(st), d_src(st);
@@ -860,33 +803,25 @@ static long long mesh_select_device(mpmvs_mesh* h, const unsigned char* keep, in
     if (h->with_color) CALLCHK(d_rgb.alloc(nv * 3));
     CALLCHK(d_tri.alloc(nt * 12));
     CALLCHK(d_src.alloc(nv * 4));
-    CALLCHK(hipEventRecord(h->ev[3], st));
-    hipLaunchKernelGGL(k_mesh_emit_verts, dim3(mesh_blocks(n)), dim3(256), 0, st, ni, h->d_xyz, h->with_color ? h->d_rgb : (const unsigned char*)nullptr, d_vflag.as<int>(),
-                       d_vexcl.as<int>(), vtile, d_xyz.as<float>(), d_rgb.as<unsigned char>(), d_src.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    if (nt > 0) {
-        hipLaunchKernelGGL(k_mesh_emit_tris, dim3(mesh_blocks(m)), dim3(256), 0, st, mi, h->d_tri, d_tflag.as<int>(), d_texcl.as<int>(), ttile, d_vexcl.as<int>(), vtile,
-                           d_tri.as<int32_t>());
-        CALLCHK(hipGetLastError());
-    }
-    CALLCHK(hipEventRecord(h->ev[4], st));
-    float* hx = (float*)std::malloc(nv * 12);
-    int32_t* ht = nt ? (int32_t*)std::malloc(nt * 12) : nullptr;
-    unsigned char* hc = h->with_color ? (unsigned char*)std::malloc(nv * 3) : nullptr;
-    int32_t* hs = src ? (int32_t*)std::malloc(nv * 4) : nullptr;
-    struct Guard {
-        void *a, *b, *c, *d;
-        ~Guard() { std::free(a); std::free(b); std::free(c); std::free(d); }
-    } guard{hx, ht, hc, hs};
+    CALLCHK(h->clock.mark(3, st));
+    CALLCHK(launch(k_mesh_emit_verts, mesh_blocks(n), blk, st, ni, h->d_xyz, h->with_color ? h->d_rgb : nullptr, d_vflag.as<int>(), d_vexcl.as<int>(), vtile,
+                   d_xyz.as<float>(), d_rgb.as<unsigned char>(), d_src.as<int32_t>()));
+    if (nt > 0)
+        CALLCHK(launch(k_mesh_emit_tris, mesh_blocks(m), blk, st, mi, h->d_tri, d_tflag.as<int>(), d_texcl.as<int>(), ttile, d_vexcl.as<int>(), vtile, d_tri.as<int32_t>()));
+    CALLCHK(h->clock.mark(4, st));
+    HostOut out;
+    float* hx = out.take<float>(nv * 3);
+    int32_t* ht = nt ? out.take<int32_t>(nt * 3) : nullptr;
+    unsigned char* hc = h->with_color ? out.take<unsigned char>(nv * 3) : nullptr;
+    int32_t* hs = src ? out.take<int32_t>(nv) : nullptr;
     if (!hx || (nt && !ht) || (h->with_color && !hc) || (src && !hs)) return call_fail(-100, "mesh select: out of host memory");
     CALLCHK(hipMemcpyAsync(hx, d_xyz.p, nv * 12, hipMemcpyDeviceToHost, st));
     if (ht) CALLCHK(hipMemcpyAsync(ht, d_tri.p, nt * 12, hipMemcpyDeviceToHost, st));
     if (hc) CALLCHK(hipMemcpyAsync(hc, d_rgb.p, nv * 3, hipMemcpyDeviceToHost, st));
     if (hs) CALLCHK(hipMemcpyAsync(hs, d_src.p, nv * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
-    const int rc = mesh_elapsed(h, 3, 7);
-    if (rc) return rc;
-    guard.a = guard.b = guard.c = guard.d = nullptr;
+    CALLCHK(h->clock.ms(3, 4, &h->ms[7]));
+    out.keep();
     *xyz = hx;
     *tri = ht;
     *rgb = hc;
@@ -926,111 +861,51 @@ int mpmvs_mesh_pass_ms(const mpmvs_mesh* h, float ms[8]) {
 }
 
 // ---- simplification by vertex clustering (statement 4 of include/mpmvs.h) -------------------------------------
-namespace {
-// the borders of the passes; destroyed after the stream has been waited for
-struct SimpEvents {
-    hipEvent_t e[13] = {};
-    ~SimpEvents() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-// the host buffers of the result: released unless the call succeeds
+// the host buffers of the result, as the entry point hands them out
 struct SimpOut {
+    HostOut mem;
     float* xyz = nullptr;
     unsigned char *rgb = nullptr, *placed = nullptr;
     int32_t *tri = nullptr, *count = nullptr, *src = nullptr;
-    bool keep = false;
-    ~SimpOut() {
-        if (!keep)
-            for (void* x : {(void*)xyz, (void*)rgb, (void*)placed, (void*)tri, (void*)count, (void*)src}) std::free(x);
-    }
 };
-}  // namespace
+static const ClusterNames kSimpNames = {"mesh simplify", "vertices", "cell", "clusters"};
 
 // the device half of mpmvs_simplify_mesh: n_fin > 0.  class_counts = {alive, non-finite, collapsed}
 static long long mesh_simplify_device(mpmvs_mesh* h, const VoxelGrid& g, int slots_log2, int placement, SimpOut& out, int32_t* out_cluster_of, bool want_count,
                                       bool want_placed, bool want_src, long long* m_out, long long class_counts[3]) {
     const hipStream_t st = h->stream;
-    const size_t n = (size_t)h->n, m = (size_t)h->m, slots = (size_t)1 << slots_log2;
-    const int ni = (int)h->n, mi = (int)h->m, ntiles = (ni + kScanBlock - 1) / kScanBlock;
-    const unsigned char* const d_rgb = h->with_color ? h->d_rgb : nullptr;
-    SimpEvents ev;
-    for (hipEvent_t& e : ev.e) CALLCHK(hipEventCreate(&e));
+    const size_t n = (size_t)h->n, m = (size_t)h->m;
+    const int mi = (int)h->m;
+    const dim3 blk(256);
     float* const ms = h->simp_ms;
-    auto elapsed = [&](int a, int b, float* t) { return hipEventElapsedTime(t, ev.e[a], ev.e[b]); };
 
-    // ---- clusters: the voxel passes as mpmvs_cloud_voxel_downsample runs them, on the resident vertices
-    Scratch d_slot_of(st), d_flag(st), d_num(st), d_tsum(st), d_nc(st), d_keys(st), d_cnt(st), d_first(st), d_vox_of_slot(st);
-    CALLCHK(d_slot_of.alloc(n * 4));
-    CALLCHK(d_flag.alloc(n * 4));
-    CALLCHK(d_num.alloc(n * 4));
-    CALLCHK(d_tsum.alloc((size_t)ntiles * 4));
-    CALLCHK(d_nc.alloc(4));
-    CALLCHK(d_keys.alloc(slots * 8));
-    CALLCHK(d_cnt.alloc(slots * 4));
-    CALLCHK(d_first.alloc(slots * 4));
-    CALLCHK(d_vox_of_slot.alloc(slots * 4));
-    CALLCHK(hipMemsetAsync(d_keys.p, 0xff, slots * 8, st));
-    CALLCHK(hipMemsetAsync(d_cnt.p, 0, slots * 4, st));
-    CALLCHK(hipMemsetAsync(d_first.p, 0xff, slots * 4, st));
-    const dim3 gp((unsigned)ntiles), blk(256);
-    CALLCHK(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(k_cloud_insert, gp, blk, 0, st, h->d_xyz, ni, g.o[0], g.o[1], g.o[2], g.e, (unsigned)(slots - 1), d_keys.as<unsigned long long>(), d_cnt.as<int>(),
-                       d_slot_of.as<int>());
-    hipLaunchKernelGGL(k_voxel_first, gp, blk, 0, st, ni, d_slot_of.as<int>(), d_first.as<unsigned>());
-    hipLaunchKernelGGL(k_voxel_flag, gp, blk, 0, st, ni, d_slot_of.as<int>(), d_first.as<unsigned>(), d_flag.as<int>());
-    hipLaunchKernelGGL(k_scan_tiles, gp, dim3(kScanBlock), 0, st, d_flag.as<int>(), ni, d_num.as<int>(), d_tsum.as<int>());
-    hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_tsum.as<int>(), ntiles, 0, d_nc.as<int>());
-    hipLaunchKernelGGL(k_vs_scan_add, gp, dim3(kScanBlock), 0, st, d_num.as<int>(), ni, d_tsum.as<int>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(ev.e[1], st));
-    int nci = 0;
-    CALLCHK(hipMemcpyAsync(&nci, d_nc.p, 4, hipMemcpyDeviceToHost, st));
-    CALLCHK(hipStreamSynchronize(st));
-    if (nci <= 0 || (long long)nci > h->n_fin)
-        return call_fail(-100, "mesh simplify: the device counted " + std::to_string(nci) + " clusters for " + std::to_string(h->n_fin) + " finite vertices");
+    // ---- clusters: the passes of mpmvs_cloud_voxel_downsample on the resident vertices, then the quadrics between accumulate and finish
+    // Declared before every other buffer, so that its clock goes last, after the stream has been waited for.  The caller's marks on
+    // it: 8 quadric end, 9 place end, 10 classify end, 11 / 12 insert begin / end, 13 owner + scan end, 14 / 15 emit begin / end
+    Clusters cl(st, kSimpNames, false);
+    auto& clock = cl.clock;
+    if (cl.mark(h->d_xyz, (int)h->n, h->n_fin, slots_log2, g)) return -100;
+    const int nci = cl.count;
     const size_t nc = (size_t)nci;
-
-    // ---- numbering, the position (and colour) sums, the quadrics, the representatives
-    Scratch d_out_first(st), d_out_count(st), d_cluster_of(st), d_acc(st), d_qrt(st), d_out_xyz(st), d_out_rgb(st), d_placed(st);
-    CALLCHK(d_out_first.alloc(nc * 4));
-    CALLCHK(d_out_count.alloc(nc * 4));
-    CALLCHK(d_cluster_of.alloc(n * 4));
-    CALLCHK(d_acc.alloc((h->with_color ? 2 : 1) * nc * 24));   // S, then C
+    Scratch d_qrt(st), d_placed(st);
     if (placement == 1) CALLCHK(d_qrt.alloc(nc * kSimpSums * 8));
-    CALLCHK(d_out_xyz.alloc(nc * 12));
-    if (h->with_color) CALLCHK(d_out_rgb.alloc(nc * 3));
     CALLCHK(d_placed.alloc(nc));
-    unsigned long long* const d_S = d_acc.as<unsigned long long>();
-    unsigned long long* const d_C = h->with_color ? d_S + 3 * nc : nullptr;
-    CALLCHK(hipMemsetAsync(d_acc.p, 0, (h->with_color ? 2 : 1) * nc * 24, st));
     CALLCHK(hipMemsetAsync(d_placed.p, 0, nc, st));
-    CALLCHK(hipEventRecord(ev.e[2], st));
-    hipLaunchKernelGGL(k_voxel_number, gp, blk, 0, st, ni, d_flag.as<int>(), d_num.as<int>(), d_slot_of.as<int>(), d_cnt.as<int>(), d_vox_of_slot.as<int>(),
-                       d_out_first.as<int32_t>(), d_out_count.as<int32_t>());
-    CALLCHK(hipEventRecord(ev.e[3], st));
-    hipLaunchKernelGGL(k_voxel_accumulate, gp, blk, 0, st, ni, h->d_xyz, (const float*)nullptr, d_rgb, g, d_slot_of.as<int>(), d_vox_of_slot.as<int>(), d_S,
-                       (unsigned long long*)nullptr, d_C, d_cluster_of.as<int32_t>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(ev.e[4], st));
-    if (placement == 1 && m > 0) {
+    if (cl.number_and_accumulate(nullptr, h->with_color ? h->d_rgb : nullptr, true)) return -100;
+    const int32_t* const d_cluster_of = cl.cluster_of.as<int32_t>();
+    if (placement == 1 && m > 0) {   // from mark 6, the end of accumulate
         CALLCHK(hipMemsetAsync(d_qrt.p, 0, nc * kSimpSums * 8, st));
-        hipLaunchKernelGGL(k_simp_quadric, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_xyz, h->d_tri, g, d_cluster_of.as<int32_t>(), d_qrt.as<unsigned long long>());
-        CALLCHK(hipGetLastError());
+        CALLCHK(launch(k_simp_quadric, mesh_blocks(m), blk, st, mi, h->d_xyz, h->d_tri, g, d_cluster_of, d_qrt.as<unsigned long long>()));
     }
-    CALLCHK(hipEventRecord(ev.e[5], st));
-    hipLaunchKernelGGL(k_voxel_finish, dim3(mesh_blocks(nc)), blk, 0, st, nci, h->d_xyz, d_out_first.as<int32_t>(), d_out_count.as<int32_t>(), g, d_S,
-                       (const unsigned long long*)nullptr, d_C, d_out_xyz.as<float>(), (float*)nullptr, h->with_color ? d_out_rgb.as<unsigned char>() : (unsigned char*)nullptr);
+    CALLCHK(clock.mark(8, st));
+    if (cl.finish()) return -100;
     if (placement == 1 && m > 0)   // without a triangle no cluster has a plane: placed stays 0 everywhere
-        hipLaunchKernelGGL(k_simp_place, dim3(mesh_blocks(nc)), blk, 0, st, nci, h->d_xyz, d_out_first.as<int32_t>(), d_out_count.as<int32_t>(), g, d_S,
-                           d_qrt.as<unsigned long long>(), d_out_xyz.as<float>(), d_placed.as<unsigned char>());
-    CALLCHK(hipGetLastError());
-    CALLCHK(hipEventRecord(ev.e[6], st));
+        CALLCHK(launch(k_simp_place, mesh_blocks(nc), blk, st, nci, h->d_xyz, cl.out_first.as<int32_t>(), cl.out_count.as<int32_t>(), g, cl.S,
+                       d_qrt.as<unsigned long long>(), cl.out_xyz.as<float>(), d_placed.as<unsigned char>()));
+    CALLCHK(clock.mark(9, st));
 
     // ---- triangles: classes and keys, the duplicate filter, the scan of the kept flags, the emit
     Scratch d_cls(st), d_key(st), d_class(st), d_table(st), d_kept(st), d_excl(st), d_ttile(st), d_grand(st), d_tri(st), d_src(st);
-    const int t_tiles = (int)((m + kScanBlock - 1) / kScanBlock);
     int cc[3] = {0, 0, 0};
     size_t nt = 0;
     if (m > 0) {
@@ -1038,10 +913,8 @@ static long long mesh_simplify_device(mpmvs_mesh* h, const VoxelGrid& g, int slo
         CALLCHK(d_key.alloc(m * 12));
         CALLCHK(d_class.alloc(12));
         CALLCHK(hipMemsetAsync(d_class.p, 0, 12, st));
-        hipLaunchKernelGGL(k_simp_classify, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_tri, d_cluster_of.as<int32_t>(), d_cls.as<unsigned char>(), d_key.as<int32_t>(),
-                           d_class.as<int>());
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(ev.e[7], st));
+        CALLCHK(launch(k_simp_classify, mesh_blocks(m), blk, st, mi, h->d_tri, d_cluster_of, d_cls.as<unsigned char>(), d_key.as<int32_t>(), d_class.as<int>()));
+        CALLCHK(clock.mark(10, st));
         CALLCHK(hipMemcpyAsync(cc, d_class.p, 12, hipMemcpyDeviceToHost, st));
         CALLCHK(hipStreamSynchronize(st));
         if (cc[0] < 0 || cc[1] < 0 || cc[2] < 0 || (long long)cc[0] + cc[1] + cc[2] != h->m) return call_fail(-100, "mesh simplify: the classes do not add up to the triangles");
@@ -1052,19 +925,16 @@ static long long mesh_simplify_device(mpmvs_mesh* h, const VoxelGrid& g, int slo
         CALLCHK(d_table.alloc(tslots * 4));
         CALLCHK(d_kept.alloc(m * 4));
         CALLCHK(d_excl.alloc(m * 4));
-        CALLCHK(d_ttile.alloc((size_t)t_tiles * 4));
+        CALLCHK(d_ttile.alloc((m + kScanBlock - 1) / kScanBlock * 4));
         CALLCHK(d_grand.alloc(4));
-        CALLCHK(hipEventRecord(ev.e[8], st));
+        CALLCHK(clock.mark(11, st));
         CALLCHK(hipMemsetAsync(d_table.p, 0xff, tslots * 4, st));
-        hipLaunchKernelGGL(k_simp_insert, dim3(mesh_blocks(m)), blk, 0, st, mi, d_cls.as<unsigned char>(), d_key.as<int32_t>(), (uint32_t)(tslots - 1), d_table.as<uint32_t>());
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(ev.e[9], st));
+        CALLCHK(launch(k_simp_insert, mesh_blocks(m), blk, st, mi, d_cls.as<unsigned char>(), d_key.as<int32_t>(), (uint32_t)(tslots - 1), d_table.as<uint32_t>()));
+        CALLCHK(clock.mark(12, st));
         CALLCHK(hipMemsetAsync(d_kept.p, 0, m * 4, st));
-        hipLaunchKernelGGL(k_simp_owner, dim3(mesh_blocks(tslots)), blk, 0, st, (uint32_t)tslots, d_table.as<uint32_t>(), d_kept.as<int>());
-        hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)t_tiles), dim3(kScanBlock), 0, st, d_kept.as<int>(), mi, d_excl.as<int>(), d_ttile.as<int>());
-        hipLaunchKernelGGL(k_scan_totals<Sum>, dim3(1), dim3(kScanBlock), 0, st, d_ttile.as<int>(), t_tiles, 0, d_grand.as<int>());
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(ev.e[10], st));
+        CALLCHK(launch(k_simp_owner, mesh_blocks(tslots), blk, st, (uint32_t)tslots, d_table.as<uint32_t>(), d_kept.as<int>()));
+        CALLCHK(scan_offsets(st, d_kept.as<int>(), mi, d_excl.as<int>(), d_ttile.as<int>(), d_grand.as<int>(), false));   // k_simp_emit adds the tile offsets
+        CALLCHK(clock.mark(13, st));
         int kept = 0;
         CALLCHK(hipMemcpyAsync(&kept, d_grand.p, 4, hipMemcpyDeviceToHost, st));
         CALLCHK(hipStreamSynchronize(st));
@@ -1072,42 +942,41 @@ static long long mesh_simplify_device(mpmvs_mesh* h, const VoxelGrid& g, int slo
         nt = (size_t)kept;
         CALLCHK(d_tri.alloc(nt * 12));
         CALLCHK(d_src.alloc(nt * 4));
-        CALLCHK(hipEventRecord(ev.e[11], st));
-        hipLaunchKernelGGL(k_simp_emit, dim3(mesh_blocks(m)), blk, 0, st, mi, h->d_tri, d_cluster_of.as<int32_t>(), d_kept.as<int>(), d_excl.as<int>(), d_ttile.as<int>(),
-                           d_tri.as<int32_t>(), d_src.as<int32_t>());
-        CALLCHK(hipGetLastError());
-        CALLCHK(hipEventRecord(ev.e[12], st));
+        CALLCHK(clock.mark(14, st));
+        CALLCHK(launch(k_simp_emit, mesh_blocks(m), blk, st, mi, h->d_tri, d_cluster_of, d_kept.as<int>(), d_excl.as<int>(), d_ttile.as<int>(), d_tri.as<int32_t>(),
+                       d_src.as<int32_t>()));
+        CALLCHK(clock.mark(15, st));
     }
 
-    out.xyz = (float*)std::malloc(nc * 12);
-    if (h->with_color) out.rgb = (unsigned char*)std::malloc(nc * 3);
-    if (want_count) out.count = (int32_t*)std::malloc(nc * 4);
-    if (want_placed) out.placed = (unsigned char*)std::malloc(nc);
-    if (nt) out.tri = (int32_t*)std::malloc(nt * 12);
-    if (nt && want_src) out.src = (int32_t*)std::malloc(nt * 4);
+    out.xyz = out.mem.take<float>(nc * 3);
+    if (h->with_color) out.rgb = out.mem.take<unsigned char>(nc * 3);
+    if (want_count) out.count = out.mem.take<int32_t>(nc);
+    if (want_placed) out.placed = out.mem.take<unsigned char>(nc);
+    if (nt) out.tri = out.mem.take<int32_t>(nt * 3);
+    if (nt && want_src) out.src = out.mem.take<int32_t>(nt);
     if (!out.xyz || (h->with_color && !out.rgb) || (want_count && !out.count) || (want_placed && !out.placed) || (nt && !out.tri) || (nt && want_src && !out.src))
         return call_fail(-100, "mesh simplify: out of host memory");
-    CALLCHK(hipMemcpyAsync(out.xyz, d_out_xyz.p, nc * 12, hipMemcpyDeviceToHost, st));
-    if (out.rgb) CALLCHK(hipMemcpyAsync(out.rgb, d_out_rgb.p, nc * 3, hipMemcpyDeviceToHost, st));
-    if (out.count) CALLCHK(hipMemcpyAsync(out.count, d_out_count.p, nc * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(out.xyz, cl.out_xyz.p, nc * 12, hipMemcpyDeviceToHost, st));
+    if (out.rgb) CALLCHK(hipMemcpyAsync(out.rgb, cl.out_rgb.p, nc * 3, hipMemcpyDeviceToHost, st));
+    if (out.count) CALLCHK(hipMemcpyAsync(out.count, cl.out_count.p, nc * 4, hipMemcpyDeviceToHost, st));
     if (out.placed) CALLCHK(hipMemcpyAsync(out.placed, d_placed.p, nc, hipMemcpyDeviceToHost, st));
     if (out.tri) CALLCHK(hipMemcpyAsync(out.tri, d_tri.p, nt * 12, hipMemcpyDeviceToHost, st));
     if (out.src) CALLCHK(hipMemcpyAsync(out.src, d_src.p, nt * 4, hipMemcpyDeviceToHost, st));
-    if (out_cluster_of) CALLCHK(hipMemcpyAsync(out_cluster_of, d_cluster_of.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_cluster_of) CALLCHK(hipMemcpyAsync(out_cluster_of, d_cluster_of, n * 4, hipMemcpyDeviceToHost, st));
     CALLCHK(hipStreamSynchronize(st));
     float a = 0.0f, b = 0.0f;
-    CALLCHK(elapsed(0, 1, &a));
-    CALLCHK(elapsed(2, 3, &b));
-    ms[0] = a + b;
-    CALLCHK(elapsed(3, 4, &ms[1]));
-    if (placement == 1 && m > 0) CALLCHK(elapsed(4, 5, &ms[2]));
-    CALLCHK(elapsed(5, 6, &ms[3]));
-    if (m > 0) CALLCHK(elapsed(6, 7, &ms[4]));
+    CALLCHK(clock.ms(0, 3, &a));
+    CALLCHK(clock.ms(4, 5, &b));
+    ms[0] = a + b;   // the clustering passes up to the numbering
+    CALLCHK(clock.ms(5, 6, &ms[1]));
+    if (placement == 1 && m > 0) CALLCHK(clock.ms(6, 8, &ms[2]));
+    CALLCHK(clock.ms(8, 9, &ms[3]));
+    if (m > 0) CALLCHK(clock.ms(9, 10, &ms[4]));
     if (cc[0] > 0) {
-        CALLCHK(elapsed(8, 9, &a));
+        CALLCHK(clock.ms(11, 12, &a));
         ms[4] += a;
-        CALLCHK(elapsed(9, 10, &ms[5]));
-        CALLCHK(elapsed(11, 12, &ms[6]));
+        CALLCHK(clock.ms(12, 13, &ms[5]));
+        CALLCHK(clock.ms(14, 15, &ms[6]));
     }
     *m_out = (long long)nt;
     class_counts[0] = cc[0], class_counts[1] = cc[1], class_counts[2] = cc[2];
@@ -1121,21 +990,9 @@ long long mpmvs_simplify_mesh(mpmvs_mesh* h, float cell, int placement, float** 
     if (placement != 0 && placement != 1) return call_fail(-2, "mesh simplify: placement must be 0 (mean) or 1 (quadric)");
     if (h->with_color && !out_rgb) return call_fail(-2, "mesh simplify: a mesh with colour needs out_rgb");
     if (!h->with_color && out_rgb) return call_fail(-2, "mesh simplify: the mesh has no colour");
-    // the refusals of mpmvs_cloud_voxel_downsample on these vertices
-    const int slots_log2 = cloud_slots_log2(h->n_fin);
-    if (slots_log2 > kCloudMaxSlotsLog2) return call_fail(-3, "mesh simplify: more than 2^29 finite vertices (the table would exceed 2^30 slots)");
+    int slots_log2 = 0;
     VoxelGrid g;
-    voxel_origin(h->mn, cell, g);
-    if (h->n_fin > 0) {
-        double top = 0.0;
-        const int a = voxel_span_axis(h->mx, g, &top);
-        if (a >= 0) {
-            char msg[200];
-            std::snprintf(msg, sizeof msg, "mesh simplify: the vertices span %.6g cells of edge %.6g along %c, more than 2^21 (extent / cell = %.6g)", top + 1.0, g.e,
-                          "xyz"[a], ((double)h->mx[a] - (double)h->mn[a]) / g.e);
-            return call_fail(-3, msg);
-        }
-    }
+    if (cluster_refusal(kSimpNames, h->n_fin, h->mn, h->mx, cell, &slots_log2, &g)) return -3;
     SimpOut out;
     long long nc = 0, nt = 0, cc[3] = {0, h->m, 0};   // without a finite vertex every triangle names a non-finite one
     std::memset(h->simp_ms, 0, sizeof h->simp_ms);
@@ -1155,7 +1012,7 @@ long long mpmvs_simplify_mesh(mpmvs_mesh* h, float cell, int placement, float** 
     if (out_tri_src) *out_tri_src = out.src;
     *m_out = nt;
     if (counts) counts[0] = cc[1], counts[1] = cc[2], counts[2] = cc[0] - nt;
-    out.keep = true;
+    out.mem.keep();
     return nc;
 }
 

@@ -260,9 +260,7 @@ static int seg_preprocess(mpmvs_skyseg* n, const unsigned char* bgr, int h, int 
     nm.mean[0] = 0.485f * 255.f, nm.mean[1] = 0.456f * 255.f, nm.mean[2] = 0.406f * 255.f;  // SkyRegionDetect.cpp:628-629
     nm.norm[0] = 1 / 0.229f / 255.f, nm.norm[1] = 1 / 0.224f / 255.f, nm.norm[2] = 1 / 0.225f / 255.f;
     const int total = 3 * ib.h * ib.w;
-    hipLaunchKernelGGL(k_seg_resize_norm, dim3((total + 255) / 256), dim3(256), 0, n->stream, cur, w, h, seg_ptr(n, ib.segs[0]), ib.w, ib.h, (float)w / ib.w,
-                       (float)h / ib.h, nm);
-    CALLCHK(hipGetLastError());
+    CALLCHK(launch(k_seg_resize_norm, dim3((total + 255) / 256), dim3(256), n->stream, cur, w, h, seg_ptr(n, ib.segs[0]), ib.w, ib.h, (float)w / ib.w, (float)h / ib.h, nm));
     return 0;
 }
 

@@ -1,11 +1,14 @@
 // pm_host.hpp -- what the host side of every family of the C ABI shares (definitions: mpmvs_host.hip): entering a device, the
-// pooled device and page-locked buffers, the scoped scratch and stateless-call helpers, the camera conversion, the error channel of
-// the calls without a PatchMatch context, and the one question the fusion asks a context.  Declarations and small inline classes
-// only; everything here is hidden: the library's dynamic symbol table is include/mpmvs.h and the kernels.
+// pooled device and page-locked buffers, the scoped scratch and stateless-call helpers, the checked kernel launch, the pass clock, the
+// guard of a call's malloc'd results, the camera conversion, the error channel of the calls without a PatchMatch context, and the one
+// question the fusion asks a context.  (The host side of the scan is pm_scan_host.hpp: it names kernels, which a unit that never
+// scans should not get into its code object.)  Declarations and small inline classes only; everything here is hidden: the library's
+// dynamic symbol table is include/mpmvs.h and the kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -115,6 +118,63 @@ class DeviceCall {
     bool begin() { return hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess && hipEventRecord(ev[0], st) == hipSuccess; }
     bool end() { return hipEventRecord(ev[1], st) == hipSuccess; }
     bool elapsed(float* ms) const { return hipEventElapsedTime(ms, ev[0], ev[1]) == hipSuccess; }
+};
+
+// One kernel launch without dynamic LDS, and what it left: CALLCHK(launch(k_name, grid, block, stream, args...)).  Every argument is
+// cast to the kernel's parameter type, so a plain nullptr serves where a kernel takes an optional typed pointer.
+template <typename... K, typename... A>
+inline hipError_t launch(void (*kernel)(K...), dim3 grid, dim3 block, hipStream_t stream, A&&... args) {
+    static_assert(sizeof...(K) == sizeof...(A), "one argument per kernel parameter");
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<K>(args)...);
+    return hipGetLastError();
+}
+
+// The pass borders of a call or a handle: N events, all created by the first mark (so that none is created between two launches of a
+// timed sequence, where the wait for the host would count as device time) and destroyed with the clock.  Whoever owns a clock lets it
+// die only after the stream it recorded on has been waited for (a handle's release function; a call declares its clock before the
+// objects that synchronise the stream when they go).
+template <int N>
+struct PassClock {
+    hipEvent_t e[N] = {};
+    PassClock() = default;
+    PassClock(const PassClock&) = delete;
+    PassClock& operator=(const PassClock&) = delete;
+    ~PassClock() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t mark(int k, hipStream_t stream) {
+        for (hipEvent_t& x : e) {
+            const hipError_t rc = x ? hipSuccess : hipEventCreate(&x);
+            if (rc != hipSuccess) return rc;
+        }
+        return hipEventRecord(e[k], stream);
+    }
+    // the device time between two marks, once the stream is idle
+    hipError_t ms(int a, int b, float* t) const { return hipEventElapsedTime(t, e[a], e[b]); }
+};
+
+// The malloc'd host buffers of a call's result: released unless the call succeeds and keep()s them for its caller.
+class HostOut {
+    std::vector<void*> bufs;
+    bool kept = false;
+
+   public:
+    HostOut() = default;
+    HostOut(const HostOut&) = delete;
+    HostOut& operator=(const HostOut&) = delete;
+    ~HostOut() {
+        if (!kept)
+            for (void* p : bufs) std::free(p);
+    }
+    // nullptr: no memory
+    template <typename T>
+    T* take(size_t count) {
+        void* p = std::malloc(count * sizeof(T));
+        if (p) bufs.push_back(p);
+        return (T*)p;
+    }
+    void keep() { kept = true; }
 };
 
 inline void cam_to_dev(const mpmvs_camera& s, pm::CamDev& d) {

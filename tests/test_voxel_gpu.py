@@ -122,6 +122,28 @@ def test_small_counts(cloud, n):
     assert 1 <= len(got["xyz"]) <= n
 
 
+def test_pass_times(cloud):
+    """the six pass times of a call with normals and colours are device times, the total is their sum as the library forms it, and a
+    call that is answered on the host clears all seven"""
+    rng = np.random.default_rng(11)
+    n = 300
+    x = (2.0 + rng.random((n, 3))).astype(np.float32)
+    nr = rng.normal(size=(n, 3)).astype(np.float32)
+    col = rng.integers(0, 256, (n, 3), dtype=np.uint8)
+    check(cloud, x, 0.125, nr, col, "pass times")
+    total, passes = cloud.last_voxel_ms(passes=True)
+    names = ("insert", "first", "scan", "number", "accumulate", "finish")
+    assert tuple(passes) == names
+    p = [np.float32(passes[k]) for k in names]
+    print("voxel pass ms:", [float(v) for v in p], "total", total)
+    assert all(v > 0.0 for v in p), passes
+    assert np.float32(total) == ((p[0] + p[1]) + (p[2] + p[3])) + (p[4] + p[5])
+    got = cloud.voxel_downsample(np.full((5, 3), np.nan, np.float32), 0.125, want_map=True)
+    assert len(got["xyz"]) == 0 and (got["voxel_of"] == -1).all()
+    total, passes = cloud.last_voxel_ms(passes=True)
+    assert total == 0.0 and all(passes[k] == 0.0 for k in names), (total, passes)
+
+
 def by_cell(res):
     """the output records as a sorted table (position, normal and colour bits, count): order-free"""
     cols = [res["xyz"].view(np.uint32), res["normals"].view(np.uint32), res["colors"].astype(np.uint32), res["count"].astype(np.uint32)[:, None]]

@@ -1,7 +1,7 @@
 // mesh_simplify_check.cpp -- mpmvs_simplify_mesh replayed on the host through the headers' own __host__ __device__ code: the clustering
-// passes as mpmvs_mesh.hip chains them (cloud_insert_one, voxel_first_one, voxel_flag_one, voxel_number_one, voxel_accumulate_one,
+// passes as Clusters of csrc/pm_cluster_host.hpp chains them (cloud_insert_one, voxel_first_one, voxel_flag_one, voxel_number_one, voxel_accumulate_one,
 // voxel_finish_one) and the new bodies of csrc/pm_simplify.hpp (simp_quadric_one, simp_place_one, simp_classify_one, simp_insert_one,
-// simp_owner_one, simp_emit_one), with buffers of exactly the sizes mpmvs_mesh.hip gives them, against plain loops written out below
+// simp_owner_one, simp_emit_one), with buffers of exactly the sizes pm_cluster_host.hpp and mpmvs_mesh.hip give them, against plain loops written out below
 // (statement 4 of include/mpmvs.h: a std::map over the cells, sequential int64 sums, a Jacobi on arrays, a std::map over the keys).
 // Every pass is replayed thread by thread in a scrambled order, the blocks ascending and descending.  The insert pass is also replayed
 //   by steps    every alive triangle's probe is a state (simp_probe_begin); one step of one probe picked at random runs at a time

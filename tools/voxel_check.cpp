@@ -1,7 +1,7 @@
 // voxel_check.cpp -- the voxel-grid downsampling of csrc/pm_voxel.hpp replayed on the host, thread by thread in a scrambled order,
 // through the header's own __host__ __device__ code (the insert of pm_cloud.hpp, then first, flag, number, accumulate and finish
-// per thread; the scan is a plain loop here), in the launch order of mpmvs_cloud_voxel_downsample of mpmvs_cloud.hip and with buffers
-// of exactly their sizes, against the plain-loop statement of include/mpmvs.h written out below with std::map.
+// per thread; the scan is a plain loop here), in the launch order of Clusters of csrc/pm_cluster_host.hpp, which mpmvs_cloud_voxel_downsample
+// of mpmvs_cloud.hip runs, and with buffers of exactly their sizes, against the plain-loop statement of include/mpmvs.h written out below with std::map.
 // A host program, so that it runs under the sanitizers without a GPU:
 //   hipcc -O1 -g -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
 //         -Imp-mvs_amd/csrc -o build/voxel_check tools/voxel_check.cpp && build/voxel_check
