@@ -1086,6 +1086,72 @@ long long mpmvs_simplify_mesh(mpmvs_mesh* h, float cell, int placement /* 0 mean
                               int32_t** out_tri_src /* may be NULL */, long long counts[3] /* may be NULL */);
 int mpmvs_simplify_mesh_ms(const mpmvs_mesh* h, float ms[7]);
 
+/* 5. DISTANCE.  mpmvs_surface_distance: per point of a cloud handle the exact capped distance to the SURFACE of the mesh, not to its
+ *    vertices, and the triangle that attains it.  N is the cloud's point count; the queries are the cloud's own points and the results
+ *    are indexed by the cloud's point index.  Kernels and per-thread bodies: mp-mvs_amd/csrc/pm_surface.hpp on the grid of
+ *    pm_cloud.hpp; DESIGN.md section 26.  Bit for bit the plain loop below and independent of scheduling.  Arithmetic is fp64 unless
+ *    stated, no contraction; only + - * /, comparisons and one conversion to fp32, to nearest even.
+ *      A triangle t = (a, b, c) TAKES PART iff its three vertices have three finite coordinates each; a point q iff its three are.
+ *      r2 = radius * radius in fp32, as in mpmvs_cloud_nearest.  dot(u, v) = (u_x*v_x + u_y*v_y) + u_z*v_z.
+ *      ab = B - A, ac = C - A, ap = q - A, bp = q - B, cp = q - C, per component from the floats converted to double.
+ *      s1 = dot(ab, ap), s2 = dot(ac, ap), s3 = dot(ab, bp), s4 = dot(ac, bp), s5 = dot(ab, cp), s6 = dot(ac, cp).
+ *      vc = s1*s4 - s3*s2, vb = s5*s2 - s1*s6, va = s3*s6 - s5*s4.
+ *    The closest point X is given by the first of these rules that applies, each tested exactly as written (a comparison with a NaN
+ *    is false):
+ *      1. s1 <= 0 && s2 <= 0:                              X = A.
+ *      2. s3 >= 0 && s4 <= s3:                             X = B.
+ *      3. vc <= 0 && s1 >= 0 && s3 <= 0:                   v = s1 / (s1 - s3), X_k = A_k + v*ab_k.
+ *      4. s6 >= 0 && s5 <= s6:                             X = C.
+ *      5. vb <= 0 && s2 >= 0 && s6 <= 0:                   w = s2 / (s2 - s6), X_k = A_k + w*ac_k.
+ *      6. va <= 0 && (s4 - s3) >= 0 && (s5 - s6) >= 0:     w = (s4 - s3) / ((s4 - s3) + (s5 - s6)), X_k = B_k + w*(C_k - B_k).
+ *      7. otherwise:                                       den = (va + vb) + vc, v = vb / den, w = vc / den,
+ *                                                          X_k = (A_k + v*ab_k) + w*ac_k.
+ *    e = q - X, dd = (e_x*e_x + e_y*e_y) + e_z*e_z, D = (float)dd.  t is a CANDIDATE of q iff D <= r2 (false for a NaN).  A degenerate
+ *    triangle follows the sequence literally: what it yields is deterministic, and where it yields a NaN it is no candidate.
+ *      out_d2[i]  = the smallest candidate D;
+ *      out_tri[i] = the smallest triangle index among the candidates that attain it (duplicate triangles, the order of the triangles
+ *                   on the device and the order of the points never show);
+ *      with no candidate, or for a point that takes no part: out_d2 = +inf, out_tri = -1.
+ *      counts = {points with a candidate, points that take part}.
+ *    -2, with every output untouched: a NULL handle of either kind, a NULL out_d2 with N > 0, a radius that is not finite or <= 0, two
+ *    handles on different devices.  -3: what the cloud's grid at this radius refuses (more than 2^21 cells along an axis, worded as
+ *    mpmvs_cloud_nearest words it).  -100: HIP failure.  All but -100 are found before the device is touched.  N == 0 touches nothing;
+ *    with m == 0, no triangle or no point taking part the call answers on the host (+inf, -1, the counts) and launches nothing.
+ *    Neither handle is changed, except that the cloud may gain a cached grid for this radius, under the rules of its grid cache; the
+ *    time of that build stays with the cloud's own report (mpmvs_cloud_kernel_ms).
+ *    mpmvs_surface_distance_ms: device ms (HIP events) of the last call on this mesh handle, the total returned and, in pass_ms, the
+ *    init, scatter and finish passes; 0 for a call that launched nothing.
+ *
+ * 6. SAMPLE.  mpmvs_surface_sample: deterministic samples of the surface at a given spacing, so that a mesh can stand where a point
+ *    cloud is asked for.  Returns the number K of samples; the buffers are released with mpmvs_free; with K == 0 all are NULL, and
+ *    nothing is launched for a mesh without a participating triangle.  Bit for bit the plain loop below.  Arithmetic is fp64 unless
+ *    stated, no contraction; only + - * / sqrt ceil, integer arithmetic and one conversion to fp32.
+ *      h_s = (double)spacing.  A triangle with a non-finite vertex yields no sample.  For any other triangle: l2 = the largest of its
+ *      three squared edge lengths, each (dx*dx + dy*dy) + dz*dz; Lm = sqrt(l2); ratio = Lm / h_s; s = max(1, (long long)ceil(ratio));
+ *      !(ratio <= 4096) is a refusal.  (A triangle of size 0 has s = 1 and yields its one vertex position.)
+ *      The triangle yields s*s samples, the centroids of the sub-triangles of its regular s-subdivision, enumerated by k = 0 .. s*s-1:
+ *      u = s*s - 1 - k; g = the largest integer with g*g <= u; i = s - 1 - g; l = k - (2*s*i - i*i); j = l >> 1;
+ *      (na, nb) = (3i + 1, 3j + 1) for even l and (3i + 2, 3j + 2) for odd l; nc = 3s - na - nb (always >= 1).
+ *      x_k = (float)(((na*A_k + nb*B_k) + nc*C_k) / (double)(3s)), the integers converted to double exactly.
+ *      Samples are output triangle by triangle in index order, k ascending; out_tri_of[sample] = t.
+ *      out_rgb = (2*(na*Ca + nb*Cb + nc*Cc) + 3s) / (2*3s) in integer division, per channel.
+ *      out_normals = nh = C / L of statement 4B converted to float, the same face normal for every sample of the triangle; (0, 0, 0)
+ *      where !(L > 0) or L is not finite.
+ *    Every sub-triangle's longest edge is at most `spacing`, so every point of a participating triangle lies within 2/3 * spacing of
+ *    one of its samples (a centroid is two thirds of a median from a vertex, and a median is no longer than the longest edge).
+ *    -2, with nothing allocated or written: a NULL handle, a spacing that is not finite or <= 0, a NULL out_xyz or out_tri_of, out_rgb
+ *    NULL for a mesh with colour or given for one without.  -3: a triangle with !(ratio <= 4096) (the text names the first such
+ *    triangle), or more than 2^30 samples in all (the text names the total).  The mesh handle drops its host copy at the first upload,
+ *    so these two -3 refusals are found after the count pass on the device: the only refusals of the family that may touch the
+ *    device first.  -100: HIP failure.  out_normals may be NULL.
+ *    mpmvs_surface_sample_ms: device ms of the last call, the total returned and, in pass_ms, count, scan and emit. */
+int mpmvs_surface_distance(mpmvs_mesh* surface, mpmvs_cloud* points, float radius, float* out_d2 /* N */, int32_t* out_tri /* N, may be NULL */,
+                           long long counts[2] /* may be NULL */);
+float mpmvs_surface_distance_ms(const mpmvs_mesh* surface, float pass_ms[3] /* may be NULL */);
+long long mpmvs_surface_sample(mpmvs_mesh* h, float spacing, float** out_xyz, int32_t** out_tri_of,
+                               unsigned char** out_rgb /* NULL iff the mesh has no colour */, float** out_normals /* may be NULL */);
+float mpmvs_surface_sample_ms(const mpmvs_mesh* h, float pass_ms[3] /* may be NULL */);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

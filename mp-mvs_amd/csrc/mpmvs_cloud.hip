@@ -29,6 +29,8 @@
 #include "pm_align_host.hpp"
 #include "pm_render.hpp"
 #include "pm_observe.hpp"
+#include "pm_mesh_host.hpp"
+#include "pm_surface.hpp"
 
 using namespace pm;
 
@@ -380,6 +382,94 @@ int mpmvs_cloud_stats(const mpmvs_cloud* c, long long stats[4]) {
 }
 
 float mpmvs_cloud_kernel_ms(const mpmvs_cloud* c, float* build_ms) { return c ? cloud_op_ms(c->query, build_ms) : 0.0f; }
+
+// ---------------------------------------------------------------------------
+// exact capped distance from a cloud's points to a mesh's surface (pm_surface.hpp; statement 5 of the mesh
+// section of include/mpmvs.h).  It lives here because it walks the cloud's grid; of the mesh it reads the resident vertices and
+// triangles (pm_mesh_host.hpp).  The launches go to the cloud's stream: the mesh's buffers are only read, and every call on either
+// handle waits for its stream before it returns.
+// ---------------------------------------------------------------------------
+// MPMVS_SURFACE_LARGE=<cells>: the size of a triangle's cell range above which a block walks it; read at every call (tests force
+// both paths through it)
+static int surface_large_threshold() {
+    const char* e = std::getenv("MPMVS_SURFACE_LARGE");
+    if (!e || !*e) return kSurfaceLargeDefault;
+    const long v = std::strtol(e, nullptr, 10);
+    return v < 0 ? 0 : (v > (1l << 30) ? (1 << 30) : (int)v);
+}
+
+int mpmvs_surface_distance(mpmvs_mesh* surface, mpmvs_cloud* points, float radius, float* out_d2, int32_t* out_tri, long long counts[2]) {
+    mpmvs_mesh* const h = surface;
+    mpmvs_cloud* const c = points;
+    if (!h || !c) return call_fail(-2, "surface distance: a NULL handle");
+    if (c->n > 0 && !out_d2) return call_fail(-2, "surface distance: out_d2 missing");
+    if (!cloud_radius_ok(radius)) return call_fail(-2, "surface distance: the radius must be finite and positive");
+    if (h->device != c->device) return call_fail(-2, "surface distance: the mesh is on device " + std::to_string(h->device) + ", the cloud on device " + std::to_string(c->device));
+    const int span = cloud_span_check(c, radius, "surface distance: the points");
+    if (span) return span;
+    h->dist_ms[0] = h->dist_ms[1] = h->dist_ms[2] = 0.0f;
+    if (c->n == 0) {
+        if (counts) counts[0] = counts[1] = 0;
+        return 0;
+    }
+    if (h->m_fin == 0 || c->n_fin == 0) {   // no triangle or no point takes part: answered here
+        for (long long i = 0; i < c->n; ++i) {
+            out_d2[i] = INFINITY;
+            if (out_tri) out_tri[i] = -1;
+        }
+        if (counts) counts[0] = 0, counts[1] = c->n_fin;
+        return 0;
+    }
+    const int rc = mesh_ready(h);
+    if (rc) return rc;
+    SurfaceGrid S;
+    const int rc2 = cloud_open(c, radius, nullptr, S.g);   // the build time stays with the cloud's own report
+    if (rc2) return rc2;
+    S.gmax = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        S.hi[a] = cloud_cell(c->mx[a], S.g.mn[a], S.g.edge);
+        S.hi[a] = S.hi[a] < 0 ? 0 : (S.hi[a] > kCloudAxisCells - 1 ? kCloudAxisCells - 1 : S.hi[a]);   // as the insert clamps
+        S.gmax = std::max(S.gmax, std::max(std::fabs((double)c->mn[a]), std::fabs((double)c->mx[a]) + S.g.edge));
+    }
+    S.reach = ((double)radius + 0.8660254037844387 * S.g.edge) * (1.0 + 0x1p-8);
+    S.large = surface_large_threshold();
+    const hipStream_t st = c->stream;
+    const size_t n = (size_t)c->n, m = (size_t)h->m;
+    PassClock<4> clock;   // before the buffers: they wait for the stream when they go
+    Scratch d_keys(st), d_list(st), d_cnt(st), d_d2(st), d_tri(st);
+    CALLCHK(d_keys.alloc(n * 8));
+    CALLCHK(d_list.alloc(m * 4));
+    CALLCHK(d_cnt.alloc(16));   // the length of the list, the points with a candidate
+    CALLCHK(d_d2.alloc(n * 4));
+    if (out_tri) CALLCHK(d_tri.alloc(n * 4));
+    unsigned long long* const n_list = d_cnt.as<unsigned long long>();
+    CALLCHK(hipMemsetAsync(d_cnt.p, 0, 16, st));
+    const dim3 blk(256), gn((unsigned)((n + 255) / 256)), gm((unsigned)((m + 255) / 256));
+    CALLCHK(clock.mark(0, st));
+    CALLCHK(launch(k_surface_init, gn, blk, st, (int)c->n, d_keys.as<unsigned long long>()));
+    CALLCHK(clock.mark(1, st));
+    CALLCHK(launch(k_surface_scatter, gm, blk, st, (int)h->m, h->d_xyz, h->d_tri, S, d_keys.as<unsigned long long>(), d_list.as<int32_t>(), n_list));
+    // the listed triangles: as many blocks as the device keeps busy, striding over a list whose length they read themselves
+    CALLCHK(launch(k_surface_large, dim3((unsigned)std::min<size_t>(m, 2048)), blk, st, h->d_xyz, h->d_tri, S, d_keys.as<unsigned long long>(), d_list.as<int32_t>(),
+                   n_list));
+    CALLCHK(clock.mark(2, st));
+    CALLCHK(launch(k_surface_finish, gn, blk, st, (int)c->n, d_keys.as<unsigned long long>(), d_d2.as<float>(), d_tri.as<int32_t>(), n_list + 1));
+    CALLCHK(clock.mark(3, st));
+    unsigned long long cnt[2] = {0, 0};
+    CALLCHK(hipMemcpyAsync(out_d2, d_d2.p, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_tri) CALLCHK(hipMemcpyAsync(out_tri, d_tri.p, n * 4, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; ++k) CALLCHK(clock.ms(k, k + 1, &h->dist_ms[k]));
+    if (counts) counts[0] = (long long)cnt[1], counts[1] = c->n_fin;
+    return 0;
+}
+
+float mpmvs_surface_distance_ms(const mpmvs_mesh* surface, float pass_ms[3]) {
+    if (!surface) return 0.0f;
+    if (pass_ms) std::memcpy(pass_ms, surface->dist_ms, sizeof surface->dist_ms);
+    return (surface->dist_ms[0] + surface->dist_ms[1]) + surface->dist_ms[2];
+}
 
 // ---------------------------------------------------------------------------
 // voxel-grid downsampling of a cloud (pm_voxel.hpp).  A stateless call: host buffers in and out, a stream

@@ -22,6 +22,8 @@
 #include "pm_scan_host.hpp"
 #include "pm_cluster_host.hpp"
 #include "pm_mesh.hpp"
+#include "pm_mesh_host.hpp"
+#include "pm_surface.hpp"
 #include "pm_simplify.hpp"
 #include "pm_tsdf.hpp"
 #include "pm_tsdf_sparse.hpp"
@@ -596,26 +598,6 @@ int mpmvs_tsdf_sparse_stats(const mpmvs_tsdf* h, long long info[4], float ms[2])
 // ---- an indexed triangle mesh: components, vertex normals, select (statements 1 to 3 of include/mpmvs.h) ----
 constexpr long long kMeshMax = 1ll << 30;
 
-struct mpmvs_mesh {
-    int device = 0;
-    long long n = 0, m = 0;
-    bool with_color = false, ready = false;
-    double scale = 0.0;                  // of the normals (mesh_scale); 0: every normal is (0, 0, 0)
-    std::vector<float> xyz;              // the copies of create, until the first operation on the device has uploaded them
-    std::vector<unsigned char> rgb;
-    std::vector<int32_t> tri;
-    float* d_xyz = nullptr;
-    unsigned char* d_rgb = nullptr;
-    int32_t* d_tri = nullptr;
-    hipStream_t stream = nullptr;
-    PassClock<5> clock;
-    float ms[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    // for mpmvs_simplify_mesh: the finite vertices and their bounding box, taken at create while the host copy exists
-    long long n_fin = 0;
-    float mn[3] = {0.0f, 0.0f, 0.0f}, mx[3] = {0.0f, 0.0f, 0.0f};
-    float simp_ms[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-};
-
 int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned char* rgb, long long m, const int32_t* tri, mpmvs_mesh** out) {
     if (!out) return call_fail(-2, "mesh create: bad argument");
     if (n < 0 || m < 0) return call_fail(-2, "mesh create: a negative count");
@@ -635,6 +617,10 @@ int mpmvs_mesh_create(int device, long long n, const float* xyz, const unsigned 
     if (m > 0) h->tri.assign(tri, tri + 3 * m);
     h->scale = mesh_scale(h->xyz.data(), n, m);
     h->n_fin = cloud_bbox(n, h->xyz.data(), h->mn, h->mx);
+    for (long long t = 0; t < m; ++t) {   // the triangles that take part in mpmvs_surface_distance
+        double P[9];
+        if (surface_corners(h->xyz.data(), h->tri.data(), (size_t)t, P)) ++h->m_fin;
+    }
     *out = h;
     return 0;
 }
@@ -651,25 +637,6 @@ void mpmvs_mesh_destroy(mpmvs_mesh* h) {
     delete h;   // the clock goes here: the stream has been waited for
 }
 
-// the first operation that needs the device: the stream and the mesh itself
-static int mesh_ready(mpmvs_mesh* h) {
-    CALLCHK(enter_device(h->device));
-    if (h->ready) return 0;
-    if (!h->stream) CALLCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    const size_t n = (size_t)h->n, m = (size_t)h->m;
-    if (!h->d_xyz) CALLCHK(pool_malloc(&h->d_xyz, n * 12));
-    if (h->with_color && !h->d_rgb) CALLCHK(pool_malloc(&h->d_rgb, n * 3));
-    if (m > 0 && !h->d_tri) CALLCHK(pool_malloc(&h->d_tri, m * 12));
-    CALLCHK(hipMemcpyAsync(h->d_xyz, h->xyz.data(), n * 12, hipMemcpyHostToDevice, h->stream));
-    if (h->with_color) CALLCHK(hipMemcpyAsync(h->d_rgb, h->rgb.data(), n * 3, hipMemcpyHostToDevice, h->stream));
-    if (m > 0) CALLCHK(hipMemcpyAsync(h->d_tri, h->tri.data(), m * 12, hipMemcpyHostToDevice, h->stream));
-    CALLCHK(hipStreamSynchronize(h->stream));
-    std::vector<float>().swap(h->xyz);
-    std::vector<unsigned char>().swap(h->rgb);
-    std::vector<int32_t>().swap(h->tri);
-    h->ready = true;
-    return 0;
-}
 static dim3 mesh_blocks(size_t count) { return dim3((unsigned)((count + 255) / 256)); }
 
 int mpmvs_mesh_components(mpmvs_mesh* h, int32_t* out_label, int32_t* out_verts, int32_t* out_tris, long long counts[4]) {
@@ -1020,6 +987,94 @@ int mpmvs_simplify_mesh_ms(const mpmvs_mesh* h, float ms[7]) {
     if (!h || !ms) return call_fail(-2, "mesh simplify_ms: bad argument");
     std::memcpy(ms, h->simp_ms, sizeof h->simp_ms);
     return 0;
+}
+
+// ---- sampling the surface (statement 6 of include/mpmvs.h; pm_surface.hpp) ------------------------------------
+// the device half of mpmvs_surface_sample: m > 0.  The host copy of the mesh is gone after the first upload, so the two -3 refusals
+// are found here, after the count pass.
+static long long surface_sample_device(mpmvs_mesh* h, float spacing, bool want_normals, float** xyz, int32_t** tri_of, unsigned char** rgb, float** normals) {
+    const hipStream_t st = h->stream;
+    const size_t m = (size_t)h->m;
+    const int mi = (int)h->m;
+    const double h_s = (double)spacing;
+    const dim3 blk(256);
+    PassClock<4> clock;   // before the buffers: they wait for the stream when they go
+    Scratch d_cnt(st), d_off(st), d_tsum(st), d_tot(st);
+    CALLCHK(d_cnt.alloc(m * 4));
+    CALLCHK(d_off.alloc(m * 4));
+    CALLCHK(d_tsum.alloc((m + kScanBlock - 1) / kScanBlock * 4));
+    CALLCHK(d_tot.alloc(16));   // the total (64 bits), the first triangle beyond the limit
+    unsigned long long tot[2] = {0, ~0ull};
+    CALLCHK(hipMemcpyAsync(d_tot.p, tot, 16, hipMemcpyHostToDevice, st));
+    CALLCHK(clock.mark(0, st));
+    CALLCHK(launch(k_surface_count, mesh_blocks(m), blk, st, mi, h->d_xyz, h->d_tri, h_s, d_cnt.as<int>(), d_tot.as<unsigned long long>(),
+                   (uint32_t*)(d_tot.as<unsigned long long>() + 1)));
+    CALLCHK(clock.mark(1, st));
+    CALLCHK(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    CALLCHK(clock.ms(0, 1, &h->sample_ms[0]));
+    const uint32_t first_bad = (uint32_t)(tot[1] & 0xffffffffull);
+    if (first_bad != 0xffffffffu)
+        return call_fail(-3, "surface sample: the longest edge of triangle " + std::to_string(first_bad) + " is more than 4096 times the spacing");
+    if (tot[0] > (unsigned long long)kSurfaceMaxSamples) return call_fail(-3, "surface sample: " + std::to_string(tot[0]) + " samples, more than 2^30");
+    const size_t K = (size_t)tot[0];
+    if (K == 0) return 0;
+    Scratch d_xyz(st), d_of(st), d_rgb(st), d_nrm(st);
+    CALLCHK(d_xyz.alloc(K * 12));
+    CALLCHK(d_of.alloc(K * 4));
+    if (h->with_color) CALLCHK(d_rgb.alloc(K * 3));
+    if (want_normals) CALLCHK(d_nrm.alloc(K * 12));
+    CALLCHK(clock.mark(1, st));
+    CALLCHK(scan_offsets(st, d_cnt.as<int>(), mi, d_off.as<int>(), d_tsum.as<int>(), nullptr, true));
+    CALLCHK(clock.mark(2, st));
+    CALLCHK(launch(k_surface_emit, mesh_blocks(K), blk, st, (int)K, h->d_xyz, h->with_color ? h->d_rgb : nullptr, h->d_tri, mi, h_s, d_off.as<int>(),
+                   d_xyz.as<float>(), d_of.as<int32_t>(), d_rgb.as<unsigned char>(), d_nrm.as<float>()));
+    CALLCHK(clock.mark(3, st));
+    HostOut out;
+    float* hx = out.take<float>(K * 3);
+    int32_t* ho = out.take<int32_t>(K);
+    unsigned char* hc = h->with_color ? out.take<unsigned char>(K * 3) : nullptr;
+    float* hn = want_normals ? out.take<float>(K * 3) : nullptr;
+    if (!hx || !ho || (h->with_color && !hc) || (want_normals && !hn)) return call_fail(-100, "surface sample: out of host memory");
+    CALLCHK(hipMemcpyAsync(hx, d_xyz.p, K * 12, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipMemcpyAsync(ho, d_of.p, K * 4, hipMemcpyDeviceToHost, st));
+    if (hc) CALLCHK(hipMemcpyAsync(hc, d_rgb.p, K * 3, hipMemcpyDeviceToHost, st));
+    if (hn) CALLCHK(hipMemcpyAsync(hn, d_nrm.p, K * 12, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    CALLCHK(clock.ms(1, 2, &h->sample_ms[1]));
+    CALLCHK(clock.ms(2, 3, &h->sample_ms[2]));
+    out.keep();
+    *xyz = hx, *tri_of = ho, *rgb = hc, *normals = hn;
+    return (long long)K;
+}
+
+long long mpmvs_surface_sample(mpmvs_mesh* h, float spacing, float** out_xyz, int32_t** out_tri_of, unsigned char** out_rgb, float** out_normals) {
+    if (!h || !out_xyz || !out_tri_of) return call_fail(-2, "surface sample: bad argument");
+    if (!std::isfinite(spacing) || !(spacing > 0.0f)) return call_fail(-2, "surface sample: the spacing must be finite and positive");
+    if (h->with_color && !out_rgb) return call_fail(-2, "surface sample: a mesh with colour needs out_rgb");
+    if (!h->with_color && out_rgb) return call_fail(-2, "surface sample: the mesh has no colour");
+    float *xyz = nullptr, *nrm = nullptr;
+    int32_t* of = nullptr;
+    unsigned char* rgb = nullptr;
+    long long K = 0;
+    h->sample_ms[0] = h->sample_ms[1] = h->sample_ms[2] = 0.0f;
+    if (h->m_fin > 0) {   // else no triangle yields a sample: nothing is launched
+        const int rc = mesh_ready(h);
+        if (rc) return rc;
+        K = surface_sample_device(h, spacing, out_normals != nullptr, &xyz, &of, &rgb, &nrm);
+        if (K < 0) return K;
+    }
+    *out_xyz = xyz;
+    *out_tri_of = of;
+    if (out_rgb) *out_rgb = rgb;
+    if (out_normals) *out_normals = nrm;
+    return K;
+}
+
+float mpmvs_surface_sample_ms(const mpmvs_mesh* h, float pass_ms[3]) {
+    if (!h) return 0.0f;
+    if (pass_ms) std::memcpy(pass_ms, h->sample_ms, sizeof h->sample_ms);
+    return (h->sample_ms[0] + h->sample_ms[1]) + h->sample_ms[2];
 }
 
 }  // extern "C"

@@ -2,7 +2,9 @@
 on the Kuhn split of its cells (mpmvs_tsdf_*, csrc/pm_tsdf.hpp, csrc/pm_tsdf_sparse.hpp, csrc/mpmvs_mesh.hip; contract:
 include/mpmvs.h, DESIGN.md sections 22 and 23); an indexed triangle mesh on the device (Mesh: mpmvs_mesh_*, csrc/pm_mesh.hpp;
 DESIGN.md section 24) with its connected components, area-weighted vertex normals and compaction, remove_small_components and
-vertex_normals on top of it; and the PLY files of a mesh.  The device calls are bit for bit their plain-loop
+vertex_normals on top of it; the mesh as a surface (mpmvs_surface_*, csrc/pm_surface.hpp): the exact capped
+distance from a cloud's points to it and its deterministic samples, with surface_distances, evaluate_mesh and compare on top of
+them; and the PLY files of a mesh.  The device calls are bit for bit their plain-loop
 statements (tests/tsdf_common.py and tests/tsdf_sparse_common.py have them in numpy).  The work runs on the GPU; there is no CPU
 path."""
 import ctypes as C
@@ -10,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi, engine
+from . import cloud as _cloud
 
 
 def _raise(f, what, rc):
@@ -391,6 +394,56 @@ class Mesh:
                     lib.mpmvs_free(p)
         return out
 
+    def distance(self, cloud, radius, want_tri=True):
+        """mpmvs_surface_distance -> (d2 float32 [N], tri int32 [N]), or d2 alone with want_tri=False: per point of `cloud` (a
+        cloud.Cloud on the same device) the squared distance to the nearest point of this mesh's surface within `radius` and the
+        triangle that holds it; inf / -1 where there is none.  self.last_counts = {"with_candidate", "taking_part"} of the call."""
+        d2 = np.empty(cloud.n, np.float32)
+        tri = np.empty(cloud.n, np.int32) if want_tri else None
+        counts = (C.c_longlong * 2)()
+        rc = self._f["surface_distance"](self._h, cloud._h, float(radius), d2.ctypes.data if cloud.n else None, tri.ctypes.data if want_tri and cloud.n else None,
+                                         counts)
+        if rc != 0:
+            _raise(self._f, "surface_distance", rc)
+        self.last_counts = {"with_candidate": int(counts[0]), "taking_part": int(counts[1])}
+        return (d2, tri) if want_tri else d2
+
+    def distance_ms(self):
+        """device ms of the last distance call: {"total", "init", "scatter", "finish"}; the grid build stays with Cloud.kernel_ms()"""
+        ms = (C.c_float * 3)()
+        total = self._f["surface_distance_ms"](self._h, ms)
+        return {"total": float(total), "init": float(ms[0]), "scatter": float(ms[1]), "finish": float(ms[2])}
+
+    def sample(self, spacing, want_normals=False):
+        """mpmvs_surface_sample -> {"xyz" float32 [K, 3], "tri_of" int32 [K], "rgb" uint8 [K, 3] or None, "normals" float32 [K, 3] or
+        None}: the centroids of the regular subdivision of every triangle whose longest sub-edge is at most `spacing`, so that every
+        point of the surface lies within 2/3 * spacing of a sample; triangle by triangle, in a fixed order."""
+        lib, _ = engine.load()
+        lib.mpmvs_free.argtypes = [C.c_void_p]
+        lib.mpmvs_free.restype = None
+        px, po, pc, pn = (C.c_void_p() for _ in range(4))
+        k = self._f["surface_sample"](self._h, float(spacing), C.byref(px), C.byref(po), C.byref(pc) if self.color else None, C.byref(pn) if want_normals else None)
+        if k < 0:
+            _raise(self._f, "surface_sample", k)
+        try:
+            def take(p, ctype, cols, dtype):
+                if not k:
+                    return np.zeros((0, cols) if cols > 1 else (0,), dtype)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), (k, cols) if cols > 1 else (k,)).copy()
+            out = {"xyz": take(px, C.c_float, 3, np.float32), "tri_of": take(po, C.c_int32, 1, np.int32),
+                   "rgb": take(pc, C.c_uint8, 3, np.uint8) if self.color else None, "normals": take(pn, C.c_float, 3, np.float32) if want_normals else None}
+        finally:
+            for p in (px, po, pc, pn):
+                if p.value:
+                    lib.mpmvs_free(p)
+        return out
+
+    def sample_ms(self):
+        """device ms of the last sample call: {"total", "count", "scan", "emit"}"""
+        ms = (C.c_float * 3)()
+        total = self._f["surface_sample_ms"](self._h, ms)
+        return {"total": float(total), "count": float(ms[0]), "scan": float(ms[1]), "emit": float(ms[2])}
+
     def simplify_ms(self):
         """device ms of the last simplify call, pass by pass"""
         ms = (C.c_float * 7)()
@@ -483,6 +536,111 @@ def simplify(m, cell, placement="quadric", drop_unreferenced=True, normals=False
                 out["normals"], out["normals_defined"] = h.normals()
                 ms.update({k: v for k, v in h.pass_ms().items() if k.startswith("normals_")})
     out["device_ms"] = ms
+    return out
+
+
+def surface_distances(points, mesh_handle, tolerances, device=0, on_level=None):
+    """float32 [n]: per point the exact distance to the surface of `mesh_handle` (a Mesh) where that is within max(tolerances), else
+    inf: cloud.distances with a mesh as the target.  The same cascade: tolerances ascending, one Mesh.distance call per tolerance
+    with radius = tolerance, and only the points still unresolved go on.  A point with a candidate at one level is final, because a
+    nearer triangle would be within that radius too.  The scatter of a triangle costs with the points in the cells around it, which
+    grow with the cube of the radius, so a coarse level should see few points; but a cloud handle of its own per level costs more
+    than the level itself while most points are still in play (the measurement is in DESIGN.md section 26.5).  So the resident cloud
+    is kept from level to level and replaced by one of the unresolved points only once those are fewer than half of it.
+    on_level(tolerance, n_points, mesh_handle), if given, is called after every level."""
+    q = _cloud._xyz(points)
+    out = np.full(len(q), np.inf, np.float32)
+    left = np.arange(len(q))
+    held, sub = None, None   # the points the resident cloud holds, and the cloud
+    try:
+        for t in sorted(set(float(t) for t in tolerances)):
+            if len(left) == 0:
+                break
+            if sub is None or 2 * len(left) < len(held):
+                if sub is not None:
+                    sub.close()
+                held, sub = left, _cloud.Cloud(q[left], device)
+            d2 = mesh_handle.distance(sub, t, want_tri=False)
+            if on_level:
+                on_level(t, len(held), mesh_handle)
+            d2 = d2[np.searchsorted(held, left)]   # held ascends and holds every unresolved point
+            hit = np.isfinite(d2)
+            out[left[hit]] = np.sqrt(d2[hit])
+            left = left[~hit]
+    finally:
+        if sub is not None:
+            sub.close()
+    return out
+
+
+def evaluate_mesh(m, gt_xyz, tolerances, spacing=None, voxel=None, device=0, timings=None):
+    """Accuracy, completeness and F1 of a mesh dict {"xyz", "tri"} against a ground-truth cloud: the dict of cloud.score.
+    Accuracy: the samples of the mesh (Mesh.sample at `spacing`; resampled with cloud.voxel_downsample first when `voxel` is given)
+    against the scan, through Cloud.nearest (cloud.distances).  Completeness: the scan's points against the SURFACE of the mesh
+    (surface_distances), not against its vertices or samples.  Points of the scan with a non-finite coordinate are dropped and
+    counted.  spacing defaults to the smallest tolerance, so that no point of the surface is farther than two thirds of it from a
+    sample: an untuned starting value.  The result also holds "spacing", "n_samples" and, with voxel, "voxel".
+    timings (a dict, optional) receives "sample_s", "accuracy_s", "completeness_s" (wall) and "device_ms" per stage."""
+    import time
+    tol = [float(t) for t in tolerances]
+    if not tol or not all(np.isfinite(t) and t > 0 for t in tol):
+        raise ValueError("tolerances must be finite and positive")
+    spacing = min(tol) if spacing is None else float(spacing)
+    if not (np.isfinite(spacing) and spacing > 0):
+        raise ValueError("spacing must be finite and positive")
+    if voxel is not None and not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel must be finite and positive")
+    gt, drop_g = _cloud.drop_nonfinite(gt_xyz)
+    ms = {}
+    with Mesh(m["xyz"], m["tri"], None, device=device) as h:
+        t0 = time.perf_counter()
+        smp = h.sample(spacing)["xyz"]
+        ms["sample"] = h.sample_ms()["total"]
+        n_samples = len(smp)
+        if voxel is not None:
+            smp = _cloud.voxel_downsample(smp, voxel, device=device)["xyz"]
+        t1 = time.perf_counter()
+        with _cloud.Cloud(gt, device) as c_gt:
+            d_rec = _cloud.distances(smp, c_gt, tol)
+        t2 = time.perf_counter()
+        ms["distance"] = 0.0
+
+        def on_level(t, n, mh):
+            ms["distance"] += mh.distance_ms()["total"]
+
+        d_gt = surface_distances(gt, h, tol, device=device, on_level=on_level)
+        t3 = time.perf_counter()
+    res = _cloud.score(d_rec, d_gt, tol, (0, drop_g))
+    res.update(spacing=spacing, n_samples=n_samples)
+    if voxel is not None:
+        res["voxel"] = float(voxel)
+    if timings is not None:
+        timings.update(sample_s=t1 - t0, accuracy_s=t2 - t1, completeness_s=t3 - t2, device_ms=ms)
+    return res
+
+
+def _direction(d2):
+    """the sums of one direction of compare() from the squared distances of Mesh.distance, on the host in fp64"""
+    d2 = np.asarray(d2, np.float64)
+    within = np.isfinite(d2)
+    d = np.sqrt(d2[within])
+    return {"n": int(d2.size), "beyond": int((~within).sum()), "max": float(d.max()) if d.size else None, "mean": float(d.mean()) if d.size else None,
+            "rms": float(np.sqrt((d * d).mean())) if d.size else None}
+
+
+def compare(m_a, m_b, spacing, radius, device=0):
+    """How far two mesh dicts are apart, as surfaces: {"a_to_b", "b_to_a", "hausdorff", "spacing", "radius"}.  Per direction, over the
+    samples of one mesh (Mesh.sample at `spacing`) against the surface of the other (Mesh.distance at `radius`): "n" samples, "beyond"
+    (no point of the other surface within the radius), and "max", "mean" and "rms" of the distances within it (None when there is
+    none).  "hausdorff" is the larger of the two maxima: the Hausdorff distance of the sample sets to the surfaces, capped at the
+    radius -- a direction with samples beyond it says that the true value is larger.  The sums are taken on the host in fp64."""
+    out = {"spacing": float(spacing), "radius": float(radius)}
+    with Mesh(m_a["xyz"], m_a["tri"], None, device=device) as ha, Mesh(m_b["xyz"], m_b["tri"], None, device=device) as hb:
+        for name, src, dst in (("a_to_b", ha, hb), ("b_to_a", hb, ha)):
+            with _cloud.Cloud(src.sample(spacing)["xyz"], device) as c:
+                out[name] = _direction(dst.distance(c, radius, want_tri=False))
+    tops = [out[k]["max"] for k in ("a_to_b", "b_to_a") if out[k]["max"] is not None]
+    out["hausdorff"] = max(tops) if tops else None
     return out
 
 
