@@ -1152,6 +1152,44 @@ long long mpmvs_surface_sample(mpmvs_mesh* h, float spacing, float** out_xyz, in
                                unsigned char** out_rgb /* NULL iff the mesh has no colour */, float** out_normals /* may be NULL */);
 float mpmvs_surface_sample_ms(const mpmvs_mesh* h, float pass_ms[3] /* may be NULL */);
 
+/* 7. RENDER.  mpmvs_surface_render_depth: the mesh rasterised into pinhole cameras: per pixel the depth of the nearest surface along
+ *    the pixel's ray and the triangle it shows.  No parameter: a mesh has no gaps, so the splat and occlusion heuristics of
+ *    mpmvs_cloud_render_depth have no counterpart.  Kernels and per-thread bodies: mp-mvs_amd/csrc/pm_raster.hpp; DESIGN.md section 27.
+ *    Bit for bit the plain loop below, whatever the order of triangles, views and threads.  Arithmetic is fp64, one operation per step
+ *    in the order written, no contraction; camera and vertex floats are converted to double first.  Pixel centres are at integers.
+ *    depth_min / depth_max and C of the cameras are not read.
+ *    For view v with K, R, t (row-major), W x H, and triangle i = (a, b, c), per vertex p:
+ *      X_j = ((R[3j]*p0 + R[3j+1]*p1) + R[3j+2]*p2) + t[j];   q_j = (K[3j]*X0 + K[3j+1]*X1) + K[3j+2]*X2;   q = (q.x, q.y, q.z), q.z
+ *      the project's depth.  There is no inverse of K and no clipping anywhere.
+ *      The triangle TAKES PART in the view iff all nine q components are finite and max(qa.z, qb.z, qc.z) > 0: one behind the camera
+ *      plane is skipped by rule, one that crosses the plane is rendered unclipped.
+ *      nbc = qb x qc, nca = qc x qa, nab = qa x qb with (u x v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x): two products
+ *      and one difference each.  det = (qa.x*nbc.x + qa.y*nbc.y) + qa.z*nbc.z.
+ *      Per pixel (x, y): E0 = (x*nbc.x + y*nbc.y) + nbc.z, E1 and E2 alike from nca and nab; S = (E0 + E1) + E2.
+ *      The pixel is a CANDIDATE iff (E0 >= 0 && E1 >= 0 && E2 >= 0, or E0 <= 0 && E1 <= 0 && E2 <= 0) and S != 0.  Both windings render;
+ *      zeros are inclusive, so a pixel centre on a shared edge belongs to both triangles.  An edge's function depends on its two
+ *      vertices only and swapping them negates every bit of it, so two triangles that share an edge leave no pixel between them.
+ *      z = det / S; if z < zlo then z = zlo; if z > zhi then z = zhi, zlo and zhi the smallest and largest of the three q.z (a
+ *      comparison with a NaN is false).  zf = (float)z.  The pixel is COVERED by the triangle iff zf is finite and zf > 0.
+ *      key = (bits(zf) << 32) | i.  Per pixel the minimum key over the covering triangles: the nearest depth, and among equal depths
+ *      the smallest triangle index.  out_depth[v][y*W + x] = zf of the minimum, or 0.0f where nothing covers; out_tri = i, or -1.
+ *    counts = {(triangle, view) pairs taking part, pixels covered summed over the views, pairs that went down the large-triangle path}:
+ *    the first two follow from the statement, the third is a diagnostic of the implementation and depends on MPMVS_RASTER_LARGE.
+ *    -2: a NULL handle or n_views < 0 (checked first, also for n_views == 0); NULL cams or out_depth, a NULL out_depth[v], a width or
+ *    height <= 0.  -3: a width or height above 2^24, or a view of more than 2^31 - 1 pixels.  -100: HIP failure.  All but -100 are found
+ *    before the device is touched, with every output untouched.  n_views == 0 returns 0 and touches nothing; a mesh without a triangle
+ *    of three finite vertices is answered on the host (0.0f, -1).  The buffers are host buffers and the call blocks; the handle is
+ *    unchanged.  out_tri, or any out_tri[v], may be NULL: not wanted.
+ *    mpmvs_surface_render_ms: device ms (HIP events) of the last call on this handle, the total returned and, in pass_ms, the init,
+ *    small, large and resolve passes summed over the chunks of views; 0 for a call that launched nothing.
+ *    mpmvs_surface_render_work: diagnostics of the last call on this handle, not part of the statement: work[0] = the pixels of the
+ *    boxes the pairs were tested in, work[1] = the atomic minima issued (it depends on the order of the threads); 0 for a call that
+ *    launched nothing.  -2: a NULL argument. */
+int mpmvs_surface_render_depth(mpmvs_mesh* surface, int n_views, const mpmvs_camera* cams, float* const* out_depth /* out_depth[v]: H*W */,
+                               int32_t* const* out_tri /* NULL, or NULL entries: not wanted */, long long counts[3] /* may be NULL */);
+float mpmvs_surface_render_ms(const mpmvs_mesh* surface, float pass_ms[4] /* may be NULL: init, small, large, resolve */);
+int mpmvs_surface_render_work(const mpmvs_mesh* surface, long long work[2]);
+
 /* ---- host arrays ------------------------------------------------------------ */
 /* Page-locked host memory for the arrays the reference allocates with new[] in AllocatePatchMatch and
  * CudaPlanarPriorInitialization (hostPlaneHypotheses, hostCosts, hostGeomCosts, hostPriorPlanes, hostPlaneMask;

@@ -2,7 +2,8 @@
 // brick-sparse, the integration of depth maps into it and the marching-tetrahedra mesh of its zero level set (kernels and per-thread
 // bodies: pm_tsdf.hpp, pm_tsdf_sparse.hpp; DESIGN.md sections 22 and 23); and the indexed triangle mesh handle (mpmvs_mesh): its
 // connected components, vertex normals and compaction (pm_mesh.hpp, pm_unionfind.hpp), and its simplification by
-// vertex clustering (pm_simplify.hpp on the clustering passes of pm_cloud.hpp and pm_voxel.hpp).  Errors are
+// vertex clustering (pm_simplify.hpp on the clustering passes of pm_cloud.hpp and pm_voxel.hpp), its samples
+// (pm_surface.hpp; section 26) and its render into cameras (pm_raster.hpp; section 27).  Errors are
 // reported like those of mpmvs_cloud_*: through mpmvs_last_error(NULL), per host thread; everything but -100 is found before the
 // device is touched.  A handle opens its device with the first call that needs it.
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "pm_mesh.hpp"
 #include "pm_mesh_host.hpp"
 #include "pm_surface.hpp"
+#include "pm_raster.hpp"
 #include "pm_simplify.hpp"
 #include "pm_tsdf.hpp"
 #include "pm_tsdf_sparse.hpp"
@@ -1075,6 +1077,138 @@ float mpmvs_surface_sample_ms(const mpmvs_mesh* h, float pass_ms[3]) {
     if (!h) return 0.0f;
     if (pass_ms) std::memcpy(pass_ms, h->sample_ms, sizeof h->sample_ms);
     return (h->sample_ms[0] + h->sample_ms[1]) + h->sample_ms[2];
+}
+
+// ---- rendering the surface into cameras (statement 7 of include/mpmvs.h; pm_raster.hpp) ----------------------
+constexpr size_t kRasterChunkPixels = (size_t)1 << 26;   // a chunk of views ends before its key buffers pass this many pixels (one view always fits)
+constexpr unsigned kRasterLargeBlocks = 4096;            // blocks of the large pass; they stride over the list
+
+// MPMVS_RASTER_LARGE=<pixels>: the size of a pair's pixel box above which it goes to the list; read at every call (tests force both
+// paths through it)
+static int raster_large_threshold() {
+    const char* e = std::getenv("MPMVS_RASTER_LARGE");
+    if (!e || !*e) return kRasterLargeDefault;
+    const long long v = std::strtoll(e, nullptr, 10);
+    return v < 0 ? 0 : (v > (1ll << 30) ? (1 << 30) : (int)v);
+}
+
+// views [v0, v1) in one launch of each pass (two of the large one); cnt: pairs taking part, covered pixels, listed pairs, pixels of the
+// boxes, atomic minima issued, added to
+static int surface_render_chunk(mpmvs_mesh* h, int v0, int v1, const mpmvs_camera* cams, int large, float* const* out_depth, int32_t* const* out_tri, long long cnt[5]) {
+    const hipStream_t st = h->stream;
+    const size_t m = (size_t)h->m;
+    size_t total = 0;
+    bool any_tri = false;
+    for (int v = v0; v < v1; ++v) {
+        total += (size_t)cams[v].width * (size_t)cams[v].height;
+        any_tri = any_tri || (out_tri && out_tri[v]);
+    }
+    Scratch d_keys(st), d_depth(st), d_tri(st), d_list(st), d_cnt(st);
+    CALLCHK(d_keys.alloc(total * 8));
+    CALLCHK(d_depth.alloc(total * 4));
+    if (any_tri) CALLCHK(d_tri.alloc(total * 4));
+    const size_t cap = m * (size_t)(v1 - v0);            // every pair at most once
+    CALLCHK(d_list.alloc(cap * 8));
+    CALLCHK(d_cnt.alloc(48));   // listed pairs up to kRasterSplit pixels, above it; pairs taking part, box pixels, atomics; covered pixels
+    RasterChunkArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.n = v1 - v0;
+    A.large = large;
+    size_t at = 0;
+    for (int v = v0; v < v1; ++v) {
+        RasterView& V = A.v[v - v0];
+        std::memcpy(V.K, cams[v].K, sizeof V.K);
+        std::memcpy(V.R, cams[v].R, sizeof V.R);
+        std::memcpy(V.t, cams[v].t, sizeof V.t);
+        V.w = cams[v].width, V.h = cams[v].height;
+        V.keys = d_keys.as<unsigned long long>() + at;
+        at += (size_t)V.w * (size_t)V.h;
+    }
+    unsigned long long* const d_n = d_cnt.as<unsigned long long>();
+    CALLCHK(hipMemsetAsync(d_cnt.p, 0, 48, st));
+    CALLCHK(h->clock.mark(0, st));
+    CALLCHK(launch(k_raster_init, mesh_blocks(total), dim3(256), st, total, d_keys.as<unsigned long long>()));
+    CALLCHK(h->clock.mark(1, st));
+    CALLCHK(launch(k_raster_small, mesh_blocks(m), dim3(256), st, (int)h->m, h->d_xyz, h->d_tri, A, d_list.as<unsigned long long>(), cap, d_n, d_n + 2));
+    CALLCHK(h->clock.mark(2, st));
+    for (int split = 0; split < 2; ++split)
+        CALLCHK(launch(k_raster_large, dim3(kRasterLargeBlocks), dim3(256), st, h->d_xyz, h->d_tri, A, d_list.as<unsigned long long>(), cap, d_n, split, d_n + 4));
+    CALLCHK(h->clock.mark(3, st));
+    CALLCHK(launch(k_raster_resolve, mesh_blocks(total), dim3(256), st, total, d_keys.as<unsigned long long>(), d_depth.as<float>(), d_tri.as<int32_t>(), d_n + 5));
+    CALLCHK(h->clock.mark(4, st));
+    at = 0;
+    for (int v = v0; v < v1; ++v) {
+        const size_t npix = (size_t)cams[v].width * (size_t)cams[v].height;
+        CALLCHK(hipMemcpyAsync(out_depth[v], d_depth.as<float>() + at, npix * 4, hipMemcpyDeviceToHost, st));
+        if (out_tri && out_tri[v]) CALLCHK(hipMemcpyAsync(out_tri[v], d_tri.as<int32_t>() + at, npix * 4, hipMemcpyDeviceToHost, st));
+        at += npix;
+    }
+    unsigned long long n[6] = {0, 0, 0, 0, 0, 0};
+    CALLCHK(hipMemcpyAsync(n, d_cnt.p, 48, hipMemcpyDeviceToHost, st));
+    CALLCHK(hipStreamSynchronize(st));
+    for (int p = 0; p < 4; ++p) {
+        float ms = 0.0f;
+        CALLCHK(h->clock.ms(p, p + 1, &ms));
+        h->render_ms[p] += ms;
+    }
+    cnt[0] += (long long)n[2], cnt[1] += (long long)n[5], cnt[2] += (long long)(n[0] + n[1]), cnt[3] += (long long)n[3], cnt[4] += (long long)n[4];
+    return 0;
+}
+
+int mpmvs_surface_render_depth(mpmvs_mesh* surface, int n_views, const mpmvs_camera* cams, float* const* out_depth, int32_t* const* out_tri, long long counts[3]) {
+    mpmvs_mesh* const h = surface;
+    if (!h || n_views < 0) return call_fail(-2, "surface render: bad argument");
+    if (n_views == 0) return 0;
+    if (!cams || !out_depth) return call_fail(-2, "surface render: bad argument");
+    for (int v = 0; v < n_views; ++v) {
+        if (!out_depth[v]) return call_fail(-2, "surface render: view " + std::to_string(v) + " has no depth buffer");
+        if (cams[v].width <= 0 || cams[v].height <= 0) return call_fail(-2, "surface render: view " + std::to_string(v) + " has a non-positive width or height");
+    }
+    for (int v = 0; v < n_views; ++v) {
+        if (cams[v].width > (1 << 24) || cams[v].height > (1 << 24)) return call_fail(-3, "surface render: view " + std::to_string(v) + " is wider or higher than 2^24");
+        if ((long long)cams[v].width * (long long)cams[v].height > (long long)INT32_MAX)
+            return call_fail(-3, "surface render: view " + std::to_string(v) + " has more than 2^31 - 1 pixels");
+    }
+    std::memset(h->render_ms, 0, sizeof h->render_ms);
+    h->render_work[0] = h->render_work[1] = 0;
+    long long cnt[5] = {0, 0, 0, 0, 0};
+    if (h->m_fin == 0) {   // no triangle takes part in any view: answered here
+        for (int v = 0; v < n_views; ++v) {
+            const size_t npix = (size_t)cams[v].width * (size_t)cams[v].height;
+            std::fill(out_depth[v], out_depth[v] + npix, 0.0f);
+            if (out_tri && out_tri[v]) std::fill(out_tri[v], out_tri[v] + npix, (int32_t)-1);
+        }
+    } else {
+        const int rc = mesh_ready(h);
+        if (rc) return rc;
+        const int large = raster_large_threshold();
+        for (int v0 = 0; v0 < n_views;) {
+            int v1 = v0 + 1;
+            size_t pixels = (size_t)cams[v0].width * (size_t)cams[v0].height;
+            while (v1 < n_views && v1 - v0 < kRasterChunk && pixels + (size_t)cams[v1].width * (size_t)cams[v1].height <= kRasterChunkPixels) {
+                pixels += (size_t)cams[v1].width * (size_t)cams[v1].height;
+                ++v1;
+            }
+            const int rc2 = surface_render_chunk(h, v0, v1, cams, large, out_depth, out_tri, cnt);
+            if (rc2) return rc2;
+            v0 = v1;
+        }
+    }
+    if (counts) counts[0] = cnt[0], counts[1] = cnt[1], counts[2] = cnt[2];
+    h->render_work[0] = cnt[3], h->render_work[1] = cnt[4];
+    return 0;
+}
+
+float mpmvs_surface_render_ms(const mpmvs_mesh* h, float pass_ms[4]) {
+    if (!h) return 0.0f;
+    if (pass_ms) std::memcpy(pass_ms, h->render_ms, sizeof h->render_ms);
+    return ((h->render_ms[0] + h->render_ms[1]) + h->render_ms[2]) + h->render_ms[3];
+}
+
+int mpmvs_surface_render_work(const mpmvs_mesh* h, long long work[2]) {
+    if (!h || !work) return call_fail(-2, "surface render_work: bad argument");
+    work[0] = h->render_work[0], work[1] = h->render_work[1];
+    return 0;
 }
 
 }  // extern "C"

@@ -34,6 +34,9 @@ struct mpmvs_mesh {
     // of the last mpmvs_surface_sample
     long long m_fin = 0;
     float dist_ms[3] = {0.0f, 0.0f, 0.0f}, sample_ms[3] = {0.0f, 0.0f, 0.0f};
+    // the passes of the last mpmvs_surface_render_depth: init, small, large, resolve
+    float render_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    long long render_work[2] = {0, 0};   // of the same call: the pixels of the pairs' boxes, the atomic minima issued
 };
 }
 

@@ -141,6 +141,10 @@ _EXTRA = {
     "surface_distance_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
     "surface_sample": (C.c_longlong, [_P, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "surface_sample_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    # a mesh rendered into cameras: depth and triangle-id maps (mesh.py: Mesh.render_depth)
+    "surface_render_depth": (C.c_int, [_P, C.c_int, _P, _P, _P, C.POINTER(C.c_longlong)]),
+    "surface_render_ms": (C.c_float, [_P, C.POINTER(C.c_float)]),
+    "surface_render_work": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
 }
 ALL_SYMBOLS = ["mpmvs_" + n for n in list(_abi.SIGNATURES) + list(_EXTRA)] + ["mpmvs_fuse", "mpmvs_fuse_kernel_ms", "mpmvs_fuse_passes", "mpmvs_sky_bilateral", "mpmvs_sky_kernel_ms", "mpmvs_fuse_ply", "mpmvs_free", "mpmvs_fuse_ctx", "mpmvs_fuse_ply_ctx", "mpmvs_fuse_ply_tracks"]
 

@@ -444,6 +444,41 @@ class Mesh:
         total = self._f["surface_sample_ms"](self._h, ms)
         return {"total": float(total), "count": float(ms[0]), "scan": float(ms[1]), "emit": float(ms[2])}
 
+    def render_depth(self, cams, want_tri=False):
+        """mpmvs_surface_render_depth: the mesh rasterised into every camera of `cams` (_abi.Camera; width and height give the map's
+        size) -> a list of float32 [H, W] depth maps along the camera's z axis, 0 = no depth; with want_tri=True (depths, tris),
+        tris a list of int32 [H, W] maps of the triangle each pixel shows (-1 = none).  Per pixel the nearest surface along its ray
+        (pixel centres at integers), both windings, no parameter; a triangle that crosses the camera plane is rendered unclipped.
+        self.last_render_counts = {"pairs", "covered", "large_pairs"} of the call."""
+        cams = list(cams)
+        n = len(cams)
+        arr = (_abi.Camera * max(n, 1))(*cams)
+        depths = [np.empty((max(int(c.height), 0), max(int(c.width), 0)), np.float32) for c in cams]
+        tris = [np.empty(d.shape, np.int32) for d in depths] if want_tri else None
+        dp = (C.c_void_p * max(n, 1))(*[d.ctypes.data for d in depths])
+        tp = (C.c_void_p * max(n, 1))(*[t.ctypes.data for t in tris]) if want_tri else None
+        counts = (C.c_longlong * 3)()
+        rc = self._f["surface_render_depth"](self._h, n, arr, dp, tp, counts)
+        if rc != 0:
+            _raise(self._f, "surface_render_depth", rc)
+        self.last_render_counts = {"pairs": int(counts[0]), "covered": int(counts[1]), "large_pairs": int(counts[2])}
+        return (depths, tris) if want_tri else depths
+
+    def render_ms(self):
+        """device ms of the last render_depth call's kernels: (total, {"init", "small", "large", "resolve"})"""
+        ms = (C.c_float * 4)()
+        total = self._f["surface_render_ms"](self._h, ms)
+        return float(total), dict(zip(("init", "small", "large", "resolve"), (float(v) for v in ms)))
+
+    def render_work(self):
+        """diagnostics of the last render_depth call: {"box_pixels": the pixels of the boxes the pairs were tested in, "atomics": the
+        atomic minima issued (it depends on the order of the threads)}"""
+        w = (C.c_longlong * 2)()
+        rc = self._f["surface_render_work"](self._h, w)
+        if rc != 0:
+            _raise(self._f, "surface_render_work", rc)
+        return {"box_pixels": int(w[0]), "atomics": int(w[1])}
+
     def simplify_ms(self):
         """device ms of the last simplify call, pass by pass"""
         ms = (C.c_float * 7)()
@@ -617,6 +652,19 @@ def evaluate_mesh(m, gt_xyz, tolerances, spacing=None, voxel=None, device=0, tim
     if timings is not None:
         timings.update(sample_s=t1 - t0, accuracy_s=t2 - t1, completeness_s=t3 - t2, device_ms=ms)
     return res
+
+
+def triangle_coverage(tri_maps, m):
+    """int64 [n_views, m]: the pixels each of the m triangles shows in each view, from the triangle-id maps of Mesh.render_depth
+    (-1 = none): the visibility table that colouring a mesh from its images, or culling what no camera saw, starts from.  Host work."""
+    out = np.zeros((len(tri_maps), int(m)), np.int64)
+    for v, t in enumerate(tri_maps):
+        t = np.asarray(t).reshape(-1)
+        t = t[t >= 0]
+        if len(t) and int(t.max()) >= m:
+            raise ValueError(f"view {v} names triangle {int(t.max())}, the mesh has {m}")
+        out[v] = np.bincount(t, minlength=int(m))
+    return out
 
 
 def _direction(d2):

@@ -5,6 +5,7 @@ DESIGN.md section 14).
     python tools/eval_depth.py --dense_folder D [--result_folder R] [--map depths.dmb] [--tolerances 0.01,0.02,0.05,0.1] [--relative]
                                --ground_truth scan.ply [--transform T.txt] [--splat 1] [--occl 0.02] [--device 0]
     python tools/eval_depth.py --dense_folder D ... --gt_depth_dir DIR --gt_format eth3d|colmap|dmb [--gt_pattern PATTERN]
+    python tools/eval_depth.py --dense_folder D ... --ground_truth_mesh mesh.ply [--transform T.txt]
 
 D holds cams/, images/ and pair.txt; the results are R/2333_<id>/<map> with R = D/MPMVS unless --result_folder names another
 root.  Every view that has a result folder with the map is scored.  The ground truth is either
@@ -16,6 +17,10 @@ root.  Every view that has a result folder with the map is scored.  The ground t
     1 + occl.  The slope rule: a slanted surface hides itself once occl is below splat x the relative change of depth per
     pixel, so raise --occl with --splat on steep or close scenes.  The defaults are starting values from the synthetic scene,
     not tuned on a real scan.  The map is rendered at the estimate's size with the camera rescaled as fusion does; or
+  * a triangle mesh (--ground_truth_mesh, a PLY file as mesh.write_ply_mesh writes it: someone's ground-truth surface, or our own
+    tools/mesh_ply.py output) rasterised into every view's camera on the GPU (mesh.Mesh.render_depth), all views in one call: the
+    depth of the nearest surface along each pixel's ray, with no parameter, so --splat and --occl are refused with it.  --transform
+    as for a scan.  Against our own mesh this measures how far each depth map lies from the surface they were all integrated into; or
   * one depth-map file per view (--gt_depth_dir): eth3d = raw little-endian fp32 of the estimate's size, colmap = COLMAP's
     "W&H&C&" maps, dmb = our own (with a second result root as DIR this is the A/B of two of our own builds).  --gt_pattern is
     a format string of the file name with {id} (defaults: "{id:08d}.JPG", "{id:08d}.jpg.geometric.bin",
@@ -91,10 +96,11 @@ def main(argv=None):
     ap.add_argument("--map", default="depths.dmb")
     ap.add_argument("--ground_truth", help="a scan (PLY), rendered into every view on the GPU")
     ap.add_argument("--transform", help="4 x 4 text matrix: the scan into the cameras' frame")
-    ap.add_argument("--splat", type=int, default=1, help="visibility window radius in pixels (0: plain z-buffer)")
-    ap.add_argument("--occl", type=float, default=0.02,
+    ap.add_argument("--ground_truth_mesh", help="a triangle mesh (PLY), rasterised into every view on the GPU; takes no --splat / --occl")
+    ap.add_argument("--splat", type=int, default=None, help="visibility window radius in pixels (0: plain z-buffer)")
+    ap.add_argument("--occl", type=float, default=None,
                     help="a point is hidden when one within --splat pixels is nearer by more than the factor 1 + occl; a slanted surface hides "
-                         "itself once occl < splat x the relative depth change per pixel")
+                         "itself once occl < splat x the relative depth change per pixel (defaults: --splat 1 --occl 0.02)")
     ap.add_argument("--gt_depth_dir")
     ap.add_argument("--gt_format", choices=sorted(GT_PATTERNS))
     ap.add_argument("--gt_pattern")
@@ -102,8 +108,11 @@ def main(argv=None):
     ap.add_argument("--relative", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
-    if bool(args.ground_truth) == bool(args.gt_depth_dir):
-        raise SystemExit("give exactly one of --ground_truth (a scan) and --gt_depth_dir (depth maps)")
+    if bool(args.ground_truth) + bool(args.gt_depth_dir) + bool(args.ground_truth_mesh) != 1:
+        raise SystemExit("give exactly one of --ground_truth (a scan), --ground_truth_mesh (a mesh) and --gt_depth_dir (depth maps)")
+    if args.ground_truth_mesh and (args.splat is not None or args.occl is not None):
+        raise SystemExit("--ground_truth_mesh takes no --splat / --occl: a rasterised mesh has no gaps to close")
+    splat, occl = (1 if args.splat is None else args.splat), (0.02 if args.occl is None else args.occl)
     if args.gt_depth_dir and not args.gt_format:
         raise SystemExit("--gt_depth_dir needs --gt_format eth3d|colmap|dmb")
     try:
@@ -128,12 +137,17 @@ def main(argv=None):
             raise SystemExit(f"{path}: {a.shape[2]} channels, a depth map has one")
         est[vid] = a
     t1 = time.perf_counter()
-    render_ms = None
+    render_ms, render_counts = None, None
     try:
-        if args.ground_truth:
+        if args.ground_truth or args.ground_truth_mesh:
             import torch  # noqa: F401  (the HIP runtime torch bundles, before our library: engine.load)
             cloud = importlib.import_module("mp-mvs_amd.cloud")
-            scan = cloud.read_ply(args.ground_truth)["xyz"]
+            if args.ground_truth:
+                scan = cloud.read_ply(args.ground_truth)["xyz"]
+            else:
+                mesh = importlib.import_module("mp-mvs_amd.mesh")
+                surface = mesh.read_ply_mesh(args.ground_truth_mesh)
+                scan = surface["xyz"]
             if args.transform:
                 scan = apply_transform(scan, np.loadtxt(args.transform))
             cams = []
@@ -142,9 +156,14 @@ def main(argv=None):
                 iw, ih = image_size(args.dense_folder, vid)
                 H, W = est[vid].shape
                 cams.append(depthmap.camera_at_size(cam, iw, ih, W, H))
-            with cloud.Cloud(scan, args.device) as c:
-                maps = c.render_depth(cams, splat=args.splat, occl_rel=args.occl)
-                render_ms = c.render_ms()[0]
+            if args.ground_truth:
+                with cloud.Cloud(scan, args.device) as c:
+                    maps = c.render_depth(cams, splat=splat, occl_rel=occl)
+                    render_ms = c.render_ms()[0]
+            else:
+                with mesh.Mesh(scan, surface["tri"], None, args.device) as h:
+                    maps = h.render_depth(cams)
+                    render_ms, render_counts = h.render_ms()[0], h.last_render_counts
             gt = {vid: m for (vid, _), m in zip(views, maps)}
         else:
             pattern = args.gt_pattern or GT_PATTERNS[args.gt_format]
@@ -154,8 +173,10 @@ def main(argv=None):
     t2 = time.perf_counter()
     per_view = {f"{vid:08d}": depthmap.score(est[vid], gt[vid], tol, args.relative) for vid, _ in views}
     t3 = time.perf_counter()
-    res = {"views": per_view, "pooled": depthmap.pool(per_view.values()), "ground_truth": "rendered" if args.ground_truth else args.gt_format,
+    res = {"views": per_view, "pooled": depthmap.pool(per_view.values()), "ground_truth": "rendered" if args.ground_truth else ("rendered_mesh" if args.ground_truth_mesh else args.gt_format),
            "seconds": {"read": round(t1 - t0, 4), "ground_truth": round(t2 - t1, 4), "score": round(t3 - t2, 4)}, "render_device_ms": render_ms}
+    if args.ground_truth_mesh:
+        res["render_counts"] = render_counts
     print(json.dumps(res))
     return res
 
